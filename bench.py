@@ -24,6 +24,7 @@ Prints ONE JSON line on rank 0.  Extra objects: roofline (dominant kernel k_welc
 stream; traffic from the PMC record of THIS build under profiles/, else null), cpu_baseline (the CPU oracle
 `welch_psd_stream` on the host cores, bounded sample: all usable cores and one core; N=1 only).
 SP_BENCH_FORCE_DIST=1 (with --gpus 1): the sharded code path with an RCCL process group of one rank.
+--dump-outputs DIR: the PSD the timed path returned for its last timed step, as DIR/pxx.npy (float64), for comparing builds.
 """
 import argparse
 import hashlib
@@ -161,6 +162,30 @@ def measure(E, x, plan, win, scale, world, dist, dev, args, collective, native):
             "kernel": E.profile_last_kernel()}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, runs, head):
+    """--dump-outputs: what the timed path returned for its last timed step -- the PSD of the whole stream, float64 [nbins],
+    the array a caller of the path receives -- as <out_dir>/pxx.npy (and pxx_weak.npy for the weak-scaling run of
+    --mode both).  The stream is seeded (synth.py), so the same arguments give the same inputs and two builds can be
+    compared output for output.  An array over its share of 64 MB is replaced by a fixed, seeded sample of its elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for name, r in runs.items():
+        a = r["pxx"]
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        cap = DUMP_LIMIT_BYTES // len(runs) // a.itemsize
+        if a.size > cap:
+            a = a.ravel()[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        fn = "pxx" if name == head else "pxx_" + name
+        np.save(os.path.join(out_dir, fn + ".npy"), a)
+        files[fn] = list(a.shape)
+    return files
+
+
 def tol_ratio(got, ref, rtol=2e-4, atol_rel=1e-6):
     """worst |got - ref| in units of the allowance rtol |ref| + atol_rel max(ref) (<= 1 passes)"""
     return float(np.max(np.abs(got - ref) / (rtol * np.abs(ref) + atol_rel * ref.max())))
@@ -189,7 +214,12 @@ def main():
     ap.add_argument("--gate-log2n", type=int, default=22,
                     help="sharded runs: the first 2^k samples of the stream go through the same sharded path and are compared "
                          "with the CPU oracle on host-generated samples (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned for its last step as DIR/<name>.npy "
+                         "(rank 0; at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args.gpus))
@@ -406,6 +436,8 @@ def main():
             result["value"] = 0.0
             result["error"] = "parity gate failed"
 
+    if rank == 0 and args.dump_outputs:
+        result["dump_outputs"] = dump_outputs(args.dump_outputs, runs, head)
     if rank == 0:
         print(json.dumps(result))
     if has_comm:
