@@ -175,7 +175,7 @@ template <bool TWD, bool PREROT = false> __device__ __forceinline__ void dft16s(
 // The same radix-16, but every finished output is handed to `store(k, value)` (k = natural-order output index) right
 // after the radix-4 butterfly that produced it, and the instruction scheduler may not move anything across the end of a
 // butterfly: the 16 LDS stores of a Stockham scatter are then spread over the last 64 VALU instructions of the pass
-// instead of forming one burst behind it (SP_EARLY_SCATTER; the burst is where the waves queue on the LDS pipe:
+// instead of forming one burst behind it (the burst is where the waves queue on the LDS pipe:
 // SQ_WAIT_INST_LDS was 16 % of the wave cycles of the metric kernel).
 template <bool TWD, class Store, bool PREROT = false> __device__ __forceinline__ void dft16s_es(cf (&x)[16], const Tw16 &w, Store store) {
     if constexpr (TWD) {
@@ -286,141 +286,6 @@ template <class Store, class Mid = NoMid> __device__ __forceinline__ void dft16s
 #undef SP_ES_OUT
 }
 
-// ---- the same butterflies in packed fp32 (v_pk_fma_f32 / v_pk_add_f32), SP_PACKED=1 ---------------------------------
-// A complex value is one 64-bit register pair and every butterfly line is ONE packed instruction; the swap of re/im,
-// the broadcast of a real scale out of a register pair and the signs ride in the op_sel / neg modifiers (inline asm:
-// hipcc folds whole-vector negations and swizzles but materialises mixed-sign operands).  87 (twiddled) / 72 (first
-// pass) instructions per radix-16 instead of 174 / 144; the SIMD's packed rate is the same flops per cycle as the
-// scalar one, but one wave alone can reach it (a wave issues at most one VALU instruction per ~5.5 cycles whatever the
-// instruction does, tools/ubench/valu_rate.hip).  Bit-identical results, all tests pass -- and MEASURED NO FASTER:
-// Welch 0.665 vs 0.640 ms, FFT / STFT / FIR equal within 1-7 % (profiles/r01_ubench.txt notes).  Kept as an option;
-// the scalar form is the default.
-typedef float v2f __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ v2f to_v2f(cf a) { return (v2f){a.x, a.y}; }
-__device__ __forceinline__ cf to_cf(v2f a) { return mk(a.x, a.y); }
-// a + (NEG ? -1 : 1) * s[H] * c          (s[H]: half H of the pair s, broadcast)
-template <int H, int NEG> __device__ __forceinline__ v2f pk_sfma(v2f s, v2f c, v2f a) {
-    v2f d;
-    if constexpr (H == 0 && NEG == 0) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,1]" : "=v"(d) : "v"(s), "v"(c), "v"(a));
-    if constexpr (H == 1 && NEG == 0) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "=v"(d) : "v"(s), "v"(c), "v"(a));
-    if constexpr (H == 0 && NEG == 1) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]" : "=v"(d) : "v"(s), "v"(c), "v"(a));
-    if constexpr (H == 1 && NEG == 1) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]" : "=v"(d) : "v"(s), "v"(c), "v"(a));
-    return d;
-}
-// a + (NEG ? -1 : 1) * s[H] * (-i c)  =  (a.x +- s c.y,  a.y -+ s c.x)
-template <int H, int NEG> __device__ __forceinline__ v2f pk_srot(v2f s, v2f c, v2f a) {
-    v2f d;
-    if constexpr (H == 0 && NEG == 0) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[0,0,1] neg_hi:[1,0,0]" : "=v"(d) : "v"(s), "v"(c), "v"(a));
-    if constexpr (H == 1 && NEG == 0) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_hi:[1,0,0]" : "=v"(d) : "v"(s), "v"(c), "v"(a));
-    if constexpr (H == 0 && NEG == 1) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[0,0,1] neg_lo:[1,0,0]" : "=v"(d) : "v"(s), "v"(c), "v"(a));
-    if constexpr (H == 1 && NEG == 1) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]" : "=v"(d) : "v"(s), "v"(c), "v"(a));
-    return d;
-}
-// a + (NEG ? -1 : 1) * (-i c)
-template <int NEG> __device__ __forceinline__ v2f pk_rot(v2f c, v2f a) {
-    v2f d;
-    if constexpr (NEG == 0) asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(c));
-    else asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(d) : "v"(a), "v"(c));
-    return d;
-}
-// forward radix-4 on (a, gb b, gc c, gd d); the scales are halves HB/HC/HD of the pairs pb/pc/pd; rd = gd/gb.  8 instr.
-template <int HB, int HC, int HD> __device__ __forceinline__ void dft4p(v2f &a, v2f &b, v2f &c, v2f &d, v2f pb, v2f pc, v2f pd) {
-    const v2f t0 = pk_sfma<HC, 0>(pc, c, a), t1 = pk_sfma<HC, 1>(pc, c, a);
-    const v2f t2 = pk_sfma<HD, 0>(pd, d, b), t3 = pk_sfma<HD, 1>(pd, d, b);
-    a = pk_sfma<HB, 0>(pb, t2, t0);
-    c = pk_sfma<HB, 1>(pb, t2, t0);
-    b = pk_srot<HB, 0>(pb, t3, t1);
-    d = pk_srot<HB, 1>(pb, t3, t1);
-}
-__device__ __forceinline__ void dft4p_plain(v2f &a, v2f &b, v2f &c, v2f &d) {
-    const v2f t0 = a + c, t1 = a - c, t2 = b + d, t3 = b - d;
-    a = t0 + t2;
-    c = t0 - t2;
-    b = pk_rot<0>(t3, t1);
-    d = pk_rot<1>(t3, t1);
-}
-// packed constants of a radix-16 pass: p[j >> 1] half j & 1 holds Tw16::f[j]
-struct Tw16p {
-    v2f p[20];
-};
-__device__ __forceinline__ void pack_tw16(Tw16p &o, const Tw16 &w) {
-#pragma unroll
-    for (int i = 0; i < 20; ++i) o.p[i] = (v2f){w.f[2 * i], w.f[2 * i + 1]};
-}
-// K0 = (C16, C8)  K1 = (S16/C16, S16)  K2 = (-C8, -C16/S16)  K3 = (T16, T316): the W16 constants, kept in VGPR pairs
-// (a VALU source that is an SGPR issues at half rate)
-struct K16p {
-    v2f k0, k1, k2, k3;
-};
-__device__ __forceinline__ K16p make_k16p() {
-    K16p k;
-    k.k0 = (v2f){SP_C16, SP_C8};
-    k.k1 = (v2f){SP_S16 / SP_C16, SP_S16};
-    k.k2 = (v2f){-SP_C8, -SP_C16 / SP_S16};
-    k.k3 = (v2f){SP_T16, SP_T316};
-    asm volatile("" : "+v"(k.k0), "+v"(k.k1), "+v"(k.k2), "+v"(k.k3));
-    return k;
-}
-#define SP_TWP(w, j) (w).p[(j) >> 1]
-#define SP_TWH(j) ((j) & 1)
-template <bool TWD> __device__ __forceinline__ void dft16p(cf (&xc)[16], const Tw16p &w, const K16p &k) {
-    v2f x[16];
-#pragma unroll
-    for (int s = 0; s < 16; ++s) x[s] = to_v2f(xc[s]);
-    if constexpr (TWD) {
-        // x (1 - i tau) = x + tau (-i x)
-#define SP_RT(s) x[s] = pk_srot<SP_TWH(Tw16::TAU + s - 1), 0>(SP_TWP(w, Tw16::TAU + s - 1), x[s], x[s]);
-        SP_RT(1) SP_RT(2) SP_RT(3) SP_RT(4) SP_RT(5) SP_RT(6) SP_RT(7) SP_RT(8) SP_RT(9) SP_RT(10) SP_RT(11) SP_RT(12)
-        SP_RT(13) SP_RT(14) SP_RT(15)
-#undef SP_RT
-#define SP_G1(b)                                                                                                     \
-    dft4p<SP_TWH(Tw16::RB + b), SP_TWH(Tw16::RC + b), SP_TWH(Tw16::RD + b)>(x[b], x[b + 4], x[b + 8], x[b + 12],     \
-                                                                           SP_TWP(w, Tw16::RB + b), SP_TWP(w, Tw16::RC + b), \
-                                                                           SP_TWP(w, Tw16::RD + b));
-        SP_G1(0) SP_G1(1) SP_G1(2) SP_G1(3)
-#undef SP_G1
-    } else {
-#pragma unroll
-        for (int b = 0; b < 4; ++b) dft4p_plain(x[b], x[b + 4], x[b + 8], x[b + 12]);
-    }
-    // x[4c+b] = Y[b][c] (pending scale g[b]); rotate by W16^{bc} / K_bc
-    x[5] = pk_srot<0, 0>(k.k3, x[5], x[5]);        // W16^1 = C16 (1 - i tan(pi/8))
-    x[9] = pk_rot<0>(x[9], x[9]);                  // W16^2 = C8 (1 - i)
-    x[13] = pk_srot<1, 0>(k.k3, x[13], x[13]);     // W16^3 = S16 (1 - i tan(3pi/8))
-    x[6] = pk_rot<0>(x[6], x[6]);                  // W16^2
-    x[10] = pk_rot<0>(x[10], (v2f){0.f, 0.f});     // W16^4 = -i
-    x[14] = pk_rot<1>(x[14], x[14]);               // W16^6 = -C8 (1 + i)
-    x[7] = pk_srot<1, 0>(k.k3, x[7], x[7]);        // W16^3
-    x[11] = pk_rot<1>(x[11], x[11]);               // W16^6
-    x[15] = pk_srot<0, 0>(k.k3, x[15], x[15]);     // W16^9 = -C16 (1 - i tan(pi/8))
-    if constexpr (TWD) {
-#define SP_G2(c)                                                                                                     \
-    dft4p<SP_TWH(Tw16::S1 + c), SP_TWH(Tw16::S2 + c), SP_TWH(Tw16::S3 + c)>(x[4 * c], x[4 * c + 1], x[4 * c + 2], x[4 * c + 3], \
-                                                                           SP_TWP(w, Tw16::S1 + c), SP_TWP(w, Tw16::S2 + c), \
-                                                                           SP_TWP(w, Tw16::S3 + c));
-        SP_G2(0) SP_G2(1) SP_G2(2) SP_G2(3)
-#undef SP_G2
-    } else {
-        dft4p_plain(x[0], x[1], x[2], x[3]);
-        dft4p<0, 1, 0>(x[4], x[5], x[6], x[7], k.k0, k.k0, k.k1);             // rb = C16, rc = C8, rd = S16/C16
-        {
-            // rb = C8, rc = 1, rd = -1
-            const v2f t0 = x[8] + x[10], t1 = x[8] - x[10], t2 = x[9] - x[11], t3 = x[9] + x[11];
-            x[8] = pk_sfma<1, 0>(k.k0, t2, t0);
-            x[10] = pk_sfma<1, 1>(k.k0, t2, t0);
-            x[9] = pk_srot<1, 0>(k.k0, t3, t1);
-            x[11] = pk_srot<1, 1>(k.k0, t3, t1);
-        }
-        dft4p<1, 0, 1>(x[12], x[13], x[14], x[15], k.k1, k.k2, k.k2);         // rb = S16, rc = -C8, rd = -C16/S16
-    }
-#pragma unroll
-    for (int s = 0; s < 16; ++s) xc[s] = to_cf(x[s]);
-    cf t;
-#define SP_SWAP(i, j) t = xc[i]; xc[i] = xc[j]; xc[j] = t;
-    SP_SWAP(1, 4) SP_SWAP(2, 8) SP_SWAP(3, 12) SP_SWAP(6, 9) SP_SWAP(7, 13) SP_SWAP(11, 14)
-#undef SP_SWAP
-}
-
 // per-thread constants of a twiddled radix-16 pass from the forward twiddles wv[s-1] = exp(-i s phi), s = 1..15
 __device__ __forceinline__ void make_tw16(Tw16 &w, const cf (&wv)[15]) {
     float g[16];
@@ -448,40 +313,8 @@ __device__ __forceinline__ void make_tw16(Tw16 &w, const cf (&wv)[15]) {
     }
 }
 
-// SP_ABLATE (diagnostic builds only, results wrong): bit 0 = skip the radix-16 butterflies, bit 1 = skip the LDS
-// exchanges (and their barriers), bit 2 = skip the inter-pass twiddles, bit 3 = no global loads in the carry loop, bit 4 = the loop's loads all hit L2
-// SP_PACKED=1: radix-16 butterflies in packed fp32 (v_pk_*_f32); 0: the scalar FMA form
-#ifndef SP_PACKED
-#define SP_PACKED 0
-#endif
-// SP_DIAG_SHARETW (diagnostic, results wrong): every twiddled radix-16 pass uses the first pass's constants
-#ifndef SP_DIAG_SHARETW
-#define SP_DIAG_SHARETW 0
-#endif
-#ifndef SP_ABLATE
-#define SP_ABLATE 0
-#endif
-// SP_READ_B64=1: the unit-stride gathers are issued as single ds_read_b64 (volatile LDS loads, which hipcc does not merge
-// into ds_read2_b64): 2 LDS cycles per 8 bytes per wave instead of 8 per 16 (MI355X_MICROARCH.md, LDS table); the first
-// exchange image then takes row pitch T+2 (32-lane groups over 64 banks) instead of T+1
-#ifndef SP_READ_B64
-#define SP_READ_B64 0
-#endif
-// SP_EARLY_SCATTER=1 (callers with two exchange images only): see dft16s_es
-#ifndef SP_EARLY_SCATTER
-#define SP_EARLY_SCATTER 0
-#endif
 typedef float sp_f2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ cf lds_load_single(const cf *p) {
-#if SP_READ_B64
-    // explicit LDS address space: a volatile access through a generic pointer is not narrowed to ds_read by hipcc
-    typedef const volatile __attribute__((address_space(3))) sp_f2v *lds_cvp;
-    const sp_f2v r = *(lds_cvp)(p);
-    return mk(r.x, r.y);
-#else
-    return *p;
-#endif
-}
+__device__ __forceinline__ cf lds_load_single(const cf *p) { return *p; }
 template <int RDX, bool INV> __device__ __forceinline__ void dftR(cf (&x)[RDX]) {
     if constexpr (RDX == 2) dft2<INV>(x[0], x[1]);
     else if constexpr (RDX == 4) dft4<INV>(x[0], x[1], x[2], x[3]);
@@ -509,7 +342,7 @@ template <int N> struct FftPlan {
     // bank = dword mod 32): lane stride must be == 2 dwords mod 32 -> pitch == 1 mod 16.  (T+2 would suit plain
     // ds_read_b64 -- 32-lane groups, 64 banks -- and costs a 2-way conflict on every read2: measured 256 LDS
     // conflict cycles per 4096-point frame.)
-    static constexpr int PITCH1 = SP_READ_B64 ? T + 2 : T + 1;
+    static constexpr int PITCH1 = T + 1;
     static constexpr int LDS_ELEMS = NP > 1 ? (R * PITCH1 > N ? R * PITCH1 : N) : 0;
 };
 
@@ -517,33 +350,21 @@ template <int N> struct FftPlan {
 // Forward transforms only (inverses are conj(fft(conj(.))) at the call sites).
 // TW1LDS: the constants of the FIRST twiddled radix-16 pass are not kept in registers but re-read every transform from a
 // 16-row table in LDS (`tw1`: row = tid % 16, SP_TW1_PITCH floats apart) -- only 16 distinct sets exist for that pass; frees
-// 40 VGPRs per thread (the occupancy experiment of the carry kernel, SP_CARRY_W3)
+// 40 VGPRs per thread (an occupancy experiment of the carry kernel, not kept; XfPow2 still names the parameter)
 #define SP_TW1_PITCH 44      /* 40 floats + 4: rows start 44 dwords apart -> the 16 rows of a b128 read hit 16 distinct bank quads */
-// RM: the first exchange image holds every thread's 16 pass-0 outputs side by side, [thread][16] at a pitch of RM_PITCH, the
-// four outputs of a final radix-4 butterfly (k = c, c+4, c+8, c+12) adjacent: two 16-byte writes instead of four 8-byte ones
-// (the [k][thread] image at pitch T + 1 takes 16 single ds_write_b64: its stride fits neither write2 form), and the unit-
-// stride gather of the next pass strides 16 RM_PITCH = 5 x 64 elements, a ds_read2st64_b64 per two elements as before.
-template <int N, bool TW1LDS = false, bool RM = false> struct WgFft {
+template <int N, bool TW1LDS = false> struct WgFft {
     using PL = FftPlan<N>;
     static constexpr int R = PL::R, T = PL::T, NP = PL::NP;
-    static constexpr int RM_PITCH = 20;
-    static constexpr int IMG0 = RM ? T * RM_PITCH : PL::LDS_ELEMS;      // elements of a first-exchange image
-    static_assert(!RM || (PL::radix(0) == 16 && R == 16 && (T % 16) == 0), "RM: radix-16 first pass");
+    static constexpr int IMG0 = PL::LDS_ELEMS;      // elements of a first-exchange image
     static constexpr int N16 = PL::NP16 > 1 ? PL::NP16 - 1 : 0;          // twiddled radix-16 passes
     static constexpr int NTR = (N >= 16 && PL::REM > 1) ? (R / PL::REM) * (PL::REM - 1) : 0;   // remainder-pass twiddles
-#if SP_PACKED
-    Tw16p t16[N16 > 0 ? N16 : 1];
-    K16p k16;
-#else
     Tw16 t16[N16 > 0 ? N16 : 1];
-#endif
     cf twr[NTR > 0 ? NTR : 1];
     const float *tw1 = nullptr;
 
     // TW1LDS: write this thread's pass-1 constants into row tid % 16 of the LDS table (threads 0..15 cover all rows); call
     // after load_twiddles, followed by a barrier
     __device__ __forceinline__ void publish_tw1(float *table, int tid) {
-#if !SP_PACKED
         if constexpr (TW1LDS && N16 > 0) {
             if (tid < 16) {
 #pragma unroll
@@ -551,14 +372,10 @@ template <int N, bool TW1LDS = false, bool RM = false> struct WgFft {
             }
             tw1 = table;
         }
-#endif
     }
 
     // table[m] = exp(-2 pi i m / N), m = 0..N-1
     __device__ __forceinline__ void load_twiddles(const cf *__restrict__ table, int tid) {
-#if SP_PACKED
-        k16 = make_k16p();
-#endif
         load_tw<1>(table, tid);
     }
 
@@ -570,13 +387,7 @@ template <int N, bool TW1LDS = false, bool RM = false> struct WgFft {
                 cf wv[15];
 #pragma unroll
                 for (int s = 1; s < 16; ++s) wv[s - 1] = table[e * s];
-#if SP_PACKED
-                Tw16 w1;
-                make_tw16(w1, wv);
-                pack_tw16(t16[P - 1], w1);
-#else
                 make_tw16(t16[P - 1], wv);
-#endif
             } else {
 #pragma unroll
                 for (int u = 0; u < NB; ++u) {
@@ -598,20 +409,12 @@ template <int N, bool TW1LDS = false, bool RM = false> struct WgFft {
         cf wv[15];
 #pragma unroll
         for (int s = 1; s < 16; ++s) wv[s - 1] = table[e * s];
-#if SP_PACKED
-        Tw16 w1;
-        make_tw16(w1, wv);
-        pack_tw16(t16[P - 1], w1);
-        k16 = make_k16p();
-#else
         make_tw16(t16[P - 1], wv);
-#endif
     }
 
     // physical LDS index of logical element i for exchange number E (0 = first)
     template <int E> static __device__ __forceinline__ int phys(int i) {
-        if constexpr (E == 0 && RM) return (i / 16) * RM_PITCH + (i % 4) * 4 + (i % 16) / 4;
-        else if constexpr (E == 0) return (i % PL::radix(0)) * PL::PITCH1 + i / PL::radix(0);
+        if constexpr (E == 0) return (i % PL::radix(0)) * PL::PITCH1 + i / PL::radix(0);
         else return i;
     }
 
@@ -625,32 +428,25 @@ template <int N, bool TW1LDS = false, bool RM = false> struct WgFft {
 #pragma unroll
             for (int s = 0; s < r; ++s) x[s] = v[u + s * NB];
             if constexpr (r == 16) {
-                if constexpr (!(SP_ABLATE & 1)) {
-#if SP_PACKED
-                    if constexpr (P > 0 && !(SP_ABLATE & 4)) dft16p<true>(x, t16[SP_DIAG_SHARETW ? 0 : P - 1], k16);
-                    else dft16p<false>(x, t16[0], k16);
-#else
-                    if constexpr (TW1LDS && P == 1 && !(SP_ABLATE & 4)) {
-                        Tw16 wl;
-                        const float4 *row = reinterpret_cast<const float4 *>(tw1 + (tid % 16) * SP_TW1_PITCH);
+                if constexpr (TW1LDS && P == 1) {
+                    Tw16 wl;
+                    const float4 *row = reinterpret_cast<const float4 *>(tw1 + (tid % 16) * SP_TW1_PITCH);
 #pragma unroll
-                        for (int j = 0; j < 10; ++j) {
-                            const float4 q = row[j];
-                            wl.f[4 * j] = q.x;
-                            wl.f[4 * j + 1] = q.y;
-                            wl.f[4 * j + 2] = q.z;
-                            wl.f[4 * j + 3] = q.w;
-                        }
-                        dft16s<true>(x, wl);
-                    } else if constexpr (P > 0 && !(SP_ABLATE & 4)) {
-                        dft16s<true>(x, t16[SP_DIAG_SHARETW ? 0 : P - 1]);
-                    } else {
-                        dft16s<false>(x, t16[0]);
+                    for (int j = 0; j < 10; ++j) {
+                        const float4 q = row[j];
+                        wl.f[4 * j] = q.x;
+                        wl.f[4 * j + 1] = q.y;
+                        wl.f[4 * j + 2] = q.z;
+                        wl.f[4 * j + 3] = q.w;
                     }
-#endif
+                    dft16s<true>(x, wl);
+                } else if constexpr (P > 0) {
+                    dft16s<true>(x, t16[P - 1]);
+                } else {
+                    dft16s<false>(x, t16[0]);
                 }
             } else {
-                if constexpr (P > 0 && !(SP_ABLATE & 4)) {
+                if constexpr (P > 0) {
 #pragma unroll
                     for (int s = 1; s < r; ++s) x[s] = twm<false>(x[s], twr[u * (r - 1) + (s - 1)]);
                 }
@@ -673,12 +469,7 @@ template <int N, bool TW1LDS = false, bool RM = false> struct WgFft {
     }
     // unit-stride gather from exchange image P: v[t] = element tid + T*t
     template <int P> __device__ __forceinline__ void gather(cf (&v)[R], const cf *lds, int tid) const {
-        if constexpr (P == 0 && RM) {
-            // i = tid + T*t  ->  (tid/16 + (T/16) t) * RM_PITCH + pos(tid % 16)
-            const int b = (tid / 16) * RM_PITCH + (tid % 4) * 4 + (tid % 16) / 4;
-#pragma unroll
-            for (int t = 0; t < R; ++t) v[t] = lds_load_single(&lds[b + (T / 16) * RM_PITCH * t]);
-        } else if constexpr (P == 0 && (T % 16) == 0 && PL::radix(0) == 16) {
+        if constexpr (P == 0 && (T % 16) == 0 && PL::radix(0) == 16) {
             // i = tid + T*t  ->  (i%16)*PITCH1 + i/16 = (tid%16)*PITCH1 + tid/16 + (T/16)*t
             const int b = (tid % 16) * PL::PITCH1 + tid / 16;
 #pragma unroll
@@ -763,18 +554,9 @@ template <int N, bool TW1LDS = false, bool RM = false> struct WgFft {
     template <int P, bool SINGLE, bool WL = false> __device__ __forceinline__ void pass(cf (&v)[R], cf *lds0, cf *lds1, int tid) const {
         constexpr bool LAST = (P == NP - 1);
         cf *lds = (P & 1) ? lds1 : lds0;
-        if constexpr (SP_EARLY_SCATTER && !SP_PACKED && !SP_ABLATE && !SINGLE && !LAST && PL::radix(P) == 16 && R == 16) {
-            bfly_scatter<P>(v, lds, tid);
-            xsync<WL>();
-            gather<P>(v, lds, tid);
-            pass<P + 1, SINGLE, WL>(v, lds0, lds1, tid);
-            return;
-        }
-        if constexpr (!LAST && SINGLE && !(SP_ABLATE & 2)) xsync<WL>();       // previous readers of this image are done
+        if constexpr (!LAST && SINGLE) xsync<WL>();       // previous readers of this image are done
         bfly<P>(v, tid);
-        if constexpr (!LAST && (SP_ABLATE & 2)) {
-            pass<P + 1, SINGLE, WL>(v, lds0, lds1, tid);
-        } else if constexpr (!LAST) {
+        if constexpr (!LAST) {
             scatter<P>(v, lds, tid);
             xsync<WL>();
             gather<P>(v, lds, tid);

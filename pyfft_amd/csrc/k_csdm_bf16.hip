@@ -23,17 +23,9 @@
 namespace sp {
 
 #define CB_BINS 8
-// CB_FORM: 8 = eight piece products per part, one operand per part and frame (10 MFMAs per pair); 6 = six products in
-// 3-dword groups over two frames (8 MFMAs per pair)
-#ifndef CB_FORM
-#define CB_FORM 6
-#endif
-#ifndef CB_NT_LOADS
-#define CB_NT_LOADS 1
-#endif
-#ifndef CB_INTERLEAVE
+// Six piece products per part in 3-dword groups over two frames (8 MFMAs per pair; eight products per part, one operand per
+// part and frame, took 10)
 #define CB_INTERLEAVE 5          // VALU instructions per MFMA in the scheduling pipeline (0: leave it to hipcc)
-#endif
 #define CB_FP 4                                   // frame pairs per tile
 #define CB_P 17                                   // LDS pitch (complex) of one (pair, channel) row of 8 bins x 2 frames
 #define CB_TILE (CB_FP * 64 * CB_P)               // complex elements per buffer
@@ -58,61 +50,18 @@ __device__ __forceinline__ Split3 split3(float x) {
 // dword holding the bf16 (top half) of a in its low half (K-slot 2j) and that of b in its high half (K-slot 2j + 1)
 __device__ __forceinline__ unsigned pk(unsigned a, unsigned b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
 
-// packed operands of one complex element for one frame: one MFMA operand (4 dwords = 8 K-slots) per part and role
-struct Ops {
-    bf16x8 ra, ia;        // A operands of the real / imaginary part:  [h h | m m | h l | m l]
-    bf16x8 rb, ib;        // B operands:                               [h m | h m | l h | l m]
-};
 __device__ __forceinline__ bf16x8 op4(unsigned a, unsigned b, unsigned c, unsigned d) {
     u32x4 v = {a, b, c, d};
     return __builtin_bit_cast(bf16x8, v);
 }
-__device__ __forceinline__ void make_part(float x, bf16x8 &a, bf16x8 &b) {
-#if CB_ABLATE & 2
-    const unsigned u = __float_as_uint(x);
-    a = op4(u, u, u, u);
-    b = a;
-    return;
-#endif
-    const Split3 s = split3(x);
-    // slots A|B: (h|h)(h|m)  (m|h)(m|m)  (h|l)(l|h)  (m|l)(l|m): no dword is common to A and B, so hipcc writes every
-    // v_perm_b32 straight into its operand register (with [hm hm hl ml] | [hm mh lh lm] it built B as a copy of A: 12
-    // instructions per part instead of 8)
-    a = op4(pk(s.h, s.h), pk(s.m, s.m), pk(s.h, s.l), pk(s.m, s.l));
-    b = op4(pk(s.h, s.m), pk(s.h, s.m), pk(s.l, s.h), pk(s.l, s.m));
-}
-__device__ __forceinline__ Ops make_ops(cf x) {
-    Ops o;
-    make_part(x.x, o.ra, o.rb);
-    make_part(x.y, o.ia, o.ib);
-    return o;
-}
-__device__ __forceinline__ bf16x8 neg8(bf16x8 a) {
-    u32x4 v = __builtin_bit_cast(u32x4, a);
-    v ^= 0x80008000u;
-    return __builtin_bit_cast(bf16x8, v);
-}
-// CB_ABLATE (diagnostic builds, results wrong): 1 = no MFMAs (the operands are consumed by one add each), 2 = no operand
-// preparation (the raw element bits as operands)
-#ifndef CB_ABLATE
-#define CB_ABLATE 0
-#endif
-#if CB_ABLATE & 1
-#define CB_MFMA(acc, a, b)                                                                            \
-    {                                                                                                 \
-        const u32x4 ua_ = __builtin_bit_cast(u32x4, a), ub_ = __builtin_bit_cast(u32x4, b);           \
-        acc[0] += __uint_as_float((ua_.x ^ ub_.y) + (ua_.z ^ ub_.w) + (ua_.y ^ ub_.x) + (ua_.w ^ ub_.z)); \
-    }
-#else
 #define CB_MFMA(acc, a, b) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0)
-#endif
 
-// FORM 4 (long records: csd_matrix_impl selects it from 1024 frame pairs on; SP_CSDM_SPLIT3=1 / SP_CSDM_SPLIT2=1 force a form): TWO pieces x ~ h + m (m rounded to nearest: 16 significant bits, residual <= 2^-16 |x|,
+// FORM 4 (long records: csd_matrix_impl selects it from 1024 frame pairs on; SP_CSDM_SPLIT3=1 forces the three-piece form): TWO pieces x ~ h + m (m rounded to nearest: 16 significant bits, residual <= 2^-16 |x|,
 // zero mean) and the four products h h, h m, m h, m m: A = [h h | m m], B = [h m | h m] -- a part is 2 dwords, an element of one
 // frame exactly one operand [re | im], so the Hermitian 64 x 64 update of a frame pair is 4 MFMAs + 1 for the two diagonal
 // blocks' imaginary parts (two pairs share those): 10 per two pairs instead of 16.  The operands carry 16 bits instead of
 // 24: the products' errors (rms 2^-17 / sqrt 3 each) average out over the frames but not for spectra that repeat exactly
-// from frame to frame (measured there: 7e-7 of the peak against 3e-7, tools/split2_ab.py), hence only for long records where
+// from frame to frame (measured there: 7e-7 of the peak against 3e-7), hence only for long records where
 // the float32 accumulation is the larger error anyway.
 template <int FORM>
 static __global__ __launch_bounds__(512) void k_csdm_bf16(const cf *__restrict__ Xs, int nch, int64_t npairs, int ld, int ngroups,
@@ -143,14 +92,10 @@ static __global__ __launch_bounds__(512) void k_csdm_bf16(const cf *__restrict__
         for (int q = 0; q < CB_FP; ++q) {
             const int64_t p = p0 + q;
             const bool ok = p < pend;
-#if CB_NT_LOADS
             {
                 const sp_f4s r = __builtin_nontemporal_load(reinterpret_cast<const sp_f4s *>(rowbase + (ok ? p : pbeg) * pstride));
                 st[q] = make_float4(r.x, r.y, r.z, r.w);       // read exactly once
             }
-#else
-            st[q] = rowbase[(ok ? p : pbeg) * pstride];        // clamped address; masked at lstore
-#endif
             keep[q] = ok ? keepc : 0.f;
         }
     };
@@ -227,7 +172,6 @@ static __global__ __launch_bounds__(512) void k_csdm_bf16(const cf *__restrict__
                         op4(B[0][1][0], B[0][1][0], B[1][1][0], B[1][1][0]));
             }
         } else {
-#if CB_FORM == 6
         // six products per part ((h|h)(h|m) (m|h)(m|m) (h|l)(l|h): everything down to 2^-16 and the two largest 2^-24 terms) in
         // 3-dword groups; a lane's two frames of a pair of pairs make 12 dwords = three MFMA operands per block: 16 MFMAs per
         // two pairs instead of 20
@@ -295,41 +239,12 @@ static __global__ __launch_bounds__(512) void k_csdm_bf16(const cf *__restrict__
 #undef PA_
 #undef PB_
         }
-#else
-        // all eight elements of the tile first (hipcc otherwise issued each ds_read right in front of its use: eight exposed
-        // LDS round trips per tile, 30 % of the wave cycles at s_waitcnt)
-        cf xe[CB_FP][2];
-#pragma unroll
-        for (int q = 0; q < CB_FP; ++q) {
-            xe[q][0] = pa[(q * 64) * CB_P];
-            xe[q][1] = pa[(q * 64 + 32) * CB_P];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < CB_FP; ++q) {
-            // this lane's frame of pair q: channels col (rows / columns 0..31) and col + 32
-            const Ops x0 = make_ops(xe[q][0]), x1 = make_ops(xe[q][1]);
-            const bf16x8 nr0 = neg8(x0.ra);
-            // Re G = Xr Xr^T + Xi Xi^T on the blocks (0,0), (0,1), (1,1); Im G = Xi Xr^T - Xr Xi^T on (0,1); on the diagonal
-            // blocks only P = Xi Xr^T (Im G = P - P^T is taken once at the end)
-            CB_MFMA(accR[0], x0.ra, x0.rb);
-            CB_MFMA(accR[1], x0.ra, x1.rb);
-            CB_MFMA(accR[2], x1.ra, x1.rb);
-            CB_MFMA(accI[1], x0.ia, x1.rb);
-            CB_MFMA(accI[0], x0.ia, x0.rb);
-            CB_MFMA(accR[0], x0.ia, x0.ib);
-            CB_MFMA(accR[1], x0.ia, x1.ib);
-            CB_MFMA(accR[2], x1.ia, x1.ib);
-            CB_MFMA(accI[1], nr0, x1.ib);
-            CB_MFMA(accI[2], x1.ia, x1.rb);
-        }
-#endif
         }
 #if CB_INTERLEAVE
         // ask the scheduler for MFMA / VALU interleaving: the operand preparation of the later K-slots runs in the shadow
         // of the earlier MFMAs (an MFMA holds the SIMD's issue for 8 of its 32 cycles)
 #pragma unroll
-        for (int i = 0; i < (FORM == 4 ? 5 : CB_FORM == 6 ? 8 : 10) * CB_FP; ++i) {
+        for (int i = 0; i < (FORM == 4 ? 5 : 8) * CB_FP; ++i) {
             __builtin_amdgcn_sched_group_barrier(0x002, CB_INTERLEAVE, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         }

@@ -2,6 +2,294 @@
 #include "launch.h"
 namespace sp {
 
+// complex transpose with out = scale * (conj ? conj(in) : in): first / last pass of the large FFT
+// blockIdx.z: matrix of a batch (contiguous rows*cols apart)
+static __global__ void k_transpose_c(const cf *__restrict__ in, cf *__restrict__ out, int64_t rows, int64_t cols,
+                                     int conj, float scale) {
+    __shared__ cf tile[32][33];
+    in += (int64_t)blockIdx.z * rows * cols;
+    out += (int64_t)blockIdx.z * rows * cols;
+    const int64_t c0 = (int64_t)blockIdx.x * 32, r0 = (int64_t)blockIdx.y * 32;
+    const float sg = conj ? -scale : scale;
+    for (int j = threadIdx.y; j < 32; j += blockDim.y) {
+        const int64_t r = r0 + j, c = c0 + threadIdx.x;
+        if (r < rows && c < cols) {
+            const cf a = in[r * cols + c];
+            tile[j][threadIdx.x] = mk(scale * a.x, sg * a.y);
+        }
+    }
+    __syncthreads();
+    for (int j = threadIdx.y; j < 32; j += blockDim.y) {
+        const int64_t c = c0 + j, r = r0 + threadIdx.x;
+        if (r < rows && c < cols) out[c * rows + r] = tile[threadIdx.x][j];
+    }
+}
+
+// out[i] = i < n_in ? (x[i] - mean, 0) : 0   for i < L   (real -> zero-padded complex)
+static __global__ void k_pack_real(const float *__restrict__ x, int64_t n_in, const double *__restrict__ mean, int64_t L,
+                                   cf *__restrict__ out) {
+    const float m = mean ? (float)mean[0] : 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < L; i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = i < n_in ? mk(x[i] - m, 0.f) : mk(0.f, 0.f);
+}
+
+// out[i] = a[i] * b[i] (optionally conj(a*b)), i < n
+// blockIdx.y: row of a batch (a and out n apart, b shared)
+static __global__ void k_cmul_vec(const cf *__restrict__ a, const cf *__restrict__ b, int64_t n, int conj_out,
+                                  cf *__restrict__ out) {
+    a += (int64_t)blockIdx.y * n;
+    out += (int64_t)blockIdx.y * n;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const cf p = cmul(a[i], b[i]);
+        out[i] = conj_out ? cconj(p) : p;
+    }
+}
+
+// Bluestein pre-multiply with zero padding: out[i] = i < n ? in[i]*chirp[i] : 0, i < L  (conj_in: use conj(in))
+// blockIdx.y: row of a batch (in n apart, out L apart)
+static __global__ void k_blue_pre(const cf *__restrict__ in, const cf *__restrict__ chirp, int64_t n, int64_t L,
+                                  int conj_in, cf *__restrict__ out) {
+    in += (int64_t)blockIdx.y * n;
+    out += (int64_t)blockIdx.y * L;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < L; i += (int64_t)gridDim.x * blockDim.x) {
+        if (i < n) {
+            const cf a = in[i];
+            out[i] = cmul(conj_in ? cconj(a) : a, chirp[i]);
+        } else {
+            out[i] = mk(0.f, 0.f);
+        }
+    }
+}
+
+// Bluestein post-multiply: out[i] = scale * conj?(in[i] * chirp[i]),  i < n
+// blockIdx.y: row of a batch (in in_ld apart, out n apart)
+static __global__ void k_blue_post(const cf *__restrict__ in, const cf *__restrict__ chirp, int64_t n, int conj_out,
+                                   float scale, cf *__restrict__ out, int64_t in_ld) {
+    in += (int64_t)blockIdx.y * in_ld;
+    out += (int64_t)blockIdx.y * n;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const cf p = cmul(in[i], chirp[i]);
+        out[i] = mk(scale * p.x, conj_out ? -scale * p.y : scale * p.y);
+    }
+}
+
+// analytic-signal mask (hilbert.py:63-64) in place: k=0 and k=nyq x1, 1..nyq-1 x2, > nyq x0
+static __global__ void k_hilbert_mask(cf *__restrict__ X, int64_t n) {
+    const int64_t nyq = (n & 1) ? (n + 1) / 2 : n / 2;
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+        const float h = (k == 0 || k == nyq) ? 1.f : (k < nyq ? 2.f : 0.f);
+        X[k] = h * X[k];
+    }
+}
+
+// c[ch][n] = sum_g detrended(x[ch][g*hop + n]), n < nfft: the time-domain sum of all frames of each channel.  By linearity
+// sum_g FFT(win * frame_g) = FFT(win * c): the mean spectrum of the nT-model branch of fft_pwelch (fft_analysis.py:346-393)
+// without writing one spectrum.  grid (ceil(nfft/256), frame slices, channels); every slice writes its own partial
+// part[slice][ch][n][2] (float64), k_frame_sum_reduce adds the slices in a fixed order: deterministic (round 1 used
+// float64 atomics).
+template <bool LIN>
+static __global__ void k_frame_sum(const void *__restrict__ x, int cplx, int64_t x_ld, int nfft, int hop, int64_t nframes,
+                                   const float *__restrict__ trend, double *__restrict__ part) {
+    const int n = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    const int ch = blockIdx.z;
+    const int64_t per = (nframes + gridDim.y - 1) / gridDim.y;
+    const int64_t g0 = (int64_t)blockIdx.y * per, g1 = g0 + per < nframes ? g0 + per : nframes;
+    if (n >= nfft) return;
+    const Trend tr = load_trend(trend + 4 * ch);
+    const int64_t off = (int64_t)ch * x_ld;
+    double sr = 0.0, si = 0.0;
+    for (int64_t g = g0; g < g1; ++g) {
+        const int64_t i = g * hop + n;
+        const cf v = detrended<LIN>(load_sample(x, off + i, cplx != 0), tr, i);
+        sr += (double)v.x;
+        si += (double)v.y;
+    }
+    double *p = part + 2 * (((int64_t)blockIdx.y * gridDim.z + ch) * nfft + n);
+    p[0] = sr;
+    p[1] = si;
+}
+
+static __global__ void k_frame_sum_reduce(const double *__restrict__ part, int slices, int64_t count /* nch*nfft*2 */,
+                                          double *__restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= count) return;
+    double s = 0.0;
+    for (int q = 0; q < slices; ++q) s += part[(int64_t)q * count + e];
+    out[e] = s;
+}
+
+// X[k] *= H[k] in place (long-row form of sp_spectral_filter)
+static __global__ void k_spec_mul(cf *__restrict__ X, const cf *__restrict__ H, int64_t n) {
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x)
+        X[k] = cmul(X[k], H[k]);
+}
+
+// z = (x1-m1) + i (x2-m2), zero-padded to L;  mom[0]=m1, mom[1]=m2
+static __global__ void k_xc_pack(const float *__restrict__ x1, const float *__restrict__ x2, int64_t n, int64_t L,
+                                 const double *__restrict__ mom, cf *__restrict__ z) {
+    const float m1 = (float)mom[0], m2 = (float)mom[1];
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < L; i += (int64_t)gridDim.x * blockDim.x)
+        z[i] = i < n ? mk(x1[i] - m1, x2[i] - m2) : mk(0.f, 0.f);
+}
+
+// R[k] = A conj(B) from Z = FFT(a + i b):  Im(Z[k] Z[L-k])/2 + i (|Z[k]|^2 - |Z[L-k]|^2)/4 ; stored CONJUGATED
+static __global__ void k_xc_mid(const cf *__restrict__ Z, int64_t L, cf *__restrict__ R) {
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < L; k += (int64_t)gridDim.x * blockDim.x) {
+        const cf z = Z[k], zm = Z[(L - k) & (L - 1)];
+        const cf zz = cmul(z, zm);
+        R[k] = mk(0.5f * zz.y, -0.25f * (cnorm(z) - cnorm(zm)));
+    }
+}
+
+// ccf with a half-length inverse (the correlation is real): from Z = FFT_L(a + i b), R(k) = A conj(B) as in k_xc_mid, and
+// Z'[k] = ((R(k) + conj R(M-k)) + i conj(w) (R(k) - conj R(M-k)))/2, M = L/2, w = exp(-2 pi i k / L): the M-point spectrum of
+// z'[n] = r[2n] + i r[2n+1].  Stored CONJUGATED (the inverse runs as a forward transform of the conjugate).
+static __global__ void k_xc_mid_half(const cf *__restrict__ Z, int64_t L, BigTw bt, cf *__restrict__ Zp) {
+    const int64_t M = L / 2;
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < M; k += (int64_t)gridDim.x * blockDim.x) {
+        const cf a = Z[k], am = Z[(L - k) & (L - 1)], b = Z[M - k], bm = Z[M + k];
+        const cf za = cmul(a, am), zb = cmul(b, bm);
+        const cf rk = mk(0.5f * za.y, 0.25f * (cnorm(a) - cnorm(am)));
+        const cf rmc = mk(0.5f * zb.y, -0.25f * (cnorm(b) - cnorm(bm)));              // conj R(M-k)
+        const cf w = cmul(bt.hi[k >> bt.lb], bt.lo[k & ((1 << bt.lb) - 1)]);          // W_L^k
+        const cf s = rk + rmc, d = rk - rmc;
+        const cf t = cmul(cconj(w), d);                                               // i t = (-t.y, t.x)
+        Zp[k] = mk(0.5f * (s.x - t.y), -0.5f * (s.y + t.x));
+    }
+}
+
+// half-length Hilbert, middle step, in place: Z = FFT_M(x[2n] + i x[2n+1]) (M = N/2) -> Z'[k] = (conj(w)(Z[k] + conj Z[M-k]) -
+// w (Z[k] - conj Z[M-k]))/2, w = exp(-2 pi i k / N), Z'[0] = 0: the half-length spectrum of y = Im(analytic signal), i.e. the
+// real-FFT split, the analytic mask (hilbert.py:63-64: DC and Nyquist contribute to the real part only) and the inverse
+// real-FFT merge in one step.  A thread owns the pair (k, M-k).
+static __global__ void k_hilbert_mid(cf *__restrict__ Z, int64_t M, BigTw bt) {
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k <= M / 2; k += (int64_t)gridDim.x * blockDim.x) {
+        if (k == 0) {
+            Z[0] = mk(0.f, 0.f);
+            continue;
+        }
+        const int64_t km = M - k;
+        const cf a = Z[k], b = Z[km];
+        const cf w = cmul(bt.hi[k >> bt.lb], bt.lo[k & ((1 << bt.lb) - 1)]);          // W_N^k
+        const cf p = mk(a.x + b.x, a.y - b.y), q = mk(a.x - b.x, a.y + b.y);          // a + conj b, a - conj b
+        const cf r = cmul(cconj(w), p) - cmul(w, q);
+        Z[k] = mk(0.5f * r.x, 0.5f * r.y);
+        if (km != k) {
+            // for M-k: w' = -conj(w), p' = conj p, q' = -conj q  ->  conj(w') p' - w' q' = -w conj(p) - conj(w) conj(q)
+            const cf r2 = cmul(w, cconj(p)) + cmul(cconj(w), cconj(q));
+            Z[km] = mk(-0.5f * r2.x, -0.5f * r2.y);
+        }
+    }
+}
+
+// co[j], j < 2n-1, 'full' order from r = real(FFT(conj R))/L:  lag >= 0 -> r[lag], lag < 0 -> r[L+lag]; times mom[2]
+static __global__ void k_xc_out(const cf *__restrict__ r, int64_t n, int64_t L, const double *__restrict__ mom,
+                                float *__restrict__ co) {
+    const float nrm = (float)(mom[2] / (double)L);
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < 2 * n - 1; j += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t lag = j - (n - 1);
+        co[j] = nrm * r[lag >= 0 ? lag : L + lag].x;
+    }
+}
+
+// one block of 256.  out_d[0..1] = mean, out_d[2] = sum|x|^2, out_d[3..4] = sum i*x.
+// trend_f[4] (optional): mode 1 -> (mean, 0 slope); mode 2 -> least-squares line m + s*i
+// blockIdx.x = signal number (partials / outputs strided accordingly)
+static __global__ __launch_bounds__(256) void k_moments_finish(const double *__restrict__ partial, int nblocks, int64_t n,
+                                                         int mode, double *__restrict__ out_d,
+                                                         float *__restrict__ trend_f) {
+    __shared__ double sh[SP_MOM][256];
+    partial += (int64_t)blockIdx.x * nblocks * 8;
+    if (out_d) out_d += (int64_t)blockIdx.x * 8;
+    if (trend_f) trend_f += (int64_t)blockIdx.x * 4;
+    double s[SP_MOM] = {0, 0, 0, 0, 0};
+    for (int b = threadIdx.x; b < nblocks; b += 256) {
+#pragma unroll
+        for (int j = 0; j < SP_MOM; ++j) s[j] += partial[b * 8 + j];
+    }
+#pragma unroll
+    for (int j = 0; j < SP_MOM; ++j) sh[j][threadIdx.x] = s[j];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+#pragma unroll
+            for (int j = 0; j < SP_MOM; ++j) sh[j][threadIdx.x] += sh[j][threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double N = (double)n;
+        const double mr = sh[0][0] / N, mi = sh[1][0] / N;
+        if (out_d) {
+            out_d[0] = mr;
+            out_d[1] = mi;
+            out_d[2] = sh[2][0];
+            out_d[3] = sh[3][0];
+            out_d[4] = sh[4][0];
+        }
+        if (trend_f) {
+            if (mode == 2 && n > 1) {
+                // least squares on i = 0..n-1:  slope = (sum i x - ibar sum x) / sum (i-ibar)^2
+                const double ibar = 0.5 * (N - 1.0);
+                const double sxx = N * (N * N - 1.0) / 12.0;
+                const double sr = (sh[3][0] - ibar * sh[0][0]) / sxx, si = (sh[4][0] - ibar * sh[1][0]) / sxx;
+                trend_f[0] = (float)(mr - sr * ibar);
+                trend_f[1] = (float)(mi - si * ibar);
+                trend_f[2] = (float)sr;
+                trend_f[3] = (float)si;
+            } else {
+                trend_f[0] = (float)mr;
+                trend_f[1] = (float)mi;
+                trend_f[2] = 0.f;
+                trend_f[3] = 0.f;
+            }
+        }
+    }
+}
+
+// ccf (ccf.py:74-76): both signals' moment records finished by ONE block and the normalisation record [mean1, mean2, 1 / (n std1
+// std2), 0] written behind them -- k_moments_finish x2 + k_xcorr_norm in one launch (two kernel boundaries less per call)
+static __global__ __launch_bounds__(256) void k_moments_finish_xc(const double *__restrict__ partial, int nblocks, int64_t n,
+                                                            double *__restrict__ out_d, double *__restrict__ xc_out) {
+    __shared__ double sh[3][256];
+    double mean[2], ssq[2];
+    for (int sig = 0; sig < 2; ++sig) {
+        const double *pp = partial + (int64_t)sig * nblocks * 8;
+        double s0 = 0, s2 = 0;
+        for (int b = threadIdx.x; b < nblocks; b += 256) {
+            s0 += pp[b * 8 + 0];
+            s2 += pp[b * 8 + 2];
+        }
+        sh[0][threadIdx.x] = s0;
+        sh[2][threadIdx.x] = s2;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if ((int)threadIdx.x < o) {
+                sh[0][threadIdx.x] += sh[0][threadIdx.x + o];
+                sh[2][threadIdx.x] += sh[2][threadIdx.x + o];
+            }
+            __syncthreads();
+        }
+        mean[sig] = sh[0][0] / (double)n;
+        ssq[sig] = sh[2][0];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        for (int sig = 0; sig < 2; ++sig) {
+            out_d[sig * 8 + 0] = mean[sig];
+            out_d[sig * 8 + 1] = 0.0;
+            out_d[sig * 8 + 2] = ssq[sig];
+            out_d[sig * 8 + 3] = 0.0;
+            out_d[sig * 8 + 4] = 0.0;
+        }
+        const double v1 = ssq[0] / (double)n - mean[0] * mean[0], v2 = ssq[1] / (double)n - mean[1] * mean[1];
+        xc_out[0] = mean[0];
+        xc_out[1] = mean[1];
+        xc_out[2] = 1.0 / ((double)n * sqrt(v1 > 0 ? v1 : 0) * sqrt(v2 > 0 ? v2 : 0));
+        xc_out[3] = 0;
+    }
+}
+
 int launch_fft_c2c(LaunchCtx c, const cf *in, cf *out, int64_t batch, int inverse, const Xf &xf, BigTw bt) {
     const int blocks = strided_blocks(xf.L, batch, c.ncu, xf.L == 4096 && !xf.blue ? 12 : 4);
 #define M_(XT)                                                                                        \
@@ -12,62 +300,21 @@ int launch_fft_c2c(LaunchCtx c, const cf *in, cf *out, int64_t batch, int invers
     return 0;
 }
 
-// one workgroup per FPW rows; the grid is padded to a multiple of 8 blocks (surplus blocks exit at once)
-int launch_fft_strided(LaunchCtx c, const cf *in, cf *out, int64_t batch, int64_t in_rs, int64_t in_es, int64_t out_rs,
-                       int64_t out_es, int conj_in, int conj_out, float scale, const Xf &xf, BigTw bt) {
-    if (xf.blue) return -1;
-    const int fpw = fpw_of(xf.L);
-    if (batch % fpw) return -1;
-    int64_t blocks = batch / fpw;
-    blocks = (blocks + 7) / 8 * 8;
-#define M_(XT)                                                                                        \
-    hipLaunchKernelGGL((k_fft_strided<XT::L>), dim3((unsigned)blocks), dim3(XT::C::WG), XT::C::lds_bytes(1), c.stream, in, out, \
-                       batch, in_rs, in_es, out_rs, out_es, conj_in, conj_out, scale, xf.tb, bt, 1);
-    SP_DISPATCH_P(xf, M_)
-#undef M_
-    return 0;
-}
-
-static bool env_cols_noxpair() {
-    const char *e = getenv("SP_COLS_NOXPAIR");     // A/B switch (read per call)
-    return e && e[0] == '1';
-}
-static bool env_cols_nohalf() {
-    const char *e = getenv("SP_COLS_NOHALF");      // A/B switch of the tests (read per call)
-    return e && e[0] == '1';
-}
 // three-pass long transform pieces (power-of-two lengths; ncols is a multiple of the columns per workgroup)
 int launch_fft_cols(LaunchCtx c, const cf *in, cf *out, int64_t ncols, int64_t nouter, int64_t es, int64_t os, int64_t twmul,
                     int conj_in, const Xf &xf, BigTw bt, int64_t hmask_n, ColsIn ci, int tw_outer) {
     if (xf.blue) return -1;
-    int fpw = fpw_of(xf.L);
+    const int fpw = fpw_of(xf.L);
     if (ncols % fpw || nouter < 1) return -1;
-    // first passes on real samples (kind 1 / 3), 256-point columns: 512-thread workgroups that own 32 adjacent columns (WM = 2,
-    // SP_COLS_WIDE=1).  Measured SLOWER than 16 columns (round 3: 70.9 against 63.1 us for the Hilbert's first pass at 2^23 points,
-    // 196.9 against 147.4 for the ccf's at 2^25): one workgroup per CU instead of two, and the twice as long row segments do
-    // not pay for it.  Off by default.
-    static const bool wide_ok = getenv("SP_COLS_WIDE") && getenv("SP_COLS_WIDE")[0] == '1';
-    const bool wide = wide_ok && (ci.kind == 1 || ci.kind == 3) && xf.L == 256 && hmask_n == 0 && ncols % (2 * fpw) == 0;
-    if (wide) fpw *= 2;
     const int64_t ncb = ncols / fpw, total = ncb * nouter;
     // (a multiple of the 2 or 3 workgroups a CU holds, so that the last round is a full one)
-    const int64_t cap = (int64_t)c.ncu * (wide ? 3 : 6);       // several blocks per workgroup amortise its twiddle set-up
+    const int64_t cap = (int64_t)c.ncu * 6;       // several blocks per workgroup amortise its twiddle set-up
     const unsigned grid = (unsigned)(total < cap ? total : cap);
-    if (wide) {
-        using XT = XfPow2<256>;
-        if (ci.kind == 1)
-            hipLaunchKernelGGL((k_fft_cols<256, 1, false, 2>), dim3(grid), dim3(XT::C::WG * 2), XT::C::lds_bytes(1) * 2, c.stream, in, out, ncb,
-                               nouter, es, os, twmul, conj_in, xf.tb, bt, hmask_n, ci, tw_outer);
-        else
-            hipLaunchKernelGGL((k_fft_cols<256, 3, false, 2>), dim3(grid), dim3(XT::C::WG * 2), XT::C::lds_bytes(1) * 2, c.stream, in, out, ncb,
-                               nouter, es, os, twmul, conj_in, xf.tb, bt, hmask_n, ci, tw_outer);
-        return 0;
-    }
     // real samples in (kind 1 / 4: 64-byte pieces per row and array): pair neighbouring column blocks on one XCD
-    if ((ci.kind == 1 || ci.kind == 4) && total % 16 == 0 && grid % 16 == 0 && !env_cols_noxpair()) tw_outer |= 2;
+    if ((ci.kind == 1 || ci.kind == 4) && total % 16 == 0 && grid % 16 == 0) tw_outer |= 2;
     // kind 1 whose samples end exactly at the middle row: the predicate-free form
     const bool half_exact = ci.kind == 1 && ci.r2 && ci.mom && nouter == 1 && xf.L >= 32 && ci.nreal == (int64_t)(xf.L / 2) * es &&
-                            !env_cols_nohalf();
+                            !env_flag("SP_COLS_NOHALF");
 #define M_(XT)                                                                                        \
     if (half_exact) hipLaunchKernelGGL((k_fft_cols<XT::L, 4>), dim3(grid), dim3(XT::C::WG), XT::C::lds_bytes(1), c.stream, in, out, \
                                        ncb, nouter, es, os, twmul, conj_in, xf.tb, bt, hmask_n, ci, tw_outer);       \
@@ -151,7 +398,7 @@ int launch_fft_cols_lag(LaunchCtx c, const cf *in, int64_t ncols, int64_t nouter
     if (ncols % fpw || nouter < 1) return -1;
     const int64_t ncb = ncols / fpw, total = ncb * nouter, cap = (int64_t)c.ncu * 6;
     const unsigned grid = (unsigned)(total < cap ? total : cap);
-    if (total % 16 == 0 && grid % 16 == 0 && !env_cols_noxpair()) ro.kind |= 16;
+    if (total % 16 == 0 && grid % 16 == 0) ro.kind |= 16;
 #define CL_(LL)                                                                                        \
     case LL:                                                                                          \
         hipLaunchKernelGGL((k_fft_cols_lag<LL>), dim3(grid), dim3(WgCfg<LL>::WG), WgCfg<LL>::lds_bytes(1), c.stream, in, ncb, nouter, es, os, \
@@ -173,7 +420,7 @@ int launch_fft_cols_inv(LaunchCtx c, const cf *in, cf *out, int64_t ncols, int64
     const unsigned grid = (unsigned)(total < cap ? total : cap);
     const RowsOut ro = analytic ? *analytic : RowsOut{nullptr, 0, 0, nullptr};
     // the whole row holds samples and pairs are 8-byte aligned: the predicate-free output form
-    const bool full = analytic && ro.n == ro.Ltot && (((uintptr_t)ro.rx) & 7) == 0 && !env_cols_nohalf();
+    const bool full = analytic && ro.n == ro.Ltot && (((uintptr_t)ro.rx) & 7) == 0 && !env_flag("SP_COLS_NOHALF");
 #define CI_(LL)                                                                                        \
     case LL:                                                                                          \
         if (analytic && full) hipLaunchKernelGGL((k_fft_cols_inv<LL, 3>), dim3(grid), dim3(WgCfg<LL>::WG), WgCfg<LL>::lds_bytes(1), c.stream, in, out, \

@@ -15,53 +15,20 @@
 // Reference path: fft_analysis.py:2126-2203 fft_win -> :1946 Pstft -> :1980 averagewins.
 #include "launch.h"
 #include <type_traits>
-// SP_PIPE_ES=1: the 16 scatter stores of a pass leave 4 at a time behind the radix-4 butterfly that produces them
-#ifndef SP_PIPE_ES
-#define SP_PIPE_ES 1
-#endif
-// SP_PIPE_AHEAD: the front role loads the new samples 1 or 2 frames ahead of use
-// SP_PIPE_SPREAD=1 (with SP_PIPE_AHEAD=2): the front role issues its loads in four groups spread over the period.  Defaults 2 / 1:
-// -2 % per bench step (0.570 against 0.583 ms, three interleaved runs); two frames ahead alone changes nothing
-#ifndef SP_PIPE_SPREAD
-#define SP_PIPE_SPREAD 1
-#endif
-// SP_PIPE_NT=1: the front role streams the samples with the non-temporal policy
-#ifndef SP_PIPE_NT
-#define SP_PIPE_NT 1
-#endif
-#ifndef SP_PIPE_TIMING
-#define SP_PIPE_TIMING 0
-#endif
-// SP_PIPE_PRIO=abc: s_setprio of the front / middle / back role (0 = leave the default)
-#ifndef SP_PIPE_PRIO
-#define SP_PIPE_PRIO 0
-#endif
-#ifndef SP_PIPE_AHEAD
+// The 16 scatter stores of a pass leave 4 at a time behind the radix-4 butterfly that produces them.
+// SP_PIPE_AHEAD: the front role loads the new samples 2 frames ahead of use and issues them in four groups spread over the
+// period: -2 % per bench step (0.570 against 0.583 ms, three interleaved runs); two frames ahead alone changes nothing.
+// Issuing the three later groups behind the first-stage butterflies instead (more lead, bunched into the first third of the
+// period) measured SLOWER (0.570 against 0.555 ms, profiles/r03_pipe_ab.txt): what the loads need is even spacing (the CU's
+// miss queue), not more lead (three frames ahead is no faster either).
 #define SP_PIPE_AHEAD 2
-#endif
-// SP_PIPE_WINFOLD=1: the front role folds the window into the first radix-4 stage (dft16s_es_win: 16 VALU less per frame)
-#ifndef SP_PIPE_WINFOLD
-#define SP_PIPE_WINFOLD 1
-#endif
-// SP_PIPE_EARLYSPREAD=1 (with the window fold): the three later groups of the front role's spread loads leave behind the first-stage
-// butterflies instead of behind the last stage's stores: in flight longer before their use -- but bunched into the first third of
-// the period, and measured SLOWER (bench step 0.570 against 0.555 ms, three interleaved warm rounds, profiles/r03_pipe_ab.txt):
-// what the loads need is even spacing (the CU's miss queue), not more lead (three frames ahead is no faster either).  Default off.
-#ifndef SP_PIPE_EARLYSPREAD
-#define SP_PIPE_EARLYSPREAD 0
-#endif
-// SP_PIPE_UPROT=1: the input rotations (1 - i tau) of pass p + 1 are applied by role p to its outputs before the scatter: 30 VALU
-// move from the back role (the longest: 206 VALU + its gather) to the front role (which has slack since the window fold and
-// the lobe sums), the middle role's count stays (it gives 30 and takes 30)
-#ifndef SP_PIPE_UPROT
-#define SP_PIPE_UPROT 1
-#endif
-#ifndef SP_PIPE_RM
-#define SP_PIPE_RM 0          // 1: first exchange image [thread][16] (fft_core.h, WgFft RM): 16-byte scatter writes
-#endif
+// The front role streams the samples with the non-temporal policy and folds the window into the first radix-4 stage
+// (dft16s_es_win: 16 VALU less per frame).
+// The input rotations (1 - i tau) of pass p + 1 are applied by role p to its outputs before the scatter: 30 VALU move from
+// the back role (the longest: 206 VALU + its gather) to the front role (which has slack since the window fold and the lobe
+// sums), the middle role's count stays (it gives 30 and takes 30)
 namespace sp {
 
-#if !SP_PACKED
 template <bool CPLX, int SHIFT, int MODE>      // MODE 0: plain accumulation, 1: one-pass mean detrend, 2: moments per frame (cog),
                                                // 3 / 4: the same as 0 / 1 for real input with two frames per transform
 __global__ __launch_bounds__(768) void k_welch_pipe(const void *__restrict__ x_in, const float *__restrict__ win,
@@ -89,8 +56,8 @@ __global__ __launch_bounds__(768) void k_welch_pipe(const void *__restrict__ x_i
     float *trend = SPEC ? trend_in + 4 * blockIdx.y : trend_in;
     static_assert(!RP || (!CPLX && SHIFT == 8), "the real-pair form is for real input at hop = nfft / 2");
     using PL = FftPlan<N>;
-    using F = WgFft<N, false, SP_PIPE_RM != 0>;
-    constexpr int T = PL::T, R = PL::R, KEEP = R - SHIFT, IMG = F::IMG0, IMGB = SP_PIPE_RM ? N : PL::LDS_ELEMS;
+    using F = WgFft<N>;
+    constexpr int T = PL::T, R = PL::R, KEEP = R - SHIFT, IMG = F::IMG0, IMGB = PL::LDS_ELEMS;
     static_assert(T == 256 && R == 16 && PL::NP == 3, "three radix-16 passes over 256 threads");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     cf *smem = reinterpret_cast<cf *>(smem_raw);
@@ -152,26 +119,11 @@ __global__ __launch_bounds__(768) void k_welch_pipe(const void *__restrict__ x_i
     const int64_t last = nframes - 1;
     int64_t trips = (RP ? (nframes + 1) / 2 : nframes) - g0;
     trips = trips < 0 ? 0 : (trips > fpg ? fpg : trips);
-#if SP_PIPE_TIMING
-    // diagnostic: per role, cycles between leaving a barrier and arriving at the next one (busy) and cycles spent at the barrier
-    unsigned long long t_busy = 0, t_wait = 0, t_issue = 0, t_mark = __builtin_amdgcn_s_memtime();
-#define PIPE_SYNC()                                                                                   \
-    {                                                                                                 \
-        const unsigned long long ta_ = __builtin_amdgcn_s_memtime();                                  \
-        __syncthreads();                                                                              \
-        const unsigned long long tb_ = __builtin_amdgcn_s_memtime();                                  \
-        t_busy += ta_ - t_mark;                                                                       \
-        t_wait += tb_ - ta_;                                                                          \
-        t_mark = tb_;                                                                                 \
-    }
-#else
-#define PIPE_SYNC() __syncthreads()
-#endif
     constexpr int DRAIN = 4;                 // a frame leaves the pipeline 4 periods after it entered
     const int64_t periods = trips + DRAIN;
     F f;
     // (not for the real-pair fronts: three rotating register sets + window leave no room for 16 more constants -- 12-37 spills)
-    constexpr bool UPROT = SP_PIPE_UPROT && !RP && !SP_PIPE_RM && !SP_ABLATE && SP_PIPE_ES;
+    constexpr bool UPROT = !RP;
     float tau_out[16];                       // UPROT: rotations this role applies to its outputs (front: for pass 1, middle: for pass 2)
     if constexpr (UPROT) {
         if (role == 0) f.template load_tau_out<0>(tb.tw, tid, tau_out);
@@ -198,11 +150,7 @@ __global__ __launch_bounds__(768) void k_welch_pipe(const void *__restrict__ x_i
 #pragma unroll
             for (int t = 0; t < R; ++t) {
                 const unsigned off = (unsigned)(tid + T * t);
-#if SP_PIPE_NT
                 dst[t] = __builtin_nontemporal_load((t < R / 2 ? b1 : b2) + off);
-#else
-                dst[t] = (t < R / 2 ? b1 : b2)[off];
-#endif
             }
         };
         float ca[R], cb[R], cc[R];
@@ -220,7 +168,7 @@ __global__ __launch_bounds__(768) void k_welch_pipe(const void *__restrict__ x_i
             __builtin_amdgcn_sched_barrier(0);
             cf v[R];
             // (not with the one-pass block sums: modes 4 / 7 then spill 17-20 registers instead of 2-6)
-            if constexpr (SP_PIPE_WINFOLD && !ONEPASS && !SP_PIPE_RM && !SP_ABLATE) {
+            if constexpr (!ONEPASS) {
 #pragma unroll
                 for (int t = 0; t < R; ++t) v[t] = mk(cur[t], HB ? (t < R / 2 ? cur[t + R / 2] : nxt[t - R / 2]) : 0.f);
                 if constexpr (UPROT) f.bfly_scatter_win_rot(v, w, tau_out, img, tid);
@@ -245,17 +193,17 @@ __global__ __launch_bounds__(768) void k_welch_pipe(const void *__restrict__ x_i
         int64_t i = 0;
         for (; i + 6 < trips; i += 6) {                           // (never the last pair: the tail loop owns it)
             frame(yes, i, imgA, ca, cb, cc);
-            PIPE_SYNC();
+            __syncthreads();
             frame(yes, i + 1, imgA + IMG, cb, cc, ca);
-            PIPE_SYNC();
+            __syncthreads();
             frame(yes, i + 2, imgA, cc, ca, cb);
-            PIPE_SYNC();
+            __syncthreads();
             frame(yes, i + 3, imgA + IMG, ca, cb, cc);
-            PIPE_SYNC();
+            __syncthreads();
             frame(yes, i + 4, imgA, cb, cc, ca);
-            PIPE_SYNC();
+            __syncthreads();
             frame(yes, i + 5, imgA + IMG, cc, ca, cb);
-            PIPE_SYNC();
+            __syncthreads();
         }
         for (; i < trips; ++i) {                                  // i is a multiple of 6 at entry: the rotation state is i % 3
             cf *img = (i & 1) ? imgA + IMG : imgA;
@@ -269,17 +217,16 @@ __global__ __launch_bounds__(768) void k_welch_pipe(const void *__restrict__ x_i
                 else if (i % 3 == 1) frame(no, i, img, cb, cc, ca);
                 else frame(no, i, img, cc, ca, cb);
             }
-            PIPE_SYNC();
+            __syncthreads();
         }
 #pragma unroll
-        for (int d = 0; d < DRAIN; ++d) PIPE_SYNC();
+        for (int d = 0; d < DRAIN; ++d) __syncthreads();
         if constexpr (ONEPASS) {
 #pragma unroll
             for (int s = 0; s < SHIFT; ++s)
                 spartial[((SPEC ? (int64_t)blockIdx.y * gridDim.x : 0) + gid) * hop + tid + T * s] = mk(sacc[s], 0.f);   // SPEC: [channel][run][hop]
         }
     } else if (role == 0) {
-        if constexpr (SP_PIPE_PRIO) __builtin_amdgcn_s_setprio((SP_PIPE_PRIO / 100) % 10);
         // keep the constant in VGPRs (an SGPR source halves the VALU issue rate on gfx950)
         asm volatile("" : "+v"(mu.x), "+v"(mu.y));
         float w[R];
@@ -297,27 +244,17 @@ __global__ __launch_bounds__(768) void k_welch_pipe(const void *__restrict__ x_i
         // slots [s0, s1) of the new samples of frame g0 + q
         auto issue_part = [&](cf (&dst)[SHIFT], int64_t q, int s0, int s1) __attribute__((always_inline)) {
             const int64_t gq = g0 + q;
-            int64_t gn = gq < nframes ? gq : last;
-            if constexpr (SP_ABLATE & 16) gn = (blockIdx.x & 7) + (q & 1);          // diagnostic: every load hits L2
+            const int64_t gn = gq < nframes ? gq : last;
             const int64_t ubase = gn * hop + (int64_t)T * KEEP;
 #pragma unroll
             for (int s = s0; s < s1; ++s) {
                 const unsigned off = (unsigned)(tid + T * s);
-                if constexpr (SP_ABLATE & 8) {          // diagnostic: no global loads in the loop
-                    dst[s] = raw[s] + mu;
-                    continue;
-                }
-#if SP_PIPE_NT
                 if (CPLX) {
                     const sp_f2v r = __builtin_nontemporal_load(reinterpret_cast<const sp_f2v *>(x) + ubase + off);
                     dst[s] = mk(r.x, r.y);
                 } else {
                     dst[s] = mk(__builtin_nontemporal_load(reinterpret_cast<const float *>(x) + ubase + off), 0.f);
                 }
-#else
-                if (CPLX) dst[s] = (reinterpret_cast<const cf *>(x) + ubase)[off];
-                else dst[s] = mk((reinterpret_cast<const float *>(x) + ubase)[off], 0.f);
-#endif
             }
         };
         auto issue = [&](cf (&dst)[SHIFT], int64_t q) __attribute__((always_inline)) { issue_part(dst, q, 0, SHIFT); };
@@ -326,25 +263,17 @@ __global__ __launch_bounds__(768) void k_welch_pipe(const void *__restrict__ x_i
         // (SP_PIPE_AHEAD=3: three frames ahead -- the new slots are then in flight for two full periods before their first use;
         //  with two, the groups issued late in a period (SPREAD) have little more than one, about the loaded HBM latency.
         //  Round 3: not usable as written -- the six-fold unrolled rotation of three register sets compiles to 168 VGPRs with
-        //  47 spilled; kept behind the knob)
+        //  47 spilled)
         constexpr int AHEAD = (SP_PIPE_AHEAD >= 2 && SHIFT <= 8) ? (SP_PIPE_AHEAD >= 3 ? 3 : 2) : 1;
-        constexpr bool SPREAD = SP_PIPE_SPREAD && AHEAD >= 2 && !SP_ABLATE;
+        constexpr bool SPREAD = AHEAD >= 2;
         // one period: loads of frame i + AHEAD go out first and are consumed AHEAD periods later (`fill`); `take` holds the
         // new slots of frame i + 1
         auto frame = [&](int64_t i, cf *img, cf (&fill)[SHIFT], cf (&take)[SHIFT]) __attribute__((always_inline)) {
-#if SP_PIPE_TIMING
-            const unsigned long long ti0_ = __builtin_amdgcn_s_memtime();
-            __builtin_amdgcn_sched_barrier(0);
-#endif
             if constexpr (SPREAD) issue_part(fill, i + AHEAD, 0, SHIFT / 4);
             else issue(fill, i + AHEAD);
             __builtin_amdgcn_sched_barrier(0);          // keep the loads above the arithmetic (hipcc sank them to the barrier)
-#if SP_PIPE_TIMING
-            t_issue += __builtin_amdgcn_s_memtime() - ti0_;
-            __builtin_amdgcn_sched_barrier(0);
-#endif
             cf v[R];
-            constexpr bool WINFOLD = SP_PIPE_WINFOLD && SPREAD && !SP_PIPE_RM;
+            constexpr bool WINFOLD = SPREAD;
 #pragma unroll
             for (int t = 0; t < R; ++t) v[t] = WINFOLD ? raw[t] : w[t] * raw[t];
             if constexpr (SPREAD) {
@@ -353,26 +282,16 @@ __global__ __launch_bounds__(768) void k_welch_pipe(const void *__restrict__ x_i
             // 16 KiB at the top of a period blocks at issue (350 cycles per period measured) while the same loads spread
             // over the period find the queue drained
             {
-                constexpr bool EARLY = SP_PIPE_EARLYSPREAD && WINFOLD;
                 auto store = [&](int k, cf val) __attribute__((always_inline)) {
                     img[F::template phys<0>(tid * 16 + k)] = UPROT ? rot_tan(val, tau_out[k]) : val;
-                    if constexpr (!EARLY)
-                        if (k >= 12 && k < 15) issue_part(fill, i + AHEAD, (k - 11) * (SHIFT / 4), (k - 10) * (SHIFT / 4));
+                    if (k >= 12 && k < 15) issue_part(fill, i + AHEAD, (k - 11) * (SHIFT / 4), (k - 10) * (SHIFT / 4));
                 };
-                auto mid = [&](int b) __attribute__((always_inline)) { issue_part(fill, i + AHEAD, (b + 1) * (SHIFT / 4), (b + 2) * (SHIFT / 4)); };
-                if constexpr (EARLY) dft16s_es_win(v, w, store, mid);
-                else if constexpr (WINFOLD) dft16s_es_win(v, w, store);
+                if constexpr (WINFOLD) dft16s_es_win(v, w, store);
                 else dft16s_es<false>(v, f.t16[0], store);
             }
             } else {
-#if SP_PIPE_ES && !SP_ABLATE
             if constexpr (UPROT) f.template bfly_scatter_rot<0, false>(v, tau_out, img, tid);
             else f.template bfly_scatter<0>(v, img, tid);
-#else
-            f.template bfly<0>(v, tid);
-            if constexpr (!(SP_ABLATE & 2)) f.template scatter<0>(v, img, tid);
-            else asm volatile("" ::"v"(v[0].x), "v"(v[5].y), "v"(v[10].x), "v"(v[15].y));
-#endif
             }
             __builtin_amdgcn_sched_barrier(0);
             // off the critical path of the period: the stores above drain while these issue
@@ -392,83 +311,69 @@ __global__ __launch_bounds__(768) void k_welch_pipe(const void *__restrict__ x_i
             issue(s2, 2);
             for (; i + 2 < trips; i += 3) {            // (image by parity of the period: a scalar select, so that the loop unrolls by 3 only)
                 frame(i, (i & 1) ? imgA + IMG : imgA, s0, s1);
-                PIPE_SYNC();
+                __syncthreads();
                 frame(i + 1, ((i + 1) & 1) ? imgA + IMG : imgA, s1, s2);
-                PIPE_SYNC();
+                __syncthreads();
                 frame(i + 2, ((i + 2) & 1) ? imgA + IMG : imgA, s2, s0);
-                PIPE_SYNC();
+                __syncthreads();
             }
             for (; i < trips; ++i) {                   // i is a multiple of 3 at entry of this tail: rotation state i % 3
                 cf *img = (i & 1) ? imgA + IMG : imgA;
                 if (i % 3 == 0) frame(i, img, s0, s1);
                 else if (i % 3 == 1) frame(i, img, s1, s2);
                 else frame(i, img, s2, s0);
-                PIPE_SYNC();
+                __syncthreads();
             }
         } else if constexpr (AHEAD == 2) {
             cf nxa[SHIFT], nxb[SHIFT];
             issue(nxa, 1);
             for (; i + 1 < trips; i += 2) {
                 frame(i, imgA, nxb, nxa);
-                PIPE_SYNC();
+                __syncthreads();
                 frame(i + 1, imgA + IMG, nxa, nxb);
-                PIPE_SYNC();
+                __syncthreads();
             }
             if (i < trips) {
                 frame(i, imgA, nxb, nxa);
-                PIPE_SYNC();
+                __syncthreads();
             }
         } else {
             for (; i + 1 < trips; i += 2) {
                 cf nx0[SHIFT], nx1[SHIFT];
                 frame(i, imgA, nx0, nx0);
-                PIPE_SYNC();
+                __syncthreads();
                 frame(i + 1, imgA + IMG, nx1, nx1);
-                PIPE_SYNC();
+                __syncthreads();
             }
             if (i < trips) {
                 cf nx0[SHIFT];
                 frame(i, imgA, nx0, nx0);
-                PIPE_SYNC();
+                __syncthreads();
             }
         }
 #pragma unroll
-        for (int d = 0; d < DRAIN; ++d) PIPE_SYNC();
+        for (int d = 0; d < DRAIN; ++d) __syncthreads();
 #pragma unroll
         for (int s = 0; s < SHIFT; ++s)
             if constexpr (ONEPASS && !LOBE) spartial[gid * hop + tid + T * s] = sacc[s];
     } else if (role == 1) {
-        if constexpr (SP_PIPE_PRIO) __builtin_amdgcn_s_setprio((SP_PIPE_PRIO / 10) % 10);
         // period p: the gather of frame p-1 is ISSUED first and lands while the butterflies of frame p-2 (gathered one period
         // earlier into the other register set) run -- no wave starts a period by waiting for the LDS pipe
         f.template load_tw_one<1>(tb.tw, tid);
         cf va[R], vb[R];
         auto step = [&](cf (&fill)[R], cf (&use)[R], int64_t p, const cf *src, cf *dst) __attribute__((always_inline)) {
-            if (p >= 1 && p <= trips) {
-                if constexpr (!(SP_ABLATE & 2)) f.template gather<0>(fill, src, tid);
-                else {
-#pragma unroll
-                    for (int t = 0; t < R; ++t) fill[t] = mk(use[t].y + 1.f, use[t].x);
-                }
-            }
+            if (p >= 1 && p <= trips) f.template gather<0>(fill, src, tid);
             if (p >= 2 && p <= trips + 1) {
-#if SP_PIPE_ES && !SP_ABLATE
                 if constexpr (UPROT) f.template bfly_scatter_rot<1, true>(use, tau_out, dst, tid);
                 else f.template bfly_scatter<1>(use, dst, tid);
-#else
-                f.template bfly<1>(use, tid);
-                if constexpr (!(SP_ABLATE & 2)) f.template scatter<1>(use, dst, tid);
-                else asm volatile("" ::"v"(use[0].x), "v"(use[5].y), "v"(use[10].x), "v"(use[15].y));
-#endif
             }
-            PIPE_SYNC();
+            __syncthreads();
         };
         for (int64_t p = 0; p < periods; p += 2) {
             step(va, vb, p, imgA + IMG, imgB);
             if (p + 1 < periods) step(vb, va, p + 1, imgA, imgB + IMGB);
         }
     } else {
-        if constexpr (SP_PIPE_PRIO) __builtin_amdgcn_s_setprio(SP_PIPE_PRIO % 10);
         f.template load_tw_one<2>(tb.tw, tid);
         float acc[R];
 #pragma unroll
@@ -490,11 +395,7 @@ __global__ __launch_bounds__(768) void k_welch_pipe(const void *__restrict__ x_i
         };
         auto step = [&](cf (&fill)[R], cf (&use)[R], int64_t p, const cf *src) __attribute__((always_inline)) {
             if (p >= 3 && p <= trips + 2) {
-                if constexpr (!(SP_ABLATE & 2)) f.template gather<1>(fill, src, tid);
-                else {
-#pragma unroll
-                    for (int t = 0; t < R; ++t) fill[t] = mk(use[t].y + 1.f, use[t].x);
-                }
+                f.template gather<1>(fill, src, tid);
             }
             if (p >= 4 && p <= trips + 3) {
                 if constexpr (UPROT) f.template bfly_prerot<2>(use, tid);
@@ -551,7 +452,7 @@ __global__ __launch_bounds__(768) void k_welch_pipe(const void *__restrict__ x_i
                     }
                 }
             }
-            PIPE_SYNC();
+            __syncthreads();
         };
         for (int64_t p = 0; p < periods; p += 2) {
             step(va, vb, p, imgB + IMGB);
@@ -567,27 +468,10 @@ __global__ __launch_bounds__(768) void k_welch_pipe(const void *__restrict__ x_i
             }
         }
     }
-#if SP_PIPE_TIMING
-    if ((blockIdx.x == 3 || blockIdx.x == 200) && tid == 0)
-        printf("block %d role %d: busy %llu wait %llu issue %llu cycles over %lld periods\n", (int)blockIdx.x, role, t_busy, t_wait, t_issue, (long long)periods);
-    if (blockIdx.x == 3 && (threadIdx.x & 63) == 0) {
-        // HW_ID (gfx9): wave_id [3:0], simd_id [5:4], pipe_id [7:6], cu_id [11:8], sh_id [12], se_id [15:13]
-        const unsigned hw = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
-        printf("hwid wave %d role %d: simd %u wave_slot %u cu %u se %u\n", (int)(threadIdx.x >> 6), role, (hw >> 4) & 3, hw & 15, (hw >> 8) & 15, (hw >> 13) & 7);
-    }
-#endif
-#undef PIPE_SYNC
 }
-#endif
 
 bool welch_pipe_eligible(const Xf &xf, int hop) {
-#if SP_PACKED
-    (void)xf;
-    (void)hop;
-    return false;
-#else
     return !xf.blue && xf.L == 4096 && (hop == 2048 || hop == 1024 || hop == 4096);
-#endif
 }
 
 // mode 2: `partial` is the cog slot array [4][nframes] of (num, den) pairs (spartial unused); mode 3: real input, two
@@ -596,11 +480,7 @@ bool welch_pipe_eligible(const Xf &xf, int hop) {
 // gpr bin groups per row (k_welch_pipe, SPEC)
 int launch_welch_pipe(LaunchCtx c, const void *x, bool cplx, const float *win, int hop, int64_t nframes, float *trend,
                       const Xf &xf, float *partial, const RunPart &rp, cf *spartial, int mode, int nch, int64_t x_cs, int gpr) {
-#if SP_PACKED
-    return -1;
-#else
-    const size_t lds = SP_PIPE_RM ? sizeof(cf) * 2 * (size_t)(WgFft<4096, false, true>::IMG0 + 4096)
-                                  : sizeof(cf) * 4 * (size_t)FftPlan<4096>::LDS_ELEMS;
+    const size_t lds = sizeof(cf) * 4 * (size_t)FftPlan<4096>::LDS_ELEMS;
 #define PIPE_(CP, S, OP)                                                                                  \
     {                                                                                                 \
         static bool once = false;                                                                     \
@@ -646,7 +526,6 @@ int launch_welch_pipe(LaunchCtx c, const void *x, bool cplx, const float *win, i
 #undef PIPE_S_
 #undef PIPE_
     return 0;
-#endif
 }
 
 }   // namespace sp

@@ -7,6 +7,24 @@
 
 namespace sp {
 
+// Run-time test hooks.  Each forces a live alternative path so that a test can compare two implementations, and each is
+// read on every call (never cached), so that setting or clearing it takes effect at once:
+//   SP_NO_REALPAIR, SP_WELCH_GENERIC, SP_WELCH_TWOPASS, SP_WELCH_PIPE (int: 0 off, 2 for any frame count)
+//   SP_OP_UNFUSED, SP_OP_NOLOBESUM
+//   SP_CSDM_SPLIT3, SP_CSDM_FP32, SP_CSDM_NOPIPESPEC, SP_CSDM_TWOPASS, SP_CSDM_TRANSPOSED
+//   SP_CSD_XIY, SP_CSD_ONEPASS, SP_CSD_TWOPASS
+//   SP_STFT_NOFAST, SP_COG_TWOPASS, SP_COG_GENERIC
+//   SP_HILBERT_NOFUSEMID, SP_HILBERT_PAIRLOAD, SP_COLS_NOHALF, SP_XC_NOFUSEMID, SP_BIGFFT_5PASS
+//   SP_DIST_RESERVE_CUS, SP_DIST_RCCL_CTAS (int: the sharded PSD's CU reserve and the communicator's workgroup limit)
+inline bool env_flag(const char *name) {
+    const char *v = getenv(name);
+    return v && v[0] && v[0] != '0';
+}
+inline int env_int(const char *name, int dflt) {
+    const char *v = getenv(name);
+    return v ? atoi(v) : dflt;
+}
+
 struct LaunchCtx {
     hipStream_t stream;
     int ncu;
@@ -36,25 +54,13 @@ struct RunPart {
 // groups_per_cu: 4 by default = two rounds at the 2 resident workgroups per CU of the 200-VGPR segment kernels.  Measured
 // on the metric shape (bench.py step / kernel, ms): 2 -> 0.651 / 0.607, 4 -> 0.660 / 0.605, 8 -> 0.680 / 0.634,
 // 3 -> 0.73 / 0.685 (one and a half rounds), 6 ~ 8, 12 and 24 worse: longer runs amortise the per-workgroup prologue
-// (twiddle constants, first frame) and halve the partial spectra the epilogue has to sum.  SP_GROUPS_PER_CU overrides it.
-inline int default_groups_per_cu() {
-    static const int v = [] {
-        const char *e = getenv("SP_GROUPS_PER_CU");
-        const int k = e ? atoi(e) : 0;
-        return k > 0 ? k : 4;
-    }();
-    return v;
-}
+// (twiddle constants, first frame) and halve the partial spectra the epilogue has to sum.
 inline RunPart run_partition(int L, int64_t nframes, int ncu, int groups_per_cu = 0) {
-    if (groups_per_cu <= 0) groups_per_cu = default_groups_per_cu();
+    if (groups_per_cu <= 0) groups_per_cu = 4;
     const int fpw = fpw_of(L);
     const int64_t target = (int64_t)ncu * groups_per_cu * fpw;
     int64_t f = (nframes + target - 1) / target;
     if (f < 1) f = 1;
-    if (const char *e = getenv("SP_FPG1")) {              // experiments: frames per group of the one-dimensional partitions
-        const int64_t v = atoll(e);
-        if (v > 0) f = v;
-    }
     const int64_t G = (nframes + f - 1) / f;
     RunPart r;
     r.fpg = f;
@@ -84,10 +90,6 @@ inline RunPart run_partition_2d(int L, int64_t nframes, int ncu, int ny, int64_t
             if (f2 >= 1 && f2 <= 4 * f) f = f2;
         }
     }
-    if (const char *e = getenv("SP_FPG")) {               // experiments: frames per group
-        const int64_t v = atoll(e);
-        if (v > 0) f = v;
-    }
     const int64_t G = (nframes + f - 1) / f;
     RunPart r;
     r.fpg = f;
@@ -97,22 +99,18 @@ inline RunPart run_partition_2d(int L, int64_t nframes, int ncu, int ny, int64_t
 }
 // grid of the row kernels (FFT rows, Hilbert rows, FIR block pairs): every workgroup pays a prologue (twiddle constants with
 // 30 divisions per twiddled pass) before its first row, so few, long-lived workgroups win for the long transforms -- measured
-// (tools/capsweep.py, ms): 4096 rows of 4096: 0.088 at 16 blocks per CU, 0.062 at 4, 0.055 at 2; 65536 rows: 0.825 / 0.790 /
+// (ms): 4096 rows of 4096: 0.088 at 16 blocks per CU, 0.062 at 4, 0.055 at 2; 65536 rows: 0.825 / 0.790 /
 // 0.823; 8192 points: 0.245 / 0.170 / 0.160; 2048 points: 4 per CU wins for 4096 rows (0.039 vs 0.050), 16 for 65536 rows
 // (0.394 vs 0.413); <= 1024 points: no difference.  Rule: 4 per CU from 4096 points up; at 2048 points at least 4 rows per
-// workgroup (not below 2 per CU); 16 per CU otherwise.  SP_STRIDED_CAP overrides it.
+// workgroup (not below 2 per CU); 16 per CU otherwise.
 // per_cu: the cap for L >= 4096 in workgroups per CU -- a multiple of what the kernel keeps resident per CU, so that the last
 // round of workgroups is a full one (round 3: k_fft_c2c<4096> holds 3 per CU; 4 per CU = 1024 workgroups ran 768 + a 256 tail:
 // 0.88 against 0.79 ms at 12 per CU for 65536 rows; the batched Hilbert, 4 rows per workgroup at 4096 rows: 0.065 -> 0.060 at 3)
 inline int strided_blocks(int L, int64_t items, int ncu, int per_cu = 4) {
-    static const int forced = [] {
-        const char *e = getenv("SP_STRIDED_CAP");
-        return e ? atoi(e) : 0;
-    }();
     const int fpw = fpw_of(L);
     int64_t b = (items + fpw - 1) / fpw;
-    int64_t cap = (int64_t)ncu * (forced > 0 ? forced : (L >= 4096 ? per_cu : 16));
-    if (forced <= 0 && L == 2048) {
+    int64_t cap = (int64_t)ncu * (L >= 4096 ? per_cu : 16);
+    if (L == 2048) {
         const int64_t q = b / 4;
         if (q < cap) cap = q > (int64_t)ncu * 2 ? q : (int64_t)ncu * 2;
     }
@@ -132,8 +130,6 @@ int stft_rp_groups_per_cu(const Xf &xf, bool lin, int hop, int sided, int out_po
 // every launcher returns 0 or -1 (unsupported L); kernel launch errors surface through hipGetLastError
 int launch_fft_c2c(LaunchCtx c, const cf *in, cf *out, int64_t batch, int inverse, const Xf &xf,
                    BigTw bt = BigTw{nullptr, nullptr, 0, 0});
-int launch_fft_strided(LaunchCtx c, const cf *in, cf *out, int64_t batch, int64_t in_rs, int64_t in_es, int64_t out_rs,
-                       int64_t out_es, int conj_in, int conj_out, float scale, const Xf &xf, BigTw bt);
 int launch_fft_cols(LaunchCtx c, const cf *in, cf *out, int64_t ncols, int64_t nouter, int64_t es, int64_t os, int64_t twmul,
                     int conj_in, const Xf &xf, BigTw bt, int64_t hmask_n = 0,
                     ColsIn ci = ColsIn{0, nullptr, nullptr, nullptr, 0}, int tw_outer = 0);
@@ -204,9 +200,7 @@ int launch_csd_pair_finish(LaunchCtx c, const float *partial, int64_t G, const X
                            const float *trend_x = nullptr, const float *trend_y = nullptr, int64_t nmean = 0, int64_t M = 0);
 #define SP_COLSUM_SLICES 256
 int launch_colsum_real(LaunchCtx c, const float *x, const float *trend, int H, int64_t M, cf *out);
-int launch_csdm_transpose(LaunchCtx c, const cf *Xs, cf *Xt, int nch, int64_t mc, int nb);
-int launch_csdm_gemm(LaunchCtx c, const cf *Xt, int nch, int64_t mc, int nb, double *G);
-int launch_csdm_finish(LaunchCtx c, double *G, int nch, int nb, double scale, int blk);
+int launch_csdm_finish(LaunchCtx c, double *G, int nch, int nb, double scale);
 int launch_csdm_transpose_kgc(LaunchCtx c, const cf *Xs, cf *Xt, int nch, int nchp, int64_t m, int64_t mp, int nb);
 int launch_csdm_mfma(LaunchCtx c, const cf *Xt, int nch, int nchp, int64_t mp, int nb, double *G);
 int launch_csdm_bf16(LaunchCtx c, const cf *Xs, cf *Xt_tail, int nch, int64_t m, int nb, double *G, int ld, int two_pieces = 0, int init = 0);

@@ -384,11 +384,6 @@ int nbins_host(int n, int sided) {
     return n;
 }
 
-bool env_flag(const char *name) {
-    const char *v = getenv(name);
-    return v && v[0] && v[0] != '0';
-}
-
 
 // ---- transforms longer than one workgroup ---------------------------------------------------------
 bool wg_capable(int64_t n) {
@@ -434,7 +429,7 @@ int get_bigtw(int64_t N, BigTw *bt) {
 // transpose, N1 row FFTs of N2, transpose back to natural order.  5 passes over the data (80 B / point).
 // three-pass form available for N (then hmask may be fused into the first pass of an inverse transform)
 bool big_three_pass(int64_t N) {
-    return is_pow2(N) && N >= ((int64_t)1 << 20) && !env_flag("SP_BIGFFT_5PASS") && !env_flag("SP_BIGFFT_2PASS");
+    return is_pow2(N) && N >= ((int64_t)1 << 20) && !env_flag("SP_BIGFFT_5PASS");
 }
 
 // fused first-pass input / last-pass output of ONE three-pass transform (see ColsIn / RowsOut in kernels.h)
@@ -481,20 +476,6 @@ int dev_fft_big_pow2(const cf *in, cf *out, int64_t N, int inverse, int hmask = 
             LAUNCHCHK(launch_fft_cols(lc(), in + b * N, tmp, B * C, 1, B * C, 0, 1, inverse, xa, bt, hmask ? N : 0));
             LAUNCHCHK(launch_fft_cols(lc(), tmp, tmp, C, A, C, B * C, A, 0, xb, bt));
             LAUNCHCHK(launch_fft_rows_rev(lc(), tmp, out + b * N, A, B, inverse, sc, xc));
-        }
-        return 0;
-    }
-    if (env_flag("SP_BIGFFT_2PASS") && N1 >= 16 && N2 >= 16) {
-        // experiment, off by default (measured 0.90-1.19 ms against 0.83 for a 2^24-point Hilbert: the column reads run at
-        // 1.3 TB/s even with XCD-local adjacent columns).  Two strided passes, no explicit transposes (x viewed as
-        // [N1][N2], n = n1 N2 + n2):
-        //   A: for every column n2: FFT over n1, times W_N^{n2 k1}  -> tmp[n2][k1]            (column read, row write)
-        //   B: for every column k1 of tmp: FFT over n2               -> out[k1 + N1 k2]       (column read, column write)
-        if (g.bigT.ensure(sizeof(cf) * (size_t)N)) return -1;
-        cf *tmp = (cf *)g.bigT.p;
-        for (int64_t b = 0; b < batch; ++b) {
-            LAUNCHCHK(launch_fft_strided(lc(), in + b * N, tmp, N2, 1, N2, N1, 1, inverse, 0, 1.f, x1, bt));
-            LAUNCHCHK(launch_fft_strided(lc(), tmp, out + b * N, N1, 1, N1, 1, N1, 0, inverse, sc, x2, BigTw{nullptr, nullptr, 0, 0}));
         }
         return 0;
     }
@@ -639,31 +620,14 @@ int get_window_spectrum(const float *win, int nfft, const Xf &xf, void **Wf_d) {
 
 // the nfft-4096 Welch shapes run as a pipeline of specialised waves (k_welch_pipe.hip): one 768-thread workgroup per CU.
 // The pipeline spends 4 periods per workgroup filling and draining; the symmetric kernel takes ~4 periods per frame and workgroup at
-// two workgroups per CU, so the pipeline wins from 2 frames per CU on (round 3, tools/minfpc_ab.sh, step / kernel ms: 2^24 samples
+// two workgroups per CU, so the pipeline wins from 2 frames per CU on (round 3, step / kernel ms: 2^24 samples
 // 0.054 / 0.045 against 0.071 / 0.060, 2^22: 0.045 / 0.024 against 0.062 / 0.036, 2^20: 0.038 / 0.019 against 0.053 / 0.020; the
-// threshold had been 32 per CU, which sent every shard below 2^25 samples to the symmetric kernel).  SP_PIPE_MINFPC sets the
-// threshold; SP_WELCH_PIPE=0 turns the pipeline off, 2 forces it for any frame count (the tests' way to reach its tail handling).
-#ifndef SP_PIPE_MINFPC_DEFAULT
+// threshold had been 32 per CU, which sent every shard below 2^25 samples to the symmetric kernel).  SP_WELCH_PIPE=0 turns the
+// pipeline off, 2 forces it for any frame count (the tests' way to reach its tail handling).
 #define SP_PIPE_MINFPC_DEFAULT 2
-#endif
-static int welch_pipe_gpc() {
-    static const int v = [] {
-        const char *e = getenv("SP_PIPE_GPC");
-        const int k = e ? atoi(e) : 0;
-        return k > 0 ? k : 1;
-    }();
-    return v;
-}
-static int welch_pipe_mode() {
-    static const int mode = [] {
-        const char *e = getenv("SP_WELCH_PIPE");
-        return e ? atoi(e) : SP_WELCH_PIPE_DEFAULT;
-    }();
-    return mode;
-}
 static bool welch_pipe_wanted(const Xf &xf, int hop, int64_t nframes) {
-    const int mode = welch_pipe_mode();
-    static const int64_t minfpc = getenv("SP_PIPE_MINFPC") ? atoll(getenv("SP_PIPE_MINFPC")) : SP_PIPE_MINFPC_DEFAULT;   // frames per CU
+    const int mode = env_int("SP_WELCH_PIPE", 1);
+    const int64_t minfpc = SP_PIPE_MINFPC_DEFAULT;   // frames per CU
     return welch_pipe_eligible(xf, hop) && (mode >= 2 || (mode == 1 && nframes >= minfpc * (int64_t)g.ncu - minfpc));
 }
 
@@ -766,15 +730,10 @@ unsigned *get_ticket(Scratch &t) {
 }
 // streaming engine (sp_welch_dist_*): a scratch set of its own per step parity, and the epilogue launched on another stream
 // behind an event recorded after the main kernel -- so that it runs beside the NEXT step's main kernel
-// main / ev_in (optional): the main kernel goes to a lane of the engine's own instead of the launch stream, ordered behind an event
-// recorded on the launch stream just before it -- so that the NEXT step's main kernel (other lane) backfills the CUs as this
-// one's workgroups retire instead of waiting behind its last one
 struct SplitLaunch {
     Scratch *work, *onepass, *trend, *ticket;
     hipStream_t epi;
     hipEvent_t ev_main;
-    hipStream_t main = nullptr;
-    hipEvent_t ev_in = nullptr;
     int reserve_cus = 0;       // CUs left to the collective's kernel: the main kernel is partitioned over ncu - reserve_cus
 };
 
@@ -807,10 +766,10 @@ int welch_accum_locked(const void *xd, bool cplx, int64_t nsig, const float *win
     // (not at hop = nfft: the one-pass front role with 16 new samples per thread and their block sums spills 20 registers and
     //  runs at half the symmetric kernel's rate, 1.00 against 0.50 ms at 2^28 samples; the plain mode is faster there, 0.40 / 0.44)
     //  (SP_WELCH_PIPE=2 still forces it: tests/test_gpu_pipe.py keeps the instantiation correct)
-    const bool pipe = realpair || ((hop != nfft || welch_pipe_mode() >= 2) && welch_pipe_wanted(xf, hop, nframes));
+    const bool pipe = realpair || ((hop != nfft || env_int("SP_WELCH_PIPE", 1) >= 2) && welch_pipe_wanted(xf, hop, nframes));
     const int ncu_p = (sl && sl->reserve_cus > 0 && sl->reserve_cus < g.ncu) ? g.ncu - sl->reserve_cus : g.ncu;   // (pipeline: one workgroup per CU)
-    const RunPart rp = realpair ? run_partition(xf.L, (nframes + 1) / 2, ncu_p, welch_pipe_gpc())
-                                : (pipe ? run_partition(xf.L, nframes, ncu_p, welch_pipe_gpc()) : run_partition(xf.L, nframes, g.ncu));
+    const RunPart rp = realpair ? run_partition(xf.L, (nframes + 1) / 2, ncu_p, 1)
+                                : (pipe ? run_partition(xf.L, nframes, ncu_p, 1) : run_partition(xf.L, nframes, g.ncu));
     if (S_work.ensure(sizeof(float) * (size_t)rp.groups * xf.L)) return -1;
     const size_t sp_bytes = sizeof(cf) * (size_t)rp.groups * (size_t)hop;
     const size_t st_doubles = (size_t)nfft + 2 * (size_t)hop + 8;
@@ -829,11 +788,7 @@ int welch_accum_locked(const void *xd, bool cplx, int64_t nsig, const float *win
     float *partial = (float *)S_work.p;
     double *est = moments_scratch();
     if (!est) return -1;
-#if !SP_EST_IN_KERNEL
-    if (!pipe) LAUNCHCHK(launch_op_estimate(lc(), xd, cplx, nsig, est, tb.f));
-#else
     (void)est;                       // the main kernel estimates mu0 itself and publishes it in tb.f
-#endif
     st.sym = realpair ? 1 : 0;
     // mode 9 of the pipeline kernel: the window's lobe bins of sum_g X_g accumulated by the BACK role (4 VALU per frame) instead of
     // the front role's block sums (16), for cosine-sum windows that are COLA at this hop and the one-launch epilogue (SP_OP_NOLOBESUM=1
@@ -843,15 +798,9 @@ int welch_accum_locked(const void *xd, bool cplx, int64_t nsig, const float *win
     const bool fused_ok = fo && !want_sum && !env_flag("SP_OP_UNFUSED") && cog_window_lobe(win, nfft, &lobe);
     const bool lobesum = fused_ok && pipe && !realpair && hop != nfft && !env_flag("SP_OP_NOLOBESUM") && window_cola(win, nfft, hop, &cola_c);
     if (!lobesum) cola_c = 0.0;
-    // the main kernel's stream: the launch stream, or the engine's lane behind everything enqueued on the launch stream so far
-    // (the caller's producer of x, the table uploads above, the wait for the epilogue that last used this scratch set)
-    const LaunchCtx mc = (sl && sl->main) ? LaunchCtx{sl->main, g.ncu} : lc();
-    if (sl && sl->main) {
-        HIPCHK(hipEventRecord(sl->ev_in, g.stream));
-        HIPCHK(hipStreamWaitEvent(sl->main, sl->ev_in, 0));
-    }
+    const LaunchCtx mc = lc();
     // (streaming engine: the main kernel's event as the launch's own completion signal, not a record behind it)
-    const bool stop_ev = sl && pipe && !g.profile && !env_flag("SP_DIST_RECORD_EVENT");
+    const bool stop_ev = sl && pipe && !g.profile;
     if (pipe) {
         ProfScope ps(mc.stream);
         LaunchCtx mcs = mc;
@@ -878,7 +827,7 @@ int welch_accum_locked(const void *xd, bool cplx, int64_t nsig, const float *win
         if (fo->prev.st && fo->prev_wait) HIPCHK(hipStreamWaitEvent(ec.stream, fo->prev_wait, 0));
         LAUNCHCHK(launch_op_fused(ec, xd, cplx, tb.f, (const float *)win_d, partial, spartial, rp.groups, nfft, hop, nframes, nmean,
                                   st, ticket, lobe, nullptr, fo->sided, fo->scale, fo->out, fo->export_state, fo->prev,
-                                  sl != nullptr && !env_flag("SP_OPF_HEAVY"), cola_c));
+                                  sl != nullptr, cola_c));
         fo->done = true;
         fo->prev_done = fo->prev.st != nullptr;
         g_pend.valid = false;
@@ -966,13 +915,12 @@ struct Comm {
 // runs beside the main kernel like the light epilogue does.  SP_DIST_RESERVE_CUS overrides the number of CUs left free (also for
 // one rank, which is how the one-GPU tests reach the path), 0 turns it off.
 static int dist_rccl_ctas() {
-    const char *e = getenv("SP_DIST_RCCL_CTAS");
-    const int v = e ? atoi(e) : 4;
+    const int v = env_int("SP_DIST_RCCL_CTAS", 4);
     return v < 0 ? 0 : (v > 64 ? 64 : v);
 }
 static int dist_reserved_cus() {
-    if (const char *e = getenv("SP_DIST_RESERVE_CUS")) {
-        const int v = atoi(e);
+    if (getenv("SP_DIST_RESERVE_CUS")) {
+        const int v = env_int("SP_DIST_RESERVE_CUS", 0);
         return v < 0 ? 0 : (v > g.ncu / 2 ? g.ncu / 2 : v);
     }
     // (twice the workgroup limit, at least 8: a limit RCCL rounds up must still find room; 8 CUs cost 1.2-1.5 % of the main
@@ -991,12 +939,7 @@ static int dist_reserved_cus() {
 // kernels from two streams share the CUs when the first leaves registers and wave slots free; the main kernel takes 408 of a
 // SIMD's 512 VGPRs and 12 of a CU's 32 wave slots).  Only then does A wait for the PREVIOUS step's epilogue event -- which is
 // what makes that step's (without communicator) or the step before's (with) output valid for the caller, in stream order.
-// Round 3, later (opt-in, SP_DIST_TWO_LANES=1): the main kernels themselves go to two lanes of the engine's own (even / odd steps),
-// each behind an event recorded on A just before (A's history = the caller's producer of x + the waits for the epilogues that free
-// the scratch set): consecutive main kernels are then independent in the eyes of the hardware, and step k + 1's workgroups take
-// the CUs as step k's retire.  Measured +0.8 % per step -- and NOT the default: two main kernels that share the chip have no
-// duration of their own any more (rocprofv3 --kernel-trace reads 0.99 ms per launch instead of 0.54), which is what bench.py's
-// roofline figure and its rocprof cross-check are built on.  x must stay valid until the step is reported.
+// x must stay valid until the step is reported.
 struct EngineSlot {
     bool busy = false;
     std::vector<float> win;
@@ -1007,8 +950,7 @@ struct EngineSlot {
 };
 struct Engine {
     hipStream_t epi = nullptr;
-    hipStream_t lane[2] = {nullptr, nullptr};          // SP_DIST_TWO_LANES=1: main kernels of even / odd steps (default: the launch stream)
-    hipEvent_t ev_main[2] = {nullptr, nullptr}, ev_epi[2] = {nullptr, nullptr}, ev_in[2] = {nullptr, nullptr};
+    hipEvent_t ev_main[2] = {nullptr, nullptr}, ev_epi[2] = {nullptr, nullptr};
     Scratch work[2], onepass[2], trend[2], ticket[2], st[2];
     EngineSlot slot[2];
     int64_t nsub = 0;            // submits since the last flush
@@ -1019,10 +961,8 @@ int engine_init() {
     if (geng.epi) return 0;
     HIPCHK(hipStreamCreateWithFlags(&geng.epi, hipStreamNonBlocking));
     for (int i = 0; i < 2; ++i) {
-        HIPCHK(hipStreamCreateWithFlags(&geng.lane[i], hipStreamNonBlocking));
         HIPCHK(hipEventCreateWithFlags(&geng.ev_main[i], hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&geng.ev_epi[i], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&geng.ev_in[i], hipEventDisableTiming));
     }
     return 0;
 }
@@ -1030,15 +970,9 @@ void engine_release() {
     if (!geng.epi) return;
     (void)hipStreamSynchronize(geng.epi);
     for (int i = 0; i < 2; ++i) {
-        if (geng.lane[i]) {
-            (void)hipStreamSynchronize(geng.lane[i]);
-            (void)hipStreamDestroy(geng.lane[i]);
-            geng.lane[i] = nullptr;
-        }
         (void)hipEventDestroy(geng.ev_main[i]);
         (void)hipEventDestroy(geng.ev_epi[i]);
-        if (geng.ev_in[i]) (void)hipEventDestroy(geng.ev_in[i]);
-        geng.ev_main[i] = geng.ev_epi[i] = geng.ev_in[i] = nullptr;
+        geng.ev_main[i] = geng.ev_epi[i] = nullptr;
         geng.work[i].release();
         geng.onepass[i].release();
         geng.trend[i].release();
@@ -1333,10 +1267,10 @@ int sp_welch_psd(const void *x, int x_dtype, int64_t nsig, const float *win, int
         const bool pair = !cplx && nframes >= 2 && !segmean && !env_flag("SP_NO_REALPAIR");
         const bool pipe = !pair && !segmean && detrend != 2 && allow_carry && welch_pipe_wanted(xf, hop, nframes);
         const bool pipe_rp = pair && detrend != 2 && allow_carry && 2 * hop == nfft && welch_pipe_wanted(xf, hop, (nframes + 1) / 2);
-        const RunPart rp = pipe_rp ? run_partition(xf.L, (nframes + 1) / 2, g.ncu, welch_pipe_gpc())
-                                   : (pipe ? run_partition(xf.L, nframes, g.ncu, welch_pipe_gpc())
+        const RunPart rp = pipe_rp ? run_partition(xf.L, (nframes + 1) / 2, g.ncu, 1)
+                                   : (pipe ? run_partition(xf.L, nframes, g.ncu, 1)
                                            : (pair ? run_partition(xf.L, (nframes + 1) / 2, g.ncu,
-                                                                   getenv("SP_GROUPS_PER_CU") ? 0 : welch_rp_groups_per_cu(xf, detrend == 2))
+                                                                   welch_rp_groups_per_cu(xf, detrend == 2))
                                                    : run_partition(xf.L, nframes, g.ncu)));
         if (g.work.ensure(sizeof(float) * (size_t)rp.groups * xf.L)) return -1;
         float *partial = (float *)g.work.p;
@@ -1562,10 +1496,6 @@ int sp_welch_dist_submit(const void *x, int x_dtype, int64_t nsig, const float *
     EngineSlot &cur = geng.slot[s], &prv = geng.slot[o];
     SplitLaunch sl{&geng.work[s], &geng.onepass[s], &geng.trend[s], &geng.ticket[s], geng.epi, geng.ev_main[s]};
     sl.reserve_cus = comm ? dist_reserved_cus() : 0;
-    if (env_flag("SP_DIST_TWO_LANES")) {          // opt-in (see the engine's comment): overlapping main kernels have no duration of their own
-        sl.main = geng.lane[s];
-        sl.ev_in = geng.ev_in[s];
-    }
     const LaunchCtx ec{geng.epi, g.ncu};
     if (comm) {
         const size_t nst = 5 * (size_t)nfft + 8;
@@ -1574,7 +1504,7 @@ int sp_welch_dist_submit(const void *x, int x_dtype, int64_t nsig, const float *
         // the launch that finishes THIS step's state also applies the previous step's all-reduced state (same transform length;
         // B-ordered behind that step's collective) -- otherwise a k_op_apply launch of its own, on B as well
         OpPrev prev{nullptr, nullptr, nullptr, 0, 0.0};
-        if (prv.busy && (int)prv.win.size() == nfft && !env_flag("SP_DIST_SEPARATE_APPLY")) {
+        if (prv.busy && (int)prv.win.size() == nfft) {
             Xf xfo;
             if (get_xf(nfft, &xfo)) return -1;
             void *Wf_o;
@@ -1876,15 +1806,10 @@ static int csd_matrix_impl(const char *who, const float *x, int nch, int64_t nsi
         const int64_t lm = long_chunk_frames(nfft, nframes);
         if (mc > lm) mc = lm;
     }
-    if (const char *e = getenv("SP_CSDM_CHUNK")) {               // experiment: frames per chunk (a multiple of 32)
-        const int64_t v = atoll(e) & ~(int64_t)31;
-        if (v >= 32 && v < mc) mc = v;
-    }
     if (mc > nframes) mc = nframes;
-    // contraction on the matrix cores: fused form reading the STFT output as it lies (default), the form with a
-    // transposed copy (SP_CSDM_TRANSPOSED=1), or the VALU kernel (SP_CSDM_VALU=1); the last two are kept for A/B tests
-    const bool use_mfma = !env_flag("SP_CSDM_VALU");
-    const bool use_fused = use_mfma && nch <= 64 && !env_flag("SP_CSDM_TRANSPOSED");   // off-diagonal superblocks need 128 accumulators
+    // contraction on the matrix cores: fused form reading the STFT output as it lies (default), or the form with a
+    // transposed copy (more than 64 channels, or SP_CSDM_TRANSPOSED=1 for the tests)
+    const bool use_fused = nch <= 64 && !env_flag("SP_CSDM_TRANSPOSED");   // off-diagonal superblocks need 128 accumulators
     const int nchp = (nch + 63) / 64 * 64;                       // MFMA layout: channels padded to whole 64-superblocks,
     const int64_t mcp = (mc + 31) / 32 * 32;                     // frames to a multiple of 32 (zero filled)
     // fused path: every (channel, frame) row of the spectra starts on a 128-byte line (row pitch padded to a multiple of 16
@@ -1895,20 +1820,18 @@ static int csd_matrix_impl(const char *who, const float *x, int nch, int64_t nsi
     const bool use_bf16 = use_fused && rp_stft && !env_flag("SP_CSDM_FP32");
     // two bf16 pieces per operand (16 bits, k_csdm_bf16<4>: 10 MFMAs per two frame pairs instead of 16) from 1024 frame pairs
     // on: there the float32 accumulation bounds the accuracy of both forms alike (1.6e-6 of the peak at 2049 frames against
-    // the float64 oracle, tools/split2_ab.py) and the operand rounding (rms 2^-17/sqrt 3 per value, zero mean) averages to
-    // <= 2e-7.  SP_CSDM_SPLIT3=1: three pieces always; SP_CSDM_SPLIT2=1: two pieces always
-    const int split2 = env_flag("SP_CSDM_SPLIT2") ? 1 : (env_flag("SP_CSDM_SPLIT3") ? 0 : ((nframes + 1) / 2 >= 1024 ? 1 : 0));
-    const int ld = use_bf16 ? (nb + 7) / 8 * 8
-                            : ((use_fused && (rp_stft || lng) && !env_flag("SP_CSDM_NOPAD")) ? (nb + 15) / 16 * 16 : nb);
+    // the float64 oracle) and the operand rounding (rms 2^-17/sqrt 3 per value, zero mean) averages to <= 2e-7.
+    // SP_CSDM_SPLIT3=1: three pieces always
+    const int split2 = env_flag("SP_CSDM_SPLIT3") ? 0 : ((nframes + 1) / 2 >= 1024 ? 1 : 0);
+    const int ld = use_bf16 ? (nb + 7) / 8 * 8 : ((use_fused && (rp_stft || lng)) ? (nb + 15) / 16 * 16 : nb);
     const size_t sbytes = use_bf16 ? sizeof(cf) * 2 * (size_t)64 * (size_t)((mc + 1) / 2) * (size_t)ld       // 64 channel slots
                                    : sizeof(cf) * (size_t)nch * (size_t)mc * (size_t)ld;
-    const size_t tbytes = use_fused ? sizeof(cf) * (size_t)nchp * (size_t)mcp * 16
-                                    : (use_mfma ? sizeof(cf) * (size_t)nchp * (size_t)mcp * (size_t)nb : sbytes);
+    const size_t tbytes = sizeof(cf) * (size_t)nchp * (size_t)mcp * (use_fused ? 16 : (size_t)nb);
     if (g.cmS.ensure(sbytes) || g.cmT.ensure(tbytes)) return -1;
     cf *Xs = (cf *)g.cmS.p, *Xt = (cf *)g.cmT.p;
     // nfft 4096 at 50 % overlap: spectra by the pipeline of specialised waves (see below); m = frames of a chunk
     auto pipe_spec = [&](int64_t m) {
-        static const int64_t minp = getenv("SP_CSDM_MINPAIRS") ? atoll(getenv("SP_CSDM_MINPAIRS")) : 32;    // pairs per run
+        const int64_t minp = 32;    // pairs per run
         return use_bf16 && nfft == 4096 && 2 * hop == nfft && detrend != 2 && (m + 1) / 2 >= minp * (int64_t)((g.ncu + nch - 1) / nch) &&
                welch_pipe_wanted(xf, hop, (int64_t)1 << 40) && !env_flag("SP_CSDM_NOPIPESPEC");
     };
@@ -1988,9 +1911,8 @@ static int csd_matrix_impl(const char *who, const float *x, int nch, int64_t nsi
         } else if (rp_stft && (m >= 2 || ld != nb)) {
             // all channels in one grid, two real frames per transform
             // (channels x groups) workgroups: about 8 per CU in all, so that each amortises its twiddle prologue over a long
-            // run of frame pairs (256 groups per channel = 16 pairs per workgroup paid ~9 % for it); SP_STFT_GPC=1: old rule
-            const RunPart rp = env_flag("SP_STFT_GPC") ? run_partition(xf.L, (m + 1) / 2, g.ncu, 1)
-                                                       : run_partition_2d(xf.L, (m + 1) / 2, g.ncu, nch);
+            // run of frame pairs (256 groups per channel = 16 pairs per workgroup paid ~9 % for it)
+            const RunPart rp = run_partition_2d(xf.L, (m + 1) / 2, g.ncu, nch);
             LAUNCHCHK(launch_stft_rp(lc(), xd + (size_t)f0 * (size_t)hop, (const float *)win_d, hop, m, tb.f + 4 * nch,
                                      detrend == 2, xf, rp, SP_SIDED_HALF, 1.f, 0, Xs, nullptr, nch, x_ld,
                                      (int64_t)m * ld, ld));
@@ -2009,13 +1931,10 @@ static int csd_matrix_impl(const char *who, const float *x, int nch, int64_t nsi
             LAUNCHCHK(launch_csdm_bf16(lc(), Xs, Xt, nch, m, nb, G, ld, split2));
         } else if (use_fused) {
             LAUNCHCHK(launch_csdm_fused(lc(), Xs, Xt, nch, m, nb, G, ld));
-        } else if (use_mfma) {
-            const int64_t mp = (m + 31) / 32 * 32;
-            LAUNCHCHK(launch_csdm_transpose_kgc(lc(), Xs, Xt, nch, nchp, m, mp, nb));   // (these two forms: ld == nb)
-            LAUNCHCHK(launch_csdm_mfma(lc(), Xt, nch, nchp, mp, nb, G));
         } else {
-            LAUNCHCHK(launch_csdm_transpose(lc(), Xs, Xt, nch, m, nb));
-            LAUNCHCHK(launch_csdm_gemm(lc(), Xt, nch, m, nb, G));
+            const int64_t mp = (m + 31) / 32 * 32;
+            LAUNCHCHK(launch_csdm_transpose_kgc(lc(), Xs, Xt, nch, nchp, m, mp, nb));   // (this form: ld == nb)
+            LAUNCHCHK(launch_csdm_mfma(lc(), Xt, nch, nchp, mp, nb, G));
         }
     }
     const double gscale = scale / (double)nframes;
@@ -2032,7 +1951,7 @@ static int csd_matrix_impl(const char *who, const float *x, int nch, int64_t nsi
     } else if (fold_pending) {
         LAUNCHCHK(launch_csdm_fold(lc(), (const double *)g.cmH.p, G, nch, nfft, nullptr, nullptr, nullptr, 0, 0, gscale, fold_init));
     }
-    if (!fold_init) LAUNCHCHK(launch_csdm_finish(lc(), G, nch, nb, gscale, use_mfma ? 32 : SP_CM_B));
+    if (!fold_init) LAUNCHCHK(launch_csdm_finish(lc(), G, nch, nb, gscale));
     if (!mem) {
         HIPCHK(hipMemcpyAsync(g_out, G, gbytes, hipMemcpyDeviceToHost, g.stream));
         HIPCHK(hipStreamSynchronize(g.stream));
@@ -2217,7 +2136,7 @@ int sp_stft_cog(const void *x, int x_dtype, int64_t nsig, const float *win, int 
         }
     } else {
         const bool pipe = cog_pipe;
-        const RunPart rp = pipe ? run_partition(xf.L, nframes, g.ncu, welch_pipe_gpc()) : run_partition(xf.L, nframes, g.ncu);
+        const RunPart rp = pipe ? run_partition(xf.L, nframes, g.ncu, 1) : run_partition(xf.L, nframes, g.ncu);
         // streaming form (every sample read once, the overlap carried in registers) when the shape allows; SP_COG_GENERIC=1
         // forces the generic frame kernel (A/B test); nfft 4096: the pipeline of specialised waves (k_welch_pipe.hip, mode 2)
         int generic = 1;
@@ -2283,8 +2202,7 @@ int sp_hilbert(const float *x, int64_t n_in, int64_t x_ld, int64_t nfft, int64_t
         if (g.bigA.ensure(sizeof(cf) * (size_t)nfft)) return -1;
         cf *A = (cf *)g.bigA.p;
         const int64_t Mh = nfft / 2;
-        const bool half_len = (nfft & (nfft - 1)) == 0 && big_three_pass(Mh) && !env_flag("SP_LONG_NOFUSE") &&
-                              !env_flag("SP_HILBERT_FULL");
+        const bool half_len = (nfft & (nfft - 1)) == 0 && big_three_pass(Mh);
         BigTw btN;
         if (half_len && get_bigtw(nfft, &btN)) return -1;
         for (int64_t b = 0; b < batch; ++b) {
@@ -2346,7 +2264,7 @@ int sp_hilbert(const float *x, int64_t n_in, int64_t x_ld, int64_t nfft, int64_t
                 if (dev_fft_big_pow2(A, A, Mh, 1, 0, 1, &fo)) return -1;
                 continue;
             }
-            if (big_three_pass(nfft) && !env_flag("SP_LONG_NOFUSE")) {
+            if (big_three_pass(nfft)) {
                 // real -> complex pack fused into the first pass of the forward transform (the zero padding is not loaded),
                 // the analytic-signal mask into the first pass of the inverse one
                 BigFuse fz;
@@ -2490,12 +2408,12 @@ int sp_xcorr(const float *x1, const float *x2, int64_t n, float *co_out, int mem
     } else {
         if (g.bigA.ensure(sizeof(cf) * (size_t)L) || g.bigB.ensure(sizeof(cf) * (size_t)L)) return -1;
         cf *A = (cf *)g.bigA.p, *B = (cf *)g.bigB.p;
-        if (big_three_pass(L) && !env_flag("SP_LONG_NOFUSE")) {
+        if (big_three_pass(L)) {
             // two of the three elementwise kernels ride on the transforms: the pack in the first pass of the first transform
             // (the zero half is never loaded), lag re-ordering + real part in the last pass of the second
             BigFuse f1, f2;
             f1.ci = ColsIn{1, a, b, tb.d + 16, n};
-            if (big_three_pass(L / 2) && !env_flag("SP_XC_FULL") && !env_flag("SP_XC_NOFUSEMID")) {
+            if (big_three_pass(L / 2) && !env_flag("SP_XC_NOFUSEMID")) {
                 // round 3: the forward transform's row pass, the middle step and the FIRST pass of the half-length transform in one
                 // kernel that owns mirror row pairs (k_xc_rowsmid); the half-length transform's two remaining passes are column
                 // passes over the half rows it leaves ([ka][kb][ka'], C/2 per row), the last one writing the lags
@@ -2531,7 +2449,7 @@ int sp_xcorr(const float *x1, const float *x2, int64_t n, float *co_out, int mem
                 }
             }
             if (dev_fft_big_pow2(A, B, L, 0, 0, 1, &f1)) return -1;          // B = FFT(z)
-            if (big_three_pass(L / 2) && !env_flag("SP_XC_FULL")) {
+            if (big_three_pass(L / 2)) {
                 // the correlation is real: its inverse transform runs at half length (k_xc_mid_half forms the M-point spectrum
                 // of r[2n] + i r[2n+1]; the last pass writes two lags per element): 3.0 GB of traffic at 2^24 samples
                 // instead of 3.8

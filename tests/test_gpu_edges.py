@@ -119,20 +119,17 @@ def test_hilbert_edge_shapes(P):
     np.testing.assert_allclose(P.hilbert(zc), O.hilbert(zc), atol=5e-6)
 
 
-def test_long_fft_two_pass_option_matches(monkeypatch):
-    """SP_BIGFFT_2PASS=1 (strided two-pass long transform, an option that measured slower) == the default five-pass form"""
+def test_long_fft_five_pass_matches_numpy():
+    """the default transform below 2^20 points (five-pass form) against numpy, forward and round trip"""
     from pyfft_amd import engine as E
     rng = np.random.default_rng(21)
     for n in (1 << 14, 1 << 17):
         x = (rng.standard_normal(n) + 1j * rng.standard_normal(n)).astype(np.complex64)
+        ref = np.fft.fft(x.astype(np.complex128))
         a = E.fft(x)
         ai = E.ifft(a)
-        monkeypatch.setenv("SP_BIGFFT_2PASS", "1")
-        b = E.fft(x)
-        bi = E.ifft(b)
-        monkeypatch.delenv("SP_BIGFFT_2PASS")
-        assert np.max(np.abs(a - b)) <= 2e-6 * np.abs(a).max()
-        assert np.max(np.abs(bi - x)) <= 3e-6 * np.abs(x).max() and np.max(np.abs(ai - x)) <= 3e-6 * np.abs(x).max()
+        assert np.max(np.abs(a - ref)) <= 2e-6 * np.abs(ref).max()
+        assert np.max(np.abs(ai - x)) <= 3e-6 * np.abs(x).max()
 
 
 @pytest.mark.parametrize("lg", [20, 21, 22])

@@ -869,8 +869,8 @@ def test_mean(E):
 
 @pytest.mark.parametrize("nch,nfft,hop,nsig", [(64, 512, 256, 40000), (37, 256, 64, 9000), (130, 256, 128, 5000)])
 def test_csd_matrix_paths_agree(E, nch, nfft, hop, nsig, monkeypatch):
-    """The three contraction paths -- fused MFMA (default for nch <= 64), MFMA on the transposed copy (default above
-    64 channels), VALU (A/B only) -- give the same matrix"""
+    """The two contraction paths -- fused MFMA (default for nch <= 64) and MFMA on the transposed copy (default above
+    64 channels) -- give the same matrix, and both match the oracle per bin and pair"""
     rng = np.random.default_rng(nch + nfft)
     x = (rng.standard_normal((nch, nsig)) + 0.3 * rng.standard_normal(nsig)[None, :] + 0.2).astype(np.float32)
     M = (nsig - nfft) // hop + 1
@@ -879,11 +879,10 @@ def test_csd_matrix_paths_agree(E, nch, nfft, hop, nsig, monkeypatch):
     monkeypatch.setenv("SP_CSDM_TRANSPOSED", "1")
     g1 = E.csd_matrix(x, win, hop, M, detrend=True, scale=1.0)
     monkeypatch.delenv("SP_CSDM_TRANSPOSED")
-    monkeypatch.setenv("SP_CSDM_VALU", "1")
-    g2 = E.csd_matrix(x, win, hop, M, detrend=True, scale=1.0)
-    scale = np.abs(g2).max()
-    assert np.max(np.abs(g0 - g2)) <= 2e-6 * scale
-    assert np.max(np.abs(g1 - g2)) <= 2e-6 * scale
+    assert np.max(np.abs(g0 - g1)) <= 2e-6 * np.abs(g1).max()
+    ref = O.csd_matrix(x.astype(np.float64), win, nfft, hop, M, 1.0) * np.sum(win ** 2)
+    assert _csd_per_bin_excess(g0, ref) <= 1.0
+    assert _csd_per_bin_excess(g1, ref) <= 1.0
 
 
 @pytest.mark.parametrize("nfft,hop,n,nch,detrend", [(1024, 512, 1024 + 512 * 40, 5, True), (256, 64, 256 + 64 * 37, 2, "linear"),

@@ -57,14 +57,14 @@ def test_fused_epilogue_matches_two_launch_form_and_oracle(wname, nfft, hop):
     np.testing.assert_allclose(pf, ref, rtol=2e-4, atol=1e-6 * ref.max())
 
 
-def test_fused_epilogue_real_pair_and_small_counts():
+def test_fused_epilogue_real_pair_and_small_counts(monkeypatch):
     """real input at hop = nfft/2 (two frames per transform: the |Z|^2 sums are symmetrised in the epilogue), 1..5 frames"""
     from pyfft_amd import engine as E
     rng = np.random.default_rng(3)
     nfft, hop = 4096, 2048
     win = O.windows("Hanning", nwins=nfft)
     S2 = float(np.sum(win ** 2))
-    os.environ["SP_WELCH_PIPE"] = "2"          # (read once per process: only effective if this is the first Welch call)
+    monkeypatch.setenv("SP_WELCH_PIPE", "2")   # the pipeline for every frame count
     for M in (1, 2, 3, 5, 64, 9000):
         n = (M - 1) * hop + nfft + 3
         s = (rng.standard_normal(n) + 1.25).astype(np.float32)

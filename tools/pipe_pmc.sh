@@ -12,7 +12,7 @@ for v in "$@"; do
   i=0
   for P in "$P1" "$P2" "$P3"; do
     i=$((i+1))
-    SP_LIB_PATH=$lib SP_WELCH_PIPE=1 SP_PIPE_GPC=1 rocprofv3 --kernel-trace --pmc $P --output-format csv -d $OUT/pass$i -- python3 tools/kbench.py --reps 4 > $OUT/pass$i.log 2>&1 || echo "pass $i failed ($v)"
+    SP_LIB_PATH=$lib SP_WELCH_PIPE=1 rocprofv3 --kernel-trace --pmc $P --output-format csv -d $OUT/pass$i -- python3 tools/kbench.py --reps 4 > $OUT/pass$i.log 2>&1 || echo "pass $i failed ($v)"
   done
   python3 tools/pmc_summary.py $OUT "k_welch_pipe" > gpurun_out/pipe_pmc_$v.txt 2>&1
   python3 - $OUT >> gpurun_out/pipe_pmc_$v.txt <<'PY'
