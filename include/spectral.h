@@ -237,6 +237,19 @@ int sp_csd_epilogue(const double *pxx, const double *pyy, const double *pxy, int
  *      exactly (float64 state, blocked scan of the affine state maps), not as a truncated FIR. */
 int sp_biquad(const double *b, const double *a, const float *x, int64_t n, float *y, int mem);
 
+/* ---- F3: cascades of second-order sections (scipy.signal.sosfilt / sosfiltfilt; the reference's application sites
+ *      filters.py:328 lfilter, :347 and :355-356 filtfilt).  sos[nsec][6] float64 HOST array (b0 b1 b2 a0 a1 a2 per
+ *      section, a0 != 0, 1 <= nsec <= 8, every pole radius <= 1), applied along each of nrows float32 rows of n samples
+ *      (x, y [nrows][n]).  The recurrence is evaluated exactly (float64 state, blocked scan of the affine state maps).
+ *      sp_sosfilt: zi / zf [nrows][nsec][2] float64 in sosfilt's convention, or NULL (rest / not wanted).
+ *      sp_sosfiltfilt: zero-phase, forward then backward from the steady state (sosfilt_zi) times the first sample of each
+ *      pass, over the record extended by padlen samples (padtype 0 none, 1 odd, 2 even, 3 constant; n > padlen).
+ *      x, y, zi, zf follow `mem`. */
+int sp_sosfilt(const double *sos, int nsec, const float *x, int64_t nrows, int64_t n, const double *zi, float *y, double *zf,
+               int mem);
+int sp_sosfiltfilt(const double *sos, int nsec, const float *x, int64_t nrows, int64_t n, int padtype, int64_t padlen, float *y,
+                   int mem);
+
 /* ---- helper: mean of a float32 / complex64 vector in double (fft_analysis.py:2148 detrend) */
 int sp_mean(const void *x, int x_dtype, int64_t n, double out[2], int mem);
 

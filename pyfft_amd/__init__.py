@@ -2,7 +2,9 @@
 
 Mirrors the reference package's export list (__init__.py:11-31) for the hot path:
     fft_analysis (alias `fft`), fft_pwelch, fftanal, windows, specgram, stft, hilbert, hilbert_1d, ccf,
-    iirnotch, iirpeak, plus the build-defined fftfilt / apply_notch.
+    iirnotch, iirpeak, butter_lowpass_filter, butter_bandpass, plus the build-defined fftfilt / apply_notch.
+(upsample / downsample / downsample_efficient need the absent pybaseutils.utils.interp: filters.py raises
+NotImplementedError for them.)
 Importing the package loads nothing from the GPU; the first kernel call initialises the HIP library
 (pyfft_amd/lib/libspectral.so) and fails loudly if it is missing -- there is no CPU fallback.
 """
@@ -20,6 +22,7 @@ from .hilbert import hilbert, hilbert_1d                     # noqa: F401
 from .ccf import ccf                                         # noqa: F401
 from .notch_filter import iirnotch, iirpeak, apply_notch     # noqa: F401
 from .filters import fftfilt                                 # noqa: F401
+from .filters import butter_lowpass_filter, butter_bandpass  # noqa: F401   (__init__.py:27)
 from . import doppler                                        # noqa: F401   (Doppler.cog / cogspec window loop)
 from .doppler import cog, cog_frames                         # noqa: F401
 from . import heatpulse                                      # noqa: F401   (HeatPulse_Funcs._PWELCH_chloop as one call)

@@ -248,6 +248,28 @@ int launch_long_cog(LaunchCtx c, const cf *S, int64_t m, int nfft, int klo, int 
 int64_t biquad_tiles(int64_t n);
 int launch_biquad(LaunchCtx c, const double *b, const double *a, const float *x, int64_t n, float *y, double *work);
 
+// cascades of second-order sections (k_sos.hip).  One pass over nrows rows; where its samples come from and where its
+// outputs go is an index map, so that sosfiltfilt's extension and reversal cost no copies.
+#define SP_SOS_MAXK 8
+struct SosIO {
+    const float *x;      // source rows, row stride x_ld, n valid samples each
+    int64_t x_ld, n;
+    int64_t len;         // samples of the pass
+    int64_t pad;         // forward: pass sample e is x_ext[e - pad] (padtype 1 odd, 2 even, 3 constant; 0: pad = 0)
+    int padtype;
+    int rev;             // 1: pass sample e is x[len - 1 - e] (pad = 0, n = len)
+    float *y;            // pass sample e lands at y[q - out_off], q = rev ? len - 1 - e : e, when 0 <= q - out_off < out_n
+    int64_t y_ld, out_off, out_n;
+};
+int64_t sos_tiles(int64_t len);
+int64_t sos_work_doubles(int nsec, int64_t len, int64_t nrows);
+int sos_plan_doubles(int nsec);
+void sos_build_plan(const double *sos, int nsec, int64_t len, double *plan);
+// work: sos_work_doubles(nsec, io.len, nrows) doubles; zmode 0: rest, 1: zi[nrows][2 nsec], 2: sosfilt_zi * the first sample;
+// zf (or null): [nrows][2 nsec] state after the pass's last sample
+int launch_sos_pass(LaunchCtx c, int nsec, const double *plan, const SosIO &io, int64_t nrows, int zmode, const double *zi,
+                    double *zf, double *work);
+
 // fft_pwelch epilogue on device-resident spectra (k_epilogue.hip)
 int launch_epi_elem(LaunchCtx c, const double *pxx, const double *pyy, const double *pxy, int nch, int nb, int nfft, int onesided,
                     double enbw, double *cxy, double *cxy2, double *phi, double *lxx, double *lyy, double *lxy);

@@ -20,7 +20,7 @@
 
 using namespace sp;
 
-#define SP_VERSION 106
+#define SP_VERSION 107
 #define SP_MAX_WG_FFT 8192
 #define SP_MAX_BIG_LOG2 26          /* longest multi-pass power-of-two transform: 2^26 points (512 MiB per buffer) */
 
@@ -84,6 +84,7 @@ struct Ctx {
     Scratch in0, in1, out0, work, small, trends, onepass, ticket, epi;
     Scratch pend_trend;                       // trend record a pending sp_welch_accum keeps until sp_welch_finish
     Scratch bigA, bigB, bigT, blueA, blueB, longrec;   // long (multi-kernel) paths
+    Scratch sosY, sosZ;                            // cascaded sections: sosfiltfilt's forward output, staged zi / zf
     Scratch cmS, cmT, cmG, cmH, cmO;               // CSD matrix: spectra, bin-major spectra, float64 accumulator, packed-spectra sums, one-pass means state
     std::map<int64_t, BigTw> bigtw;           // N -> two-level twiddle tables of the multi-pass FFT
     std::map<int64_t, BlueTab> blue_big;      // n -> chirp[n], FFT_L(chirp*) (unscaled) for multi-pass Bluestein
@@ -2590,6 +2591,115 @@ int sp_fftfilt(const float *h, int ntaps, const float *x, int64_t n, int nfft, f
         yd = (float *)g.out0.p;
     }
     LAUNCHCHK(launch_fftfilt(lc(), xd, n, ntaps, (const cf *)H_d, xf, yd));
+    if (!mem) {
+        HIPCHK(hipMemcpyAsync(y, yd, bytes, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
+// checks shared by sp_sosfilt / sp_sosfiltfilt: refuses before any launch
+static int sos_check(const char *who, const double *sos, int nsec) {
+    if (sos == nullptr) return fail("%s: sos is NULL", who);
+    if (nsec < 1 || nsec > SP_SOS_MAXK) return fail("%s: %d sections; 1 to %d are supported (filter order <= %d)", who, nsec,
+                                                    SP_SOS_MAXK, 2 * SP_SOS_MAXK);
+    for (int k = 0; k < nsec; ++k) {
+        const double *r = sos + 6 * k;
+        for (int i = 0; i < 6; ++i)
+            if (!isfinite(r[i])) return fail("%s: section %d has a non-finite coefficient", who, k);
+        if (r[3] == 0.0) return fail("%s: section %d has a0 = 0", who, k);
+        // the scan raises the state maps to powers up to the record length: an unstable section would overflow them
+        const double a1 = r[4] / r[3], a2 = r[5] / r[3], disc = a1 * a1 - 4.0 * a2;
+        const double rad = disc < 0.0 ? sqrt(a2) : 0.5 * (fabs(a1) + sqrt(disc));
+        if (!(rad <= 1.0 + 1e-12))
+            return fail("%s: section %d is unstable (pole radius %.9g > 1): the blocked scan of the state maps does not apply", who,
+                        k, rad);
+    }
+    return 0;
+}
+
+static int sos_plan_table(const double *sos, int nsec, int64_t len, const double **plan_d) {
+    std::vector<double> plan((size_t)sos_plan_doubles(nsec));
+    sos_build_plan(sos, nsec, len, plan.data());
+    void *d = nullptr;
+    if (get_table(5, plan.data(), sizeof(double) * plan.size(), &d, nullptr)) return -1;
+    *plan_d = (const double *)d;
+    return 0;
+}
+
+int sp_sosfilt(const double *sos, int nsec, const float *x, int64_t nrows, int64_t n, const double *zi, float *y, double *zf,
+               int mem) {
+    if (sos_check("sp_sosfilt", sos, nsec)) return -1;
+    if (x == nullptr || y == nullptr || nrows < 1 || n < 1) return fail("sp_sosfilt: bad arguments");
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const int S = 2 * nsec;
+    const double *plan_d;
+    if (sos_plan_table(sos, nsec, n, &plan_d)) return -1;
+    const float *xd = x;
+    float *yd = y;
+    const double *zid = zi;
+    double *zfd = zf;
+    const size_t bytes = sizeof(float) * (size_t)(nrows * n), zbytes = sizeof(double) * (size_t)(nrows * S);
+    if (!mem) {
+        if (g.in0.ensure(bytes) || g.out0.ensure(bytes) || g.sosZ.ensure(2 * zbytes)) return -1;
+        HIPCHK(hipMemcpyAsync(g.in0.p, x, bytes, hipMemcpyHostToDevice, g.stream));
+        xd = (const float *)g.in0.p;
+        yd = (float *)g.out0.p;
+        if (zi) {
+            HIPCHK(hipMemcpyAsync(g.sosZ.p, zi, zbytes, hipMemcpyHostToDevice, g.stream));
+            zid = (const double *)g.sosZ.p;
+        }
+        if (zf) zfd = (double *)g.sosZ.p + nrows * S;
+    }
+    if (g.work.ensure(sizeof(double) * (size_t)sos_work_doubles(nsec, n, nrows) + 64)) return -1;
+    const SosIO io{xd, n, n, n, 0, 0, 0, yd, n, 0, n};
+    LAUNCHCHK(launch_sos_pass(lc(), nsec, plan_d, io, nrows, zid ? 1 : 0, zid, zfd, (double *)g.work.p));
+    if (!mem) {
+        HIPCHK(hipMemcpyAsync(y, yd, bytes, hipMemcpyDeviceToHost, g.stream));
+        if (zf) HIPCHK(hipMemcpyAsync(zf, zfd, zbytes, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
+int sp_sosfiltfilt(const double *sos, int nsec, const float *x, int64_t nrows, int64_t n, int padtype, int64_t padlen, float *y,
+                   int mem) {
+    if (sos_check("sp_sosfiltfilt", sos, nsec)) return -1;
+    if (x == nullptr || y == nullptr || nrows < 1 || n < 1) return fail("sp_sosfiltfilt: bad arguments");
+    if (padtype < 0 || padtype > 3) return fail("sp_sosfiltfilt: padtype must be 0 (none), 1 (odd), 2 (even) or 3 (constant)");
+    if (padlen < 0) return fail("sp_sosfiltfilt: padlen must not be negative");
+    if (padtype == 0) padlen = 0;
+    if (padlen > 0 && n <= padlen)
+        return fail("sp_sosfiltfilt: the signal length (%lld) must be greater than padlen (%lld)", (long long)n, (long long)padlen);
+    for (int k = 0; k < nsec; ++k) {            // sosfilt_zi: a section with a pole at z = 1 has no steady state
+        const double *r = sos + 6 * k;
+        if (r[3] + r[4] + r[5] == 0.0) return fail("sp_sosfiltfilt: section %d has a pole at z = 1 (no steady state)", k);
+    }
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const int64_t N = n + 2 * padlen;
+    const double *plan_d;
+    if (sos_plan_table(sos, nsec, N, &plan_d)) return -1;
+    const float *xd = x;
+    float *yd = y;
+    const size_t bytes = sizeof(float) * (size_t)(nrows * n);
+    if (!mem) {
+        if (g.in0.ensure(bytes) || g.out0.ensure(bytes)) return -1;
+        HIPCHK(hipMemcpyAsync(g.in0.p, x, bytes, hipMemcpyHostToDevice, g.stream));
+        xd = (const float *)g.in0.p;
+        yd = (float *)g.out0.p;
+    }
+    if (g.sosY.ensure(sizeof(float) * (size_t)(nrows * N)) ||
+        g.work.ensure(sizeof(double) * (size_t)sos_work_doubles(nsec, N, nrows) + 64))
+        return -1;
+    float *mid = (float *)g.sosY.p;
+    // forward over the extended record into the scratch, from zss * x_ext[0]; then backwards over it from zss * its last
+    // sample, keeping [padlen, padlen + n) -- two passes on one stream, no host synchronisation in between
+    const SosIO fwd{xd, n, n, N, padlen, padtype, 0, mid, N, 0, N};
+    const SosIO bwd{mid, N, N, N, 0, 0, 1, yd, n, padlen, n};
+    LAUNCHCHK(launch_sos_pass(lc(), nsec, plan_d, fwd, nrows, 2, nullptr, nullptr, (double *)g.work.p));
+    LAUNCHCHK(launch_sos_pass(lc(), nsec, plan_d, bwd, nrows, 2, nullptr, nullptr, (double *)g.work.p));
     if (!mem) {
         HIPCHK(hipMemcpyAsync(y, yd, bytes, hipMemcpyDeviceToHost, g.stream));
         HIPCHK(hipStreamSynchronize(g.stream));

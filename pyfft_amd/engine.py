@@ -594,6 +594,143 @@ def biquad_filter(b, a, x):
     return out
 
 
+# ------------------------------------------------------------------------------------------ F3
+PADTYPES = {None: 0, "none": 0, "odd": 1, "even": 2, "constant": 3}
+MAX_SECTIONS = 8
+
+
+def sos_array(sos):
+    """(n_sections, 6) float64 copy of a second-order-section design, checked the way sp_sosfilt checks it (1 to 8
+    sections, finite, a0 != 0, every pole radius <= 1) -- refused here before any device work."""
+    s = np.array(sos, dtype=np.float64)
+    if s.ndim == 1 and s.size == 6:
+        s = s[None, :]
+    if s.ndim != 2 or s.shape[1] != 6:
+        raise ValueError("sos must have shape (n_sections, 6)")
+    if not 1 <= s.shape[0] <= MAX_SECTIONS:
+        raise ValueError("sos: %d sections; 1 to %d are supported (filter order <= %d)" % (s.shape[0], MAX_SECTIONS,
+                                                                                             2 * MAX_SECTIONS))
+    if not np.all(np.isfinite(s)):
+        raise ValueError("sos: non-finite coefficient")
+    if np.any(s[:, 3] == 0.0):
+        raise ValueError("sos: a0 must not be zero")
+    for k in range(s.shape[0]):
+        rts = np.roots(s[k, 3:])
+        if rts.size and float(np.max(np.abs(rts))) > 1.0 + 1e-12:
+            raise ValueError("sos: section %d is unstable (pole radius %.9g > 1)" % (k, float(np.max(np.abs(rts)))))
+    return np.ascontiguousarray(s)
+
+
+def _sos_rows(x):
+    """x (numpy or device tensor, rows along the last axis) -> (float32 [R, n] contiguous rows, lead shape, complex?);
+    complex input becomes its real rows followed by its imaginary rows."""
+    if _is_torch(x):
+        cplx = x.is_complex()
+        lead, n = tuple(x.shape[:-1]), int(x.shape[-1])
+        parts = torch.stack([x.real, x.imag]) if cplx else x
+        return parts.reshape(-1, n).to(torch.float32).contiguous(), lead, cplx
+    x = np.asarray(x)
+    cplx = np.iscomplexobj(x)
+    lead, n = x.shape[:-1], x.shape[-1]
+    parts = np.stack([x.real, x.imag]) if cplx else x
+    return np.ascontiguousarray(parts.reshape(-1, n), dtype=np.float32), lead, cplx
+
+
+def _sos_out(y, x, lead, cplx):
+    """device rows -> the input's shape; float64 / complex128 (and integer) input comes back in double precision"""
+    n = y.shape[-1]
+    if _is_torch(x):
+        if cplx:
+            y = torch.complex(y[:y.shape[0] // 2], y[y.shape[0] // 2:])
+            return y.reshape(lead + (n,)).to(torch.complex64 if x.dtype == torch.complex64 else torch.complex128)
+        return y.reshape(lead + (n,)).to(torch.float32 if x.dtype == torch.float32 else torch.float64)
+    xd = np.asarray(x).dtype
+    if cplx:
+        y = y[:y.shape[0] // 2] + 1j * y[y.shape[0] // 2:]
+        return y.reshape(lead + (n,)).astype(np.complex64 if xd == np.complex64 else np.complex128)
+    return y.reshape(lead + (n,)).astype(np.float32 if xd == np.float32 else np.float64, copy=False)
+
+
+def sos_filter(sos, x, zi=None):
+    """y = scipy.signal.sosfilt(sos, x, axis=-1) on the GPU, exact (float64 recurrence, blocked scan of the state maps;
+    include/spectral.h: sp_sosfilt), float32 samples.  x: numpy, or a device tensor that stays on the device (torch's
+    current stream).  zi (or None): scipy's shape (n_sections, ...lead, 2); with zi, returns (y, zf) of the same shapes."""
+    s = sos_array(sos)
+    nsec = s.shape[0]
+    if (x.dim() if _is_torch(x) else np.ndim(x)) < 1 or x.shape[-1] < 1:
+        raise ValueError("sos_filter: empty signal")
+    rows, lead, cplx = _sos_rows(x)
+    R, n = rows.shape
+    zr = None
+    if zi is not None:
+        want = (nsec,) + tuple(lead) + (2,)
+        if tuple(zi.shape) != want:
+            raise ValueError("sos_filter: zi must have shape %s, got %s" % (want, tuple(zi.shape)))
+    if _is_torch(x):
+        _bind_stream(x)
+        if zi is not None:
+            z = torch.as_tensor(zi, device=x.device)
+            z = z.reshape(nsec, -1, 2)
+            if cplx:                          # a real zi is the real parts' state; the imaginary parts start from rest
+                z = torch.cat([z.real, z.imag if z.is_complex() else torch.zeros_like(z)], 1)
+            elif z.is_complex():
+                z = z.real
+            zr = z.permute(1, 0, 2).to(torch.float64).contiguous()
+        y = torch.empty_like(rows)
+        zf = torch.empty_like(zr) if zr is not None else None
+        check(lib().sp_sosfilt(ptr(s), nsec, ptr(rows.data_ptr()), R, n, ptr(zr.data_ptr()) if zr is not None else None,
+                               ptr(y.data_ptr()), ptr(zf.data_ptr()) if zf is not None else None, 1))
+    else:
+        if zi is not None:
+            z = np.asarray(zi).reshape(nsec, -1, 2)
+            z = np.concatenate([z.real, z.imag], 1) if cplx else np.real(z)
+            zr = np.ascontiguousarray(z.transpose(1, 0, 2), dtype=np.float64)
+        y = np.empty_like(rows)
+        zf = np.empty_like(zr) if zr is not None else None
+        _ffi.init()
+        check(lib().sp_sosfilt(ptr(s), nsec, ptr(rows), R, n, ptr(zr), ptr(y), ptr(zf), 0))
+    out = _sos_out(y, x, lead, cplx)
+    if zi is None:
+        return out
+    zf = zf.permute(1, 0, 2) if _is_torch(zf) else zf.transpose(1, 0, 2)       # [nsec][R][2]
+    if cplx:
+        h = zf.shape[1] // 2
+        zf = zf[:, :h] + 1j * zf[:, h:]
+    return out, zf.reshape((nsec,) + tuple(lead) + (2,))
+
+
+def sos_filtfilt(sos, x, padtype="odd", padlen=0):
+    """y = scipy.signal.sosfiltfilt(sos, x, axis=-1, padtype, padlen) on the GPU: forward over the extended record from
+    sosfilt_zi times its first sample, then backwards (include/spectral.h: sp_sosfiltfilt).  padlen is explicit here
+    (pyfft_amd.filters.sosfiltfilt applies scipy's default); numpy or device-tensor x as in sos_filter."""
+    s = sos_array(sos)
+    nsec = s.shape[0]
+    if padtype not in PADTYPES:
+        raise ValueError("padtype must be 'odd', 'even', 'constant' or None, got %r" % (padtype,))
+    pt = PADTYPES[padtype]
+    padlen = 0 if pt == 0 else int(padlen)
+    if padlen < 0:
+        raise ValueError("padlen must not be negative")
+    if (x.dim() if _is_torch(x) else np.ndim(x)) < 1 or x.shape[-1] < 1:
+        raise ValueError("sos_filtfilt: empty signal")
+    n = int(x.shape[-1])
+    if padlen > 0 and n <= padlen:
+        raise ValueError("The length of the input vector x must be greater than padlen, which is %d." % padlen)
+    if np.any(s[:, 3] + s[:, 4] + s[:, 5] == 0.0):
+        raise ValueError("sos_filtfilt: a section with a pole at z = 1 has no steady state")
+    rows, lead, cplx = _sos_rows(x)
+    R = rows.shape[0]
+    if _is_torch(x):
+        _bind_stream(x)
+        y = torch.empty_like(rows)
+        check(lib().sp_sosfiltfilt(ptr(s), nsec, ptr(rows.data_ptr()), R, n, pt, padlen, ptr(y.data_ptr()), 1))
+    else:
+        y = np.empty_like(rows)
+        _ffi.init()
+        check(lib().sp_sosfiltfilt(ptr(s), nsec, ptr(rows), R, n, pt, padlen, ptr(y), 0))
+    return _sos_out(y, x, lead, cplx)
+
+
 # ------------------------------------------------------------------------------------------ A6 / N1
 def csd_epilogue(pxx, pyy, pxy, nfft, onesided, enbw):
     """The fft_pwelch epilogue (fft_analysis.py:489-648) on the averaged spectra, on the device: pxx[nb], pyy[nch, nb],

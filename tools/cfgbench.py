@@ -3,7 +3,7 @@
 current stream = the library's launch stream) and prints algorithmic GB/s per SURVEY.md section 8d.  Round 3: the headline
 figure of a line is the SUSTAINED time per call (settled clocks, calls back to back); the isolated median of the earlier rounds
 follows in brackets (SP_CFGBENCH_ISOLATED=1: only that).
-  python tools/cfgbench.py [--only cfg2,cfg3,...] [--reps 5]"""
+  python tools/cfgbench.py [--only cfg2,cfg3,...] [--reps 5]     (also: biquad, sos)"""
 import argparse
 import os
 import sys
@@ -129,6 +129,28 @@ def main():
         b, a_ = iirnotch(0.01, 30.0)
         ms, _ = timed(lambda: E.biquad_filter(b, a_, x), a.reps)
         report("cfg4 notch (exact biquad) 2^28 f32", ms, 8.0 * n, n, "samples")
+        del x
+    if "sos" in only:       # cascaded second-order sections (k_sos.hip): the reference's band-pass (K = 3) and K = 8
+        import scipy.signal as ss
+        sos3 = ss.butter(3, [0.0005, 0.25], btype="band", output="sos")
+        sos8 = ss.butter(8, [0.0005, 0.25], btype="band", output="sos")
+        n = 1 << 28
+        x = torch.randn(n, generator=g, device=dev, dtype=torch.float32)
+        pl3 = 3 * 7
+        ms, _ = timed(lambda: E.sos_filter(sos3, x), a.reps)
+        report("sosfilt K=3 2^28 f32", ms, 8.0 * n, n, "samples")
+        ms, _ = timed(lambda: E.sos_filtfilt(sos3, x, "odd", pl3), a.reps)
+        report("sosfiltfilt K=3 2^28 f32", ms, 16.0 * n, n, "samples")
+        ms, _ = timed(lambda: E.sos_filter(sos8, x), a.reps)
+        report("sosfilt K=8 2^28 f32", ms, 8.0 * n, n, "samples")
+        ms, _ = timed(lambda: E.sos_filtfilt(sos8, x, "odd", 3 * 17), a.reps)
+        report("sosfiltfilt K=8 2^28 f32", ms, 16.0 * n, n, "samples")
+        del x
+        x = torch.randn((64, 1 << 22), generator=g, device=dev, dtype=torch.float32)
+        ms, _ = timed(lambda: E.sos_filter(sos3, x), a.reps)
+        report("sosfilt K=3 64 x 2^22 f32", ms, 8.0 * x.numel(), x.numel(), "samples")
+        ms, _ = timed(lambda: E.sos_filtfilt(sos3, x, "odd", pl3), a.reps)
+        report("sosfiltfilt K=3 64 x 2^22 f32", ms, 16.0 * x.numel(), x.numel(), "samples")
         del x
     if "hilbert" in only:
         x = torch.randn((4096, 4096), generator=g, device=dev, dtype=torch.float32)
