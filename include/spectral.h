@@ -97,8 +97,9 @@ int sp_welch_psd(const void *x, int x_dtype, int64_t nsig, const float *win, int
 /* ---- the same path split in two for segment-sharded multi-process runs (one process per GPU): every process
  *      accumulates its own frames against a local estimate of the mean, the processes all-reduce sum_out (2 doubles)
  *      to get the global mean of the stream, and each finishes with it; the finished spectra (scaled by
- *      scale/frames_total) then add up to the Welch PSD of the whole stream.  Needs a power-of-two nfft in
- *      [256, sp_max_wg_fft()] with hop = nfft/4, nfft/2 or nfft.  One accumulation may be pending at a time; x must
+ *      scale/frames_total) then add up to the Welch PSD of the whole stream.  Shapes: any segment of one workgroup
+ *      transform (powers of two up to sp_max_wg_fft(), other lengths up to half of it) and any hop >= 1; a shard owns at
+ *      most nframes*hop + nfft - 1 samples (nmean).  One accumulation may be pending at a time; x must
  *      stay valid until sp_welch_finish when mem=1.
  *      nmean: this shard's own samples x[0:nmean] (halo excluded) -> sum_out[2] = sum of them.
  *      mean: [2] doubles (host if mem=0, device if mem=1), or NULL = the shard's own mean sum_out/nmean. */
@@ -109,7 +110,7 @@ int sp_welch_finish(const double *mean, int64_t frames_total, int sided, double 
  *      state[5*nfft + 8] (doubles): sum|X|^2, sum X and conj(mu0) sum X per bin (spectra taken against the shard's
  *      own mean estimate mu0), M mu0, M |mu0|^2, the sum of its nmean own samples, M and nmean.  The states of all
  *      shards are summed with ONE all-reduce and sp_welch_apply turns the sum into the PSD of the whole stream
- *      detrended by its global mean (same output conventions as sp_welch_finish). */
+ *      detrended by its global mean (same output conventions as sp_welch_finish).  Shapes: as sp_welch_accum. */
 int sp_welch_export(const void *x, int x_dtype, int64_t nsig, const float *win, int nfft, int hop,
                     int64_t nframes, int64_t nmean, double *state, int mem);
 int sp_welch_apply(const double *state, const float *win, int nfft, int64_t frames_total, int sided, double scale,

@@ -261,15 +261,17 @@ static __global__ __launch_bounds__(WgCfg<N>::WG) void k_op_finish(const void *_
 // The all-reduced (summed over shards) state of k_op_finish<EXPORT> -> the PSD of the whole stream, detrended by the
 // global mean mu = S / n:  P[k] = A - 2 Re(conj(W) (conj(mu) B - C)) + |W|^2 (|mu|^2 M - 2 Re(conj(mu) S1) + S2)
 // (each shard's sum |X - (mu - mu0_r) W|^2, expanded so that only sums over shards appear).
+// mean != null: the caller's (re, im) mean instead of the state's own S / n (the split ABI's finish on a pending state)
 static __global__ __launch_bounds__(256) void k_op_apply(const double *__restrict__ st, const cf *__restrict__ Wf, int n,
-                                                         int sided, double scale, double *__restrict__ out) {
+                                                         int sided, double scale, double *__restrict__ out,
+                                                         const double *__restrict__ mean) {
     const int k = blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
     const int slot = bin_slot(k, n, sided);
     if (slot < 0) return;
     const double *sc = st + 5 * (int64_t)n;
     const double Mt = sc[5], nt = sc[6];
-    const double mr = sc[3] / nt, mi = sc[4] / nt;
+    const double mr = mean ? mean[0] : sc[3] / nt, mi = mean ? mean[1] : sc[4] / nt;
     const double br = st[n + 2 * k], bi = st[n + 2 * k + 1], cr = st[3 * n + 2 * k], ci = st[3 * n + 2 * k + 1];
     const double dr = mr * br + mi * bi - cr, di = mr * bi - mi * br - ci;            // conj(mu) B - C
     const double wr = Wf[k].x, wi = Wf[k].y;
@@ -936,8 +938,9 @@ int launch_op_fused(LaunchCtx c, const void *x, bool cplx, const float *trend, c
     return 0;
 }
 
-int launch_op_apply(LaunchCtx c, const double *state, const cf *Wf, int n, int sided, double scale, double *out) {
-    hipLaunchKernelGGL(k_op_apply, dim3((n + 255) / 256), dim3(256), 0, c.stream, state, Wf, n, sided, scale, out);
+int launch_op_apply(LaunchCtx c, const double *state, const cf *Wf, int n, int sided, double scale, double *out,
+                    const double *mean) {
+    hipLaunchKernelGGL(k_op_apply, dim3((n + 255) / 256), dim3(256), 0, c.stream, state, Wf, n, sided, scale, out, mean);
     return 0;
 }
 

@@ -161,7 +161,18 @@ int launch_op_reduce(LaunchCtx c, const void *x, bool cplx, const float *trend, 
 int launch_op_finish(LaunchCtx c, const void *x, bool cplx, const float *trend, const float *win, OnePass st,
                      const double *mean_in, int64_t nmean, const Xf &xf, int hop, int64_t nframes, cf *cw, const cf *Wf,
                      int sided, double scale, double *out, bool export_state = false);
-int launch_op_apply(LaunchCtx c, const double *state, const cf *Wf, int n, int sided, double scale, double *out);
+// mean (device, optional): apply this (re, im) mean instead of the state's own sample sum / count
+int launch_op_apply(LaunchCtx c, const double *state, const cf *Wf, int n, int sided, double scale, double *out,
+                    const double *mean = nullptr);
+// one-pass sharded state for any hop and any workgroup transform (k_welch_opx.hip).  Scratch: partial[G][L] floats, cpart[G][n],
+// A[n], csum[2n], tpart[2 * opx_tot_blocks()] doubles
+int opx_tot_blocks();
+int launch_welch_opx(LaunchCtx c, const void *x, bool cplx, bool pair, const float *win, int hop, int64_t nframes,
+                     const float *trend, const Xf &xf, const RunPart &rp, float *partial, cf *cpart);
+int launch_opx_reduce(LaunchCtx c, const float *partial, const cf *cpart, int64_t G, const Xf &xf, const void *x, bool cplx,
+                      const float *trend, int hop, int64_t nframes, int64_t nmean, double *A, double *csum, double *tpart);
+int launch_opx_finish(LaunchCtx c, const float *win, const double *A, const double *csum, const double *tpart, const float *trend,
+                      int hop, int64_t nframes, int64_t nmean, bool sym, const Xf &xf, double *out);
 // colsums + finish (or export) in one launch for a window whose spectrum is confined to the bins -3 .. 3 (k_op_fused)
 int launch_op_fused(LaunchCtx c, const void *x, bool cplx, const float *trend, const float *win, const float *partial,
                     const cf *spartial, int64_t G, int n, int hop, int64_t nframes, int64_t nmean, OnePass st, unsigned *ticket,

@@ -110,6 +110,7 @@ struct Pending {
     float *trend_f = nullptr;
     cf *cw = nullptr;
     double *sum_d = nullptr;
+    double *state = nullptr;     // generic shapes (k_welch_opx): the exported state, finished by k_op_apply
 } g_pend;
 
 struct ProfScope {   // brackets one kernel launch with HIP events on its stream (default: the launch stream) when profiling is on
@@ -738,6 +739,51 @@ struct SplitLaunch {
     int reserve_cus = 0;       // CUs left to the collective's kernel: the main kernel is partitioned over ncu - reserve_cus
 };
 
+// the shard state (5 n + 8 doubles, k_op_finish<EXPORT>'s layout) of a shape the carry / pipeline kernels do not take -- any hop,
+// any workgroup transform length (k_welch_opx.hip): mean estimate and main kernel on the launch stream, the two reductions on
+// the streaming engine's epilogue stream behind the main kernel's event when `sl` is given (its scratch set of the step's
+// parity), else on the launch stream.  Real input runs two frames per transform from two frames on (SP_NO_REALPAIR: one).
+int welch_export_generic(const void *xd, bool cplx, int64_t nsig, const float *win, int nfft, int hop, int64_t nframes,
+                         int64_t nmean, const Xf &xf, double *st_d, const void **win_out = nullptr, const SplitLaunch *sl = nullptr) {
+    Scratch &S_work = sl ? *sl->work : g.work, &S_trend = sl ? *sl->trend : g.pend_trend;
+    void *win_d;
+    if (get_table(1, win, sizeof(float) * (size_t)nfft, &win_d, nullptr)) return -1;
+    if (win_out) *win_out = win_d;
+    // FFT(window) for the apply that follows: made (when not cached) on the launch stream BEFORE the main kernel, so that an
+    // epilogue-stream apply ordered behind the main kernel's event finds it
+    void *Wf_d;
+    if (get_window_spectrum(win, nfft, xf, &Wf_d)) return -1;
+    if (S_trend.ensure(256)) return -1;
+    float *trend = (float *)S_trend.p;
+    const bool pair = !cplx && nframes >= 2 && !env_flag("SP_NO_REALPAIR");
+    const int ncu_p = (sl && sl->reserve_cus > 0 && sl->reserve_cus < g.ncu) ? g.ncu - sl->reserve_cus : g.ncu;
+    const RunPart rp = run_partition(xf.L, pair ? (nframes + 1) / 2 : nframes, ncu_p);
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_part = pad(sizeof(float) * (size_t)rp.groups * xf.L), b_cpart = pad(sizeof(cf) * (size_t)rp.groups * nfft);
+    const size_t b_red = pad(sizeof(double) * (3 * (size_t)nfft + 2 * (size_t)opx_tot_blocks()));
+    if (S_work.ensure(b_part + b_cpart + b_red)) return -1;
+    char *w0 = (char *)S_work.p;
+    float *partial = (float *)w0;
+    cf *cpart = (cf *)(w0 + b_part);
+    double *A = (double *)(w0 + b_part + b_cpart), *csum = A + nfft, *tpart = csum + 2 * (size_t)nfft;
+    const LaunchCtx mc = lc();
+    LAUNCHCHK(launch_op_estimate(mc, xd, cplx, nsig, nullptr, trend));
+    {
+        ProfScope ps(mc.stream);
+        LAUNCHCHK(launch_welch_opx(mc, xd, cplx, pair, (const float *)win_d, hop, nframes, trend, xf, rp, partial, cpart));
+    }
+    g.last_kernel = pair ? "k_welch_opx(realpair)" : "k_welch_opx";
+    LaunchCtx ec = mc;
+    if (sl) {
+        HIPCHK(hipEventRecord(sl->ev_main, mc.stream));
+        HIPCHK(hipStreamWaitEvent(sl->epi, sl->ev_main, 0));
+        ec = LaunchCtx{sl->epi, g.ncu};
+    }
+    LAUNCHCHK(launch_opx_reduce(ec, partial, cpart, rp.groups, xf, xd, cplx, trend, hop, nframes, nmean, A, csum, tpart));
+    LAUNCHCHK(launch_opx_finish(ec, (const float *)win_d, A, csum, tpart, trend, hop, nframes, nmean, pair, xf, st_d));
+    return 0;
+}
+
 // want_sum: also produce the shard's plain sample sum (split ABI, one more tiny launch); without it the finish kernel
 // derives the shard mean itself
 int welch_accum_locked(const void *xd, bool cplx, int64_t nsig, const float *win, int nfft, int hop, int64_t nframes,
@@ -746,14 +792,47 @@ int welch_accum_locked(const void *xd, bool cplx, int64_t nsig, const float *win
     Scratch &S_ticket = sl ? *sl->ticket : g.ticket;
     if (!wg_capable(nfft))
         return fail("sharded / split Welch PSD (sp_welch_accum, sp_welch_export, sp_welch_dist_*): segments longer than one workgroup "
-                    "transform are not sharded (nfft = %d; powers of two in [256, %d] with hop = nfft/4, nfft/2 or nfft) -- the "
-                    "long-segment regime has few, large frames: run sp_welch_psd on one GPU", nfft, SP_MAX_WG_FFT);
+                    "transform are not sharded (nfft = %d; powers of two up to %d, other lengths up to %d) -- the "
+                    "long-segment regime has few, large frames: run sp_welch_psd on one GPU", nfft, SP_MAX_WG_FFT, SP_MAX_WG_FFT / 2);
     Xf xf;
     if (get_xf(nfft, &xf)) return -1;
-    if (!welch_carry_eligible(xf, hop, false))
-        return fail("one-pass Welch needs a power-of-two nfft in [256, %d] and hop = nfft/4, nfft/2 or nfft (got nfft=%d hop=%d)",
-                    SP_MAX_WG_FFT, nfft, hop);
     if (nmean < 1 || nmean > nsig) return fail("sp_welch_accum: nmean must be in [1, nsig]");
+    if (!welch_carry_eligible(xf, hop, false)) {
+        // every other shape: the generic one-pass kernel exports the state; the split ABI keeps it pending for k_op_apply.
+        // A shard of a frame-sharded stream owns at most its frames' hops plus the halo and tail: more is a caller error
+        if (nmean > nframes * (int64_t)hop + nfft - 1)
+            return fail("one-pass Welch: %lld own samples (nmean) cannot belong to %lld frames of %d with hop %d (at most "
+                        "nframes * hop + nfft - 1 = %lld)", (long long)nmean, (long long)nframes, nfft, hop,
+                        (long long)(nframes * (int64_t)hop + nfft - 1));
+        if (fo && fo->export_state) {
+            if (welch_export_generic(xd, cplx, nsig, win, nfft, hop, nframes, nmean, xf, fo->out, nullptr, sl)) return -1;
+            fo->done = true;
+            g_pend.valid = false;
+            return 0;
+        }
+        if (fo || sl) return fail("internal: generic one-pass Welch exports its state only");
+        if (S_one.ensure(sizeof(double) * (5 * (size_t)nfft + 8))) return -1;
+        double *st_d = (double *)S_one.p;
+        const void *win_d = nullptr;
+        if (welch_export_generic(xd, cplx, nsig, win, nfft, hop, nframes, nmean, xf, st_d, &win_d)) return -1;
+        void *Wf_d;
+        if (get_window_spectrum(win, nfft, xf, &Wf_d)) return -1;
+        g_pend = Pending{};
+        g_pend.valid = true;
+        g_pend.xd = xd;
+        g_pend.cplx = cplx;
+        g_pend.nsig = nsig;
+        g_pend.nframes = nframes;
+        g_pend.nmean = nmean;
+        g_pend.nfft = nfft;
+        g_pend.hop = hop;
+        g_pend.xf = xf;
+        g_pend.win_d = (const float *)win_d;
+        g_pend.Wf = (const cf *)Wf_d;
+        g_pend.state = st_d;
+        g_pend.sum_d = st_d + 5 * (size_t)nfft + 3;          // the own samples' plain sum (re, im)
+        return 0;
+    }
     void *win_d;
     if (get_table(1, win, sizeof(float) * (size_t)nfft, &win_d, nullptr)) return -1;
     void *Wf_d;
@@ -836,6 +915,7 @@ int welch_accum_locked(const void *xd, bool cplx, int64_t nsig, const float *win
     }
     LAUNCHCHK(launch_op_reduce(ec, xd, cplx, tb.f, partial, spartial, rp.groups, xf, hop, nframes, nmean, st,
                                want_sum ? sum_d : nullptr));
+    g_pend.state = nullptr;
     g_pend.valid = true;
     g_pend.xd = xd;
     g_pend.cplx = cplx;
@@ -858,6 +938,11 @@ int welch_finish_locked(const double *mean_d /*device or null*/, int64_t frames_
                         double *out_d, const LaunchCtx *ctx = nullptr) {
     if (!g_pend.valid) return fail("sp_welch_finish: no pending sp_welch_accum");
     g_pend.valid = false;
+    if (g_pend.state) {          // generic shape: the pending state applied with the caller's mean, or the shard's own
+        LAUNCHCHK(launch_op_apply(ctx ? *ctx : lc(), g_pend.state, g_pend.Wf, g_pend.nfft, sided, scale / (double)frames_total, out_d,
+                                  mean_d));
+        return 0;
+    }
     LAUNCHCHK(launch_op_finish(ctx ? *ctx : lc(), g_pend.xd, g_pend.cplx, g_pend.trend_f, g_pend.win_d, g_pend.st, mean_d, g_pend.nmean,
                                g_pend.xf, g_pend.hop, g_pend.nframes, g_pend.cw, g_pend.Wf, sided,
                                scale / (double)frames_total, out_d));
@@ -997,6 +1082,14 @@ int engine_apply_locked(int s) {
     LAUNCHCHK(launch_op_apply(LaunchCtx{geng.epi, g.ncu}, (const double *)geng.st[s].p, (const cf *)Wf_d, nfft, sl.sided,
                               sl.scale / (double)sl.frames_total, sl.out));
     return 0;
+}
+
+// a shape the generic one-pass kernel takes (every workgroup transform that the carry / pipeline kernels do not)
+bool welch_generic_shape(int nfft, int hop) {
+    if (!wg_capable(nfft)) return false;
+    Xf xf;
+    if (get_xf(nfft, &xf)) return false;
+    return !welch_carry_eligible(xf, hop, false);
 }
 
 // this shard's additive state (sp_welch_export) into st_d (device, 5 nfft + 8 doubles)
@@ -1390,7 +1483,6 @@ int sp_welch_apply(const double *state, const float *win, int nfft, int64_t fram
                     SP_MAX_WG_FFT);
     Xf xf;
     if (get_xf(nfft, &xf)) return -1;
-    if (xf.blue) return fail("sp_welch_apply: power-of-two nfft only");
     void *Wf_d;
     if (get_window_spectrum(win, nfft, xf, &Wf_d)) return -1;
     const int nb = nbins_host(nfft, sided);
@@ -1517,6 +1609,16 @@ int sp_welch_dist_submit(const void *x, int x_dtype, int64_t nsig, const float *
             return -1;
         if (prv.busy && !prev_done && engine_apply_locked(o)) return -1;
         NCCLCHK(rccl.AllReduce(st_d, st_d, nst, ncclDouble, ncclSum, gcomm.comm, geng.epi));
+    } else if (welch_generic_shape(nfft, hop)) {
+        // shapes of the generic one-pass kernel: this step's state, then k_op_apply on the engine's stream (B-ordered)
+        if (geng.st[s].ensure(sizeof(double) * (5 * (size_t)nfft + 8))) return -1;
+        double *st_d = (double *)geng.st[s].p;
+        if (welch_export_locked(x, cplx, nsig, win, nfft, hop, nframes, nmean, st_d, nullptr, nullptr, nullptr, &sl)) return -1;
+        Xf xf;
+        if (get_xf(nfft, &xf)) return -1;
+        void *Wf_d;
+        if (get_window_spectrum(win, nfft, xf, &Wf_d)) return -1;
+        LAUNCHCHK(launch_op_apply(ec, st_d, (const cf *)Wf_d, nfft, sided, scale / (double)frames_total, pxx_out));
     } else {
         FusedOut fo{false, sided, scale / (double)frames_total, pxx_out, false};
         if (welch_accum_locked(x, cplx, nsig, win, nfft, hop, nframes, nmean, false, &fo, &sl)) return -1;

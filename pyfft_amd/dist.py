@@ -19,7 +19,7 @@ ShardPlan = namedtuple("ShardPlan", "rank world nfft hop frames_total first_fram
 def shard_plan(total_samples, nfft, hop, world, rank):
     """Contiguous frame ranges, as even as possible.  Rank r owns the samples from its first frame's first sample up
     to the next rank's first frame (the last rank: to the end of the stream); it additionally READS the halo that
-    its last frames extend into."""
+    its last frames extend into (with hop > nfft it reads up to the next rank's first frame: the gap samples it owns)."""
     total_samples, nfft, hop = int(total_samples), int(nfft), int(hop)
     if total_samples < nfft:
         raise ValueError("stream shorter than one segment")
@@ -30,7 +30,7 @@ def shard_plan(total_samples, nfft, hop, world, rank):
     f0 = rank * base + min(rank, extra)
     nf = base + (1 if rank < extra else 0)
     first = f0 * hop
-    nsamp = (nf - 1) * hop + nfft
+    nsamp = max((nf - 1) * hop + nfft, nf * hop)
     own_end = total_samples if rank == world - 1 else (f0 + nf) * hop
     own_start = 0 if rank == 0 else first
     return ShardPlan(rank, world, nfft, hop, M, f0, nf, first, nsamp if rank < world - 1 else total_samples - first,
@@ -54,7 +54,8 @@ def welch_psd_sharded(x_local, win, plan, scale=1.0, sided=2, group=None, backen
     scalars: 5 nfft + 8 doubles, 160 KiB at nfft = 4096 -- latency-bound on any topology), the states are summed with
     one all_reduce, and every rank applies the global mean to the sum.  `backend` = (export, apply) callables; default:
     the HIP kernels (sp_welch_export / sp_welch_apply).  With world == 1 no collective is issued unless force_collective
-    (a process group of one rank: the RCCL call path on a one-GPU box)."""
+    (a process group of one rank: the RCCL call path on a one-GPU box).  Shapes: any nfft of one workgroup transform
+    (powers of two up to 8192, other lengths up to 4096) with any hop; longer segments are refused."""
     import torch
     import torch.distributed as dist
     export, apply = backend if backend is not None else _device_backend()
