@@ -182,6 +182,21 @@ int sp_stft(const void *x, int x_dtype, int64_t nsig, const float *win, int nfft
             int detrend, double mean_re, double mean_im, int sided, double amp_scale, int out_kind,
             int out_major, void *out, double *pseg_out, int mem);
 
+/* ---- bispectrum and bicoherence (Kim & Powers 1979) over the frames of sp_stft: frame g = win * (x[g*hop : g*hop+nfft] - trend),
+ *      detrend SP_DETREND_CONST (mean_re + i mean_im), SP_DETREND_MEAN or SP_DETREND_LINEAR over the whole record, unnormalised
+ *      forward FFTs X_g, Y_g, Z_g of x, y, z.  Real float32 input: bins 0 .. nfft/2 (SP_SIDED_HALF), nb = nfft/2 + 1, sum bin
+ *      s = i + j; complex64 input: two-sided fftshift-ed bins (SP_SIDED_TWO, bin nfft/2 is frequency 0), nb = nfft,
+ *      s = i + j - nfft/2.  A pair (i, j) is valid when 0 <= s < nb.  With M = nframes, on the nb x nb grid:
+ *        B_out[i][j]  = (1/M) sum_g X_g(i) Y_g(j) conj(Z_g(s))          complex128
+ *        b2_out[i][j] = |B|^2 / (D P[s]), D = (1/M) sum_g |X_g(i) Y_g(j)|^2; 0 where D P = 0
+ *        pzz_out[s]   = P[s] = (1/M) sum_g |Z_g(s)|^2                    float64 [nb], may be NULL
+ *      B and b2 are NaN outside the valid region.  y = z = NULL: the auto bispectrum of x (computed for j <= i and mirrored:
+ *      exactly symmetric); otherwise y and z (NULL = x) are records of x's length and dtype.  8 <= nfft <= 4096.  Every
+ *      pointer follows `mem`.  Deterministic: the frame sums are reduced in a fixed order. */
+int sp_bispectrum(const void *x, const void *y, const void *z, int x_dtype, int64_t nsig, const float *win, int nfft, int hop,
+                  int64_t nframes, int detrend, double mean_re, double mean_im, void *B_out, double *b2_out, double *pzz_out,
+                  int mem);
+
 /* ---- N3: Doppler.cog applied per STFT frame (Doppler.py:43-58; the loop body of cogspec, Doppler.py:73-81):
  *      cog_out[g] = sum_k f_k |X_g[k]|^2 / sum_k |X_g[k]|^2 over the two-sided spectrum of frame g, f_k = fftfreq(nfft, 1/fs),
  *      restricted to fmin <= |f_k| <= fmax (fmin = 0, fmax >= fs/2: every bin); 0 where the band holds no power.  The

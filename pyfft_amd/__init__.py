@@ -27,3 +27,5 @@ from . import doppler                                        # noqa: F401   (Dop
 from .doppler import cog, cog_frames                         # noqa: F401
 from . import heatpulse                                      # noqa: F401   (HeatPulse_Funcs._PWELCH_chloop as one call)
 from .heatpulse import pwelch_chloop                         # noqa: F401
+from . import bispectrum as _bispectrum_mod                     # noqa: F401
+from .bispectrum import bispectrum, bicoherence              # noqa: F401

@@ -16,6 +16,7 @@ namespace sp {
 //   SP_STFT_NOFAST, SP_COG_TWOPASS, SP_COG_GENERIC
 //   SP_HILBERT_NOFUSEMID, SP_HILBERT_PAIRLOAD, SP_COLS_NOHALF, SP_XC_NOFUSEMID, SP_BIGFFT_5PASS
 //   SP_DIST_RESERVE_CUS, SP_DIST_RCCL_CTAS (int: the sharded PSD's CU reserve and the communicator's workgroup limit)
+//   SP_BISPEC_MIB (int: the bispectrum's spectra and partials budget per frame chunk, MiB)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
     return v && v[0] && v[0] != '0';
@@ -288,6 +289,20 @@ int launch_epi_spec(LaunchCtx c, const double *pxx, const double *pyy, const dou
                     int nfft, int onesided, cf *X, double *rowmax /* [1 + nch] scratch: the rows' scales */);
 int launch_epi_corr(LaunchCtx c, const cf *X, int nch, int nfft, int onesided, double *rxx, double *ryy, double *rxy, double *icxy,
                     double *ee, double *cc, const double *rowmax);
+
+// bispectrum (k_bispec.hip): 64 x 64 tiles of (i, j) pairs x chunks of 256 frames over frame-major spectra [m][nb]; fp32 partials
+// part[tile][chunk][3][4096] summed in float64 into acc[tile][3][4096] and p64[nb] (first: start from zero), then the nb x nb outputs
+int bispec_tile_dim();
+int bispec_frame_chunk();
+size_t bispec_part_floats();
+int launch_bispec_tile(LaunchCtx c, const cf *X, const cf *Y, const cf *Z, int nb, int c0, int64_t m, const int2 *tiles, int ntiles,
+                       float *part);
+int launch_bispec_pzz(LaunchCtx c, const cf *Z, int nb, int64_t m, double *ppart);
+int launch_bispec_reduce(LaunchCtx c, const float *part, const double *ppart, int ntiles, int64_t m, int nb, int first, double *acc,
+                         double *p64);
+int launch_bispec_finish(LaunchCtx c, const double *acc, const double *p64, const int *tmap, int ntd, int nb, int c0, int sym, int64_t M,
+                         void *B, double *b2, double *pzz);
+int launch_bispec_trend_shift(LaunchCtx c, const float *src, float *dst, int nrec, int64_t off);
 
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;

@@ -85,6 +85,7 @@ struct Ctx {
     Scratch pend_trend;                       // trend record a pending sp_welch_accum keeps until sp_welch_finish
     Scratch bigA, bigB, bigT, blueA, blueB, longrec;   // long (multi-kernel) paths
     Scratch sosY, sosZ;                            // cascaded sections: sosfiltfilt's forward output, staged zi / zf
+    Scratch bsIn, bsS, bsP, bsA;                    // bispectrum: staged inputs, spectra, fp32 partials, float64 sums
     Scratch cmS, cmT, cmG, cmH, cmO;               // CSD matrix: spectra, bin-major spectra, float64 accumulator, packed-spectra sums, one-pass means state
     std::map<int64_t, BigTw> bigtw;           // N -> two-level twiddle tables of the multi-pass FFT
     std::map<int64_t, BlueTab> blue_big;      // n -> chirp[n], FFT_L(chirp*) (unscaled) for multi-pass Bluestein
@@ -2276,6 +2277,110 @@ int sp_stft_cog(const void *x, int x_dtype, int64_t nsig, const float *win, int 
     LAUNCHCHK(launch_cog_finish(lc(), acc, wpf, nframes, df, fin));
     if (!mem) {
         HIPCHK(hipMemcpyAsync(cog_out, fin, sizeof(double) * (size_t)nframes, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
+int sp_bispectrum(const void *x, const void *y, const void *z, int x_dtype, int64_t nsig, const float *win, int nfft, int hop,
+                  int64_t nframes, int detrend, double mean_re, double mean_im, void *B_out, double *b2_out, double *pzz_out,
+                  int mem) {
+    if (ensure_init()) return -1;
+    if (nfft < 8 || nfft > 4096 || !wg_capable(nfft)) return fail("sp_bispectrum: nfft %d outside 8 .. 4096", nfft);
+    if (check_frames("sp_bispectrum", nsig, nfft, hop, nframes)) return -1;
+    if (x_dtype != SP_DTYPE_F32 && x_dtype != SP_DTYPE_C64) return fail("sp_bispectrum: unknown dtype %d", x_dtype);
+    if (detrend < SP_DETREND_CONST || detrend > SP_DETREND_LINEAR) return fail("sp_bispectrum: detrend must be 0, 1 or 2");
+    if (!x || !B_out || !b2_out) return fail("sp_bispectrum: x, B_out and b2_out are required");
+    ApiLock lk;
+    Xf xf;
+    if (get_xf(nfft, &xf)) return -1;
+    const bool cplx = x_dtype == SP_DTYPE_C64;
+    const bool sym = y == nullptr && z == nullptr;       // auto bispectrum: one spectrum, j <= i tiles, mirrored
+    const int nsp = sym ? 1 : 3;
+    const int nb = cplx ? nfft : nfft / 2 + 1, c0 = cplx ? nfft / 2 : 0;
+    const int sided = cplx ? SP_SIDED_TWO : SP_SIDED_HALF;
+    const size_t esz = cplx ? 8 : 4;
+    const void *src[3] = {x, y ? y : x, z ? z : x};
+    const void *xd[3] = {x, src[1], src[2]};
+    if (!mem) {
+        if (g.bsIn.ensure(esz * (size_t)nsig * (size_t)nsp)) return -1;
+        for (int k = 0; k < nsp; ++k) {
+            xd[k] = (char *)g.bsIn.p + esz * (size_t)nsig * (size_t)k;
+            HIPCHK(hipMemcpyAsync((void *)xd[k], src[k], esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
+        }
+    }
+    if (sym) xd[1] = xd[2] = xd[0];
+    // the tiles that meet the valid region (j <= i for the auto case) and the map (ti, tj) -> tile number (-1: none)
+    const int T = bispec_tile_dim(), ntd = (nb + T - 1) / T;
+    std::vector<int> tbl((size_t)ntd * ntd, -1);        // [tmap | tile list as int2]
+    std::vector<int> tl;
+    for (int ti = 0; ti < ntd; ++ti)
+        for (int tj = 0; tj < (sym ? ti + 1 : ntd); ++tj) {
+            const int imax = std::min(ti * T + T, nb) - 1, jmax = std::min(tj * T + T, nb) - 1;
+            if (ti * T + tj * T - c0 > nb - 1 || imax + jmax - c0 < 0) continue;
+            tbl[(size_t)ti * ntd + tj] = (int)tl.size() / 2;
+            tl.push_back(ti);
+            tl.push_back(tj);
+        }
+    const int ntiles = (int)tl.size() / 2;
+    const size_t nmap = tbl.size() + (tbl.size() & 1);   // the int2 list starts 8-byte aligned
+    tbl.resize(nmap, -1);
+    tbl.insert(tbl.end(), tl.begin(), tl.end());
+    void *tab_d;
+    if (get_table(6, tbl.data(), sizeof(int) * tbl.size(), &tab_d, nullptr)) return -1;
+    const int *tmap_d = (const int *)tab_d;
+    const int2 *tiles_d = (const int2 *)((const int *)tab_d + nmap);
+    // frames in chunks of whole 256-frame partial chunks: the spectra and the partials stay within SP_BISPEC_MIB MiB each
+    // (default 256; a test hook like those of launch.h, read on every call)
+    const int64_t FC = bispec_frame_chunk();
+    const size_t budget = (size_t)std::max(1, env_int("SP_BISPEC_MIB", 256)) << 20;
+    const size_t part_bytes = sizeof(float) * bispec_part_floats() * (size_t)ntiles;   // per partial chunk
+    const size_t spec_bytes = sizeof(cf) * (size_t)nb * (size_t)nsp * (size_t)FC;      // per partial chunk
+    int64_t cpc = (int64_t)std::min(budget / spec_bytes, budget / part_bytes);
+    cpc = std::max<int64_t>(1, std::min<int64_t>(cpc, 4096));
+    const int64_t mc = std::min(nframes, cpc * FC);
+    const int64_t nfc = (mc + FC - 1) / FC;
+    if (g.bsS.ensure(sizeof(cf) * (size_t)nb * (size_t)nsp * (size_t)mc) || g.bsP.ensure(part_bytes * (size_t)nfc) ||
+        g.bsA.ensure(sizeof(double) * (bispec_part_floats() * (size_t)ntiles + (size_t)nb * (size_t)(nfc + 1))))
+        return -1;
+    cf *S[3];
+    for (int k = 0; k < 3; ++k) S[k] = (cf *)g.bsS.p + (size_t)nb * (size_t)mc * (size_t)(sym ? 0 : k);
+    float *part = (float *)g.bsP.p;
+    double *acc = (double *)g.bsA.p, *p64 = acc + bispec_part_floats() * (size_t)ntiles, *ppart = p64 + nb;
+    void *win_d;
+    if (get_table(1, win, sizeof(float) * (size_t)nfft, &win_d, nullptr)) return -1;
+    TrendBuf tb;
+    if (get_trendbuf(6, &tb)) return -1;                  // records 0 .. 2: the signals' trends; 3 .. 5: shifted to a chunk
+    for (int k = 0; k < nsp; ++k)
+        if (set_trend(tb, k, xd[k], cplx, nsig, detrend, mean_re, mean_im)) return -1;
+    for (int64_t f0 = 0; f0 < nframes; f0 += mc) {
+        const int64_t m = std::min(mc, nframes - f0);
+        LAUNCHCHK(launch_bispec_trend_shift(lc(), tb.f, tb.f + 12, nsp, f0 * (int64_t)hop));
+        const RunPart rp = run_partition(xf.L, m, g.ncu);
+        for (int k = 0; k < nsp; ++k)
+            LAUNCHCHK(launch_stft(lc(), (const char *)xd[k] + esz * (size_t)(f0 * hop), cplx, (const float *)win_d, hop, m,
+                                  tb.f + 12 + 4 * k, detrend == SP_DETREND_LINEAR, xf, rp, sided, 1.f, 0, S[k], nullptr));
+        {
+            ProfScope ps;
+            LAUNCHCHK(launch_bispec_tile(lc(), S[0], S[1], S[2], nb, c0, m, tiles_d, ntiles, part));
+        }
+        LAUNCHCHK(launch_bispec_pzz(lc(), S[2], nb, m, ppart));
+        LAUNCHCHK(launch_bispec_reduce(lc(), part, ppart, ntiles, m, nb, f0 == 0, acc, p64));
+    }
+    void *Bd = B_out;
+    double *b2d = b2_out, *pzd = pzz_out;
+    const size_t nn = (size_t)nb * (size_t)nb;
+    if (!mem) {
+        if (g.out0.ensure(sizeof(double) * (3 * nn + (size_t)nb))) return -1;
+        Bd = g.out0.p;
+        b2d = (double *)g.out0.p + 2 * nn;
+        pzd = pzz_out ? b2d + nn : nullptr;
+    }
+    LAUNCHCHK(launch_bispec_finish(lc(), acc, p64, tmap_d, ntd, nb, c0, sym ? 1 : 0, nframes, Bd, b2d, pzd));
+    if (!mem) {
+        HIPCHK(hipMemcpyAsync(B_out, Bd, 2 * sizeof(double) * nn, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipMemcpyAsync(b2_out, b2d, sizeof(double) * nn, hipMemcpyDeviceToHost, g.stream));
+        if (pzz_out) HIPCHK(hipMemcpyAsync(pzz_out, pzd, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, g.stream));
         HIPCHK(hipStreamSynchronize(g.stream));
     }
     return 0;

@@ -427,6 +427,47 @@ def stft_frames(x, win, hop, nframes, detrend=True, sided=SIDED_ONE, amp_scale=1
     return out, pseg
 
 
+# ------------------------------------------------------------------------------------------ bispectrum
+def bispectrum(x, win, hop, nframes, y=None, z=None, detrend=True, mean_value=None):
+    """Bispectrum of the frames win * (x[g*hop : g*hop+nfft] - trend): (B complex128 [nb, nb], b2 float64 [nb, nb], Pzz float64
+    [nb]), sp_bispectrum's conventions (real input: bins 0 .. nfft/2; complex: two-sided, fftshift-ed; NaN outside the valid
+    region).  y = z = None: the auto bispectrum; otherwise y and z (None = x) match x's length and dtype.  detrend: as
+    stft_frames, whole-record modes only.  numpy in -> numpy out; device tensors in -> device tensors on x's stream."""
+    w = _win32(win)
+    nfft = w.size
+    want, mv = _detrend_args(detrend, mean_value)
+    if want not in (_ffi.DETREND_CONST, _ffi.DETREND_MEAN, _ffi.DETREND_LINEAR):
+        raise ValueError("bispectrum: detrend must be none, mean or linear over the whole record")
+    if _is_torch(x):
+        _bind_stream(x)
+        xs = _torch_samples(x)
+        others = [None if v is None else _torch_samples(v) for v in (y, z)]
+        for v in others:
+            if v is not None and (v.dtype != xs.dtype or v.numel() != xs.numel() or v.device != xs.device):
+                raise ValueError("bispectrum: y and z must match x's length, dtype and device")
+        nb = nfft if xs.dtype == torch.complex64 else nfft // 2 + 1
+        B = torch.empty((nb, nb), dtype=torch.complex128, device=xs.device)
+        b2 = torch.empty((nb, nb), dtype=torch.float64, device=xs.device)
+        pzz = torch.empty(nb, dtype=torch.float64, device=xs.device)
+        yp, zp = (None if v is None else ptr(v.data_ptr()) for v in others)
+        check(lib().sp_bispectrum(ptr(xs.data_ptr()), yp, zp, _tcode(xs), xs.numel(), ptr(w), nfft, int(hop), int(nframes), want,
+                                  mv.real, mv.imag, ptr(B.data_ptr()), ptr(b2.data_ptr()), ptr(pzz.data_ptr()), 1))
+        return B, b2, pzz
+    xs = _ffi.as_samples(x)
+    others = [None if v is None else _ffi.as_samples(v) for v in (y, z)]
+    for v in others:
+        if v is not None and (v.dtype != xs.dtype or v.size != xs.size):
+            raise ValueError("bispectrum: y and z must match x's length and dtype")
+    nb = nfft if xs.dtype == np.complex64 else nfft // 2 + 1
+    B = np.empty((nb, nb), dtype=np.complex128)
+    b2 = np.empty((nb, nb), dtype=np.float64)
+    pzz = np.empty(nb, dtype=np.float64)
+    _ffi.init()
+    check(lib().sp_bispectrum(ptr(xs), ptr(others[0]), ptr(others[1]), _ffi.dtype_code(xs.dtype), xs.size, ptr(w), nfft, int(hop),
+                              int(nframes), want, mv.real, mv.imag, ptr(B), ptr(b2), ptr(pzz), 0))
+    return B, b2, pzz
+
+
 # ------------------------------------------------------------------------------------------ N3
 def stft_cog(x, win, hop, nframes, fs, fmin=0.0, fmax=None, detrend=False, mean_value=None):
     """Centre of gravity (power-weighted mean frequency, Doppler.py:43-58) of every frame's two-sided spectrum, reduced

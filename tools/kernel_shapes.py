@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-launch-shape kernel times from a rocprofv3 --kernel-trace CSV: median / min / count per (kernel, grid X, grid Y),
 for the kernels whose name contains PATTERN.
-  python tools/kernel_shapes.py <kernel_trace.csv> [PATTERN]"""
+  python tools/kernel_shapes.py <kernel_trace.csv> [PATTERN]
+e.g. PATTERN k_bispec: k_bispec_tile (grid X: 256 threads per tile, Y: 256-frame chunks), k_bispec_pzz, k_bispec_reduce, k_bispec_finish."""
 import collections
 import csv
 import sys
