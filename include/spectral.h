@@ -182,6 +182,26 @@ int sp_stft(const void *x, int x_dtype, int64_t nsig, const float *win, int nfft
             int detrend, double mean_re, double mean_im, int sided, double amp_scale, int out_kind,
             int out_major, void *out, double *pseg_out, int mem);
 
+/* ---- inverse STFT: overlap-add synthesis, the inverse of sp_stft's frames (scipy.signal.istft's arithmetic).
+ *      Frames Z_g, g = 0 .. M-1 (M = nframes), window win[0:nfft], 1 <= hop <= nfft:
+ *        x_g    = ifft_nfft(Z_g)                                  (1/nfft normalisation)
+ *        L      = (M-1)*hop + nfft
+ *        num[n] = sum_g win[n - g*hop] * x_g[n - g*hop]           0 <= n < L
+ *        env[n] = sum_g win[n - g*hop]^2
+ *        y[n]   = scale * num[n] / env[n]  where env[n] > 1e-10,  scale * num[n] elsewhere
+ *      and the call writes y[skip : skip + nout].  scale = sum(win), skip = nfft/2, nout = L - 2*(nfft/2) is
+ *      scipy.signal.istft(boundary=True); skip = 0, nout = L is boundary=False.
+ *      sided SP_SIDED_HALF: one-sided spectra, nb = nfft/2 + 1 bins, y float32 (the imaginary parts of bin 0 and, for even
+ *      nfft, bin nfft/2 are ignored as irfft does); SP_SIDED_RAW: two-sided spectra in fftfreq order, nb = nfft, y complex64.
+ *      in_major 0: Z[nch][M][nb] (sp_stft's out_major 0), 1: Z[nch][nb][M] (out_major 1, scipy's layout).
+ *      nch >= 1 independent records, contiguous: y[nch][nout].
+ *      nfft: what runs in one workgroup transform (powers of two up to sp_max_wg_fft(), other lengths up to half of it).
+ *      env is summed in float64 on the host.  No atomics: every output sample is summed by one workgroup in frame order, so the
+ *      result is bitwise reproducible.  A bad argument returns < 0 with sp_last_error() set and leaves y untouched.
+ *      Every pointer but win follows `mem`. */
+int sp_istft(const void *Z, int sided, int in_major, int nch, int64_t nframes, const float *win, int nfft, int hop,
+             double scale, int64_t skip, int64_t nout, void *y, int mem);
+
 /* ---- bispectrum and bicoherence (Kim & Powers 1979) over the frames of sp_stft: frame g = win * (x[g*hop : g*hop+nfft] - trend),
  *      detrend SP_DETREND_CONST (mean_re + i mean_im), SP_DETREND_MEAN or SP_DETREND_LINEAR over the whole record, unnormalised
  *      forward FFTs X_g, Y_g, Z_g of x, y, z.  Real float32 input: bins 0 .. nfft/2 (SP_SIDED_HALF), nb = nfft/2 + 1, sum bin

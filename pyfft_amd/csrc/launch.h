@@ -17,6 +17,7 @@ namespace sp {
 //   SP_HILBERT_NOFUSEMID, SP_HILBERT_PAIRLOAD, SP_COLS_NOHALF, SP_XC_NOFUSEMID, SP_BIGFFT_5PASS
 //   SP_DIST_RESERVE_CUS, SP_DIST_RCCL_CTAS (int: the sharded PSD's CU reserve and the communicator's workgroup limit)
 //   SP_BISPEC_MIB (int: the bispectrum's spectra and partials budget per frame chunk, MiB)
+//   SP_ISTFT_FPG, SP_ISTFT_MIB (int: the inverse STFT's frames per run; its budget for transposed bin-major spectra, MiB)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
     return v && v[0] && v[0] != '0';
@@ -303,6 +304,17 @@ int launch_bispec_reduce(LaunchCtx c, const float *part, const double *ppart, in
 int launch_bispec_finish(LaunchCtx c, const double *acc, const double *p64, const int *tmap, int ntd, int nb, int c0, int sym, int64_t M,
                          void *B, double *b2, double *pzz);
 int launch_bispec_trend_shift(LaunchCtx c, const float *src, float *dst, int nrec, int64_t off);
+
+// inverse STFT (k_istft.hip): runs of `fpg` frames from [fbeg, fend) overlap-added in an LDS ring, each preceded by `halo` frames that
+// are only accumulated; Z holds the frames zbase .. frame-major (zbase <= max(0, fbeg - halo)).  mode 0: two-sided spectra -> complex
+// output, 1: one-sided -> real, 2: one-sided, two frames per transform (power-of-two n >= 32; fbeg, fpg and halo even).
+// rcp = reciprocal envelope [period: hop][head: head_len][tail: n - hop]; emit_tail: the run that ends at frame M also writes [M hop, L)
+int istft_resident(const Xf &xf, int mode);
+int launch_istft(LaunchCtx c, const cf *Z, int64_t z_cs, int64_t zbase, int64_t M, int64_t fbeg, int64_t fend, int64_t fpg, int halo,
+                 const float *win, float wscale, int hop, const Xf &xf, int mode, const float *rcp, int64_t head_len, int64_t skip,
+                 int64_t nout, void *y, int nch, int emit_tail);
+// bin-major in[ch][nb][M] -> frame-major out[ch][m][nb] for the frames f0 .. f0 + m - 1
+int launch_istft_gather(LaunchCtx c, const cf *in, int64_t M, int nb, int64_t f0, int64_t m, cf *out, int nch);
 
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;

@@ -2386,6 +2386,120 @@ int sp_bispectrum(const void *x, const void *y, const void *z, int x_dtype, int6
     return 0;
 }
 
+// reciprocal window-square envelope of sp_istft as [period: hop][head: head_len][tail: n - hop] float32 from float64 sums; entries
+// whose envelope is <= 1e-10 are 1 (scipy's rule: such samples are not divided).  Away from the ends env[a] = P[a mod hop]; the first
+// n - hop samples lack the frames before 0 and the last n - hop those from M on.  With so few frames that the two ends meet
+// (M hop < n - hop) the head piece covers the whole output instead and there is no tail.
+static int64_t istft_head_len(int n, int hop, int64_t M) {
+    return M * (int64_t)hop >= (int64_t)(n - hop) ? (int64_t)(n - hop) : (M - 1) * (int64_t)hop + n;
+}
+static void istft_envelope(const float *win, int n, int hop, int64_t M, std::vector<float> *out) {
+    const int64_t H = istft_head_len(n, hop, M);
+    const bool whole = H != (int64_t)(n - hop);
+    std::vector<double> per((size_t)hop, 0.0), head((size_t)H, 0.0), tail(whole ? 0 : (size_t)(n - hop), 0.0);
+    for (int j = 0; j < n; ++j) per[(size_t)(j % hop)] += (double)win[j] * (double)win[j];
+    if (whole) {
+        for (int64_t g = 0; g < M; ++g)
+            for (int j = 0; j < n; ++j) head[(size_t)(g * hop + j)] += (double)win[j] * (double)win[j];
+    } else {
+        for (int a = 0; a < n - hop; ++a) head[(size_t)a] = (double)win[a] * (double)win[a] + (a >= hop ? head[(size_t)(a - hop)] : 0.0);
+        for (int i = n - hop - 1; i >= 0; --i)
+            tail[(size_t)i] = (double)win[i + hop] * (double)win[i + hop] + (i + hop < n - hop ? tail[(size_t)(i + hop)] : 0.0);
+    }
+    out->clear();
+    out->reserve(per.size() + head.size() + tail.size());
+    for (const std::vector<double> *v : {&per, &head, &tail})
+        for (double e : *v) out->push_back(e > 1e-10 ? (float)(1.0 / e) : 1.f);
+}
+
+int sp_istft(const void *Z, int sided, int in_major, int nch, int64_t nframes, const float *win, int nfft, int hop, double scale,
+             int64_t skip, int64_t nout, void *y, int mem) {
+    if (!Z || !win || !y) return fail("sp_istft: Z, win and y are required");
+    if (sided != SP_SIDED_HALF && sided != SP_SIDED_RAW) return fail("sp_istft: sided must be SP_SIDED_HALF or SP_SIDED_RAW");
+    if (in_major != 0 && in_major != 1) return fail("sp_istft: in_major must be 0 or 1");
+    if (nfft < 2 || hop < 1 || hop > nfft) return fail("sp_istft: need nfft >= 2 and 1 <= hop <= nfft (nfft %d, hop %d)", nfft, hop);
+    if (nframes < 1 || nch < 1) return fail("sp_istft: nframes and nch must be at least 1");
+    if (!wg_capable(nfft))
+        return fail("sp_istft: nfft %d not supported (powers of two up to %d, other lengths up to %d)", nfft, SP_MAX_WG_FFT,
+                    SP_MAX_WG_FFT / 2);
+    if (nframes > ((int64_t)1 << 40) / hop) return fail("sp_istft: too many frames");
+    const int64_t M = nframes, Lout = (M - 1) * (int64_t)hop + nfft;
+    if (skip < 0 || nout < 1 || skip > Lout || nout > Lout - skip)
+        return fail("sp_istft: skip %lld + nout %lld outside the %lld overlap-added samples", (long long)skip, (long long)nout,
+                    (long long)Lout);
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    Xf xf;
+    if (get_xf(nfft, &xf)) return -1;
+    const bool cplx = sided == SP_SIDED_RAW;
+    const int nb = cplx ? nfft : nfft / 2 + 1;
+    // real output from a power-of-two transform: two frames per transform
+    const int mode = cplx ? 0 : ((!xf.blue && xf.L >= 32 && M >= 2 && !env_flag("SP_NO_REALPAIR")) ? 2 : 1);
+    const size_t zbytes = sizeof(cf) * (size_t)nb * (size_t)M * (size_t)nch, ybytes = (cplx ? 8 : 4) * (size_t)nout * (size_t)nch;
+    const cf *zd = (const cf *)Z;
+    void *yd = y;
+    if (!mem) {
+        if (g.in0.ensure(zbytes) || g.out0.ensure(ybytes)) return -1;
+        HIPCHK(hipMemcpyAsync(g.in0.p, Z, zbytes, hipMemcpyHostToDevice, g.stream));
+        zd = (const cf *)g.in0.p;
+        yd = g.out0.p;
+    }
+    void *win_d;
+    if (get_table(1, win, sizeof(float) * (size_t)nfft, &win_d, nullptr)) return -1;
+    // the envelope pieces, cached beside the window by (window, hop, and the frame count where the two ends meet)
+    const int64_t head_len = istft_head_len(nfft, hop, M);
+    const bool ends_apart = head_len == (int64_t)(nfft - hop);
+    const uint64_t ekey[4] = {window_key(win, nfft), (uint64_t)nfft, (uint64_t)hop, ends_apart ? ~(uint64_t)0 : (uint64_t)M};
+    const size_t ebytes = sizeof(float) * ((size_t)hop + (size_t)head_len + (ends_apart ? (size_t)(nfft - hop) : 0));
+    void *rcp_d;
+    bool fresh = false;
+    if (get_table_keyed(7, ekey, sizeof ekey, nullptr, ebytes, &rcp_d, &fresh)) return -1;
+    if (fresh) {
+        std::vector<float> e;
+        istft_envelope(win, nfft, hop, M, &e);
+        HIPCHK(hipMemcpy(rcp_d, e.data(), ebytes, hipMemcpyHostToDevice));
+    }
+    // runs: about 4 groups per CU, and long enough that the q - 1 halo frames a run transforms twice stay a few per cent of it
+    // (SP_ISTFT_FPG: a test hook like those of launch.h, read on every call; any value >= 1 is valid, also below q)
+    const int FR = mode == 2 ? 2 : 1;
+    const int q = (nfft + hop - 1) / hop;
+    const int halo = (q - 1 + FR - 1) / FR * FR;
+    const int fpw = fpw_of(xf.L);
+    auto run_len = [&](int64_t m) {
+        int64_t f = env_int("SP_ISTFT_FPG", 0);
+        if (f < 1) {
+            const int64_t target = std::max<int64_t>(1, (int64_t)g.ncu * 4 * fpw / nch);
+            f = std::max((m + target - 1) / target, std::min<int64_t>(16 * (int64_t)halo, m));
+        }
+        f = std::max<int64_t>(f, 1);
+        return (f + FR - 1) / FR * FR;
+    };
+    const float wscale = (float)(scale / (double)nfft);
+    if (in_major == 0) {
+        LAUNCHCHK(launch_istft(lc(), zd, (int64_t)nb * M, 0, M, 0, M, run_len(M), halo, (const float *)win_d, wscale, hop, xf, mode,
+                               (const float *)rcp_d, head_len, skip, nout, yd, nch, 1));
+    } else {
+        // bin-major spectra: chunks of frames, each with its halo, are transposed into scratch held to SP_ISTFT_MIB MiB (default 256)
+        const size_t budget = (size_t)std::max(1, env_int("SP_ISTFT_MIB", 256)) << 20;
+        int64_t mc = (int64_t)(budget / (sizeof(cf) * (size_t)nb * (size_t)nch)) - halo;
+        mc = std::max<int64_t>(mc, std::max<int64_t>(halo, 2)) / FR * FR;
+        mc = std::min(mc, (M + FR - 1) / FR * FR);
+        if (g.work.ensure(sizeof(cf) * (size_t)nb * (size_t)nch * (size_t)(mc + halo))) return -1;
+        for (int64_t c0 = 0; c0 < M; c0 += mc) {
+            const int64_t c1 = std::min(M, c0 + mc), zb = std::max<int64_t>(0, c0 - halo), m = c1 - zb;
+            LAUNCHCHK(launch_istft_gather(lc(), zd, M, nb, zb, m, (cf *)g.work.p, nch));
+            LAUNCHCHK(launch_istft(lc(), (const cf *)g.work.p, (int64_t)nb * m, zb, M, c0, c1, run_len(c1 - c0), halo,
+                                   (const float *)win_d, wscale, hop, xf, mode, (const float *)rcp_d, head_len, skip, nout, yd, nch,
+                                   c1 == M));
+        }
+    }
+    if (!mem) {
+        HIPCHK(hipMemcpyAsync(y, yd, ybytes, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
 int sp_hilbert(const float *x, int64_t n_in, int64_t x_ld, int64_t nfft, int64_t batch, void *out, int mem) {
     if (ensure_init()) return -1;
     if (n_in < 1 || nfft < 2 || batch < 1 || x_ld < n_in) return fail("sp_hilbert: bad sizes");

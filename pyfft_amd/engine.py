@@ -427,6 +427,46 @@ def stft_frames(x, win, hop, nframes, detrend=True, sided=SIDED_ONE, amp_scale=1
     return out, pseg
 
 
+# ------------------------------------------------------------------------------------------ inverse STFT
+def istft_frames(Z, win, hop, sided=SIDED_HALF, scale=None, bin_major=False, skip=0, nout=None):
+    """Overlap-add synthesis of the frames Z (sp_istft): y[n] = scale * sum_g win[n - g hop] ifft(Z_g)[n - g hop] / sum_g
+    win[n - g hop]^2 over the L = (M - 1) hop + nfft samples the M frames reach, returned as y[skip : skip + nout] (nout=None:
+    up to L).  Z: complex64 [..., M, nb], or [..., nb, M] with bin_major; nb = nfft // 2 + 1 for sided=SIDED_HALF (float32
+    output) or nfft for SIDED_RAW (fftfreq order, complex64 output); the leading axes are independent records.  scale=None:
+    sum(win), the inverse of stft_frames(amp_scale=1 / sum(win)).  numpy in -> numpy out; device tensor in -> device tensor
+    on the caller's stream."""
+    w = _win32(win)
+    nfft = w.size
+    if sided not in (SIDED_HALF, SIDED_RAW):
+        raise ValueError("istft_frames: sided must be SIDED_HALF or SIDED_RAW")
+    nb = nbins(nfft, sided)
+    if Z.ndim < 2:
+        raise ValueError("istft_frames: Z must be at least two-dimensional")
+    M = int(Z.shape[-1] if bin_major else Z.shape[-2])
+    if int(Z.shape[-2] if bin_major else Z.shape[-1]) != nb:
+        raise ValueError("istft_frames: Z has %d bins, the window needs %d" % (Z.shape[-2] if bin_major else Z.shape[-1], nb))
+    hop, skip = int(hop), int(skip)
+    total = (M - 1) * hop + nfft
+    nout = total - skip if nout is None else int(nout)
+    sc = float(np.sum(np.asarray(win, dtype=np.float64))) if scale is None else float(scale)
+    lead = tuple(int(d) for d in Z.shape[:-2])
+    nch = int(np.prod(lead)) if lead else 1
+    if _is_torch(Z):
+        _bind_stream(Z)
+        if Z.dtype != torch.complex64:
+            raise TypeError("device path takes complex64 spectra, got %s" % Z.dtype)
+        zs = Z.contiguous()
+        y = torch.empty(lead + (max(nout, 0),), dtype=torch.complex64 if sided == SIDED_RAW else torch.float32, device=zs.device)
+        check(lib().sp_istft(ptr(zs.data_ptr()), sided, 1 if bin_major else 0, nch, M, ptr(w), nfft, hop, sc, skip, nout,
+                             ptr(y.data_ptr()), 1))
+        return y
+    zs = np.ascontiguousarray(Z, dtype=np.complex64)
+    y = np.empty(lead + (max(nout, 0),), dtype=np.complex64 if sided == SIDED_RAW else np.float32)
+    _ffi.init()
+    check(lib().sp_istft(ptr(zs), sided, 1 if bin_major else 0, nch, M, ptr(w), nfft, hop, sc, skip, nout, ptr(y), 0))
+    return y
+
+
 # ------------------------------------------------------------------------------------------ bispectrum
 def bispectrum(x, win, hop, nframes, y=None, z=None, detrend=True, mean_value=None):
     """Bispectrum of the frames win * (x[g*hop : g*hop+nfft] - trend): (B complex128 [nb, nb], b2 float64 [nb, nb], Pzz float64

@@ -951,6 +951,20 @@ class fftanal(Struct):
         reference's exception.  sig: default self.sigx."""
         return self._scipy_stft(self.sigx if sig is None else sig)
 
+    def scipy_istft(self, Zxx=None, onesided=None):
+        """(t, x): the inverse of scipy_stft() -- scipy.signal.istft(Zxx, fs, window=self.win, nperseg=nwins, noverlap,
+        input_onesided, boundary=True) with the overlap-add on the GPU, x trimmed to len(self.sigx) (scipy_stft pads the record
+        to a whole number of hops).  Zxx: [nfreq, nseg] as scipy_stft returns it, default the spectra of self.sigx;
+        onesided: default self.onesided."""
+        from .spectrogram import istft as _istft
+        if Zxx is None:
+            Zxx = self.scipy_stft()[2]
+        onesided = self.onesided if onesided is None else onesided
+        t, x = _istft(Zxx, fs=self.Fs, window=np.asarray(self.win, dtype=np.float64), nperseg=self.nwins, noverlap=self.noverlap,
+                      input_onesided=bool(onesided), boundary=True)
+        nsig = len(self.sigx)
+        return t[:nsig], x[..., :nsig]
+
     def fftpwelch(self):
         self.freq, self.Pxy, self.Pxx, self.Pyy, self.Cxy, self.phi_xy, self.fftinfo = fft_pwelch(
             self.tvec, self.sigx, self.sigy, self.tbounds, Navr=self.Navr, windowoverlap=self.overlap,

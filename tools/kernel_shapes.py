@@ -2,7 +2,8 @@
 """Per-launch-shape kernel times from a rocprofv3 --kernel-trace CSV: median / min / count per (kernel, grid X, grid Y),
 for the kernels whose name contains PATTERN.
   python tools/kernel_shapes.py <kernel_trace.csv> [PATTERN]
-e.g. PATTERN k_bispec: k_bispec_tile (grid X: 256 threads per tile, Y: 256-frame chunks), k_bispec_pzz, k_bispec_reduce, k_bispec_finish."""
+e.g. PATTERN k_bispec: k_bispec_tile (grid X: 256 threads per tile, Y: 256-frame chunks), k_bispec_pzz, k_bispec_reduce, k_bispec_finish;
+     PATTERN k_istft: k_istft (grid X: workgroups of 256 / T runs of frames, Y: records), k_istft_gather (bin-major input)."""
 import collections
 import csv
 import sys
