@@ -217,6 +217,24 @@ int sp_bispectrum(const void *x, const void *y, const void *z, int x_dtype, int6
                   int64_t nframes, int detrend, double mean_re, double mean_im, void *B_out, double *b2_out, double *pzz_out,
                   int mem);
 
+/* ---- Thomson multitaper spectra: the frames of sp_welch_psd / sp_welch_csd under K tapers in ONE pass over the record:
+ *        X_{g,k} = FFT(tapers[k] * (x[g*hop : g*hop+nfft] - trend)), Y_{g,k} likewise (y = NULL: the PSD only)
+ *        weights == NULL:  pxx[f] = scale/nframes * sum_k sum_g |X_{g,k}[f]|^2, pyy likewise, pxy = ... conj(X_{g,k}) Y_{g,k}
+ *                          (the caller folds sqrt(c_k) / sqrt(sum tapers[k]^2) into the taper rows)
+ *        weights != NULL:  the eigenspectra skx[k][f] = scale/nframes * sum_g |X_{g,k}[f]|^2 (sky likewise; float64 [K][nb], required)
+ *                          and pxx = sum_k c_k skx[k], pyy, pxy likewise, c = weights / sum(weights), all in float64
+ *                          (the caller folds only 1 / sqrt(sum tapers[k]^2) into the rows; weights: K host doubles >= 0, not all 0)
+ *      tapers: HOST float32 [K][nfft] (device table cache, like the windows), 1 <= K <= 32.  nfft: 8 .. what one workgroup
+ *      transform takes (powers of two up to sp_max_wg_fft(), other lengths up to half of it).  detrend SP_DETREND_CONST (mean_x /
+ *      mean_y: 2 doubles re, im, or NULL for none), SP_DETREND_MEAN or SP_DETREND_LINEAR over the whole record.
+ *      Outputs in float64, raw bin order, nothing doubled: real float32 input -> bins 0 .. nfft/2 (SP_SIDED_HALF, nb = nfft/2 + 1),
+ *      complex64 input -> natural FFT order (SP_SIDED_RAW, nb = nfft); pxy is [nb][2] (re, im).  pyy, pxy, sky are not touched when
+ *      y == NULL.  x, y and the outputs follow `mem`.  No atomics: group partials are summed in float64 in a fixed order, so two calls
+ *      agree bitwise.  A bad argument returns < 0 with sp_last_error() set before the device is touched. */
+int sp_multitaper(const void *x, const void *y, int dtype, int64_t nsig, const float *tapers, int ntapers, int nfft, int hop,
+                  int64_t nframes, int detrend, const double *mean_x, const double *mean_y, const double *weights, double scale,
+                  double *pxx, double *pyy, double *pxy, double *skx, double *sky, int mem);
+
 /* ---- N3: Doppler.cog applied per STFT frame (Doppler.py:43-58; the loop body of cogspec, Doppler.py:73-81):
  *      cog_out[g] = sum_k f_k |X_g[k]|^2 / sum_k |X_g[k]|^2 over the two-sided spectrum of frame g, f_k = fftfreq(nfft, 1/fs),
  *      restricted to fmin <= |f_k| <= fmax (fmin = 0, fmax >= fs/2: every bin); 0 where the band holds no power.  The

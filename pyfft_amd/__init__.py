@@ -29,3 +29,6 @@ from . import heatpulse                                      # noqa: F401   (Hea
 from .heatpulse import pwelch_chloop                         # noqa: F401
 from . import bispectrum as _bispectrum_mod                     # noqa: F401
 from .bispectrum import bispectrum, bicoherence              # noqa: F401
+from . import multitaper as _multitaper_mod                  # noqa: F401
+from .multitaper import (multitaper_psd, multitaper_spectra, multitaper_csd, multitaper_coherence,  # noqa: F401
+                         multitaper_plan)

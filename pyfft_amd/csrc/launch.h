@@ -316,6 +316,18 @@ int launch_istft(LaunchCtx c, const cf *Z, int64_t z_cs, int64_t zbase, int64_t 
 // bin-major in[ch][nb][M] -> frame-major out[ch][m][nb] for the frames f0 .. f0 + m - 1
 int launch_istft_gather(LaunchCtx c, const cf *in, int64_t M, int nb, int64_t f0, int64_t m, cf *out, int nch);
 
+// multitaper spectra (k_mtaper.hip): the frames of x (and y: cross spectra) under every taper of tapers[nblocks * ktap][n] in one
+// launch; grid.y = nblocks taper blocks, each with its own partials.  rp partitions PAIRS of frames for the PSD of a real record and
+// frames otherwise.  partial[nblocks][rp.groups][planes][L], planes = mtaper_partial_planes: 1 in the layout k_welch_finish reads (sym
+// for a real record), 3 that of k_csd_rp_finish (mtaper_xrp_eligible), 4 that of k_csd_finish.  trend: the records of x and y.
+#define SP_MTAPER_MAXK 32
+bool mtaper_xrp_eligible(const Xf &xf, bool cplx);
+int mtaper_partial_planes(const Xf &xf, bool cplx, bool cross);
+int launch_mtaper(LaunchCtx c, const void *x, const void *y, bool cplx, const float *tapers, int nblocks, int ktap, int hop,
+                  int64_t nframes, const float *trend, bool lin, const Xf &xf, float *partial, const RunPart &rp);
+// out[b] = sum_k weights[k] sk[k][b] in float64 (weights: host, K <= SP_MTAPER_MAXK)
+int launch_mtaper_combine(LaunchCtx c, const double *sk, int K, int64_t nb, const double *weights, double *out);
+
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;
 #define SP_CASE_B(Lv, MACRO) case Lv: { MACRO(XfBlue<Lv>) } break;

@@ -86,6 +86,7 @@ struct Ctx {
     Scratch bigA, bigB, bigT, blueA, blueB, longrec;   // long (multi-kernel) paths
     Scratch sosY, sosZ;                            // cascaded sections: sosfiltfilt's forward output, staged zi / zf
     Scratch bsIn, bsS, bsP, bsA;                    // bispectrum: staged inputs, spectra, fp32 partials, float64 sums
+    Scratch mtS;                                    // multitaper: the per-taper cross spectra behind the weighted one
     Scratch cmS, cmT, cmG, cmH, cmO;               // CSD matrix: spectra, bin-major spectra, float64 accumulator, packed-spectra sums, one-pass means state
     std::map<int64_t, BigTw> bigtw;           // N -> two-level twiddle tables of the multi-pass FFT
     std::map<int64_t, BlueTab> blue_big;      // n -> chirp[n], FFT_L(chirp*) (unscaled) for multi-pass Bluestein
@@ -1179,6 +1180,7 @@ void sp_shutdown(void) {
     g.blueA.release();
     g.blueB.release();
     g.longrec.release();
+    g.mtS.release();
     for (auto &kv : g.bigtw) {
         (void)hipFree((void *)kv.second.hi);
         (void)hipFree((void *)kv.second.lo);
@@ -2381,6 +2383,115 @@ int sp_bispectrum(const void *x, const void *y, const void *z, int x_dtype, int6
         HIPCHK(hipMemcpyAsync(B_out, Bd, 2 * sizeof(double) * nn, hipMemcpyDeviceToHost, g.stream));
         HIPCHK(hipMemcpyAsync(b2_out, b2d, sizeof(double) * nn, hipMemcpyDeviceToHost, g.stream));
         if (pzz_out) HIPCHK(hipMemcpyAsync(pzz_out, pzd, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
+int sp_multitaper(const void *x, const void *y, int dtype, int64_t nsig, const float *tapers, int ntapers, int nfft, int hop,
+                  int64_t nframes, int detrend, const double *mean_x, const double *mean_y, const double *weights, double scale,
+                  double *pxx, double *pyy, double *pxy, double *skx, double *sky, int mem) {
+    // every refusal comes before the device is touched
+    if (ntapers < 1 || ntapers > SP_MTAPER_MAXK) return fail("sp_multitaper: %d tapers, need 1 .. %d", ntapers, SP_MTAPER_MAXK);
+    if (nfft < 8 || !wg_capable(nfft))
+        return fail("sp_multitaper: nfft %d outside one workgroup transform (8 .. %d for powers of two, .. %d otherwise)", nfft,
+                    SP_MAX_WG_FFT, SP_MAX_WG_FFT / 2);
+    if (check_frames("sp_multitaper", nsig, nfft, hop, nframes)) return -1;
+    if (dtype != SP_DTYPE_F32 && dtype != SP_DTYPE_C64) return fail("sp_multitaper: unknown dtype %d", dtype);
+    if (detrend < SP_DETREND_CONST || detrend > SP_DETREND_LINEAR) return fail("sp_multitaper: detrend must be 0, 1 or 2");
+    const bool cross = y != nullptr, eigen = weights != nullptr;
+    if (!x || !tapers || !pxx || (cross && (!pyy || !pxy))) return fail("sp_multitaper: x, tapers and the weighted outputs are required");
+    if (eigen && (!skx || (cross && !sky))) return fail("sp_multitaper: weights are given, so the eigenspectra outputs are required");
+    double wsum = 0.0;
+    if (eigen) {
+        for (int k = 0; k < ntapers; ++k) {
+            if (!(weights[k] >= 0.0) || !isfinite(weights[k])) return fail("sp_multitaper: weight %d is negative or not finite", k);
+            wsum += weights[k];
+        }
+        if (!(wsum > 0.0)) return fail("sp_multitaper: the weights are all zero");
+    }
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    Xf xf;
+    if (get_xf(nfft, &xf)) return -1;
+    const bool cplx = dtype == SP_DTYPE_C64, lin = detrend == SP_DETREND_LINEAR;
+    const size_t esz = cplx ? 8 : 4;
+    const int sided = cplx ? SP_SIDED_RAW : SP_SIDED_HALF;
+    const size_t nb = (size_t)nbins_host(nfft, sided), K = (size_t)ntapers;
+    const void *xd = x, *yd = y;
+    if (!mem) {
+        if (g.in0.ensure(esz * (size_t)nsig) || (cross && g.in1.ensure(esz * (size_t)nsig))) return -1;
+        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
+        xd = g.in0.p;
+        if (cross) {
+            HIPCHK(hipMemcpyAsync(g.in1.p, y, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
+            yd = g.in1.p;
+        }
+    }
+    void *tap_d;
+    if (get_table(8, tapers, sizeof(float) * K * (size_t)nfft, &tap_d, nullptr)) return -1;
+    TrendBuf tb;
+    if (get_trendbuf(2, &tb)) return -1;
+    if (set_trend(tb, 0, xd, cplx, nsig, detrend, mean_x ? mean_x[0] : 0, mean_x ? mean_x[1] : 0)) return -1;
+    if (cross && set_trend(tb, 1, yd, cplx, nsig, detrend, mean_y ? mean_y[0] : 0, mean_y ? mean_y[1] : 0)) return -1;
+    // outputs: [pxx | pyy | pxy | skx | sky] staged for host callers
+    const size_t n_w = cross ? 4 * nb : nb, n_e = eigen ? (cross ? 2 : 1) * K * nb : 0;
+    double *pxx_d = pxx, *pyy_d = pyy, *pxy_d = pxy, *skx_d = skx, *sky_d = sky;
+    if (!mem) {
+        if (g.out0.ensure(sizeof(double) * (n_w + n_e))) return -1;
+        pxx_d = (double *)g.out0.p;
+        pyy_d = pxx_d + nb;
+        pxy_d = pyy_d + nb;
+        skx_d = pxx_d + n_w;
+        sky_d = skx_d + K * nb;
+    }
+    // the PSD of a real record transforms PAIRS of frames; the eigenspectra run one taper per grid row
+    const bool pair = !cross && !cplx;
+    const int64_t nunits = pair ? (nframes + 1) / 2 : nframes;
+    const int nblocks = eigen ? ntapers : 1, ktap = eigen ? 1 : ntapers;
+    const RunPart rp = eigen ? run_partition_2d(xf.L, nunits, g.ncu, nblocks) : run_partition(xf.L, nunits, g.ncu);
+    const size_t planes = (size_t)mtaper_partial_planes(xf, cplx, cross), blk = (size_t)rp.groups * planes * (size_t)xf.L;
+    if (g.work.ensure(sizeof(float) * blk * (size_t)nblocks)) return -1;
+    float *partial = (float *)g.work.p;
+    {
+        ProfScope ps;
+        LAUNCHCHK(launch_mtaper(lc(), xd, cross ? yd : nullptr, cplx, (const float *)tap_d, nblocks, ktap, hop, nframes, tb.f, lin, xf,
+                                partial, rp));
+        g.last_kernel = "k_mtaper";
+    }
+    const double sc = scale / (double)nframes;
+    double *sxy_d = nullptr;
+    if (eigen && cross) {
+        if (g.mtS.ensure(sizeof(double) * 2 * K * nb)) return -1;
+        sxy_d = (double *)g.mtS.p;
+    }
+    for (int b = 0; b < nblocks; ++b) {
+        const float *pb = partial + blk * (size_t)b;
+        double *oxx = eigen ? skx_d + nb * (size_t)b : pxx_d, *oyy = eigen ? sky_d + nb * (size_t)b : pyy_d;
+        double *oxy = eigen ? sxy_d + 2 * nb * (size_t)b : pxy_d;
+        if (!cross) LAUNCHCHK(launch_welch_finish(lc(), pb, rp.groups, xf, sided, sc, oxx, pair ? 1 : 0));
+        else if (planes == 3) LAUNCHCHK(launch_csd_rp_finish(lc(), pb, rp.groups, xf, 1, sided, sc, oxx, oyy, oxy));
+        else LAUNCHCHK(launch_csd_finish(lc(), pb, rp.groups, xf, 1, sided, sc, oxx, oyy, oxy));
+    }
+    if (eigen) {
+        double cn[SP_MTAPER_MAXK];
+        for (int k = 0; k < ntapers; ++k) cn[k] = weights[k] / wsum;
+        LAUNCHCHK(launch_mtaper_combine(lc(), skx_d, ntapers, (int64_t)nb, cn, pxx_d));
+        if (cross) {
+            LAUNCHCHK(launch_mtaper_combine(lc(), sky_d, ntapers, (int64_t)nb, cn, pyy_d));
+            LAUNCHCHK(launch_mtaper_combine(lc(), sxy_d, ntapers, (int64_t)(2 * nb), cn, pxy_d));
+        }
+    }
+    if (!mem) {
+        HIPCHK(hipMemcpyAsync(pxx, pxx_d, sizeof(double) * nb, hipMemcpyDeviceToHost, g.stream));
+        if (cross) {
+            HIPCHK(hipMemcpyAsync(pyy, pyy_d, sizeof(double) * nb, hipMemcpyDeviceToHost, g.stream));
+            HIPCHK(hipMemcpyAsync(pxy, pxy_d, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost, g.stream));
+        }
+        if (eigen) {
+            HIPCHK(hipMemcpyAsync(skx, skx_d, sizeof(double) * K * nb, hipMemcpyDeviceToHost, g.stream));
+            if (cross) HIPCHK(hipMemcpyAsync(sky, sky_d, sizeof(double) * K * nb, hipMemcpyDeviceToHost, g.stream));
+        }
         HIPCHK(hipStreamSynchronize(g.stream));
     }
     return 0;

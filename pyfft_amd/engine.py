@@ -508,6 +508,62 @@ def bispectrum(x, win, hop, nframes, y=None, z=None, detrend=True, mean_value=No
     return B, b2, pzz
 
 
+# ------------------------------------------------------------------------------------------ multitaper
+def multitaper(x, tapers, hop, nframes, y=None, detrend=True, mean_value=None, weights=None, scale=1.0):
+    """Multitaper spectra of the frames tapers[k] * (x[g*hop : g*hop+nfft] - trend) in one pass (sp_multitaper):
+    (pxx, pyy, pxy, skx, sky), float64 / complex128 in raw bin order with nothing doubled (real input: bins 0 .. nfft/2; complex:
+    natural FFT order); pyy, pxy (= sum conj(X) Y), sky are None without y, skx and sky are None without weights.
+    weights=None: plain sums over the K tapers (fold sqrt(c_k) into the rows); weights=[K]: the eigenspectra skx / sky [K, nb] too, and
+    the spectra as their c-weighted sums, c = weights / sum(weights).  detrend: whole-record modes, as bispectrum; mean_value applies
+    to x and y.  numpy in -> numpy out; device tensors in -> device tensors on x's stream."""
+    tp = np.ascontiguousarray(np.asarray(tapers), dtype=np.float32)
+    if tp.ndim != 2:
+        raise ValueError("multitaper: tapers must be a [K, nfft] array")
+    K, nfft = tp.shape
+    want, mv = _detrend_args(detrend, mean_value)
+    if want not in (_ffi.DETREND_CONST, _ffi.DETREND_MEAN, _ffi.DETREND_LINEAR):
+        raise ValueError("multitaper: detrend must be none, mean or linear over the whole record")
+    mean = np.array([mv.real, mv.imag], dtype=np.float64)
+    wt = None if weights is None else np.ascontiguousarray(np.asarray(weights), dtype=np.float64)
+    if wt is not None and wt.shape != (K,):
+        raise ValueError("multitaper: weights must hold one number per taper")
+    cross, eigen = y is not None, wt is not None
+    dev = _is_torch(x)
+    if dev:
+        _bind_stream(x)
+        xs = _torch_samples(x)
+        ys = _torch_samples(y) if cross else None
+        if cross and (ys.dtype != xs.dtype or ys.numel() != xs.numel() or ys.device != xs.device):
+            raise ValueError("multitaper: y must match x's length, dtype and device")
+        cplx, nsig, code = xs.dtype == torch.complex64, xs.numel(), _tcode(xs)
+
+        def new(shape, dt=torch.float64):
+            return torch.empty(shape, dtype=dt, device=xs.device)
+
+        def addr(a):
+            return None if a is None else ptr(a.data_ptr())
+    else:
+        xs = _ffi.as_samples(x)
+        ys = _ffi.as_samples(y) if cross else None
+        if cross and (ys.dtype != xs.dtype or ys.size != xs.size):
+            raise ValueError("multitaper: y must match x's length and dtype")
+        cplx, nsig, code = xs.dtype == np.complex64, xs.size, _ffi.dtype_code(xs.dtype)
+
+        def new(shape, dt=np.float64):
+            return np.empty(shape, dtype=dt)
+        addr = ptr
+        _ffi.init()
+    nb = nfft if cplx else nfft // 2 + 1
+    c128 = torch.complex128 if dev else np.complex128
+    pxx = new(nb)
+    pyy, pxy = (new(nb), new(nb, c128)) if cross else (None, None)
+    skx = new((K, nb)) if eigen else None
+    sky = new((K, nb)) if eigen and cross else None
+    check(lib().sp_multitaper(addr(xs), addr(ys), code, nsig, ptr(tp), K, nfft, int(hop), int(nframes), want, ptr(mean), ptr(mean),
+                              ptr(wt), float(scale), addr(pxx), addr(pyy), addr(pxy), addr(skx), addr(sky), 1 if dev else 0))
+    return pxx, pyy, pxy, skx, sky
+
+
 # ------------------------------------------------------------------------------------------ N3
 def stft_cog(x, win, hop, nframes, fs, fmin=0.0, fmax=None, detrend=False, mean_value=None):
     """Centre of gravity (power-weighted mean frequency, Doppler.py:43-58) of every frame's two-sided spectrum, reduced

@@ -3,7 +3,9 @@
 for the kernels whose name contains PATTERN.
   python tools/kernel_shapes.py <kernel_trace.csv> [PATTERN]
 e.g. PATTERN k_bispec: k_bispec_tile (grid X: 256 threads per tile, Y: 256-frame chunks), k_bispec_pzz, k_bispec_reduce, k_bispec_finish;
-     PATTERN k_istft: k_istft (grid X: workgroups of 256 / T runs of frames, Y: records), k_istft_gather (bin-major input)."""
+     PATTERN k_istft: k_istft (grid X: workgroups of 256 / T runs of frames, Y: records), k_istft_gather (bin-major input);
+     PATTERN k_mtaper: k_mtaper (grid X: workgroups of 256 / T runs of frames or frame pairs, Y: taper blocks -- 1, or K for the
+     eigenspectra), k_mtaper_combine (the weighted sum of the eigenspectra)."""
 import collections
 import csv
 import sys
