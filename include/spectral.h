@@ -235,6 +235,28 @@ int sp_multitaper(const void *x, const void *y, int dtype, int64_t nsig, const f
                   int64_t nframes, int detrend, const double *mean_x, const double *mean_y, const double *weights, double scale,
                   double *pxx, double *pyy, double *pxy, double *skx, double *sky, int mem);
 
+/* ---- Chirp-z transform on an arc of the unit circle (scipy.signal.czt / zoom_fft with |w| = |a| = 1):
+ *        X[k] = sum_{j<n} x[j] exp(-2 pi i (start + k step) j),  k < m;   start, step in cycles per sample (float64)
+ *      so start = f1 / fs and step = (f2 - f1) / (m fs) give m bins over [f1, f2).  Bluestein: two L-point transforms,
+ *      L = next_pow2(n + m - 1), inside one workgroup up to L = sp_max_wg_fft() and through the multi-pass transform up to 2^26.
+ *      sp_czt: batch rows of n float32 / complex64 samples (row stride x_ld >= n) -> out[batch][m] complex64; x and out follow `mem`.
+ *      sp_zoom_welch: the frames of sp_welch_psd / sp_welch_csd (win: HOST float32 [nfft]; detrend SP_DETREND_CONST with mean_x /
+ *      mean_y = 2 doubles or NULL, SP_DETREND_MEAN or SP_DETREND_LINEAR over the whole record), each transformed on the arc:
+ *        frames != NULL:  frames[g][k] = scale X_g[k], complex64 [nframes][m] (y must be NULL; pxx, pyy, pxy are not touched)
+ *        otherwise:       pxx[k] = scale / nframes sum_g |X_g[k]|^2 and, with y, pyy likewise and pxy[k] = ... conj(X_g[k]) Y_g[k]
+ *                         as [m][2]; float64, nothing doubled; pyy and pxy are not touched when y == NULL
+ *      x, y and the outputs follow `mem`.  No atomics: partial sums are reduced in float64 in a fixed order, so two calls agree
+ *      bitwise.  Refused (< 0, the message names the entry point, the device is not touched): n or nfft < 1, m < 1, a start or step
+ *      that is not finite, n + m - 1 beyond 2^26 points after rounding up to a power of two, hop < 1, frames that overrun the record.
+ *      sp_czt_chirp: the table phases for checking, host only (no device call): cs_out[c] = (cos, sin) of
+ *      exp(-2 pi i (start i + step i^2 / 2)) at i = i0 + c, c < count, reduced modulo one turn in 128-bit fixed point. */
+int sp_czt(const void *x, int x_dtype, int64_t n, int64_t x_ld, int64_t batch, int64_t m, double start, double step, void *out,
+           int mem);
+int sp_zoom_welch(const void *x, const void *y, int dtype, int64_t nsig, const float *win, int nfft, int hop, int64_t nframes,
+                  int detrend, const double *mean_x, const double *mean_y, int64_t m, double start, double step, double scale,
+                  double *pxx, double *pyy, double *pxy, void *frames, int mem);
+int sp_czt_chirp(int64_t i0, int64_t count, double step, double start, float *cs_out);
+
 /* ---- N3: Doppler.cog applied per STFT frame (Doppler.py:43-58; the loop body of cogspec, Doppler.py:73-81):
  *      cog_out[g] = sum_k f_k |X_g[k]|^2 / sum_k |X_g[k]|^2 over the two-sided spectrum of frame g, f_k = fftfreq(nfft, 1/fs),
  *      restricted to fmin <= |f_k| <= fmax (fmin = 0, fmax >= fs/2: every bin); 0 where the band holds no power.  The

@@ -32,3 +32,5 @@ from .bispectrum import bispectrum, bicoherence              # noqa: F401
 from . import multitaper as _multitaper_mod                  # noqa: F401
 from .multitaper import (multitaper_psd, multitaper_spectra, multitaper_csd, multitaper_coherence,  # noqa: F401
                          multitaper_plan)
+from . import zoom as _zoom_mod                                # noqa: F401
+from .zoom import czt, zoom_fft, zoom_stft, zoom_psd, zoom_csd, zoom_coherence, zoom_plan   # noqa: F401

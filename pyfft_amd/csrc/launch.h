@@ -328,6 +328,29 @@ int launch_mtaper(LaunchCtx c, const void *x, const void *y, bool cplx, const fl
 // out[b] = sum_k weights[k] sk[k][b] in float64 (weights: host, K <= SP_MTAPER_MAXK)
 int launch_mtaper_combine(LaunchCtx c, const double *sk, int K, int64_t nb, const double *weights, double *out);
 
+// chirp-z transform on an arc and the zoom spectra (k_czt.hip).  Device tables of one (n, m, start, step):
+struct CztTables {
+    const cf *tw;      // exp(-2 pi i j / L), j < L
+    const cf *pre;     // e(-start j - step j^2 / 2), j < n
+    const cf *post;    // e(-step k^2 / 2), k < m
+    const cf *bf;      // FFT_L(wrapped e(+step i^2 / 2)) / L
+    int n, m;
+};
+// one workgroup transform, n + m - 1 <= L, L in {512 .. 8192}: rows of n samples (row stride x_ld) -> out[batch][m]
+int launch_czt_rows(LaunchCtx c, const void *x, bool cplx, int64_t x_ld, int64_t batch, int L, const CztTables &tb, cf *out);
+// frames of x (and y) under the window: frames != null -> frames[nframes][m] = amp X; else y != null -> partial[rp.groups][4][L] in
+// k_csd_finish's layout; else partial[rp.groups][L] in k_welch_finish's.  trend: the records of x and y.
+int launch_zoom(LaunchCtx c, const void *x, const void *y, bool cplx, const float *win, int hop, int64_t nframes, const float *trend,
+                bool lin, int L, const CztTables &tb, const RunPart &rp, float amp, float *partial, cf *frames);
+// the ends of the multi-pass form, rows L apart.  pre: A[b][i] = src(b, i) pre[i] zero-padded to L, src = row f0 + b of x (stride ld;
+// win == null) or win * (frame f0 + b at hop ld, minus the trend record); post: out[(f0 + b) m + k] = amp A[b][k] post[k];
+// acc: float64 sums over the rows of |Sx|^2 and, with Sy, |Sy|^2, Sy conj(Sx) as acc[4][m]; acc_out: scaled into the outputs
+int launch_czt_pre(LaunchCtx c, const void *x, bool cplx, int64_t ld, int64_t f0, int64_t rows, const float *win, const float *trend,
+                   bool lin, const cf *pre, int64_t n, int64_t L, cf *A);
+int launch_czt_post(LaunchCtx c, const cf *A, int64_t L, int64_t rows, const cf *post, int64_t m, float amp, int64_t f0, cf *out);
+int launch_zoom_acc(LaunchCtx c, const cf *Sx, const cf *Sy, int64_t rows, int64_t L, int64_t m, double *acc);
+int launch_zoom_acc_out(LaunchCtx c, const double *acc, int64_t m, double scale, double *pxx, double *pyy, double *pxy);
+
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;
 #define SP_CASE_B(Lv, MACRO) case Lv: { MACRO(XfBlue<Lv>) } break;

@@ -583,6 +583,129 @@ int dev_fft_any(const cf *in, cf *out, int64_t n, int64_t batch, int inverse) {
 }
 
 
+// ---- chirp-z transform on an arc of the unit circle (k_czt.hip) ----------------------------------
+// Table phases.  step j^2 / 2 must be reduced modulo 1 BEFORE it becomes a floating-point number: at j ~ 2^25 the float64 product has
+// no fractional bit left.  The integer tables above reduce m^2 modulo 2n; a real step has no such modulus, so the phase is held in
+// wrap-around fixed point: step / 2 mod 1 and start mod 1 as 128-bit binary fractions (a double is a dyadic rational: the conversion
+// drops only bits below 2^-128), multiplied by the integers j^2 and j modulo 2^128 -- which IS reduction modulo one turn.  The
+// error of a phase is the dropped bits times j^2 (< 2^-128 2^52 = 2^-76 turns for the indices the library accepts, |j| < 2^26) plus
+// the rounding of the top 64 bits to a double (2^-54 turns): far below the 1e-9 turns asked for, at every such index.
+typedef unsigned __int128 u128;
+u128 frac128(double x) {
+    const double a = fmod(fabs(x), 1.0);                   // exact
+    const double s = ldexp(a, 64), hi = floor(s);          // exact: a < 1 has at most 53 significant bits
+    const double lo = floor(ldexp(s - hi, 64));
+    const u128 v = ((u128)(uint64_t)hi << 64) | (u128)(uint64_t)lo;
+    return x < 0 ? (u128)0 - v : v;
+}
+// cs[c] = (cos, sin) of e(-start i - step i^2 / 2), i = i0 + c.  Host only: no HIP call.
+void czt_chirp_host(int64_t i0, int64_t count, double step, double start, float *cs) {
+    const u128 S = frac128(0.5 * step), A = frac128(start);
+    for (int64_t c = 0; c < count; ++c) {
+        const u128 ui = (u128)(__int128)(i0 + c);
+        const u128 t = S * (ui * ui) + A * ui;
+        const double turns = ldexp((double)(int64_t)(uint64_t)(t >> 64), -64);       // in [-1/2, 1/2)
+        const double a = -2.0 * M_PI * turns;
+        cs[2 * c] = (float)cos(a);
+        cs[2 * c + 1] = (float)sin(a);
+    }
+}
+
+#define SP_CZT_MIN_L 512            /* the fused kernels are compiled for L = 512 .. SP_MAX_WG_FFT; shorter shapes are padded up */
+#define SP_CZT_CACHE 32
+struct CztTab {
+    cf *pre, *post, *bf;            // bf: FFT_L(kern) / L for one workgroup transform, unscaled for the multi-pass form
+    int64_t L;
+};
+struct CztKey {
+    int64_t n, m;
+    uint64_t start, step;           // the doubles' bits
+    bool operator<(const CztKey &o) const {
+        if (n != o.n) return n < o.n;
+        if (m != o.m) return m < o.m;
+        if (start != o.start) return start < o.start;
+        return step < o.step;
+    }
+};
+std::map<CztKey, CztTab> g_czt;
+Scratch g_cztAcc;                   // float64 sums of the long zoom spectra
+
+int64_t czt_len(int64_t n, int64_t m) {
+    const int64_t L = next_pow2(n + m - 1);
+    return L < SP_CZT_MIN_L ? SP_CZT_MIN_L : L;
+}
+void czt_release() {
+    for (auto &kv : g_czt) {
+        (void)hipFree(kv.second.pre);
+        (void)hipFree(kv.second.post);
+        (void)hipFree(kv.second.bf);
+    }
+    g_czt.clear();
+}
+// tables of one (n, m, start, step), cached like g.blue / g.blue_big
+int get_czt(int64_t n, int64_t m, double start, double step, CztTab *t) {
+    CztKey key{n, m, 0, 0};
+    memcpy(&key.start, &start, 8);
+    memcpy(&key.step, &step, 8);
+    auto it = g_czt.find(key);
+    if (it != g_czt.end()) {
+        *t = it->second;
+        return 0;
+    }
+    if (g_czt.size() >= SP_CZT_CACHE) {            // asynchronous work of an earlier call may still read a table
+        HIPCHK(hipDeviceSynchronize());
+        czt_release();
+    }
+    const int64_t L = czt_len(n, m);
+    const bool fused = L <= SP_MAX_WG_FFT;
+    std::vector<cf> pre((size_t)n), post((size_t)m), arc((size_t)(n + m - 1)), kern((size_t)L, make_float2(0.f, 0.f));
+    czt_chirp_host(0, n, step, start, (float *)pre.data());
+    czt_chirp_host(0, m, step, 0.0, (float *)post.data());
+    czt_chirp_host(-(n - 1), n + m - 1, step, 0.0, (float *)arc.data());
+    const float sc = fused ? 1.f / (float)L : 1.f;                              // a power of two: exact
+    for (int64_t i = -(n - 1); i < m; ++i) {
+        const cf c = arc[(size_t)(i + n - 1)];
+        kern[(size_t)(i < 0 ? i + L : i)] = make_float2(sc * c.x, -sc * c.y);     // e(+step i^2 / 2)
+    }
+    CztTab nt{nullptr, nullptr, nullptr, L};
+    HIPCHK(hipMalloc((void **)&nt.pre, sizeof(cf) * (size_t)n));
+    HIPCHK(hipMalloc((void **)&nt.post, sizeof(cf) * (size_t)m));
+    HIPCHK(hipMalloc((void **)&nt.bf, sizeof(cf) * (size_t)L));
+    HIPCHK(hipMemcpy(nt.pre, pre.data(), sizeof(cf) * (size_t)n, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(nt.post, post.data(), sizeof(cf) * (size_t)m, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(nt.bf, kern.data(), sizeof(cf) * (size_t)L, hipMemcpyHostToDevice));
+    if (fused) {
+        Xf p2;
+        if (get_xf(L, &p2)) return -1;
+        LAUNCHCHK(launch_fft_c2c(lc(), nt.bf, nt.bf, 1, 0, p2));
+    } else if (dev_fft_big_pow2(nt.bf, nt.bf, L, 0)) {
+        return -1;
+    }
+    HIPCHK(hipStreamSynchronize(g.stream));
+    g_czt[key] = nt;
+    *t = nt;
+    return 0;
+}
+// the shared refusals of sp_czt / sp_zoom_welch, before the device is touched
+int czt_check(const char *who, int64_t n, int64_t m, double start, double step) {
+    if (n < 1 || m < 1) return fail("%s: n = %lld inputs and m = %lld outputs must both be at least 1", who, (long long)n, (long long)m);
+    if (!isfinite(start) || !isfinite(step)) return fail("%s: start and step must be finite", who);
+    const int64_t cap = (int64_t)1 << SP_MAX_BIG_LOG2;
+    if (n > cap || m > cap || czt_len(n, m) > cap)
+        return fail("%s: n + m - 1 = %lld needs a transform beyond the limit of 2^%d points", who, (long long)(n + m - 1),
+                    SP_MAX_BIG_LOG2);
+    return 0;
+}
+// rows [r0, r0 + rows) through the multi-pass chirp-z: A[rows][L] <- IFFT_L(FFT_L(src pre) . bf); the caller keeps the first m
+int czt_long_rows(const void *xd, bool cplx, int64_t ld, int64_t r0, int64_t rows, const float *win_d, const float *trend, bool lin,
+                  const CztTab &t, int64_t n, cf *A) {
+    LAUNCHCHK(launch_czt_pre(lc(), xd, cplx, ld, r0, rows, win_d, trend, lin, t.pre, n, t.L, A));
+    if (dev_fft_big_pow2(A, A, t.L, 0, 0, rows)) return -1;
+    LAUNCHCHK(launch_cmul_vec(lc(), A, t.bf, t.L, 0, A, rows));
+    return dev_fft_big_pow2(A, A, t.L, 1, 0, rows);
+}
+
+
 // ---- segments longer than one workgroup transform (k_long.hip) -----------------------------------
 // frames per chunk: the chunk's spectra (m x nfft complex64) stay below SP_LONG_CHUNK_BYTES
 #define SP_LONG_CHUNK_BYTES ((size_t)192 << 20)
@@ -1191,6 +1314,8 @@ void sp_shutdown(void) {
         (void)hipFree(kv.second.bf);
     }
     g.blue_big.clear();
+    czt_release();
+    g_cztAcc.release();
     g_pend.valid = false;
     tables_release();
     g.ready = false;
@@ -2491,6 +2616,174 @@ int sp_multitaper(const void *x, const void *y, int dtype, int64_t nsig, const f
         if (eigen) {
             HIPCHK(hipMemcpyAsync(skx, skx_d, sizeof(double) * K * nb, hipMemcpyDeviceToHost, g.stream));
             if (cross) HIPCHK(hipMemcpyAsync(sky, sky_d, sizeof(double) * K * nb, hipMemcpyDeviceToHost, g.stream));
+        }
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
+int sp_czt_chirp(int64_t i0, int64_t count, double step, double start, float *cs_out) {
+    if (count < 0 || (count > 0 && !cs_out)) return fail("sp_czt_chirp: count must not be negative and cs_out is required");
+    if (!isfinite(start) || !isfinite(step)) return fail("sp_czt_chirp: start and step must be finite");
+    if (count > 0 && i0 > INT64_MAX - count) return fail("sp_czt_chirp: the index range overflows");
+    czt_chirp_host(i0, count, step, start, cs_out);
+    return 0;
+}
+
+int sp_czt(const void *x, int x_dtype, int64_t n, int64_t x_ld, int64_t batch, int64_t m, double start, double step, void *out,
+           int mem) {
+    // every refusal comes before the device is touched
+    if (czt_check("sp_czt", n, m, start, step)) return -1;
+    if (x_dtype != SP_DTYPE_F32 && x_dtype != SP_DTYPE_C64) return fail("sp_czt: unknown dtype %d", x_dtype);
+    if (batch < 0 || x_ld < n) return fail("sp_czt: need batch >= 0 and a row stride x_ld >= n");
+    if (batch == 0) return 0;
+    if (!x || !out) return fail("sp_czt: x and out are required");
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const bool cplx = x_dtype == SP_DTYPE_C64;
+    const size_t esz = cplx ? 8 : 4, in_elems = (size_t)((batch - 1) * x_ld + n), obytes = sizeof(cf) * (size_t)batch * (size_t)m;
+    const void *xd = x;
+    cf *od = (cf *)out;
+    if (!mem) {
+        if (g.in0.ensure(esz * in_elems) || g.out0.ensure(obytes)) return -1;
+        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * in_elems, hipMemcpyHostToDevice, g.stream));
+        xd = g.in0.p;
+        od = (cf *)g.out0.p;
+    }
+    CztTab t;
+    if (get_czt(n, m, start, step, &t)) return -1;
+    if (t.L <= SP_MAX_WG_FFT) {
+        CztTables tb{nullptr, t.pre, t.post, t.bf, (int)n, (int)m};
+        if (get_twiddles(t.L, &tb.tw)) return -1;
+        ProfScope ps;
+        LAUNCHCHK(launch_czt_rows(lc(), xd, cplx, x_ld, batch, (int)t.L, tb, od));
+        g.last_kernel = "k_czt_rows";
+    } else {
+        int64_t slice = (int64_t)(SP_LONG_SLICE_BYTES / (sizeof(cf) * (size_t)t.L));
+        if (slice < 1) slice = 1;
+        if (slice > 32768) slice = 32768;
+        if (slice > batch) slice = batch;
+        if (g.blueA.ensure(sizeof(cf) * (size_t)t.L * (size_t)slice)) return -1;
+        cf *A = (cf *)g.blueA.p;
+        for (int64_t b0 = 0; b0 < batch; b0 += slice) {
+            const int64_t rows = batch - b0 < slice ? batch - b0 : slice;
+            if (czt_long_rows(xd, cplx, x_ld, b0, rows, nullptr, nullptr, false, t, n, A)) return -1;
+            LAUNCHCHK(launch_czt_post(lc(), A, t.L, rows, t.post, m, 1.f, b0, od));
+        }
+    }
+    if (!mem) {
+        HIPCHK(hipMemcpyAsync(out, od, obytes, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
+int sp_zoom_welch(const void *x, const void *y, int dtype, int64_t nsig, const float *win, int nfft, int hop, int64_t nframes,
+                  int detrend, const double *mean_x, const double *mean_y, int64_t m, double start, double step, double scale,
+                  double *pxx, double *pyy, double *pxy, void *frames, int mem) {
+    // every refusal comes before the device is touched
+    if (czt_check("sp_zoom_welch", nfft, m, start, step)) return -1;
+    if (hop < 1) return fail("sp_zoom_welch: hop must be at least 1");
+    if (nframes < 1) return fail("sp_zoom_welch: nframes must be at least 1");
+    if ((nframes - 1) * (int64_t)hop + nfft > nsig)
+        return fail("sp_zoom_welch: %lld frames of %d with hop %d need %lld samples, signal has %lld", (long long)nframes, nfft, hop,
+                    (long long)((nframes - 1) * (int64_t)hop + nfft), (long long)nsig);
+    if (dtype != SP_DTYPE_F32 && dtype != SP_DTYPE_C64) return fail("sp_zoom_welch: unknown dtype %d", dtype);
+    if (detrend < SP_DETREND_CONST || detrend > SP_DETREND_LINEAR) return fail("sp_zoom_welch: detrend must be 0, 1 or 2");
+    const bool cross = y != nullptr, stft = frames != nullptr;
+    if (!x || !win) return fail("sp_zoom_welch: x and win are required");
+    if (stft && cross) return fail("sp_zoom_welch: the frames output takes one signal");
+    if (!stft && (!pxx || (cross && (!pyy || !pxy)))) return fail("sp_zoom_welch: an output is required: frames, pxx, or pxx, pyy and pxy");
+    if (!isfinite(scale)) return fail("sp_zoom_welch: scale must be finite");
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const bool cplx = dtype == SP_DTYPE_C64, lin = detrend == SP_DETREND_LINEAR;
+    const size_t esz = cplx ? 8 : 4, mm = (size_t)m;
+    const void *xd = x, *yd = y;
+    if (!mem) {
+        if (g.in0.ensure(esz * (size_t)nsig) || (cross && g.in1.ensure(esz * (size_t)nsig))) return -1;
+        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
+        xd = g.in0.p;
+        if (cross) {
+            HIPCHK(hipMemcpyAsync(g.in1.p, y, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
+            yd = g.in1.p;
+        }
+    }
+    void *win_d;
+    if (get_table(1, win, sizeof(float) * (size_t)nfft, &win_d, nullptr)) return -1;
+    TrendBuf tb;
+    if (get_trendbuf(2, &tb)) return -1;
+    if (set_trend(tb, 0, xd, cplx, nsig, detrend, mean_x ? mean_x[0] : 0, mean_x ? mean_x[1] : 0)) return -1;
+    if (cross && set_trend(tb, 1, yd, cplx, nsig, detrend, mean_y ? mean_y[0] : 0, mean_y ? mean_y[1] : 0)) return -1;
+    CztTab t;
+    if (get_czt(nfft, m, start, step, &t)) return -1;
+    // outputs staged for host callers: [pxx | pyy | pxy], or the frames
+    const size_t obytes = stft ? sizeof(cf) * (size_t)nframes * mm : sizeof(double) * (cross ? 4 : 1) * mm;
+    double *pxx_d = pxx, *pyy_d = pyy, *pxy_d = pxy;
+    cf *fr_d = (cf *)frames;
+    if (!mem) {
+        if (g.out0.ensure(obytes)) return -1;
+        if (stft) fr_d = (cf *)g.out0.p;
+        pxx_d = (double *)g.out0.p;
+        pyy_d = cross ? pxx_d + mm : nullptr;
+        pxy_d = cross ? pyy_d + mm : nullptr;
+    }
+    if (!cross) pyy_d = pxy_d = nullptr;
+    const double sc = scale / (double)nframes;
+    if (t.L <= SP_MAX_WG_FFT) {
+        CztTables ct{nullptr, t.pre, t.post, t.bf, nfft, (int)m};
+        if (get_twiddles(t.L, &ct.tw)) return -1;
+        const RunPart rp = run_partition((int)t.L, nframes, g.ncu);
+        float *partial = nullptr;
+        if (!stft) {
+            if (g.work.ensure(sizeof(float) * (size_t)rp.groups * (cross ? 4 : 1) * (size_t)t.L)) return -1;
+            partial = (float *)g.work.p;
+        }
+        {
+            ProfScope ps;
+            LAUNCHCHK(launch_zoom(lc(), xd, cross ? yd : nullptr, cplx, (const float *)win_d, hop, nframes, tb.f, lin, (int)t.L, ct, rp,
+                                  (float)scale, partial, stft ? fr_d : nullptr));
+            g.last_kernel = "k_zoom";
+        }
+        if (!stft) {
+            Xf fx;                       // the finish kernels read rows of L floats and keep the first m bins
+            fx.L = (int)t.L;
+            fx.blue = true;
+            fx.tb = XfTables{ct.tw, nullptr, nullptr, (int)m};
+            if (!cross) LAUNCHCHK(launch_welch_finish(lc(), partial, rp.groups, fx, SP_SIDED_RAW, sc, pxx_d, 0));
+            else LAUNCHCHK(launch_csd_finish(lc(), partial, rp.groups, fx, 1, SP_SIDED_RAW, sc, pxx_d, pyy_d, pxy_d));
+        }
+    } else {
+        // chunks of frames, as long_spectra: pre-multiply straight from the signal, the multi-pass transforms, then one kernel adds
+        // the chunk's products of the first m bins into float64 sums in frame order
+        const int64_t mc = long_chunk_frames((int)t.L, nframes);
+        if (g.bigA.ensure(sizeof(cf) * (size_t)mc * (size_t)t.L) || (cross && g.bigB.ensure(sizeof(cf) * (size_t)mc * (size_t)t.L)))
+            return -1;
+        cf *Sx = (cf *)g.bigA.p, *Sy = cross ? (cf *)g.bigB.p : nullptr;
+        double *acc = nullptr;
+        if (!stft) {
+            if (g_cztAcc.ensure(sizeof(double) * 4 * mm)) return -1;
+            acc = (double *)g_cztAcc.p;
+            HIPCHK(hipMemsetAsync(acc, 0, sizeof(double) * 4 * mm, g.stream));
+        }
+        for (int64_t f0 = 0; f0 < nframes; f0 += mc) {
+            const int64_t rows = nframes - f0 < mc ? nframes - f0 : mc;
+            if (czt_long_rows(xd, cplx, hop, f0, rows, (const float *)win_d, tb.f, lin, t, nfft, Sx)) return -1;
+            if (cross && czt_long_rows(yd, cplx, hop, f0, rows, (const float *)win_d, tb.f + 4, lin, t, nfft, Sy)) return -1;
+            if (stft) LAUNCHCHK(launch_czt_post(lc(), Sx, t.L, rows, t.post, m, (float)scale, f0, fr_d));
+            else LAUNCHCHK(launch_zoom_acc(lc(), Sx, Sy, rows, t.L, m, acc));
+        }
+        if (!stft) LAUNCHCHK(launch_zoom_acc_out(lc(), acc, m, sc, pxx_d, pyy_d, pxy_d));
+    }
+    if (!mem) {
+        if (stft) {
+            HIPCHK(hipMemcpyAsync(frames, fr_d, obytes, hipMemcpyDeviceToHost, g.stream));
+        } else {
+            HIPCHK(hipMemcpyAsync(pxx, pxx_d, sizeof(double) * mm, hipMemcpyDeviceToHost, g.stream));
+            if (cross) {
+                HIPCHK(hipMemcpyAsync(pyy, pyy_d, sizeof(double) * mm, hipMemcpyDeviceToHost, g.stream));
+                HIPCHK(hipMemcpyAsync(pxy, pxy_d, sizeof(double) * 2 * mm, hipMemcpyDeviceToHost, g.stream));
+            }
         }
         HIPCHK(hipStreamSynchronize(g.stream));
     }

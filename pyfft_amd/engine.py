@@ -564,6 +564,85 @@ def multitaper(x, tapers, hop, nframes, y=None, detrend=True, mean_value=None, w
     return pxx, pyy, pxy, skx, sky
 
 
+# ------------------------------------------------------------------------------------------ chirp-z / zoom
+def czt(x, m, start, step):
+    """Chirp-z transform on an arc along the last axis (sp_czt): X[..., k] = sum_j x[..., j] exp(-2 pi i (start + k step) j), k < m,
+    start and step in cycles per sample.  complex64 [..., m]; numpy in -> numpy out, device tensor in -> device tensor on x's
+    stream (rows of a 2-D tensor may be strided)."""
+    m, start, step = int(m), float(start), float(step)
+    if _is_torch(x):
+        _bind_stream(x)
+        if x.dtype not in (torch.float32, torch.complex64):
+            raise TypeError("device path takes float32 or complex64 samples, got %s" % x.dtype)
+        if x.dim() < 1:
+            raise ValueError("czt: x must have at least one axis")
+        n = int(x.shape[-1])
+        if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= n and x.shape[0] >= 1:
+            xs, ld = x, int(x.stride(0))                      # a row-strided view goes through as it is
+        else:
+            xs, ld = x.contiguous(), n
+        batch = xs.numel() // n if n else 0
+        out = torch.empty(tuple(x.shape[:-1]) + (max(m, 0),), dtype=torch.complex64, device=x.device)
+        check(lib().sp_czt(ptr(xs.data_ptr()), _tcode(xs), n, ld, batch, m, start, step, ptr(out.data_ptr()), 1))
+        return out
+    xs = _ffi.as_samples(x)
+    if xs.ndim < 1:
+        raise ValueError("czt: x must have at least one axis")
+    n = xs.shape[-1]
+    out = np.empty(xs.shape[:-1] + (max(m, 0),), dtype=np.complex64)
+    _ffi.init()
+    check(lib().sp_czt(ptr(xs), _ffi.dtype_code(xs.dtype), n, n, xs.size // n if n else 0, m, start, step, ptr(out), 0))
+    return out
+
+
+def zoom_welch(x, win, hop, nframes, m, start, step, y=None, detrend=False, mean_value=None, scale=1.0, frames=False):
+    """The frames win * (x[g*hop : g*hop+nfft] - trend) transformed on the arc start + k step, k < m (sp_zoom_welch).
+    frames=False: (pxx, pyy, pxy) = scale / nframes * sums over the frames of |X|^2, |Y|^2, conj(X) Y, float64 / complex128 [m], nothing
+    doubled (pyy, pxy None without y); frames=True: complex64 [nframes, m] = scale * X_g.  detrend: whole-record modes, as
+    multitaper.  numpy in -> numpy out; device tensors in -> device tensors on x's stream."""
+    w = _win32(win)
+    nfft, m = w.size, int(m)
+    want, mv = _detrend_args(detrend, mean_value)
+    if want not in (_ffi.DETREND_CONST, _ffi.DETREND_MEAN, _ffi.DETREND_LINEAR):
+        raise ValueError("zoom_welch: detrend must be none, mean or linear over the whole record")
+    if frames and y is not None:
+        raise ValueError("zoom_welch: frames=True takes one signal")
+    mean = np.array([mv.real, mv.imag], dtype=np.float64)
+    cross = y is not None
+    dev = _is_torch(x)
+    if dev:
+        _bind_stream(x)
+        xs = _torch_samples(x)
+        ys = _torch_samples(y) if cross else None
+        if cross and (ys.dtype != xs.dtype or ys.numel() != xs.numel() or ys.device != xs.device):
+            raise ValueError("zoom_welch: y must match x's length, dtype and device")
+        nsig, code = xs.numel(), _tcode(xs)
+
+        def new(shape, dt=torch.float64):
+            return torch.empty(shape, dtype=dt, device=xs.device)
+
+        def addr(a):
+            return None if a is None else ptr(a.data_ptr())
+    else:
+        xs = _ffi.as_samples(x)
+        ys = _ffi.as_samples(y) if cross else None
+        if cross and (ys.dtype != xs.dtype or ys.size != xs.size):
+            raise ValueError("zoom_welch: y must match x's length and dtype")
+        nsig, code = xs.size, _ffi.dtype_code(xs.dtype)
+
+        def new(shape, dt=np.float64):
+            return np.empty(shape, dtype=dt)
+        addr = ptr
+        _ffi.init()
+    mm = max(m, 0)
+    fr = new((max(int(nframes), 0), mm), torch.complex64 if dev else np.complex64) if frames else None
+    pxx = None if frames else new(mm)
+    pyy, pxy = (new(mm), new(mm, torch.complex128 if dev else np.complex128)) if cross else (None, None)
+    check(lib().sp_zoom_welch(addr(xs), addr(ys), code, nsig, ptr(w), nfft, int(hop), int(nframes), want, ptr(mean), ptr(mean), m,
+                              float(start), float(step), float(scale), addr(pxx), addr(pyy), addr(pxy), addr(fr), 1 if dev else 0))
+    return fr if frames else (pxx, pyy, pxy)
+
+
 # ------------------------------------------------------------------------------------------ N3
 def stft_cog(x, win, hop, nframes, fs, fmin=0.0, fmax=None, detrend=False, mean_value=None):
     """Centre of gravity (power-weighted mean frequency, Doppler.py:43-58) of every frame's two-sided spectrum, reduced
