@@ -55,9 +55,10 @@ def nbins(nfft, sided):
 
 
 def _detrend_args(detrend, mean_value):
-    """detrend: False/0/None none, True/1/'mean' mean, 2/'linear' least-squares line, 3/'segmean' every segment's own
-    mean (welch_psd / welch_csd only: the matplotlib.mlab convention); an explicit mean_value
-    (with detrend truthy) is subtracted as a constant instead of being computed."""
+    """detrend: False/0/None none, True/1/'mean' mean of the whole record, 2/'linear' its least-squares line, 3/'segmean' every
+    segment's own mean, 4/'seglinear' every segment's own least-squares line (the matplotlib.mlab convention; modes 3 and 4 of
+    the C ABI, on welch_psd, welch_csd, stft_frames and stft_cog); an explicit mean_value (with detrend truthy and none of
+    2, 3, 4) is subtracted as a constant instead of being computed."""
     if detrend in (None, False, 0, "none"):
         return _ffi.DETREND_CONST, 0j
     if detrend in (2, "linear"):
