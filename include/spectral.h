@@ -257,6 +257,22 @@ int sp_zoom_welch(const void *x, const void *y, int dtype, int64_t nsig, const f
                   double *pxx, double *pyy, double *pxy, void *frames, int mem);
 int sp_czt_chirp(int64_t i0, int64_t count, double step, double start, float *cs_out);
 
+/* ---- Digital down-converter: mix with a carrier, low-pass, decimate -- one pass over every row of a batch:
+ *        v[n] = x[n] exp(-2 pi i nu (n0 + n)),  n < nsig, 0 outside the row;   nu in cycles per sample (float64)
+ *        y[k] = sum_{j<ntaps} h[j] v[k q + (ntaps - 1) / 2 - j],  k < ceil(nsig / q)
+ *      which is scipy.signal.resample_poly(v, 1, q, window=h) for an odd ntaps.  x: float32 or complex64 rows of nsig samples, row
+ *      stride x_ld >= nsig; h: HOST float32 [ntaps], real; out: complex64 [batch][ceil(nsig / q)]; x and out follow `mem`.
+ *      n0 is the absolute index of every row's first sample: the chunks of one stream, each with its own n0, continue the oscillator
+ *      without a phase jump.  nu n0 is reduced modulo one turn in 128-bit fixed point on the host and advanced on the device in
+ *      64-bit fixed point (<= 2^-33 turns over a launch); nu = 0 (or any integer) skips the mixer and filters the input as it is.
+ *      Limits of one launch: 1 <= q <= 64; ntaps odd, 1 .. 4095; 1 <= nsig <= 2^32; |n0| <= 2^40; nu and h finite.
+ *      Anything else returns < 0 with sp_last_error() naming the entry point, before the device is touched.
+ *      sp_ddc_tile: the outputs one workgroup of sp_ddc produces for this q (0 outside 1 .. 64); a tile consumes q times as many
+ *      samples.  Host only. */
+int sp_ddc(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t batch, double nu, int64_t n0, int q, const float *h,
+           int ntaps, void *out, int mem);
+int sp_ddc_tile(int q);
+
 /* ---- N3: Doppler.cog applied per STFT frame (Doppler.py:43-58; the loop body of cogspec, Doppler.py:73-81):
  *      cog_out[g] = sum_k f_k |X_g[k]|^2 / sum_k |X_g[k]|^2 over the two-sided spectrum of frame g, f_k = fftfreq(nfft, 1/fs),
  *      restricted to fmin <= |f_k| <= fmax (fmin = 0, fmax >= fs/2: every bin); 0 where the band holds no power.  The

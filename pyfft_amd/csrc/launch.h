@@ -351,6 +351,47 @@ int launch_czt_post(LaunchCtx c, const cf *A, int64_t L, int64_t rows, const cf 
 int launch_zoom_acc(LaunchCtx c, const cf *Sx, const cf *Sy, int64_t rows, int64_t L, int64_t m, double *acc);
 int launch_zoom_acc_out(LaunchCtx c, const double *acc, int64_t m, double scale, double *pxx, double *pyy, double *pxy);
 
+// digital down-converter (k_ddc.hip): mixer + polyphase decimating FIR, one workgroup of 256 threads per tile of K outputs of a row.
+// The thread grid is og x sg: an output group owns SP_DDC_R consecutive outputs, a phase group the polyphase components s = sg, sg + SG, ..
+// of the q; SG = the largest power of two <= min(q, 32), so that K q, the samples a tile consumes, stays between 2048 and 4096.
+#define SP_DDC_R 8
+#define SP_DDC_MAXQ 64
+#define SP_DDC_MAXTAPS 4095
+struct DdcGeom {
+    int q, ntaps;
+    int sg, og_log2;   // phase groups; log2 of the 256 / sg output groups
+    int K;             // outputs per tile
+    int PP;            // taps per polyphase component, rounded up to a multiple of 4
+    int NI;            // staged entries per component
+    int pitch;         // LDS row pitch of a component in float2 (entry i sits at i + (i >> 5))
+    int span;          // staged samples, NI q
+    int W;             // entries of the phasor table
+    size_t lds;        // bytes: the staged components, then the taps [q][PP]
+};
+inline DdcGeom ddc_geom(int q, int ntaps) {
+    DdcGeom g;
+    g.q = q;
+    g.ntaps = ntaps;
+    g.sg = 1;
+    while (g.sg * 2 <= q && g.sg < 32) g.sg *= 2;
+    g.og_log2 = 0;
+    while ((g.sg << g.og_log2) < 256) ++g.og_log2;
+    g.K = (256 / g.sg) * SP_DDC_R;
+    g.PP = ((ntaps + q - 1) / q + 3) & ~3;
+    g.NI = g.K + g.PP + 3;              // the sliding window's last (unused) refill reads entry K + PP + 2
+    g.pitch = g.NI + (g.NI >> 5) + 1;
+    while ((g.pitch & 7) != 2) ++g.pitch;   // even (the taps behind stay 16-byte aligned); rows of neighbouring phases on other banks
+    g.span = g.NI * q;
+    g.W = g.span + 8;
+    g.lds = sizeof(float2) * (size_t)q * g.pitch + sizeof(float) * (size_t)q * g.PP;
+    return g;
+}
+// x: rows of nsig samples (row stride x_ld) -> out[batch][nout], nout = ceil(nsig / q).  ph0: the phase of the row's first sample,
+// dnu: the step per sample, both in 2^-64 turns; tab[j] = exp(-2 pi i nu j), j < g.W (null: no mixing); taps[s][p] = h[(PP - 1 - p) q + s]
+// or 0 past the last tap; vec: x is 16-byte aligned
+int launch_ddc(LaunchCtx c, const void *x, bool cplx, int64_t x_ld, int64_t nsig, int64_t batch, const DdcGeom &g, uint64_t ph0,
+               uint64_t dnu, const cf *tab, const float *taps, bool vec, cf *out);
+
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;
 #define SP_CASE_B(Lv, MACRO) case Lv: { MACRO(XfBlue<Lv>) } break;

@@ -20,7 +20,7 @@
 
 using namespace sp;
 
-#define SP_VERSION 107
+#define SP_VERSION 108
 #define SP_MAX_WG_FFT 8192
 #define SP_MAX_BIG_LOG2 26          /* longest multi-pass power-of-two transform: 2^26 points (512 MiB per buffer) */
 
@@ -2670,6 +2670,93 @@ int sp_czt(const void *x, int x_dtype, int64_t n, int64_t x_ld, int64_t batch, i
             if (czt_long_rows(xd, cplx, x_ld, b0, rows, nullptr, nullptr, false, t, n, A)) return -1;
             LAUNCHCHK(launch_czt_post(lc(), A, t.L, rows, t.post, m, 1.f, b0, od));
         }
+    }
+    if (!mem) {
+        HIPCHK(hipMemcpyAsync(out, od, obytes, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
+// ---- digital down-converter (k_ddc.hip) -----------------------------------------------------------
+#define SP_DDC_MAX_INDEX ((int64_t)1 << 40)
+#define SP_DDC_MAX_NSIG ((int64_t)1 << 32)
+// the refusals of sp_ddc, before the device is touched
+static int ddc_check(const char *who, int x_dtype, int64_t nsig, int64_t x_ld, int64_t batch, double nu, int64_t n0, int q, int ntaps) {
+    if (q < 1 || q > SP_DDC_MAXQ) return fail("%s: the decimation q = %d must lie in 1 .. %d", who, q, SP_DDC_MAXQ);
+    if (ntaps < 1 || ntaps > SP_DDC_MAXTAPS || ntaps % 2 == 0)
+        return fail("%s: ntaps = %d must be odd and lie in 1 .. %d", who, ntaps, SP_DDC_MAXTAPS);
+    if (x_dtype != SP_DTYPE_F32 && x_dtype != SP_DTYPE_C64) return fail("%s: unknown dtype %d", who, x_dtype);
+    if (nsig < 1 || nsig > SP_DDC_MAX_NSIG) return fail("%s: nsig = %lld must lie in 1 .. 2^32 samples per launch", who, (long long)nsig);
+    if (batch < 0 || x_ld < nsig) return fail("%s: need batch >= 0 and a row stride x_ld >= nsig", who);
+    if (!isfinite(nu)) return fail("%s: nu must be finite", who);
+    if (n0 > SP_DDC_MAX_INDEX || n0 < -SP_DDC_MAX_INDEX) return fail("%s: n0 = %lld must lie within +-2^40", who, (long long)n0);
+    return 0;
+}
+
+int sp_ddc_tile(int q) {
+    if (q < 1 || q > SP_DDC_MAXQ) return 0;
+    return ddc_geom(q, 1).K;
+}
+
+int sp_ddc(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t batch, double nu, int64_t n0, int q, const float *h,
+           int ntaps, void *out, int mem) {
+    if (ddc_check("sp_ddc", x_dtype, nsig, x_ld, batch, nu, n0, q, ntaps)) return -1;
+    if (batch == 0) return 0;
+    if (!x || !h || !out) return fail("sp_ddc: x, h and out are required");
+    for (int j = 0; j < ntaps; ++j)
+        if (!isfinite(h[j])) return fail("sp_ddc: the taps must be finite");
+    const DdcGeom geom = ddc_geom(q, ntaps);
+    const int64_t nout = (nsig + q - 1) / q;
+    if ((nout + geom.K - 1) / geom.K * batch > INT_MAX) return fail("sp_ddc: %lld rows of %lld outputs are too many tiles for one launch",
+                                                                   (long long)batch, (long long)nout);
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const bool cplx = x_dtype == SP_DTYPE_C64;
+    const size_t esz = cplx ? 8 : 4, in_elems = (size_t)((batch - 1) * x_ld + nsig), obytes = sizeof(cf) * (size_t)batch * (size_t)nout;
+    const void *xd = x;
+    cf *od = (cf *)out;
+    if (!mem) {
+        if (g.in0.ensure(esz * in_elems) || g.out0.ensure(obytes)) return -1;
+        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * in_elems, hipMemcpyHostToDevice, g.stream));
+        xd = g.in0.p;
+        od = (cf *)g.out0.p;
+    }
+    // the taps, one row per polyphase component, reversed: taps[s][p] = h[(PP - 1 - p) q + s]
+    std::vector<float> tp((size_t)q * geom.PP, 0.f);
+    for (int s = 0; s < q; ++s)
+        for (int p = 0; p < geom.PP; ++p) {
+            const int j = (geom.PP - 1 - p) * q + s;
+            if (j < ntaps) tp[(size_t)s * geom.PP + p] = h[j];
+        }
+    void *taps_d = nullptr;
+    if (get_table(10, tp.data(), sizeof(float) * tp.size(), &taps_d, nullptr)) return -1;
+    // the oscillator: nu n0 modulo one turn in 128-bit fixed point, the step rounded to 2^-64 turns (over the <= 2^32 samples of a
+    // launch that is <= 2^-33 turns), and the float32 table exp(-2 pi i nu j) over the staged span of a tile
+    const u128 A = frac128(nu);
+    const uint64_t ph0 = (uint64_t)((A * (u128)(__int128)n0) >> 64);
+    const uint64_t dnu = (uint64_t)((A + ((u128)1 << 63)) >> 64);
+    void *tab_d = nullptr;
+    if (A != 0) {
+        struct {
+            double nu;
+            int64_t W;
+        } key = {nu, geom.W};
+        bool fresh = false;
+        if (get_table_keyed(9, &key, sizeof key, nullptr, sizeof(cf) * (size_t)geom.W, &tab_d, &fresh)) return -1;
+        if (fresh) {
+            std::vector<cf> tab((size_t)geom.W);
+            czt_chirp_host(0, geom.W, 0.0, nu, (float *)tab.data());
+            HIPCHK(hipMemcpy(tab_d, tab.data(), sizeof(cf) * (size_t)geom.W, hipMemcpyHostToDevice));
+        }
+    }
+    {
+        ProfScope ps;
+        if (launch_ddc(lc(), xd, cplx, x_ld, nsig, batch, geom, ph0, dnu, (const cf *)tab_d, (const float *)taps_d,
+                       ((uintptr_t)xd & 15) == 0, od) != 0)
+            return fail("sp_ddc: the launch was refused (q = %d, ntaps = %d, %zu bytes of LDS)", q, ntaps, geom.lds);
+        HIPCHK(hipGetLastError());
+        g.last_kernel = "k_ddc";
     }
     if (!mem) {
         HIPCHK(hipMemcpyAsync(out, od, obytes, hipMemcpyDeviceToHost, g.stream));

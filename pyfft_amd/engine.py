@@ -644,6 +644,52 @@ def zoom_welch(x, win, hop, nframes, m, start, step, y=None, detrend=False, mean
     return fr if frames else (pxx, pyy, pxy)
 
 
+# ------------------------------------------------------------------------------------------ down-converter
+def ddc_tile(q):
+    """Outputs one workgroup of sp_ddc produces at the decimation q (it consumes q times as many samples).  Host only."""
+    k = int(lib().sp_ddc_tile(int(q)))
+    if k <= 0:
+        raise ValueError("ddc_tile: q = %r is outside 1 .. 64" % (q,))
+    return k
+
+
+def ddc(x, nu, q, h, n0=0):
+    """Mix, low-pass and decimate along the last axis (sp_ddc): y[..., k] = sum_j h[j] v[..., k q + (T - 1) / 2 - j] with
+    v[..., n] = x[..., n] exp(-2 pi i nu (n0 + n)), nu in cycles per sample, h real with an odd length T, k < ceil(n / q).  complex64
+    [..., ceil(n / q)]; numpy in -> numpy out, device tensor in -> device tensor on x's stream (rows of a 2-D tensor may be strided)."""
+    nu, q, n0 = float(nu), int(q), int(n0)
+    if np.iscomplexobj(h):
+        raise ValueError("ddc: the taps must be real")
+    taps = np.ascontiguousarray(np.asarray(h), dtype=np.float32)
+    if taps.ndim != 1:
+        raise ValueError("ddc: the taps must be one-dimensional")
+    if not 1 <= q <= 64:
+        raise ValueError("ddc: q = %d is outside 1 .. 64" % q)
+    if _is_torch(x):
+        _bind_stream(x)
+        if x.dtype not in (torch.float32, torch.complex64):
+            raise TypeError("device path takes float32 or complex64 samples, got %s" % x.dtype)
+        if x.dim() < 1:
+            raise ValueError("ddc: x must have at least one axis")
+        n = int(x.shape[-1])
+        if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= n and x.shape[0] >= 1:
+            xs, ld = x, int(x.stride(0))                      # a row-strided view goes through as it is
+        else:
+            xs, ld = x.contiguous(), n
+        batch = xs.numel() // n if n else 0
+        out = torch.empty(tuple(x.shape[:-1]) + (-(-n // q),), dtype=torch.complex64, device=x.device)
+        check(lib().sp_ddc(ptr(xs.data_ptr()), _tcode(xs), n, ld, batch, nu, n0, q, ptr(taps), taps.size, ptr(out.data_ptr()), 1))
+        return out
+    xs = _ffi.as_samples(x)
+    if xs.ndim < 1:
+        raise ValueError("ddc: x must have at least one axis")
+    n = xs.shape[-1]
+    out = np.empty(xs.shape[:-1] + (-(-n // q),), dtype=np.complex64)
+    _ffi.init()
+    check(lib().sp_ddc(ptr(xs), _ffi.dtype_code(xs.dtype), n, n, xs.size // n if n else 0, nu, n0, q, ptr(taps), taps.size, ptr(out), 0))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ N3
 def stft_cog(x, win, hop, nframes, fs, fmin=0.0, fmax=None, detrend=False, mean_value=None):
     """Centre of gravity (power-weighted mean frequency, Doppler.py:43-58) of every frame's two-sided spectrum, reduced
