@@ -273,6 +273,32 @@ int sp_ddc(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t batch
            int ntaps, void *out, int mem);
 int sp_ddc_tile(int q);
 
+/* ---- Polyphase filter-bank channelizer (weighted overlap-add DFT bank): every row of a batch split into M uniformly spaced
+ *      bands under a prototype filter of ntaps = P*M real taps, longer than the transform.  For one row x[0:nsig], zero outside
+ *      the row, and frame m = 0 .. nframes-1 with s = first + m*hop (first: the row index of frame 0's first sample, may be < 0):
+ *        X[m][k] = sum_{n<ntaps} h[n] * x[s+n] * exp(-2 pi i k (n + rho_m) / M),   k < M
+ *        rho_m   = 0                       phase_ref 0 ("frame": bin P*k of an ntaps-point STFT under the window h)
+ *        rho_m   = (r0 + m*hop) mod M      phase_ref 1 ("time": the caller passes r0 = (n0 + first) mod M, n0 the absolute index of
+ *                                          the row's sample 0; a tone at k/M cycles per sample is then constant in channel k)
+ *      computed as a fold and ONE M-point transform:  u[i] = sum_{p<P} h[p*M+j] * x[s+p*M+j],  j = (i - rho_m) mod M,
+ *      X[m][:] = FFT_M(u); the sum over p runs in the order p = 0 .. P-1 with fused multiply-adds.  Each channel is a baseband
+ *      series with one sample per hop input samples.
+ *      x: float32 or complex64 rows of nsig samples, row stride x_ld >= nsig; h: HOST float32 [ntaps] (device table cache, like
+ *      the windows); complex input -> nb = M bins in natural FFT order; real input -> the bins 0 .. M/2, nb = M/2 + 1.
+ *      out_kind 0: the frames, complex64, out_major 0 = [batch][nframes][nb], 1 = [batch][nb][nframes] (scipy's layout); scale is
+ *                  not applied.  A frame's bits do not depend on how the frames are dealt out to workgroups, nor on the other
+ *                  frames of the call.
+ *      out_kind 1: the accumulated power pxx[batch][nb] = scale/nframes * sum_m |X[m][k]|^2, float64, nothing doubled (out_major
+ *                  ignored).  No atomics: group partials are summed in float64 in a fixed order, so two calls agree bitwise.
+ *      x and out follow `mem`.
+ *      Limits of one launch: M a power of two, 2 .. sp_max_wg_fft(); ntaps = P*M with 1 <= P <= 32; hop >= 1; nframes >= 1;
+ *      0 <= r0 < M; h and scale finite; every frame touches at least one sample of the row (first > -ntaps and
+ *      first + (nframes-1)*hop < nsig); x_ld >= nsig >= 1; batch * ceil(nframes / frames per workgroup) fits 31 bits.
+ *      out_major 1: nframes <= 65535*32.
+ *      Anything else returns < 0 with sp_last_error() naming sp_pfb, before the device is touched, and leaves out untouched. */
+int sp_pfb(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t batch, const float *h, int ntaps, int M, int hop,
+           int64_t first, int64_t nframes, int phase_ref, int r0, int out_kind, int out_major, double scale, void *out, int mem);
+
 /* ---- N3: Doppler.cog applied per STFT frame (Doppler.py:43-58; the loop body of cogspec, Doppler.py:73-81):
  *      cog_out[g] = sum_k f_k |X_g[k]|^2 / sum_k |X_g[k]|^2 over the two-sided spectrum of frame g, f_k = fftfreq(nfft, 1/fs),
  *      restricted to fmin <= |f_k| <= fmax (fmin = 0, fmax >= fs/2: every bin); 0 where the band holds no power.  The

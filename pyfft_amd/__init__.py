@@ -36,3 +36,5 @@ from . import zoom as _zoom_mod                                # noqa: F401
 from .zoom import czt, zoom_fft, zoom_stft, zoom_psd, zoom_csd, zoom_coherence, zoom_plan   # noqa: F401
 from . import baseband as _baseband_mod                        # noqa: F401
 from .baseband import ddc, ddc_plan, band_stft, band_psd, band_csd, band_coherence, band_plan   # noqa: F401
+from . import channelizer as _channelizer_mod                  # noqa: F401
+from .channelizer import pfb_prototype, pfb_plan, channelize, pfb_psd   # noqa: F401

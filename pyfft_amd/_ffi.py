@@ -59,6 +59,7 @@ SIGNATURES = {
     "sp_czt_chirp": (_i, [_i64, _i64, _d, _d, _vp]),
     "sp_ddc": (_i, [_vp, _i, _i64, _i64, _i64, _d, _i64, _i, _vp, _i, _vp, _i]),
     "sp_ddc_tile": (_i, [_i]),
+    "sp_pfb": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _i, _i, _i, _i64, _i64, _i, _i, _i, _i, _d, _vp, _i]),
     "sp_stft_cog":(_i, [_vp, _i, _i64, _vp, _i, _i, _i64, _i, _d, _d, _d, _d, _d, _vp, _i]),
     "sp_hilbert": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i]),
     "sp_frame_sum": (_i, [_vp, _i, _i64, _i, _i64, _i, _i, _i64, _i, _vp, _i]),

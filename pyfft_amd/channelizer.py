@@ -1,0 +1,146 @@
+"""Polyphase filter-bank channelizer: a record split into all M uniformly spaced bands at once under a prototype low-pass of
+L = taps * M coefficients, longer than the transform (the weighted overlap-add DFT bank; k_pfb.hip).
+
+    X[m, k] = sum_{n<L} h[n] x[s + n] exp(-2 pi i k (n + rho_m) / M),   s = first + m hop,   x = 0 outside the record
+    rho_m   = 0 (phase "frame")  or  (n0 + s) mod M (phase "time": every channel is referred to absolute time, so that a tone at
+              exactly k / M cycles per sample is a constant in channel k whatever the hop, and chunks of one stream continue)
+
+Channel k is the baseband series of the band around k fs / M at the rate fs / hop; with phase "frame" and first = 0 it is bin
+taps * k of scipy.signal.stft(window=h, nperseg=L, noverlap=L - hop, boundary=None, padded=False) before its scaling.  pfb_prototype
+designs h, pfb_plan is the host geometry, channelize returns the frames and pfb_psd their mean power, accumulated on the device.
+"""
+import math
+
+import numpy as np
+
+from .baseband import Unsupported, MAX_WG_FFT, _is_torch
+
+MAX_P = 32                          # branches (taps per channel) one launch takes
+
+
+def pfb_prototype(M, taps=8, window=("kaiser", 8.0), cutoff=1.0):
+    """The prototype low-pass of a bank of M channels, float64 [taps * M]: scipy.signal.firwin(taps * M, cutoff / M, window=window),
+    so the -6 dB edge sits at cutoff / (2 M) cycles per sample (half the channel spacing at cutoff = 1) and the DC gain is 1.
+    Pure scipy, never loads the library."""
+    M, taps = int(M), int(taps)
+    if M < 1 or taps < 1:
+        raise ValueError("pfb_prototype: M and taps must be positive")
+    cutoff = float(cutoff)
+    if not 0.0 < cutoff < M:
+        raise ValueError("pfb_prototype: cutoff must lie in (0, M), got %r" % cutoff)
+    import scipy.signal as ss
+    return ss.firwin(taps * M, cutoff / M, window=window)
+
+
+def pfb_plan(nsig, cplx, M, taps=8, hop=None, fs=1.0, h=None, center=False, n0=0, return_onesided=None):
+    """The validated host plan of a channelizer run (pure numpy / scipy, never loads the library): a dict with h (float64 [L]), L, P,
+    M, hop, first (the index of frame 0's first sample), nframes, r0 = (n0 + first) mod M, f (the channel centres), t (the frame
+    centres in seconds: (n0 + first + m hop + (L - 1) / 2) / fs), nb, onesided.  center=False: the frames that lie inside the record;
+    center=True: frame m is centred on sample m hop, the record zero-extended.  A real input is one-sided (the bins 0 .. M/2)."""
+    who = "pfb"
+    nsig, M, n0 = int(nsig), int(M), int(n0)
+    fs = float(fs)
+    if not (fs > 0 and math.isfinite(fs)):
+        raise ValueError("%s: fs must be positive" % who)
+    if M < 2 or M & (M - 1) or M > MAX_WG_FFT:
+        raise Unsupported("%s: M = %d is not a power of two from 2 to %d; other channel counts are not built" % (who, M, MAX_WG_FFT))
+    if h is None:
+        taps = int(taps)
+        if taps < 1:
+            raise ValueError("%s: taps must be at least 1" % who)
+        if taps > MAX_P:
+            raise Unsupported("%s: %d taps per channel are beyond the %d one launch takes" % (who, taps, MAX_P))
+        hh = pfb_prototype(M, taps)
+    else:
+        if np.iscomplexobj(h):
+            raise Unsupported("%s: complex taps are not built" % who)
+        hh = np.asarray(h, dtype=np.float64)
+        if hh.ndim != 1 or hh.size < M or hh.size % M:
+            raise ValueError("%s: len(h) must be a positive multiple of M = %d, got %s" % (who, M, hh.shape))
+        if not np.all(np.isfinite(hh)):
+            raise ValueError("%s: the taps must be finite" % who)
+        if hh.size // M > MAX_P:
+            raise Unsupported("%s: %d taps per channel are beyond the %d one launch takes" % (who, hh.size // M, MAX_P))
+    L = hh.size
+    hop = M if hop is None else int(hop)
+    if hop < 1:
+        raise ValueError("%s: hop must be at least 1" % who)
+    cplx = bool(cplx)
+    onesided = (not cplx) if return_onesided is None else bool(return_onesided)
+    if onesided and cplx:
+        raise ValueError("%s: a complex input has no one-sided spectrum" % who)
+    if not onesided and not cplx:
+        raise Unsupported("%s: a real input gives the bins 0 .. M/2 only (return_onesided=False is not built)" % who)
+    if nsig < 1:
+        raise ValueError("%s: the record is empty" % who)
+    if center:
+        first, nframes = -(L // 2), -(-nsig // hop)
+    else:
+        if nsig < L:
+            raise ValueError("%s: the record (%d samples) is shorter than the filter (%d taps); center=True zero-extends it" %
+                             (who, nsig, L))
+        first, nframes = 0, (nsig - L) // hop + 1
+    m = np.arange(nframes, dtype=np.float64)
+    t = (n0 + first + m * hop + (L - 1) / 2.0) / fs
+    f = np.arange(M // 2 + 1, dtype=np.float64) * (fs / M) if onesided else np.fft.fftfreq(M, 1.0 / fs)
+    return dict(h=hh, L=L, P=L // M, M=M, hop=hop, first=first, nframes=nframes, r0=(n0 + first) % M, f=f, t=t, nb=f.size,
+                onesided=onesided, fs=fs, cplx=cplx)
+
+
+def _prepare(x, axis, who):
+    """(x with the time axis last, device?, ndim, is complex, nsig)."""
+    dev = _is_torch(x)
+    if not dev:
+        x = np.asarray(x)
+    nd = x.dim() if dev else x.ndim
+    if nd < 1:
+        raise ValueError("%s: x must have at least one axis" % who)
+    if not -nd <= axis < nd:
+        raise ValueError("%s: axis %d is out of range" % (who, axis))
+    last = axis in (-1, nd - 1)
+    if not last:
+        x = x.movedim(axis, -1) if dev else np.moveaxis(x, axis, -1)
+    cplx = x.is_complex() if dev else np.iscomplexobj(x)
+    return x, dev, last, cplx, int(x.shape[-1])
+
+
+def channelize(x, M, taps=8, hop=None, fs=1.0, *, h=None, center=False, phase="time", n0=0, axis=-1, return_onesided=None):
+    """(f, t, X): the M-channel polyphase filter bank of x along `axis`.  X is complex64 [..., nb, nframes] (scipy.signal.stft's
+    layout, the frames last); f the channel centres (fftfreq order for a complex input, 0 .. fs/2 for a real one), t the frame centres.
+    h: the prototype (default pfb_prototype(M, taps)); hop defaults to M (critical sampling).  phase "time" refers every channel to
+    absolute time (n0 = the absolute index of the first sample: chunks of one stream continue), "frame" to the frame's first sample.
+    numpy in -> numpy out, device tensor in -> device tensor out."""
+    if phase not in ("time", "frame"):
+        raise ValueError("channelize: phase must be 'time' or 'frame'")
+    y, dev, last, cplx, nsig = _prepare(x, axis, "channelize")
+    p = pfb_plan(nsig, cplx, M, taps, hop, fs, h, center, n0, return_onesided)
+    from . import engine
+    X = engine.pfb(y, p["h"], p["M"], p["hop"], p["first"], p["nframes"], phase_ref=1 if phase == "time" else 0,
+                   r0=p["r0"] if phase == "time" else 0, out_major=1)
+    if not last:                                  # [..., nb, nframes] with the frames last: the bins go where the time axis was
+        nd = X.dim() if dev else X.ndim
+        src = nd - 2
+        dst = axis if axis >= 0 else axis + nd - 1
+        X = X.movedim(src, dst) if dev else np.moveaxis(X, src, dst)
+    return p["f"], p["t"], X
+
+
+def pfb_psd(x, M, taps=8, hop=None, fs=1.0, *, h=None, center=False, scaling="density", axis=-1, return_onesided=None):
+    """(f, Pxx): the mean power of every channel over the frames of channelize, accumulated on the device in one pass (the frames
+    are never written): float64 [..., nb].  scaling 'density': 1 / (fs sum h^2), 'spectrum': 1 / (sum h)^2, as scipy.signal.welch
+    with the window h; for a real input the bins 1 .. M/2 - 1 are doubled."""
+    if scaling not in ("density", "spectrum"):
+        raise ValueError("pfb_psd: scaling must be 'density' or 'spectrum'")
+    y, dev, last, cplx, nsig = _prepare(x, axis, "pfb_psd")
+    p = pfb_plan(nsig, cplx, M, taps, hop, fs, h, center, 0, return_onesided)
+    s1, s2 = float(np.sum(p["h"])), float(np.sum(p["h"] * p["h"]))
+    if not s2 > 0 or (scaling == "spectrum" and s1 == 0):
+        raise ValueError("pfb_psd: the taps sum to zero")
+    scale = 1.0 / (p["fs"] * s2) if scaling == "density" else 1.0 / (s1 * s1)
+    from . import engine
+    pxx = engine.pfb(y, p["h"], p["M"], p["hop"], p["first"], p["nframes"], power=True, scale=scale)
+    if p["onesided"]:
+        pxx[..., 1:p["M"] // 2] *= 2.0
+    if not last:
+        pxx = pxx.movedim(-1, axis) if dev else np.moveaxis(pxx, -1, axis)
+    return p["f"], pxx

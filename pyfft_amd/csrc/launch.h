@@ -18,6 +18,7 @@ namespace sp {
 //   SP_DIST_RESERVE_CUS, SP_DIST_RCCL_CTAS (int: the sharded PSD's CU reserve and the communicator's workgroup limit)
 //   SP_BISPEC_MIB (int: the bispectrum's spectra and partials budget per frame chunk, MiB)
 //   SP_ISTFT_FPG, SP_ISTFT_MIB (int: the inverse STFT's frames per run; its budget for transposed bin-major spectra, MiB)
+//   SP_PFB_FPG, SP_PFB_TREG (int: the channelizer's frames per run; 0 / 1: its taps from the table / held in registers)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
     return v && v[0] && v[0] != '0';
@@ -391,6 +392,21 @@ inline DdcGeom ddc_geom(int q, int ntaps) {
 // or 0 past the last tap; vec: x is 16-byte aligned
 int launch_ddc(LaunchCtx c, const void *x, bool cplx, int64_t x_ld, int64_t nsig, int64_t batch, const DdcGeom &g, uint64_t ph0,
                uint64_t dnu, const cf *tab, const float *taps, bool vec, cf *out);
+
+// polyphase filter-bank channelizer (k_pfb.hip): frames m < nframes of every row, frame m = the L = P M samples from first + m hop on
+// (zero outside the row) folded to M under the taps and transformed; rp partitions the frames of ONE row, the grid is rp.blocks x batch
+// workgroups in one dimension.  out_kind 0: out = complex64 [batch][nframes][nb], nb = M (complex rows) or M/2 + 1 (real rows);
+// out_kind 1: partial[batch][rp.groups][M] floats, summed by launch_pfb_finish into float64 out[batch][nb] = scale * sum.
+// The taps stay in registers when every frame sees the same rotation, P <= SP_PFB_TREG_P and M <= SP_PFB_TREG_MAXM (SP_PFB_TREG=0: never).
+#define SP_PFB_MAXP 32
+#define SP_PFB_TREG_P 4
+#define SP_PFB_TREG_MAXM 4096
+#define SP_PFB_TREG_DEFAULT 1
+bool pfb_treg_wanted(int M, int P, int hop, int phase_ref);
+int launch_pfb(LaunchCtx c, const void *x, bool cplx, int64_t x_ld, int64_t nsig, int64_t batch, const float *taps, int P, int hop,
+               int64_t first, int64_t nframes, int phase_ref, int r0, const Xf &xf, const RunPart &rp, int out_kind, void *out,
+               float *partial);
+int launch_pfb_finish(LaunchCtx c, const float *partial, int64_t G, int M, int nb, int64_t batch, double scale, double *out);
 
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;

@@ -20,7 +20,7 @@
 
 using namespace sp;
 
-#define SP_VERSION 108
+#define SP_VERSION 109
 #define SP_MAX_WG_FFT 8192
 #define SP_MAX_BIG_LOG2 26          /* longest multi-pass power-of-two transform: 2^26 points (512 MiB per buffer) */
 
@@ -2757,6 +2757,96 @@ int sp_ddc(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t batch
             return fail("sp_ddc: the launch was refused (q = %d, ntaps = %d, %zu bytes of LDS)", q, ntaps, geom.lds);
         HIPCHK(hipGetLastError());
         g.last_kernel = "k_ddc";
+    }
+    if (!mem) {
+        HIPCHK(hipMemcpyAsync(out, od, obytes, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
+// ---- polyphase filter-bank channelizer (k_pfb.hip) ------------------------------------------------
+int sp_pfb(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t batch, const float *h, int ntaps, int M, int hop,
+           int64_t first, int64_t nframes, int phase_ref, int r0, int out_kind, int out_major, double scale, void *out, int mem) {
+    // every refusal comes before the device is touched
+    if (x_dtype != SP_DTYPE_F32 && x_dtype != SP_DTYPE_C64) return fail("sp_pfb: unknown dtype %d", x_dtype);
+    if (M < 2 || M > SP_MAX_WG_FFT || !is_pow2(M))
+        return fail("sp_pfb: M = %d must be a power of two from 2 to %d", M, SP_MAX_WG_FFT);
+    if (ntaps < M || ntaps % M != 0 || ntaps / M > SP_PFB_MAXP)
+        return fail("sp_pfb: ntaps = %d must be P M with 1 <= P <= %d (M = %d)", ntaps, SP_PFB_MAXP, M);
+    if (hop < 1) return fail("sp_pfb: hop = %d must be at least 1", hop);
+    if (nframes < 1) return fail("sp_pfb: nframes = %lld must be at least 1", (long long)nframes);
+    if (phase_ref != 0 && phase_ref != 1) return fail("sp_pfb: phase_ref must be 0 (frame) or 1 (time)");
+    if (r0 < 0 || r0 >= M) return fail("sp_pfb: r0 = %d must lie in 0 .. M - 1", r0);
+    if (out_kind != 0 && out_kind != 1) return fail("sp_pfb: out_kind must be 0 (frames) or 1 (accumulated power)");
+    if (out_major != 0 && out_major != 1) return fail("sp_pfb: out_major must be 0 or 1");
+    if (!isfinite(scale)) return fail("sp_pfb: scale must be finite");
+    if (nsig < 1 || batch < 0 || x_ld < nsig) return fail("sp_pfb: need nsig >= 1, batch >= 0 and a row stride x_ld >= nsig");
+    // every frame touches the row: the first ends inside it or later, the last starts inside it or earlier
+    if (first <= -(int64_t)ntaps || first >= nsig || nframes - 1 > (nsig - 1 - first) / hop)
+        return fail("sp_pfb: frames 0 .. %lld from first = %lld at hop %d do not all touch the %lld samples of the row",
+                    (long long)(nframes - 1), (long long)first, hop, (long long)nsig);
+    const int fpw = fpw_of(M);
+    if (batch > 0 && (nframes + fpw - 1) / fpw > INT_MAX / batch)
+        return fail("sp_pfb: %lld rows of %lld frames are too many workgroups for one launch", (long long)batch, (long long)nframes);
+    if (out_kind == 0 && out_major == 1 && nframes > (int64_t)65535 * 32)
+        return fail("sp_pfb: the bin-major layout takes at most %lld frames per launch", (long long)65535 * 32);
+    if (batch == 0) return 0;
+    if (!x || !h || !out) return fail("sp_pfb: x, h and out are required");
+    for (int j = 0; j < ntaps; ++j)
+        if (!isfinite(h[j])) return fail("sp_pfb: the taps must be finite");
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    Xf xf;
+    if (get_xf(M, &xf)) return -1;
+    const bool cplx = x_dtype == SP_DTYPE_C64;
+    const int P = ntaps / M, nb = cplx ? M : M / 2 + 1;
+    const size_t esz = cplx ? 8 : 4, in_elems = (size_t)((batch - 1) * x_ld + nsig);
+    const size_t obytes = (out_kind ? sizeof(double) : sizeof(cf) * (size_t)nframes) * (size_t)nb * (size_t)batch;
+    const void *xd = x;
+    void *od = out;
+    if (!mem) {
+        if (g.in0.ensure(esz * in_elems) || g.out0.ensure(obytes)) return -1;
+        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * in_elems, hipMemcpyHostToDevice, g.stream));
+        xd = g.in0.p;
+        od = g.out0.p;
+    }
+    void *taps_d = nullptr;
+    if (get_table(11, h, sizeof(float) * (size_t)ntaps, &taps_d, nullptr)) return -1;
+    // the run partition of one row (SP_PFB_FPG: a test hook like those of launch.h, read on every call; any value >= 1 is valid)
+    RunPart rp = run_partition_2d(M, nframes, g.ncu, (int)(batch < INT_MAX ? batch : INT_MAX));
+    {
+        const int64_t f = env_int("SP_PFB_FPG", 0);
+        if (f >= 1) {
+            const int64_t G = (nframes + f - 1) / f;
+            rp.fpg = f;
+            rp.blocks = (int)((G + fpw - 1) / fpw);
+            rp.groups = (int64_t)rp.blocks * fpw;
+        }
+    }
+    void *kout = od;                     // what the kernel writes: frame-major frames, or the groups' partial sums
+    if (out_kind == 1) {
+        if (g.work.ensure(sizeof(float) * (size_t)batch * (size_t)rp.groups * (size_t)M)) return -1;
+        kout = g.work.p;
+    } else if (out_major == 1) {
+        if (g.work.ensure(obytes)) return -1;
+        kout = g.work.p;
+    }
+    {
+        ProfScope ps;
+        if (launch_pfb(lc(), xd, cplx, x_ld, nsig, batch, (const float *)taps_d, P, hop, first, nframes, phase_ref, r0, xf, rp, out_kind,
+                       out_kind ? nullptr : kout, out_kind ? (float *)kout : nullptr) != 0)
+            return fail("sp_pfb: the launch was refused (M = %d, P = %d, %lld rows)", M, P, (long long)batch);
+        HIPCHK(hipGetLastError());
+        g.last_kernel = "k_pfb";
+    }
+    if (out_kind == 1) {
+        LAUNCHCHK(launch_pfb_finish(lc(), (const float *)kout, rp.groups, M, nb, batch, scale / (double)nframes, (double *)od));
+    } else if (out_major == 1) {
+        const size_t row = sizeof(cf) * (size_t)nframes * (size_t)nb;
+        for (int64_t b = 0; b < batch; ++b)
+            LAUNCHCHK(launch_transpose(lc(), (const char *)kout + (size_t)b * row, (char *)od + (size_t)b * row, nframes, (int64_t)nb,
+                                       (int)sizeof(cf)));
     }
     if (!mem) {
         HIPCHK(hipMemcpyAsync(out, od, obytes, hipMemcpyDeviceToHost, g.stream));

@@ -690,6 +690,55 @@ def ddc(x, nu, q, h, n0=0):
     return out
 
 
+def pfb(x, h, M, hop, first, nframes, phase_ref=0, r0=0, power=False, out_major=0, scale=1.0):
+    """Polyphase filter bank along the last axis (sp_pfb): frame m holds the len(h) = P M samples from first + m hop on (zero outside the
+    row), folded to M under the real taps h and transformed: X[..., m, k] = sum_n h[n] x[..., first + m hop + n] exp(-2 pi i k (n + rho_m) / M),
+    rho_m = 0 (phase_ref 0) or (r0 + m hop) mod M (phase_ref 1).  Complex input: nb = M bins in FFT order; real input: the bins 0 .. M/2.
+    power=False: complex64 [..., nframes, nb] (out_major 0) or [..., nb, nframes] (out_major 1); power=True: float64 [..., nb] =
+    scale / nframes sum_m |X|^2.  numpy in -> numpy out, device tensor in -> device tensor on x's stream (rows of a 2-D tensor may be
+    strided)."""
+    M, hop, first, nframes, r0 = int(M), int(hop), int(first), int(nframes), int(r0)
+    if np.iscomplexobj(h):
+        raise ValueError("pfb: the taps must be real")
+    taps = np.ascontiguousarray(np.asarray(h), dtype=np.float32)
+    if taps.ndim != 1:
+        raise ValueError("pfb: the taps must be one-dimensional")
+    if M < 2 or nframes < 1:
+        raise ValueError("pfb: need M >= 2 and nframes >= 1")
+    kind, major = (1 if power else 0), int(out_major)
+
+    def oshape(lead, nb):
+        if power:
+            return tuple(lead) + (nb,)
+        return tuple(lead) + ((nb, nframes) if major == 1 else (nframes, nb))
+    if _is_torch(x):
+        _bind_stream(x)
+        if x.dtype not in (torch.float32, torch.complex64):
+            raise TypeError("device path takes float32 or complex64 samples, got %s" % x.dtype)
+        if x.dim() < 1 or x.shape[-1] < 1:
+            raise ValueError("pfb: x must have at least one axis, with at least one sample")
+        n = int(x.shape[-1])
+        if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= n and x.shape[0] >= 1:
+            xs, ld = x, int(x.stride(0))                      # a row-strided view goes through as it is
+        else:
+            xs, ld = x.contiguous(), n
+        nb = M if xs.is_complex() else M // 2 + 1
+        out = torch.empty(oshape(x.shape[:-1], nb), dtype=torch.float64 if power else torch.complex64, device=x.device)
+        check(lib().sp_pfb(ptr(xs.data_ptr()), _tcode(xs), n, ld, xs.numel() // n, ptr(taps), taps.size, M, hop, first, nframes,
+                           int(phase_ref), r0, kind, major, float(scale), ptr(out.data_ptr()), 1))
+        return out
+    xs = _ffi.as_samples(x)
+    if xs.ndim < 1 or xs.shape[-1] < 1:
+        raise ValueError("pfb: x must have at least one axis, with at least one sample")
+    n = xs.shape[-1]
+    nb = M if np.iscomplexobj(xs) else M // 2 + 1
+    out = np.empty(oshape(xs.shape[:-1], nb), dtype=np.float64 if power else np.complex64)
+    _ffi.init()
+    check(lib().sp_pfb(ptr(xs), _ffi.dtype_code(xs.dtype), n, n, xs.size // n, ptr(taps), taps.size, M, hop, first, nframes,
+                       int(phase_ref), r0, kind, major, float(scale), ptr(out), 0))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ N3
 def stft_cog(x, win, hop, nframes, fs, fmin=0.0, fmax=None, detrend=False, mean_value=None):
     """Centre of gravity (power-weighted mean frequency, Doppler.py:43-58) of every frame's two-sided spectrum, reduced
