@@ -299,6 +299,36 @@ int sp_ddc_tile(int q);
 int sp_pfb(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t batch, const float *h, int ntaps, int M, int hop,
            int64_t first, int64_t nframes, int phase_ref, int r0, int out_kind, int out_major, double scale, void *out, int mem);
 
+/* ---- Polyphase synthesis bank: the adjoint of sp_pfb's fold, the way back from its frames to a waveform.  Same symbols as sp_pfb:
+ *      frames X[m][k], m < nframes, on M channels, s_m = first + m*hop, rho_m = 0 (phase_ref 0) or (r0 + m*hop) mod M (phase_ref 1),
+ *      a synthesis prototype g[0:ntaps], ntaps = P*M:
+ *        v_m[i] = sum_{k<M} X[m][k] * exp(+2 pi i k i / M)                     (unnormalised inverse transform)
+ *        y[a]   = sum_{m : 0 <= a - s_m < ntaps} tap[a - s_m] * v_m[(a - s_m + rho_m) mod M],   0 <= a < nout
+ *        tap[n] = float32(g[n] * scale / M)                                    (rounded once on the host)
+ *      The sum over m runs in ascending frame order from zero with one fused multiply-add per component, which fixes a sample's bits:
+ *      they depend neither on how the frames are dealt out to workgroups nor on the path (below), and two calls agree bitwise.
+ *      Frames that lie partly or wholly outside [0, nout) contribute what falls inside; a sample that no frame reaches is zero; every
+ *      one of the nout samples is written.  With the analysis prototype h of sp_pfb and scale = 1,
+ *      y[a] = sum_q T[q][(a - first) mod hop] * x[a + q*M], T[q][r] = sum_j g[r + j*hop] * h[r + j*hop + q*M], on the samples whose
+ *      frames all belong to the call: g reconstructs when T = delta_q (pyfft_amd.channelizer.pfb_dual designs such a g for hop < M).
+ *      sided SP_SIDED_HALF: nb = M/2 + 1 bins, Hermitian-extended, the imaginary parts of bins 0 and M/2 ignored -> y float32;
+ *      SP_SIDED_RAW: nb = M bins in natural FFT order -> y complex64.  in_major 0: X[batch][nframes][nb]; 1: X[batch][nb][nframes]
+ *      (sp_pfb's two out_major layouts; the second is transposed into library scratch of the input's size).  g: HOST float32 [ntaps]
+ *      (device table cache, like the windows); X and y follow `mem`; y is [batch][nout].
+ *      Two paths with the same bits: where the exchange images and a ring of ntaps accumulators per transform group fit the 160 KiB
+ *      of LDS a workgroup may take, one fused kernel overlap-adds in LDS (no scratch, no atomics); otherwise the inverse transforms go
+ *      to library scratch [batch][nframes][M] and a second kernel sums every output sample from the frames that reach it.
+ *      Limits of one launch: M a power of two, 2 .. sp_max_wg_fft(); ntaps = P*M with 1 <= P <= 32; hop >= 1; nframes >= 1; nout >= 1;
+ *      batch >= 0; 0 <= r0 < M; g, scale and every tap finite; |first|, nframes*hop and nout within 2^40;
+ *      batch * ceil(nframes / frames per workgroup) fits 31 bits; X, g and y not NULL.
+ *      Anything else returns < 0 with sp_last_error() naming sp_pfb_synth, before the device is touched, and leaves y untouched. */
+int sp_pfb_synth(const void *X, int sided, int in_major, int64_t batch, int64_t nframes, const float *g, int ntaps, int M, int hop,
+                 int64_t first, int phase_ref, int r0, double scale, int64_t nout, void *y, int mem);
+/*      sp_pfb_synth_plan: what sp_pfb_synth would do by default at this shape, for tools: out[5] = { 1 fused / 0 composed, the transform
+ *      groups of a workgroup whose ring fits the LDS (0: not one), the groups per workgroup, the frames per run of the fused path, its
+ *      halo frames }.  Initialises the device (the run length depends on its CU count); SP_PFBS_PATH and SP_PFBS_FPG are not applied. */
+int sp_pfb_synth_plan(int sided, int64_t batch, int64_t nframes, int ntaps, int M, int hop, int64_t *out);
+
 /* ---- N3: Doppler.cog applied per STFT frame (Doppler.py:43-58; the loop body of cogspec, Doppler.py:73-81):
  *      cog_out[g] = sum_k f_k |X_g[k]|^2 / sum_k |X_g[k]|^2 over the two-sided spectrum of frame g, f_k = fftfreq(nfft, 1/fs),
  *      restricted to fmin <= |f_k| <= fmax (fmin = 0, fmax >= fs/2: every bin); 0 where the band holds no power.  The

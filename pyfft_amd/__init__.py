@@ -38,3 +38,4 @@ from . import baseband as _baseband_mod                        # noqa: F401
 from .baseband import ddc, ddc_plan, band_stft, band_psd, band_csd, band_coherence, band_plan   # noqa: F401
 from . import channelizer as _channelizer_mod                  # noqa: F401
 from .channelizer import pfb_prototype, pfb_plan, channelize, pfb_psd   # noqa: F401
+from .channelizer import pfb_alias_terms, pfb_dual, pfb_synthesis_plan, synthesize   # noqa: F401

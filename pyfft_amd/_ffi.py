@@ -60,6 +60,8 @@ SIGNATURES = {
     "sp_ddc": (_i, [_vp, _i, _i64, _i64, _i64, _d, _i64, _i, _vp, _i, _vp, _i]),
     "sp_ddc_tile": (_i, [_i]),
     "sp_pfb": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _i, _i, _i, _i64, _i64, _i, _i, _i, _i, _d, _vp, _i]),
+    "sp_pfb_synth": (_i, [_vp, _i, _i, _i64, _i64, _vp, _i, _i, _i, _i64, _i, _i, _d, _i64, _vp, _i]),
+    "sp_pfb_synth_plan": (_i, [_i, _i64, _i64, _i, _i, _i, C.POINTER(_i64)]),
     "sp_stft_cog":(_i, [_vp, _i, _i64, _vp, _i, _i, _i64, _i, _d, _d, _d, _d, _d, _vp, _i]),
     "sp_hilbert": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i]),
     "sp_frame_sum": (_i, [_vp, _i, _i64, _i, _i64, _i, _i, _i64, _i, _vp, _i]),

@@ -19,6 +19,7 @@ namespace sp {
 //   SP_BISPEC_MIB (int: the bispectrum's spectra and partials budget per frame chunk, MiB)
 //   SP_ISTFT_FPG, SP_ISTFT_MIB (int: the inverse STFT's frames per run; its budget for transposed bin-major spectra, MiB)
 //   SP_PFB_FPG, SP_PFB_TREG (int: the channelizer's frames per run; 0 / 1: its taps from the table / held in registers)
+//   SP_PFBS_FPG, SP_PFBS_PATH (int: the synthesis bank's frames per run; "fused" / "composed": its path, a fused that does not fit is refused)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
     return v && v[0] && v[0] != '0';
@@ -407,6 +408,21 @@ int launch_pfb(LaunchCtx c, const void *x, bool cplx, int64_t x_ld, int64_t nsig
                int64_t first, int64_t nframes, int phase_ref, int r0, const Xf &xf, const RunPart &rp, int out_kind, void *out,
                float *partial);
 int launch_pfb_finish(LaunchCtx c, const float *partial, int64_t G, int M, int nb, int64_t batch, double scale, double *out);
+
+// polyphase synthesis bank (k_pfb_synth.hip): X = complex64 [batch][nframes][nb] frame-major, nb = M (cplx) or M/2 + 1; taps = the
+// scaled synthesis prototype [P M] on the device; y = [batch][nout] cf (cplx) or float.  fused: runs of fpg frames, each preceded by
+// `halo` frames that are only accumulated, overlap-added in an LDS ring of P M accumulators per group (v unused).  Not fused: fpg frames
+// per group, the inverse transforms go to v[batch][nframes][M] (cf, or float when !cplx; halo and y unused), and
+// launch_pfb_synth_gather sums every output sample from them.  SP_PFBS_LDS_MAX: the LDS one workgroup may take on gfx950 (160 KiB);
+// pfb_synth_groups: the groups of a workgroup that get a ring in the fused form (<= FPW; 0: not even one ring fits) and the LDS bytes
+// that takes (host only).
+#define SP_PFBS_LDS_MAX ((size_t)160 * 1024)
+int pfb_synth_groups(int M, int ntaps, bool cplx, size_t *lds_out);
+int launch_pfb_synth(LaunchCtx c, const cf *X, bool cplx, int64_t batch, int64_t nframes, const float *taps, int P, int hop,
+                     int64_t first, int phase_ref, int r0, const Xf &xf, int64_t fpg, int halo, bool fused, int64_t nout, void *y,
+                     void *v);
+int launch_pfb_synth_gather(LaunchCtx c, const void *v, bool cplx, int64_t batch, int64_t nframes, const float *taps, int ntaps, int M,
+                            int hop, int64_t first, int phase_ref, int r0, int64_t nout, void *y);
 
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;

@@ -20,7 +20,7 @@
 
 using namespace sp;
 
-#define SP_VERSION 109
+#define SP_VERSION 110
 #define SP_MAX_WG_FFT 8192
 #define SP_MAX_BIG_LOG2 26          /* longest multi-pass power-of-two transform: 2^26 points (512 MiB per buffer) */
 
@@ -2850,6 +2850,151 @@ int sp_pfb(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t batch
     }
     if (!mem) {
         HIPCHK(hipMemcpyAsync(out, od, obytes, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
+// ---- polyphase synthesis bank (k_pfb_synth.hip) -----------------------------------------------------
+// the default route and run length of one call (host arithmetic; ncu = the device's CU count).  The route is the composed path at
+// every shape: measured (profiles/pfb_synth_bench.txt, M = 1024 / 4096, P = 4 / 8) the fused kernel takes 2.3 - 3.3 x the composed
+// time where all its rings fit and 2.2 - 6.9 x where only some do, so it runs only when SP_PFBS_PATH=fused asks for it
+// runs: about 4 groups per CU, and long enough that the halo frames a run transforms without writing stay <= 1/16 of it
+namespace {
+struct PfbsPlan {
+    int groups, fpw, halo;     // groups of a workgroup that fit a ring (0: none), groups per workgroup, halo frames of a fused run
+    bool fused;                // the default route
+    int64_t fpg;               // frames per run on the fused path
+};
+PfbsPlan pfbs_plan(int M, int ntaps, bool cplx, int hop, int64_t nframes, int64_t batch, int ncu) {
+    PfbsPlan p;
+    p.fpw = fpw_of(M);
+    p.groups = pfb_synth_groups(M, ntaps, cplx, nullptr);
+    p.fused = false;
+    p.halo = (ntaps + hop - 1) / hop - 1;
+    const int64_t target = std::max<int64_t>(1, (int64_t)ncu * 4 * std::max(p.groups, 1) / std::max<int64_t>(batch, 1));
+    p.fpg = std::max<int64_t>(1, std::max((nframes + target - 1) / target, std::min<int64_t>(16 * (int64_t)p.halo, nframes)));
+    return p;
+}
+}   // namespace
+
+int sp_pfb_synth_plan(int sided, int64_t batch, int64_t nframes, int ntaps, int M, int hop, int64_t *out) {
+    if (sided != SP_SIDED_HALF && sided != SP_SIDED_RAW) return fail("sp_pfb_synth_plan: sided must be SP_SIDED_HALF or SP_SIDED_RAW");
+    if (M < 2 || M > SP_MAX_WG_FFT || !is_pow2(M) || ntaps < M || ntaps % M != 0 || ntaps / M > SP_PFB_MAXP || hop < 1 || nframes < 1 ||
+        batch < 1 || !out)
+        return fail("sp_pfb_synth_plan: a shape sp_pfb_synth refuses, or out is NULL");
+    if (ensure_init()) return -1;
+    const PfbsPlan p = pfbs_plan(M, ntaps, sided == SP_SIDED_RAW, hop, nframes, batch, g.ncu);
+    out[0] = p.fused ? 1 : 0;
+    out[1] = p.groups;
+    out[2] = p.fpw;
+    out[3] = p.fpg;
+    out[4] = p.halo;
+    return 0;
+}
+
+int sp_pfb_synth(const void *X, int sided, int in_major, int64_t batch, int64_t nframes, const float *gt, int ntaps, int M, int hop,
+                 int64_t first, int phase_ref, int r0, double scale, int64_t nout, void *y, int mem) {
+    // every refusal comes before the device is touched
+    if (sided != SP_SIDED_HALF && sided != SP_SIDED_RAW) return fail("sp_pfb_synth: sided must be SP_SIDED_HALF or SP_SIDED_RAW");
+    if (in_major != 0 && in_major != 1) return fail("sp_pfb_synth: in_major must be 0 or 1");
+    if (M < 2 || M > SP_MAX_WG_FFT || !is_pow2(M))
+        return fail("sp_pfb_synth: M = %d must be a power of two from 2 to %d", M, SP_MAX_WG_FFT);
+    if (ntaps < M || ntaps % M != 0 || ntaps / M > SP_PFB_MAXP)
+        return fail("sp_pfb_synth: ntaps = %d must be P M with 1 <= P <= %d (M = %d)", ntaps, SP_PFB_MAXP, M);
+    if (hop < 1) return fail("sp_pfb_synth: hop = %d must be at least 1", hop);
+    if (nframes < 1) return fail("sp_pfb_synth: nframes = %lld must be at least 1", (long long)nframes);
+    if (nout < 1) return fail("sp_pfb_synth: nout = %lld must be at least 1", (long long)nout);
+    if (batch < 0) return fail("sp_pfb_synth: batch = %lld must not be negative", (long long)batch);
+    if (phase_ref != 0 && phase_ref != 1) return fail("sp_pfb_synth: phase_ref must be 0 (frame) or 1 (time)");
+    if (r0 < 0 || r0 >= M) return fail("sp_pfb_synth: r0 = %d must lie in 0 .. M - 1", r0);
+    if (!isfinite(scale)) return fail("sp_pfb_synth: scale must be finite");
+    const int64_t lim = (int64_t)1 << 40;
+    if (first > lim || first < -lim || nframes > lim / hop || nout > lim)
+        return fail("sp_pfb_synth: first = %lld, nframes * hop = %lld * %d and nout = %lld must stay within 2^40", (long long)first,
+                    (long long)nframes, hop, (long long)nout);
+    if (!X || !gt || !y) return fail("sp_pfb_synth: X, g and y are required");
+    // tap = float32(g scale / M), rounded once
+    std::vector<float> tap((size_t)ntaps);
+    for (int j = 0; j < ntaps; ++j) {
+        if (!isfinite(gt[j])) return fail("sp_pfb_synth: the taps must be finite");
+        tap[(size_t)j] = (float)((double)gt[j] * scale / (double)M);
+        if (!isfinite(tap[(size_t)j])) return fail("sp_pfb_synth: tap %d times scale / M is beyond float32", j);
+    }
+    // the path (SP_PFBS_PATH: a test hook like those of launch.h, read on every call): by default the rule of pfbs_plan
+    const bool cplx = sided == SP_SIDED_RAW;
+    const int fpw = fpw_of(M), ag = pfb_synth_groups(M, ntaps, cplx, nullptr);
+    bool fused = pfbs_plan(M, ntaps, cplx, hop, nframes, batch, 1).fused;
+    if (const char *pv = getenv("SP_PFBS_PATH")) {
+        if (!strcmp(pv, "fused")) {
+            if (ag < 1)
+                return fail("sp_pfb_synth: SP_PFBS_PATH=fused, but one ring of %d %s accumulators behind the %d-point exchange image "
+                            "is beyond the %zu bytes of LDS a workgroup may take", ntaps, cplx ? "complex" : "real", M, SP_PFBS_LDS_MAX);
+            fused = true;
+        } else if (!strcmp(pv, "composed")) {
+            fused = false;
+        } else if (pv[0]) {
+            return fail("sp_pfb_synth: SP_PFBS_PATH must be fused or composed, got '%s'", pv);
+        }
+    }
+    const int gpw = fused ? ag : fpw;                      // groups of a workgroup that own frames
+    if (batch > 0 && (nframes + gpw - 1) / gpw > INT_MAX / batch)
+        return fail("sp_pfb_synth: %lld rows of %lld frames are too many workgroups for one launch", (long long)batch,
+                    (long long)nframes);
+    if (batch == 0) return 0;
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    Xf xf;
+    if (get_xf(M, &xf)) return -1;
+    const int P = ntaps / M, nb = cplx ? M : M / 2 + 1;
+    const size_t xbytes = sizeof(cf) * (size_t)nb * (size_t)nframes * (size_t)batch;
+    const size_t esz = cplx ? sizeof(cf) : sizeof(float), ybytes = esz * (size_t)nout * (size_t)batch;
+    const cf *xd = (const cf *)X;
+    void *yd = y;
+    if (!mem) {
+        if (g.in0.ensure(xbytes) || g.out0.ensure(ybytes)) return -1;
+        HIPCHK(hipMemcpyAsync(g.in0.p, X, xbytes, hipMemcpyHostToDevice, g.stream));
+        xd = (const cf *)g.in0.p;
+        yd = g.out0.p;
+    }
+    void *taps_d = nullptr;
+    if (get_table(12, tap.data(), sizeof(float) * (size_t)ntaps, &taps_d, nullptr)) return -1;
+    if (in_major == 1) {                 // bin-major frames [row][nb][nframes]: transposed per row into scratch, as sp_pfb writes them
+        if (g.bigA.ensure(xbytes)) return -1;
+        const size_t rowb = sizeof(cf) * (size_t)nframes * (size_t)nb;
+        for (int64_t b = 0; b < batch; ++b)
+            LAUNCHCHK(launch_transpose(lc(), (const char *)xd + (size_t)b * rowb, (char *)g.bigA.p + (size_t)b * rowb, (int64_t)nb, nframes,
+                                       (int)sizeof(cf)));
+        xd = (const cf *)g.bigA.p;
+    }
+    if (fused) {
+        // the run length of pfbs_plan (SP_PFBS_FPG: a test hook, read on every call; any value >= 1 is valid, also below the halo)
+        const PfbsPlan pl = pfbs_plan(M, ntaps, cplx, hop, nframes, batch, g.ncu);
+        const int halo = pl.halo;
+        int64_t f = env_int("SP_PFBS_FPG", 0);
+        if (f < 1) f = pl.fpg;
+        ProfScope ps;
+        if (launch_pfb_synth(lc(), xd, cplx, batch, nframes, (const float *)taps_d, P, hop, first, phase_ref, r0, xf, f, halo, true, nout,
+                             yd, nullptr) != 0)
+            return fail("sp_pfb_synth: the fused launch was refused (M = %d, P = %d, %lld rows)", M, P, (long long)batch);
+        HIPCHK(hipGetLastError());
+        g.last_kernel = "k_pfb_synth(fused)";
+    } else {
+        if (g.work.ensure(esz * (size_t)M * (size_t)nframes * (size_t)batch)) return -1;
+        RunPart rp = run_partition_2d(M, nframes, g.ncu, (int)(batch < INT_MAX ? batch : INT_MAX));
+        const int64_t fe = env_int("SP_PFBS_FPG", 0);
+        if (fe >= 1) rp.fpg = fe;
+        ProfScope ps;
+        if (launch_pfb_synth(lc(), xd, cplx, batch, nframes, (const float *)taps_d, P, hop, first, phase_ref, r0, xf, rp.fpg, 0, false, nout,
+                             nullptr, g.work.p) != 0)
+            return fail("sp_pfb_synth: the launch was refused (M = %d, P = %d, %lld rows)", M, P, (long long)batch);
+        HIPCHK(hipGetLastError());
+        LAUNCHCHK(launch_pfb_synth_gather(lc(), g.work.p, cplx, batch, nframes, (const float *)taps_d, ntaps, M, hop, first, phase_ref, r0,
+                                          nout, yd));
+        g.last_kernel = "k_pfb_synth(composed)";
+    }
+    if (!mem) {
+        HIPCHK(hipMemcpyAsync(y, yd, ybytes, hipMemcpyDeviceToHost, g.stream));
         HIPCHK(hipStreamSynchronize(g.stream));
     }
     return 0;

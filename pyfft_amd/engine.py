@@ -739,6 +739,60 @@ def pfb(x, h, M, hop, first, nframes, phase_ref=0, r0=0, power=False, out_major=
     return out
 
 
+def pfb_synth(X, g, M, hop, first, nout, phase_ref=0, r0=0, onesided=True, in_major=0, scale=1.0):
+    """Polyphase synthesis bank (sp_pfb_synth), the adjoint of pfb's fold: y[..., a] = sum_m tap[a - s_m] v_m[(a - s_m + rho_m) mod M]
+    over the frames with 0 <= a - s_m < len(g), s_m = first + m hop, v_m = the unnormalised inverse M-point transform of frame m,
+    tap = float32(g scale / M), rho_m = 0 (phase_ref 0) or (r0 + m hop) mod M (phase_ref 1); a < nout, zero where no frame reaches.
+    X: complex64 [..., nframes, nb] (in_major 0) or [..., nb, nframes] (in_major 1, what channelize returns); nb = M // 2 + 1 for
+    onesided=True (float32 output) or M (FFT order, complex64 output).  numpy in -> numpy out, device tensor in -> device tensor on
+    X's stream (the C entry takes dense rows: a strided view is made contiguous first)."""
+    M, hop, first, nout, r0, major = int(M), int(hop), int(first), int(nout), int(r0), int(in_major)
+    if np.iscomplexobj(g):
+        raise ValueError("pfb_synth: the taps must be real")
+    taps = np.ascontiguousarray(np.asarray(g), dtype=np.float32)
+    if taps.ndim != 1:
+        raise ValueError("pfb_synth: the taps must be one-dimensional")
+    if major not in (0, 1):
+        raise ValueError("pfb_synth: in_major must be 0 or 1")
+    if X.ndim < 2:
+        raise ValueError("pfb_synth: X must be at least two-dimensional")
+    if M < 2 or nout < 1:
+        raise ValueError("pfb_synth: need M >= 2 and nout >= 1")
+    nb = M // 2 + 1 if onesided else M
+    nframes = int(X.shape[-1] if major else X.shape[-2])
+    if int(X.shape[-2] if major else X.shape[-1]) != nb:
+        raise ValueError("pfb_synth: X has %d bins, M = %d needs %d" % (X.shape[-2] if major else X.shape[-1], M, nb))
+    if nframes < 1:
+        raise ValueError("pfb_synth: there are no frames")
+    sided = SIDED_HALF if onesided else SIDED_RAW
+    lead = tuple(int(d) for d in X.shape[:-2])
+    batch = int(np.prod(lead)) if lead else 1
+    if _is_torch(X):
+        _bind_stream(X)
+        if X.dtype != torch.complex64:
+            raise TypeError("device path takes complex64 frames, got %s" % X.dtype)
+        xs = X.contiguous()
+        y = torch.empty(lead + (nout,), dtype=torch.float32 if onesided else torch.complex64, device=xs.device)
+        check(lib().sp_pfb_synth(ptr(xs.data_ptr()), sided, major, batch, nframes, ptr(taps), taps.size, M, hop, first, int(phase_ref),
+                                 r0, float(scale), nout, ptr(y.data_ptr()), 1))
+        return y
+    xs = np.ascontiguousarray(X, dtype=np.complex64)
+    y = np.empty(lead + (nout,), dtype=np.float32 if onesided else np.complex64)
+    _ffi.init()
+    check(lib().sp_pfb_synth(ptr(xs), sided, major, batch, nframes, ptr(taps), taps.size, M, hop, first, int(phase_ref), r0,
+                             float(scale), nout, ptr(y), 0))
+    return y
+
+
+def pfb_synth_plan(M, ntaps, hop, nframes, onesided=True, batch=1):
+    """What pfb_synth does by default at this shape (sp_pfb_synth_plan): a dict with fused (bool), groups (the transform groups of a
+    workgroup whose ring fits the LDS), fpw (groups per workgroup), fpg (frames per run of the fused path) and halo."""
+    out = (_ffi.C.c_int64 * 5)()
+    _ffi.init()
+    check(lib().sp_pfb_synth_plan(SIDED_HALF if onesided else SIDED_RAW, int(batch), int(nframes), int(ntaps), int(M), int(hop), out))
+    return dict(fused=bool(out[0]), groups=int(out[1]), fpw=int(out[2]), fpg=int(out[3]), halo=int(out[4]))
+
+
 # ------------------------------------------------------------------------------------------ N3
 def stft_cog(x, win, hop, nframes, fs, fmin=0.0, fmax=None, detrend=False, mean_value=None):
     """Centre of gravity (power-weighted mean frequency, Doppler.py:43-58) of every frame's two-sided spectrum, reduced
