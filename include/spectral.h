@@ -361,6 +361,42 @@ int sp_spectral_filter(const float *x, int64_t n_in, int64_t x_ld, int64_t nfft,
  *      2n-1 lags, via zero-padded FFTs; co_out[2n-1] float32 in np.correlate(...,'full') order. */
 int sp_xcorr(const float *x1, const float *x2, int64_t n, float *co_out, int mem);
 
+/* ---- Short-time cross-correlation (ccf.ccf_sh, ccf.py: the correlation inside a sliding window, averaged over the windows; the
+ *      window layout is this build's: complete windows at a fixed hop) and the delay track read off it.
+ *      Two records x, y of nsig samples, both float32 or both complex64.  Frame g < nframes takes a = x[g hop : g hop + nw] and b
+ *      likewise from y, (nframes - 1) hop + nw <= nsig.  detrend SP_DETREND_SEGMEAN subtracts each window's own mean from a and from b
+ *      (the reference's ccf), SP_DETREND_CONST subtracts nothing.  An optional taper win[nw] then multiplies a and b (NULL: boxcar).
+ *      With L = max(32, next_pow2(nw + maxlag)), 0 <= maxlag <= nw - 1:
+ *        A = FFT_L(a), B = FFT_L(b)  (zero-padded, unnormalised);   S[k] = A[k] conj(B[k]);   E = sqrt(sum |a|^2 * sum |b|^2)
+ *        beta == 0:  S'[k] = W[k] S[k];  c = IFFT_L(S')        norm SP_XC_RAW
+ *                                        c = IFFT_L(S') / E    norm SP_XC_COEFF  (a frame with E = 0 gives 0)
+ *        beta  > 0:  S'[k] = W[k] S[k] / (|S[k]| + beta E);  c = IFFT_L(S')   regularised PHAT, norm must be SP_XC_COEFF
+ *        c_g[l] = c[l mod L],  -maxlag <= l <= maxlag,  stored at index l + maxlag
+ *      so that with W = 1 and beta = 0, c_g[l] = sum_n a[n + l] conj(b[n]): the order of np.correlate(a, b, 'full') and of sp_xcorr.
+ *      weight: W, an optional HOST float32 table of L real weights in natural FFT order (NULL: all ones): band limits, or SCOT / ML
+ *      weights from averaged spectra.  For real input only the real part of the inverse transform is kept, so the table must be even,
+ *      W[k] == W[L - k]; one that is not is refused.  win and weight go through the device table cache, like the windows.
+ *      Outputs, each may be NULL, at least one is required, one launch serves them all:
+ *        frames  [nframes][2 maxlag + 1], float32 for real input, complex64 for complex input
+ *        avg     float64 [2 maxlag + 1] ([..][2] re, im for complex input): the mean of c_g over the frames (ccf_sh's csh).  Transform
+ *                groups accumulate their run of frames in float32 registers, a finish kernel sums the partials in float64 in a fixed
+ *                order: no atomics, two calls agree bitwise.
+ *        peak    float32 [nframes][2].  q[l] = c[l] (real input) or |c[l]| (complex input); l* = the smallest l attaining max q;
+ *                d = q[l*-1] - 2 q[l*] + q[l*+1];  delta = (q[l*-1] - q[l*+1]) / (2 d) if |l*| < maxlag and d < 0, else 0;
+ *                peak[g] = (l* + delta, q[l*] - (q[l*-1] - q[l*+1]) delta / 4): the parabola through the top three lags.
+ *      x, y and the three outputs follow `mem`.  Real input costs one forward (z = a + i b) and one inverse transform per frame, complex
+ *      input two forward and one inverse, all inside one workgroup.
+ *      Refused (< 0, sp_last_error() names sp_xcorr_frames, the device is not touched, the outputs are untouched): nw < 2; maxlag outside
+ *      [0, nw - 1]; L > sp_max_wg_fft(); hop < 1; nframes < 1; frames that overrun the record; an unknown dtype, detrend or norm;
+ *      beta < 0 or not finite; beta > 0 with SP_XC_RAW; x or y NULL; all three outputs NULL; a weight that is not even with real input.
+ *      sp_xcorr_frames_len: L for this (nw, maxlag), or < 0 where sp_xcorr_frames would refuse them.  Host only. */
+#define SP_XC_RAW 0
+#define SP_XC_COEFF 1
+int sp_xcorr_frames(const void *x, const void *y, int dtype, int64_t nsig, const float *win, int nw, int hop, int64_t nframes,
+                    int maxlag, int detrend, int norm, double beta, const float *weight, void *frames, double *avg, float *peak,
+                    int mem);
+int sp_xcorr_frames_len(int nw, int maxlag);
+
 /* ---- F1 (build-defined; nearest reference code filters.py:282, ccf.py:283): causal FIR
  *      y = lfilter(h, 1, x)[0:n] by overlap-save with nfft-point blocks (nfft power of two > ntaps;
  *      0 = choose). */

@@ -19,7 +19,7 @@ from .fft_analysis import detrend_none, detrend_mean, detrend_linear, unwrap_tol
 from .fft_analysis import integratespectra, varcoh, varphi, mean_angle                       # noqa: F401  (fft_analysis.py:835, :1218-1376)
 from .spectrogram import specgram, stft, istft               # noqa: F401
 from .hilbert import hilbert, hilbert_1d                     # noqa: F401
-from .ccf import ccf                                         # noqa: F401
+from .ccf import ccf, ccf_sh, ccf_frames, delay_track, ccf_plan   # noqa: F401
 from .notch_filter import iirnotch, iirpeak, apply_notch     # noqa: F401
 from .filters import fftfilt                                 # noqa: F401
 from .filters import butter_lowpass_filter, butter_bandpass  # noqa: F401   (__init__.py:27)

@@ -20,6 +20,7 @@ namespace sp {
 //   SP_ISTFT_FPG, SP_ISTFT_MIB (int: the inverse STFT's frames per run; its budget for transposed bin-major spectra, MiB)
 //   SP_PFB_FPG, SP_PFB_TREG (int: the channelizer's frames per run; 0 / 1: its taps from the table / held in registers)
 //   SP_PFBS_FPG, SP_PFBS_PATH (int: the synthesis bank's frames per run; "fused" / "composed": its path, a fused that does not fit is refused)
+//   SP_XCF_FPG (int: the short-time correlation's frames per run)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
     return v && v[0] && v[0] != '0';
@@ -423,6 +424,22 @@ int launch_pfb_synth(LaunchCtx c, const cf *X, bool cplx, int64_t batch, int64_t
                      void *v);
 int launch_pfb_synth_gather(LaunchCtx c, const void *v, bool cplx, int64_t batch, int64_t nframes, const float *taps, int ntaps, int M,
                             int hop, int64_t first, int phase_ref, int r0, int64_t nout, void *y);
+
+// short-time cross-correlation (k_xcorr_frames.hip): frame g of x and y (nw samples at g hop) -> the lags -maxlag .. maxlag of the
+// L-point circular correlation, L a power of two in 32 .. 8192, nw + maxlag <= L.  win (null: boxcar) and weight (null: ones, else
+// L floats in FFT order) are device tables; segmean: every window's own mean is removed; coeff: / sqrt(sum |a|^2 sum |b|^2);
+// beta > 0: the regularised PHAT.  Any of frames ([nframes][2 maxlag + 1] float or cf), partial ([rp.groups][L] float or cf, summed by
+// launch_xcorr_frames_finish into avg = float64 [2 maxlag + 1] (x 2 for cf) / nframes) and peak ([nframes][2]) may be null.
+struct XcfArgs {
+    const void *x, *y;
+    const float *win, *weight;
+    int nw, hop, maxlag, segmean, coeff;
+    float beta;
+    int64_t nframes;
+};
+int launch_xcorr_frames(LaunchCtx c, const XcfArgs &a, bool cplx, int L, const cf *tw, const RunPart &rp, void *frames, void *partial,
+                        float *peak);
+int launch_xcorr_frames_finish(LaunchCtx c, const void *partial, bool cplx, int64_t G, int L, int maxlag, int64_t nframes, double *avg);
 
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;

@@ -3112,6 +3112,100 @@ int sp_zoom_welch(const void *x, const void *y, int dtype, int64_t nsig, const f
     return 0;
 }
 
+// ---- short-time cross-correlation (k_xcorr_frames.hip) -------------------------------------------
+int sp_xcorr_frames_len(int nw, int maxlag) {
+    if (nw < 2 || maxlag < 0 || maxlag > nw - 1) return -1;
+    const int64_t L = next_pow2((int64_t)nw + maxlag);
+    if (L > SP_MAX_WG_FFT) return -1;
+    return L < 32 ? 32 : (int)L;
+}
+
+int sp_xcorr_frames(const void *x, const void *y, int dtype, int64_t nsig, const float *win, int nw, int hop, int64_t nframes,
+                    int maxlag, int detrend, int norm, double beta, const float *weight, void *frames, double *avg, float *peak,
+                    int mem) {
+    // every refusal comes before the device is touched
+    if (nw < 2) return fail("sp_xcorr_frames: the window needs at least 2 samples, got %d", nw);
+    if (maxlag < 0 || maxlag > nw - 1) return fail("sp_xcorr_frames: maxlag %d outside 0 .. nw - 1 = %d", maxlag, nw - 1);
+    const int L = sp_xcorr_frames_len(nw, maxlag);
+    if (L < 0)
+        return fail("sp_xcorr_frames: nw + maxlag = %lld is beyond one workgroup transform (%d points)", (long long)nw + maxlag,
+                    SP_MAX_WG_FFT);
+    if (hop < 1) return fail("sp_xcorr_frames: hop must be at least 1");
+    if (nframes < 1) return fail("sp_xcorr_frames: nframes must be at least 1");
+    if (nsig < nw || (nframes - 1) > (nsig - nw) / hop)
+        return fail("sp_xcorr_frames: %lld frames of %d with hop %d overrun the record of %lld samples", (long long)nframes, nw, hop,
+                    (long long)nsig);
+    if (dtype != SP_DTYPE_F32 && dtype != SP_DTYPE_C64) return fail("sp_xcorr_frames: unknown dtype %d", dtype);
+    if (detrend != SP_DETREND_CONST && detrend != SP_DETREND_SEGMEAN)
+        return fail("sp_xcorr_frames: detrend must be SP_DETREND_CONST or SP_DETREND_SEGMEAN, got %d", detrend);
+    if (norm != SP_XC_RAW && norm != SP_XC_COEFF) return fail("sp_xcorr_frames: unknown norm %d", norm);
+    if (!(beta >= 0.0) || !isfinite(beta)) return fail("sp_xcorr_frames: beta must be finite and not negative");
+    if (beta > 0.0 && norm != SP_XC_COEFF) return fail("sp_xcorr_frames: beta > 0 (PHAT) takes norm SP_XC_COEFF");
+    if (!x || !y) return fail("sp_xcorr_frames: x and y are required");
+    if (!frames && !avg && !peak) return fail("sp_xcorr_frames: an output is required: frames, avg or peak");
+    if (weight && dtype == SP_DTYPE_F32) {               // a real pair keeps Re(IFFT): the weights must be even, W[k] == W[L - k]
+        for (int k = 1; k < L - k; ++k)
+            if (!(weight[k] == weight[L - k])) return fail("sp_xcorr_frames: the weight of a real pair must be even, W[%d] != W[%d]", k, L - k);
+    }
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const bool cplx = dtype == SP_DTYPE_C64;
+    const size_t esz = cplx ? 8 : 4, lsz = cplx ? sizeof(cf) : sizeof(float), nl = 2 * (size_t)maxlag + 1;
+    const void *xd = x, *yd = y;
+    if (!mem) {
+        if (g.in0.ensure(esz * (size_t)nsig) || g.in1.ensure(esz * (size_t)nsig)) return -1;
+        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
+        HIPCHK(hipMemcpyAsync(g.in1.p, y, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
+        xd = g.in0.p;
+        yd = g.in1.p;
+    }
+    void *win_d = nullptr, *wt_d = nullptr;
+    if (win && get_table(1, win, sizeof(float) * (size_t)nw, &win_d, nullptr)) return -1;
+    if (weight && get_table(13, weight, sizeof(float) * (size_t)L, &wt_d, nullptr)) return -1;
+    const cf *tw;
+    if (get_twiddles(L, &tw)) return -1;
+    // outputs staged for host callers: [frames | avg | peak], each piece 256-byte aligned
+    const size_t fbytes = frames ? lsz * (size_t)nframes * nl : 0, abytes = avg ? sizeof(double) * (cplx ? 2 : 1) * nl : 0;
+    const size_t pbytes = peak ? sizeof(float) * 2 * (size_t)nframes : 0;
+    const size_t aoff = (fbytes + 255) & ~(size_t)255, poff = aoff + ((abytes + 255) & ~(size_t)255);
+    void *fr_d = frames;
+    double *avg_d = avg;
+    float *pk_d = peak;
+    if (!mem) {
+        if (g.out0.ensure(poff + pbytes)) return -1;
+        fr_d = frames ? g.out0.p : nullptr;
+        avg_d = avg ? (double *)((char *)g.out0.p + aoff) : nullptr;
+        pk_d = peak ? (float *)((char *)g.out0.p + poff) : nullptr;
+    }
+    RunPart rp = run_partition(L, nframes, g.ncu);
+    if (const int fpg = env_int("SP_XCF_FPG", 0); fpg > 0) {           // test hook: runs of this many frames
+        const int fpw = fpw_of(L);
+        rp.fpg = fpg;
+        rp.blocks = (int)(((nframes + fpg - 1) / fpg + fpw - 1) / fpw);
+        rp.groups = (int64_t)rp.blocks * fpw;
+    }
+    void *partial = nullptr;
+    if (avg) {
+        if (g.work.ensure(lsz * (size_t)rp.groups * (size_t)L)) return -1;
+        partial = g.work.p;
+    }
+    const XcfArgs a{xd, yd, (const float *)win_d, (const float *)wt_d, nw, hop, maxlag, detrend == SP_DETREND_SEGMEAN ? 1 : 0,
+                    norm == SP_XC_COEFF ? 1 : 0, (float)beta, nframes};
+    {
+        ProfScope ps;
+        LAUNCHCHK(launch_xcorr_frames(lc(), a, cplx, L, tw, rp, fr_d, partial, pk_d));
+        g.last_kernel = "k_xcorr_frames";
+    }
+    if (avg) LAUNCHCHK(launch_xcorr_frames_finish(lc(), partial, cplx, rp.groups, L, maxlag, nframes, avg_d));
+    if (!mem) {
+        if (frames) HIPCHK(hipMemcpyAsync(frames, fr_d, fbytes, hipMemcpyDeviceToHost, g.stream));
+        if (avg) HIPCHK(hipMemcpyAsync(avg, avg_d, abytes, hipMemcpyDeviceToHost, g.stream));
+        if (peak) HIPCHK(hipMemcpyAsync(peak, pk_d, pbytes, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
 // reciprocal window-square envelope of sp_istft as [period: hop][head: head_len][tail: n - hop] float32 from float64 sums; entries
 // whose envelope is <= 1e-10 are 1 (scipy's rule: such samples are not divided).  Away from the ends env[a] = P[a mod hop]; the first
 // n - hop samples lack the frames before 0 and the last n - hop those from M on.  With so few frames that the two ends meet

@@ -910,6 +910,57 @@ def xcorr_normalised(x1, x2):
     return out
 
 
+def xcorr_frames(x, y, nw, hop, nframes, maxlag, win=None, segmean=True, coeff=True, beta=0.0, weight=None, frames=False, avg=False,
+                 peak=False):
+    """Short-time cross-correlation (sp_xcorr_frames): frame g pairs x[g*hop : g*hop+nw] with the same stretch of y and yields the
+    lags -maxlag .. maxlag of their correlation, c[l] = sum_n a[n+l] conj(b[n]).  segmean: every window's own mean removed; win: an
+    optional taper [nw]; coeff: divided by sqrt(sum |a|^2 sum |b|^2); beta > 0: the regularised PHAT weighting; weight: an optional
+    table of L = sp_xcorr_frames_len(nw, maxlag) real weights on the cross spectrum in FFT order.
+    -> (frames, avg, peak), None for the ones not asked for: frames [nframes, 2 maxlag + 1] float32 / complex64, avg float64 /
+    complex128 [2 maxlag + 1] (the mean over the frames), peak float32 [nframes, 2] = (lag of the top, its height), parabola-refined.
+    numpy in -> numpy out; device tensors in -> device tensors on x's stream."""
+    nw, hop, nframes, maxlag = int(nw), int(hop), int(nframes), int(maxlag)
+    w = None if win is None else _win32(win)
+    wt = None if weight is None else _win32(weight)
+    if w is not None and w.shape != (nw,):
+        raise ValueError("xcorr_frames: win must hold nw = %d values" % nw)
+    if wt is not None and wt.shape != (int(lib().sp_xcorr_frames_len(nw, maxlag)),):
+        raise ValueError("xcorr_frames: weight must hold sp_xcorr_frames_len(nw, maxlag) values")
+    if not (frames or avg or peak):
+        raise ValueError("xcorr_frames: ask for at least one of frames, avg, peak")
+    dev = _is_torch(x)
+    if dev:
+        _bind_stream(x)
+        xs, ys = _torch_samples(x), _torch_samples(y) if _is_torch(y) else None
+        if ys is None or ys.dtype != xs.dtype or ys.numel() != xs.numel() or ys.device != xs.device:
+            raise ValueError("xcorr_frames: y must be a tensor of x's length, dtype and device")
+        nsig, code, cplx = xs.numel(), _tcode(xs), xs.dtype == torch.complex64
+
+        def new(shape, dt):
+            return torch.empty(shape, dtype=getattr(torch, dt), device=xs.device)
+
+        def addr(a):
+            return None if a is None else ptr(a.data_ptr())
+    else:
+        xs, ys = _ffi.as_samples(x), _ffi.as_samples(y)
+        if ys.dtype != xs.dtype or ys.size != xs.size:
+            raise ValueError("xcorr_frames: y must match x's length and dtype")
+        nsig, code, cplx = xs.size, _ffi.dtype_code(xs.dtype), xs.dtype == np.complex64
+
+        def new(shape, dt):
+            return np.empty(shape, dtype=getattr(np, dt))
+        addr = ptr
+        _ffi.init()
+    nl, m = 2 * max(maxlag, 0) + 1, max(nframes, 0)
+    fr = new((m, nl), "complex64" if cplx else "float32") if frames else None
+    av = new((nl,), "complex128" if cplx else "float64") if avg else None
+    pk = new((m, 2), "float32") if peak else None
+    check(lib().sp_xcorr_frames(addr(xs), addr(ys), code, nsig, ptr(w), nw, hop, nframes, maxlag,
+                                _ffi.DETREND_SEGMEAN if segmean else _ffi.DETREND_CONST, _ffi.XC_COEFF if coeff else _ffi.XC_RAW,
+                                float(beta), ptr(wt), addr(fr), addr(av), addr(pk), 1 if dev else 0))
+    return fr, av, pk
+
+
 # ------------------------------------------------------------------------------------------ F1
 def fir_filter(h, x, nfft=0):
     """Causal FIR y = lfilter(h, 1, x) (float32) by overlap-save on the GPU."""
