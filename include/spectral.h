@@ -86,6 +86,7 @@ int sp_fft_c2c(const void *in, void *out, int64_t n, int64_t batch, int directio
  *        SP_DETREND_SEGLINEAR (4) the same with every segment's own least-squares line.
  *      nbins = Nnyquist for SP_SIDED_ONE (nfft/2, or (nfft+1)/2 when odd), nfft otherwise. */
 #define SP_DETREND_CONST 0
+#define SP_DETREND_NONE 0 /* SP_DETREND_CONST for the entries that take no constant: nothing is subtracted */
 #define SP_DETREND_MEAN 1
 #define SP_DETREND_LINEAR 2
 #define SP_DETREND_SEGMEAN 3
@@ -396,6 +397,35 @@ int sp_xcorr_frames(const void *x, const void *y, int dtype, int64_t nsig, const
                     int maxlag, int detrend, int norm, double beta, const float *weight, void *frames, double *avg, float *peak,
                     int mem);
 int sp_xcorr_frames_len(int nw, int maxlag);
+
+/* ---- Two-point wavenumber-frequency spectrum S(k, f) (Beall, Kim & Powers 1982; build-defined, the reference has no counterpart).
+ *      Two records x, y of nsig samples, both float32 or both complex64, from probes a distance dx apart.  Frame g < nframes is
+ *      a = win (x[g hop : g hop + nfft] - m), b likewise from y, (nframes - 1) hop + nfft <= nsig; m is the frame's own mean
+ *      (SP_DETREND_SEGMEAN) or 0 (SP_DETREND_NONE); win is a HOST float32 [nfft] (device table cache) or NULL (boxcar).  X, Y are the
+ *      unnormalised forward transforms, nfft a power of two in 32 .. 4096.  For every frame and every bin f of the band:
+ *        theta = arg(X[f] conj(Y[f])) in [-pi, pi]    (y[n] = x[n - d] gives theta = +2 pi f d / fs for f > 0);  theta = k dx
+ *        j = floor((theta / 2 pi + 1/2) nk) mod nk     (nk equal bins over [-pi, pi); theta = pi wraps to bin 0), 2 <= nk <= 1024
+ *        p = (|X|^2 + |Y|^2) / 2  (SP_SKF_MEAN)   or   |X| |Y|  (SP_SKF_CROSS)
+ *        s_out[f - b0][j] = scale / nframes * sum_g p          float64 [nb][nk], nothing doubled
+ *      so that sum_j s_out[.][j] is (Pxx + Pyy) / 2 of sp_welch_csd at the same scale (SP_SKF_MEAN).  The band is the nb bins from b0
+ *      on in natural FFT order: b0 + nb <= nfft / 2 + 1 for real input; for complex input counted modulo nfft, so that it may run
+ *      through zero (b0 = 200, nb = 112 at nfft = 256 is bins 200 .. 255, 0 .. 55).  Bin j is centred on the wavenumber
+ *      k_j = (j + 1/2 - nk / 2) 2 pi / (nk dx).
+ *      The histogram of a workgroup's run of frames lives in LDS, every cell with one writer and a fixed order of additions; float32
+ *      partials per run are summed in float64 in a fixed order: no atomics on memory, two calls agree bitwise.  A band with more cells
+ *      nb x nk than the LDS tile holds is cut into frequency tiles and the transforms are repeated per tile (sp_skf_plan).
+ *      x, y and s_out follow `mem`.
+ *      Refused (< 0, sp_last_error() names sp_skf, the device is not touched, s_out is untouched): nfft not a power of two in
+ *      32 .. 4096; nk outside 2 .. 1024; nb < 1 or a band outside the bins; hop < 1; nframes < 1; frames that overrun the record; a
+ *      dtype other than float32 / complex64; a detrend other than NONE / SEGMEAN; an unknown power; a scale that is not finite; x, y
+ *      or s_out NULL.
+ *      sp_skf_plan (host only): out[4] = frequency tiles, bins per tile, LDS bytes of a workgroup, transforms per frame (tiles for
+ *      real input, 2 tiles for complex); < 0 for an nfft, nk or nb that sp_skf refuses. */
+#define SP_SKF_MEAN 0
+#define SP_SKF_CROSS 1
+int sp_skf(const void *x, const void *y, int dtype, int64_t nsig, const float *win, int nfft, int hop, int64_t nframes, int detrend,
+           int power, int b0, int nb, int nk, double scale, double *s_out, int mem);
+int sp_skf_plan(int cplx, int nfft, int nb, int nk, int64_t *out);
 
 /* ---- F1 (build-defined; nearest reference code filters.py:282, ccf.py:283): causal FIR
  *      y = lfilter(h, 1, x)[0:n] by overlap-save with nfft-point blocks (nfft power of two > ntaps;

@@ -39,3 +39,5 @@ from .baseband import ddc, ddc_plan, band_stft, band_psd, band_csd, band_coheren
 from . import channelizer as _channelizer_mod                  # noqa: F401
 from .channelizer import pfb_prototype, pfb_plan, channelize, pfb_psd   # noqa: F401
 from .channelizer import pfb_alias_terms, pfb_dual, pfb_synthesis_plan, synthesize   # noqa: F401
+from . import wavenumber as _wavenumber_mod                    # noqa: F401
+from .wavenumber import skf, skf_moments, dispersion, skf_plan   # noqa: F401

@@ -16,6 +16,8 @@ DTYPE_F32, DTYPE_C64 = 0, 1
 SIDED_ONE, SIDED_TWO, SIDED_RAW, SIDED_HALF = 1, 2, 3, 4
 DETREND_CONST, DETREND_MEAN, DETREND_LINEAR, DETREND_SEGMEAN, DETREND_SEGLINEAR = 0, 1, 2, 3, 4
 XC_RAW, XC_COEFF = 0, 1
+DETREND_NONE = 0
+SKF_MEAN, SKF_CROSS = 0, 1
 
 _lib = None
 
@@ -70,6 +72,8 @@ SIGNATURES = {
     "sp_xcorr": (_i, [_vp, _vp, _i64, _vp, _i]),
     "sp_xcorr_frames": (_i, [_vp, _vp, _i, _i64, _vp, _i, _i, _i64, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _i]),
     "sp_xcorr_frames_len": (_i, [_i, _i]),
+    "sp_skf": (_i, [_vp, _vp, _i, _i64, _vp, _i, _i, _i64, _i, _i, _i, _i, _i, _d, _vp, _i]),
+    "sp_skf_plan": (_i, [_i, _i, _i, _i, _vp]),
     "sp_fftfilt": (_i, [_vp, _i, _vp, _i64, _i, _vp, _i]),
     "sp_biquad": (_i, [_vp, _vp, _vp, _i64, _vp, _i]),
     "sp_sosfilt": (_i, [_vp, _i, _vp, _i64, _i64, _vp, _vp, _vp, _i]),

@@ -21,6 +21,7 @@ namespace sp {
 //   SP_PFB_FPG, SP_PFB_TREG (int: the channelizer's frames per run; 0 / 1: its taps from the table / held in registers)
 //   SP_PFBS_FPG, SP_PFBS_PATH (int: the synthesis bank's frames per run; "fused" / "composed": its path, a fused that does not fit is refused)
 //   SP_XCF_FPG (int: the short-time correlation's frames per run)
+//   SP_SKF_FPG, SP_SKF_CELLS (int: the wavenumber-frequency histogram's frames per run; a cap on the cells nk x bins of a tile)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
     return v && v[0] && v[0] != '0';
@@ -440,6 +441,46 @@ struct XcfArgs {
 int launch_xcorr_frames(LaunchCtx c, const XcfArgs &a, bool cplx, int L, const cf *tw, const RunPart &rp, void *frames, void *partial,
                         float *peak);
 int launch_xcorr_frames_finish(LaunchCtx c, const void *partial, bool cplx, int64_t G, int L, int maxlag, int64_t nframes, double *avg);
+
+// two-point wavenumber-frequency spectrum S(k, f) (k_skf.hip): frame g of x and y (L samples at g hop, L a power of two in 32 .. 4096)
+// -> theta = arg(X conj Y) and p = (|X|^2 + |Y|^2) / 2 (cross: |X| |Y|) at the nb bins from b0 on (modulo L for complex records),
+// histogrammed over nk equal phase bins.  A workgroup owns a run of fpr consecutive frames and one frequency tile of the band; its
+// histogram lives in LDS behind the transform images, row j (one phase bin) `stride` floats long.  Grid: runs x tiles.
+// partial: float [runs][nk][nb] (phase-major like the tile, so that the tile leaves LDS and enters memory at unit stride), summed by
+// launch_skf_finish in float64 in ascending run order into s_out[nb][nk] * scale / nframes.
+#define SP_SKF_LDS_MAX ((size_t)160 * 1024)
+#define SP_SKF_MAX_L 4096
+#define SP_SKF_MAX_NK 1024
+struct SkfPlan {
+    int tiles, tile_bins, stride;       // frequency tiles, bins of a tile (the last may hold fewer), floats per histogram row
+    size_t lds_bytes;                   // transform images + histogram tile
+};
+// LDS of the transform images of one workgroup: max(1, 4096 / L) groups of L + 16 complex each, twice for complex records
+inline size_t skf_image_bytes(bool cplx, int L) { return (size_t)fpw_of(L) * (size_t)(L + 16) * 8 * (cplx ? 2 : 1); }
+// cells_cap > 0: at most that many cells (nk x bins) per tile.  Rows are padded to a multiple of 32 floats (the bank of an LDS add is
+// its dword address mod 32, so the bank is the lane's bin whatever the phase bin); where not even 32 bins fit, 16, 8 .. 1.
+inline SkfPlan skf_plan_of(bool cplx, int L, int nb, int nk, int cells_cap) {
+    const int64_t room = (int64_t)(SP_SKF_LDS_MAX - skf_image_bytes(cplx, L)) / 4 / nk;      // floats per row
+    int gran = 32;
+    while (gran > 1 && room < gran) gran /= 2;
+    int tb = (int)(room / gran) * gran;
+    if (tb > nb) tb = nb;
+    if (cells_cap > 0 && tb > cells_cap / nk) tb = cells_cap / nk < 1 ? 1 : cells_cap / nk;
+    SkfPlan p;
+    p.tile_bins = tb;
+    p.tiles = (nb + tb - 1) / tb;
+    p.stride = (tb + gran - 1) / gran * gran;
+    p.lds_bytes = skf_image_bytes(cplx, L) + sizeof(float) * (size_t)nk * (size_t)p.stride;
+    return p;
+}
+struct SkfArgs {
+    const void *x, *y;
+    const float *win;
+    int hop, segmean, cross, b0, nb, nk, tile_bins, stride;
+    int64_t nframes, fpr;
+};
+int launch_skf(LaunchCtx c, const SkfArgs &a, bool cplx, int L, const cf *tw, int64_t runs, const SkfPlan &pl, float *partial);
+int launch_skf_finish(LaunchCtx c, const float *partial, int64_t runs, int nb, int nk, double mult, double *s_out);
 
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;

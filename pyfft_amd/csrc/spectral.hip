@@ -3206,6 +3206,89 @@ int sp_xcorr_frames(const void *x, const void *y, int dtype, int64_t nsig, const
     return 0;
 }
 
+// ---- two-point wavenumber-frequency spectrum S(k, f) (k_skf.hip) --------------------------------
+static bool skf_shape_ok(int nfft, int nk) {
+    return nfft >= 32 && nfft <= SP_SKF_MAX_L && is_pow2(nfft) && nk >= 2 && nk <= SP_SKF_MAX_NK;
+}
+
+int sp_skf_plan(int cplx, int nfft, int nb, int nk, int64_t *out) {
+    if (!skf_shape_ok(nfft, nk) || !out) return -1;
+    if (nb < 1 || nb > (cplx ? nfft : nfft / 2 + 1)) return -1;
+    const SkfPlan p = skf_plan_of(cplx != 0, nfft, nb, nk, env_int("SP_SKF_CELLS", 0));
+    out[0] = p.tiles;
+    out[1] = p.tile_bins;
+    out[2] = (int64_t)p.lds_bytes;
+    out[3] = (int64_t)p.tiles * (cplx ? 2 : 1);
+    return 0;
+}
+
+int sp_skf(const void *x, const void *y, int dtype, int64_t nsig, const float *win, int nfft, int hop, int64_t nframes, int detrend,
+           int power, int b0, int nb, int nk, double scale, double *s_out, int mem) {
+    // every refusal comes before the device is touched
+    if (nfft < 32 || nfft > SP_SKF_MAX_L || !is_pow2(nfft))
+        return fail("sp_skf: nfft = %d must be a power of two from 32 to %d", nfft, SP_SKF_MAX_L);
+    if (nk < 2 || nk > SP_SKF_MAX_NK) return fail("sp_skf: nk = %d outside 2 .. %d", nk, SP_SKF_MAX_NK);
+    if (dtype != SP_DTYPE_F32 && dtype != SP_DTYPE_C64) return fail("sp_skf: dtype must be float32 or complex64, got %d", dtype);
+    const bool cplx = dtype == SP_DTYPE_C64;
+    if (nb < 1) return fail("sp_skf: the band needs at least one bin, got nb = %d", nb);
+    if (cplx ? (b0 < 0 || b0 >= nfft || nb > nfft) : (b0 < 0 || nb > nfft / 2 + 1 || b0 > nfft / 2 + 1 - nb))
+        return fail("sp_skf: the band of %d bins from %d lies outside the %d bins of the spectrum", nb, b0, cplx ? nfft : nfft / 2 + 1);
+    if (hop < 1) return fail("sp_skf: hop must be at least 1");
+    if (nframes < 1) return fail("sp_skf: nframes must be at least 1");
+    if (nsig < nfft || (nframes - 1) > (nsig - nfft) / hop)
+        return fail("sp_skf: %lld frames of %d with hop %d overrun the record of %lld samples", (long long)nframes, nfft, hop,
+                    (long long)nsig);
+    if (detrend != SP_DETREND_NONE && detrend != SP_DETREND_SEGMEAN)
+        return fail("sp_skf: detrend must be SP_DETREND_NONE or SP_DETREND_SEGMEAN, got %d", detrend);
+    if (power != SP_SKF_MEAN && power != SP_SKF_CROSS) return fail("sp_skf: unknown power %d", power);
+    if (!isfinite(scale)) return fail("sp_skf: scale must be finite");
+    if (!x || !y || !s_out) return fail("sp_skf: x, y and s_out are required");
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const size_t esz = cplx ? 8 : 4;
+    const void *xd = x, *yd = y;
+    if (!mem) {
+        if (g.in0.ensure(esz * (size_t)nsig) || g.in1.ensure(esz * (size_t)nsig)) return -1;
+        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
+        HIPCHK(hipMemcpyAsync(g.in1.p, y, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
+        xd = g.in0.p;
+        yd = g.in1.p;
+    }
+    void *win_d = nullptr;
+    if (win && get_table(1, win, sizeof(float) * (size_t)nfft, &win_d, nullptr)) return -1;
+    const cf *tw;
+    if (get_twiddles(nfft, &tw)) return -1;
+    const SkfPlan pl = skf_plan_of(cplx, nfft, nb, nk, env_int("SP_SKF_CELLS", 0));
+    // runs: about four workgroups per CU over runs x tiles, as few more as keeps the partials within 64 MiB; a run is whole rounds
+    const int fpw = fpw_of(nfft);
+    const int64_t cells = (int64_t)nb * nk;
+    int64_t want = (int64_t)g.ncu * 4 / pl.tiles, room = ((int64_t)64 << 20) / (4 * cells);
+    if (want > room) want = room;
+    if (want < 1) want = 1;
+    int64_t fpr = ((nframes + want - 1) / want + fpw - 1) / fpw * fpw;
+    if (const int v = env_int("SP_SKF_FPG", 0); v > 0) fpr = v;            // test hook: runs of this many frames
+    const int64_t runs = (nframes + fpr - 1) / fpr;
+    if (g.work.ensure(sizeof(float) * (size_t)runs * (size_t)cells)) return -1;
+    double *out_d = s_out;
+    if (!mem) {
+        if (g.out0.ensure(sizeof(double) * (size_t)cells)) return -1;
+        out_d = (double *)g.out0.p;
+    }
+    const SkfArgs a{xd, yd, (const float *)win_d, hop, detrend == SP_DETREND_SEGMEAN ? 1 : 0, power == SP_SKF_CROSS ? 1 : 0, b0, nb, nk,
+                    pl.tile_bins, pl.stride, nframes, fpr};
+    {
+        ProfScope ps;
+        LAUNCHCHK(launch_skf(lc(), a, cplx, nfft, tw, runs, pl, (float *)g.work.p));
+        g.last_kernel = "k_skf";
+    }
+    LAUNCHCHK(launch_skf_finish(lc(), (const float *)g.work.p, runs, nb, nk, scale / (double)nframes, out_d));
+    if (!mem) {
+        HIPCHK(hipMemcpyAsync(s_out, out_d, sizeof(double) * (size_t)cells, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
 // reciprocal window-square envelope of sp_istft as [period: hop][head: head_len][tail: n - hop] float32 from float64 sums; entries
 // whose envelope is <= 1e-10 are 1 (scipy's rule: such samples are not divided).  Away from the ends env[a] = P[a mod hop]; the first
 // n - hop samples lack the frames before 0 and the last n - hop those from M on.  With so few frames that the two ends meet

@@ -961,6 +961,40 @@ def xcorr_frames(x, y, nw, hop, nframes, maxlag, win=None, segmean=True, coeff=T
     return fr, av, pk
 
 
+def skf(x, y, nfft, hop, nframes, b0, nb, nk, win=None, segmean=True, cross=False, scale=1.0):
+    """Two-point wavenumber-frequency histogram (sp_skf): frame g pairs x[g*hop : g*hop+nfft] with the same stretch of y; every frame
+    and every bin f of the band (nb bins from b0 on, modulo nfft for complex records) adds p = (|X|^2 + |Y|^2) / 2 (cross: |X| |Y|) to
+    cell j = floor((arg(X conj Y) / 2 pi + 1/2) nk) mod nk.  -> S float64 [nb, nk] = scale / nframes * the sums, nothing doubled.
+    segmean: every frame's own mean removed; win: an optional taper [nfft].  numpy in -> numpy out; device tensors in -> a device
+    tensor on x's stream."""
+    nfft, hop, nframes, b0, nb, nk = int(nfft), int(hop), int(nframes), int(b0), int(nb), int(nk)
+    w = None if win is None else _win32(win)
+    if w is not None and w.shape != (nfft,):
+        raise ValueError("skf: win must hold nfft = %d values" % nfft)
+    dev = _is_torch(x)
+    shape = (max(nb, 0), max(nk, 0))
+    if dev:
+        _bind_stream(x)
+        xs, ys = _torch_samples(x), _torch_samples(y) if _is_torch(y) else None
+        if ys is None or ys.dtype != xs.dtype or ys.numel() != xs.numel() or ys.device != xs.device:
+            raise ValueError("skf: y must be a tensor of x's length, dtype and device")
+        nsig, code = xs.numel(), _tcode(xs)
+        out = torch.empty(shape, dtype=torch.float64, device=xs.device)
+        check(lib().sp_skf(ptr(xs.data_ptr()), ptr(ys.data_ptr()), code, nsig, ptr(w), nfft, hop, nframes,
+                           _ffi.DETREND_SEGMEAN if segmean else _ffi.DETREND_NONE, _ffi.SKF_CROSS if cross else _ffi.SKF_MEAN, b0, nb,
+                           nk, float(scale), ptr(out.data_ptr()), 1))
+        return out
+    xs, ys = _ffi.as_samples(x), _ffi.as_samples(y)
+    if ys.dtype != xs.dtype or ys.size != xs.size:
+        raise ValueError("skf: y must match x's length and dtype")
+    _ffi.init()
+    out = np.empty(shape, dtype=np.float64)
+    check(lib().sp_skf(ptr(xs), ptr(ys), _ffi.dtype_code(xs.dtype), xs.size, ptr(w), nfft, hop, nframes,
+                       _ffi.DETREND_SEGMEAN if segmean else _ffi.DETREND_NONE, _ffi.SKF_CROSS if cross else _ffi.SKF_MEAN, b0, nb, nk,
+                       float(scale), ptr(out), 0))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ F1
 def fir_filter(h, x, nfft=0):
     """Causal FIR y = lfilter(h, 1, x) (float32) by overlap-save on the GPU."""
