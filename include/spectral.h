@@ -427,6 +427,35 @@ int sp_skf(const void *x, const void *y, int dtype, int64_t nsig, const float *w
            int power, int b0, int nb, int nk, double scale, double *s_out, int mem);
 int sp_skf_plan(int cplx, int nfft, int nb, int nk, int64_t *out);
 
+/* ---- Batched Hermitian eigensolver (build-defined; the piece the reference's PCA.py takes from numpy.linalg.eigh): the
+ *      eigendecomposition of `batch` matrices of order n, 1 <= n <= 64, e.g. the cross-spectral-density matrix of sp_csd_matrix at
+ *      every bin (spectral POD).  a[batch][n][n] complex128 as (re, im) doubles, row-major.  Only the LOWER triangle (row >= column)
+ *      and the real part of the diagonal are read: numpy.linalg.eigh's UPLO = 'L'; the upper triangle may hold anything.
+ *        w[batch][n]         float64 eigenvalues, DESCENDING (ties in the order of the solver's internal index)
+ *        v[batch][n][nvec]   complex128, column j the unit eigenvector of w[j]; only the nvec leading ones, 0 <= nvec <= n.  Each is
+ *                            turned so that its component of largest modulus (the first on ties) is real and positive, so a real
+ *                            symmetric matrix gives vectors real to rounding.  nvec == 0: v may be NULL and no vectors are formed.
+ *        sweeps[batch]       int32 Jacobi sweeps used, 0 for a matrix that is diagonal already.  A matrix that has not converged
+ *                            after max_sweeps sweeps (30 is ample: 8 for random CSD matrices of order 64, 17 at most on clustered
+ *                            spectra), or that holds a NaN or an infinity where it is read, reports max_sweeps + 1; its w and v are
+ *                            unspecified, the other matrices of the batch are unaffected, and the call still returns 0.
+ *      Parallel cyclic Jacobi in float64, one matrix per workgroup, held in LDS at the order padded to 8, 16, 32 or 64; stops when
+ *      sqrt(sum_{i<j} |a_ij|^2) <= n eps ||A||_F.  Each matrix is scaled by an exact power of two first, so entries of 1e+-150 are
+ *      safe.  No atomics: two calls agree bitwise.  a, w, v, sweeps follow `mem`.
+ *      Refused (< 0, sp_last_error() names sp_eigh, the device is not touched): n < 1 or n > 64; nvec outside 0 .. n; batch < 0;
+ *      max_sweeps < 1; a, w or sweeps NULL, or v NULL with nvec > 0.  batch == 0 returns 0 and touches nothing.
+ *      A deliberate deviation from "a rotation is skipped when a_pq == 0 exactly": a pair is skipped unless |a_pq| >= 2^-1000 of the
+ *      scaled matrix (largest component in [1, 2)).  That covers the exact zeros of the padding, keeps a NaN from rotating anything,
+ *      and keeps the phase a_pq / |a_pq| away from subnormal operands; an entry below 2^-1000 is left where it is, 700 orders of
+ *      magnitude under the stopping threshold.
+ *      sp_eigh_plan (host only, never touches the device): out[4] = padded order NP, LDS bytes of a workgroup, workgroups per CU
+ *      (what the LDS, the threads and the registers of a CU allow), workgroups launched = min(batch, workgroups per CU x CUs).
+ *      The CU count is that of the device once the library is initialised (sp_init or any call that runs on the device) and 256, an
+ *      MI355X, before: out[3] may differ between the two on another part.  < 0 for an n, nvec or batch that sp_eigh refuses, or
+ *      out NULL. */
+int sp_eigh(const double *a, int n, int64_t batch, int nvec, int max_sweeps, double *w, double *v, int32_t *sweeps, int mem);
+int sp_eigh_plan(int n, int nvec, int64_t batch, int64_t out[4]);
+
 /* ---- F1 (build-defined; nearest reference code filters.py:282, ccf.py:283): causal FIR
  *      y = lfilter(h, 1, x)[0:n] by overlap-save with nfft-point blocks (nfft power of two > ntaps;
  *      0 = choose). */

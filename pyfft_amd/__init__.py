@@ -41,3 +41,5 @@ from .channelizer import pfb_prototype, pfb_plan, channelize, pfb_psd   # noqa: 
 from .channelizer import pfb_alias_terms, pfb_dual, pfb_synthesis_plan, synthesize   # noqa: F401
 from . import wavenumber as _wavenumber_mod                    # noqa: F401
 from .wavenumber import skf, skf_moments, dispersion, skf_plan   # noqa: F401
+from . import spod as _spod_mod                                # noqa: F401
+from .spod import spod, spod_energy, spod_reconstruct, spod_plan   # noqa: F401

@@ -74,6 +74,8 @@ SIGNATURES = {
     "sp_xcorr_frames_len": (_i, [_i, _i]),
     "sp_skf": (_i, [_vp, _vp, _i, _i64, _vp, _i, _i, _i64, _i, _i, _i, _i, _i, _d, _vp, _i]),
     "sp_skf_plan": (_i, [_i, _i, _i, _i, _vp]),
+    "sp_eigh": (_i, [_vp, _i, _i64, _i, _i, _vp, _vp, _vp, _i]),
+    "sp_eigh_plan": (_i, [_i, _i, _i64, C.POINTER(_i64)]),
     "sp_fftfilt": (_i, [_vp, _i, _vp, _i64, _i, _vp, _i]),
     "sp_biquad": (_i, [_vp, _vp, _vp, _i64, _vp, _i]),
     "sp_sosfilt": (_i, [_vp, _i, _vp, _i64, _i64, _vp, _vp, _vp, _i]),

@@ -22,6 +22,7 @@ namespace sp {
 //   SP_PFBS_FPG, SP_PFBS_PATH (int: the synthesis bank's frames per run; "fused" / "composed": its path, a fused that does not fit is refused)
 //   SP_XCF_FPG (int: the short-time correlation's frames per run)
 //   SP_SKF_FPG, SP_SKF_CELLS (int: the wavenumber-frequency histogram's frames per run; a cap on the cells nk x bins of a tile)
+//   SP_EIGH_GRID (int: the eigensolver's workgroups, so that a small batch walks the batch loop)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
     return v && v[0] && v[0] != '0';
@@ -481,6 +482,41 @@ struct SkfArgs {
 };
 int launch_skf(LaunchCtx c, const SkfArgs &a, bool cplx, int L, const cf *tw, int64_t runs, const SkfPlan &pl, float *partial);
 int launch_skf_finish(LaunchCtx c, const float *partial, int64_t runs, int nb, int nk, double mult, double *s_out);
+
+// batched Hermitian eigensolver (k_eigh.hip): a[batch][n][n] complex128, lower triangle -> w[batch][n] descending, the nvec leading
+// vectors v[batch][n][nvec] and the sweeps used; parallel cyclic Jacobi, one matrix per workgroup, A (and V, if nvec > 0) in LDS at the
+// padded order NP.  The grid walks the batch: at most workgroups-per-CU x CUs workgroups.
+#define SP_EIGH_MAX_N 64
+#define SP_EIGH_LDS_MAX ((size_t)160 * 1024)
+struct EighPlan {
+    int NP, wg, wg_per_cu;
+    size_t lds_bytes;
+    int64_t grid;
+};
+size_t eigh_lds_bytes(int NP, bool vec);       // sizeof the kernel's LDS image
+inline int eigh_np_of(int n) { return n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64; }
+inline int eigh_wg_of(int NP) { return NP * NP / 4 < 64 ? 64 : NP * NP / 4; }
+// workgroups per CU: what the LDS, the 2048 threads of a CU and the registers allow, 16 at the most.  The kernels take 78 .. 92 VGPRs,
+// which is 5 waves per SIMD, 20 per CU (profiles/eigh_kernel_resources.txt): one workgroup of 1024 threads, five of 256.
+// grid_cap > 0 limits the grid (test hook)
+#define SP_EIGH_WAVES_PER_CU 20
+inline EighPlan eigh_plan_of(int n, bool vec, int64_t batch, int ncu, int grid_cap) {
+    EighPlan p;
+    p.NP = eigh_np_of(n);
+    p.wg = eigh_wg_of(p.NP);
+    p.lds_bytes = eigh_lds_bytes(p.NP, vec);
+    int per = (int)(SP_EIGH_LDS_MAX / p.lds_bytes);
+    if (per > 2048 / p.wg) per = 2048 / p.wg;
+    if (per > SP_EIGH_WAVES_PER_CU * 64 / p.wg) per = SP_EIGH_WAVES_PER_CU * 64 / p.wg;
+    if (per > 16) per = 16;
+    p.wg_per_cu = per;
+    p.grid = (int64_t)per * ncu;
+    if (grid_cap > 0 && p.grid > grid_cap) p.grid = grid_cap;
+    if (p.grid > batch) p.grid = batch;
+    return p;
+}
+int launch_eigh(LaunchCtx c, const double *a, int n, int64_t batch, int nvec, int max_sweeps, double *w, double *v, int32_t *sweeps,
+                const EighPlan &pl);
 
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;

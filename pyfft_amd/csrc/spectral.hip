@@ -3289,6 +3289,56 @@ int sp_skf(const void *x, const void *y, int dtype, int64_t nsig, const float *w
     return 0;
 }
 
+// ---- batched Hermitian eigensolver (k_eigh.hip) --------------------------------------------------
+int sp_eigh_plan(int n, int nvec, int64_t batch, int64_t out[4]) {
+    if (n < 1 || n > SP_EIGH_MAX_N || nvec < 0 || nvec > n || batch < 0 || !out) return -1;
+    const EighPlan p = eigh_plan_of(n, nvec > 0, batch, g.ncu, env_int("SP_EIGH_GRID", 0));
+    out[0] = p.NP;
+    out[1] = (int64_t)p.lds_bytes;
+    out[2] = p.wg_per_cu;
+    out[3] = p.grid;
+    return 0;
+}
+
+int sp_eigh(const double *a, int n, int64_t batch, int nvec, int max_sweeps, double *w, double *v, int32_t *sweeps, int mem) {
+    // every refusal comes before the device is touched
+    if (n < 1 || n > SP_EIGH_MAX_N) return fail("sp_eigh: n = %d outside 1 .. %d", n, SP_EIGH_MAX_N);
+    if (nvec < 0 || nvec > n) return fail("sp_eigh: nvec = %d outside 0 .. n = %d", nvec, n);
+    if (batch < 0) return fail("sp_eigh: batch = %lld must not be negative", (long long)batch);
+    if (max_sweeps < 1 || max_sweeps > INT_MAX - 1) return fail("sp_eigh: max_sweeps = %d must be at least 1", max_sweeps);
+    if (batch == 0) return 0;
+    if (!a || !w || !sweeps) return fail("sp_eigh: a, w and sweeps are required");
+    if (nvec > 0 && !v) return fail("sp_eigh: v is required for nvec = %d > 0", nvec);
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const size_t abytes = sizeof(double) * 2 * (size_t)batch * n * n, wbytes = sizeof(double) * (size_t)batch * n;
+    const size_t vbytes = sizeof(double) * 2 * (size_t)batch * n * nvec, sbytes = sizeof(int32_t) * (size_t)batch;
+    const double *ad = a;
+    double *wd = w, *vd = v;
+    int32_t *sd = sweeps;
+    if (!mem) {
+        if (g.in0.ensure(abytes) || g.out0.ensure(vbytes + wbytes + sbytes)) return -1;
+        HIPCHK(hipMemcpyAsync(g.in0.p, a, abytes, hipMemcpyHostToDevice, g.stream));
+        ad = (const double *)g.in0.p;
+        vd = (double *)g.out0.p;
+        wd = (double *)((char *)g.out0.p + vbytes);
+        sd = (int32_t *)((char *)g.out0.p + vbytes + wbytes);
+    }
+    const EighPlan pl = eigh_plan_of(n, nvec > 0, batch, g.ncu, env_int("SP_EIGH_GRID", 0));
+    {
+        ProfScope ps;
+        LAUNCHCHK(launch_eigh(lc(), ad, n, batch, nvec, max_sweeps, wd, nvec > 0 ? vd : nullptr, sd, pl));
+        g.last_kernel = "k_eigh";
+    }
+    if (!mem) {
+        if (nvec > 0) HIPCHK(hipMemcpyAsync(v, vd, vbytes, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipMemcpyAsync(w, wd, wbytes, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipMemcpyAsync(sweeps, sd, sbytes, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
 // reciprocal window-square envelope of sp_istft as [period: hop][head: head_len][tail: n - hop] float32 from float64 sums; entries
 // whose envelope is <= 1e-10 are 1 (scipy's rule: such samples are not divided).  Away from the ends env[a] = P[a mod hop]; the first
 // n - hop samples lack the frames before 0 and the last n - hop those from M on.  With so few frames that the two ends meet

@@ -995,6 +995,69 @@ def skf(x, y, nfft, hop, nframes, b0, nb, nk, win=None, segmean=True, cross=Fals
     return out
 
 
+EIGH_MAX_N = 64
+
+
+class OrderTooLarge(ValueError, NotImplementedError):
+    """A matrix order above 64: outside the limits, and a path that is not built (A and V of one matrix live in the LDS of one CU)."""
+
+
+def eigh(A, nvec=None, max_sweeps=30, check=True):
+    """Eigendecomposition of the Hermitian matrices A[..., n, n], 1 <= n <= 64, on the GPU (sp_eigh: parallel cyclic Jacobi in
+    float64, one matrix per workgroup) -> (w, V, sweeps):
+      w      [..., n] float64, DESCENDING (numpy.linalg.eigh ascends);
+      V      [..., n, nvec] complex128, column j the unit eigenvector of w[..., j]; nvec (default n) leading ones, 0 for none.  Each is
+             turned so that its component of largest modulus is real and positive;
+      sweeps [...] int32 Jacobi sweeps used; max_sweeps + 1 marks a matrix that did not converge (or holds a NaN or an infinity),
+             whose w and V mean nothing.
+    Only the LOWER triangle and the real part of the diagonal are read, as numpy.linalg.eigh's UPLO='L' does.  complex128 is native;
+    complex64, float32 and float64 are cast.  check=True reads sweeps back and raises numpy.linalg.LinAlgError naming the first
+    matrix that did not converge; check=False leaves the judgement (and, for device tensors, the asynchrony) to the caller.
+    numpy in -> numpy out; a device tensor in -> device tensors out on the same device and on torch's current stream."""
+    dev = _is_torch(A)
+    shape = tuple(A.shape)
+    if len(shape) < 2 or shape[-1] != shape[-2]:
+        raise ValueError("eigh: A must be [..., n, n], got %s" % (shape,))
+    n = int(shape[-1])
+    if n < 1:
+        raise ValueError("eigh: the order must be at least 1")
+    if n > EIGH_MAX_N:
+        raise OrderTooLarge("eigh: order n = %d above %d is not built (one matrix and its vectors live in the LDS of one CU)"
+                            % (n, EIGH_MAX_N))
+    nvec = n if nvec is None else int(nvec)
+    if not 0 <= nvec <= n:
+        raise ValueError("eigh: nvec = %d outside 0 .. n = %d" % (nvec, n))
+    max_sweeps = int(max_sweeps)
+    if max_sweeps < 1:
+        raise ValueError("eigh: max_sweeps must be at least 1")
+    lead = shape[:-2]
+    batch = 1
+    for d in lead:
+        batch *= int(d)
+    if dev:
+        _bind_stream(A)
+        a = A.to(torch.complex128).contiguous()
+        w = torch.empty(lead + (n,), dtype=torch.float64, device=a.device)
+        V = torch.empty(lead + (n, nvec), dtype=torch.complex128, device=a.device)
+        sw = torch.empty(lead, dtype=torch.int32, device=a.device)
+        _ffi.check(lib().sp_eigh(ptr(a.data_ptr()), n, batch, nvec, max_sweeps, ptr(w.data_ptr()),
+                             ptr(V.data_ptr()) if nvec > 0 and batch > 0 else None, ptr(sw.data_ptr()), 1))
+        bad = sw.reshape(-1).cpu().numpy() > max_sweeps if check else None
+    else:
+        a = np.ascontiguousarray(A, dtype=np.complex128)
+        _ffi.init()
+        w = np.empty(lead + (n,), dtype=np.float64)
+        V = np.empty(lead + (n, nvec), dtype=np.complex128)
+        sw = np.empty(lead, dtype=np.int32)
+        _ffi.check(lib().sp_eigh(ptr(a), n, batch, nvec, max_sweeps, ptr(w), ptr(V) if nvec > 0 and batch > 0 else None, ptr(sw), 0))
+        bad = sw.reshape(-1) > max_sweeps if check else None
+    if check and bad.any():
+        first = int(np.argmax(bad))
+        raise np.linalg.LinAlgError("eigh: matrix %s (flat index %d) did not converge in %d sweeps (non-finite input?)"
+                                    % (np.unravel_index(first, lead) if lead else (), first, max_sweeps))
+    return w, V, sw
+
+
 # ------------------------------------------------------------------------------------------ F1
 def fir_filter(h, x, nfft=0):
     """Causal FIR y = lfilter(h, 1, x) (float32) by overlap-save on the GPU."""
