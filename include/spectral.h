@@ -274,6 +274,23 @@ int sp_ddc(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t batch
            int ntaps, void *out, int mem);
 int sp_ddc_tile(int q);
 
+/* ---- Rational resampler (scipy.signal.upfirdn): zero-stuff by `up`, filter with h, keep every `down`-th sample -- one pass over
+ *      every row of a batch.  With xu[i up] = x[i] for 0 <= i < nsig and xu = 0 elsewhere,
+ *        y[m] = sum_{j<ntaps} h[j] xu[m down - j] = sum_p h[phi + p up] x[i0 - p],   i0 = floor(m down / up), phi = (m down) mod up
+ *        out[b][k] = y_b[m0 + k],  k < nout,  row stride nout.
+ *      x: float32 or complex64 rows of nsig samples, row stride x_ld >= nsig; h: HOST float32 [ntaps], real; out has the dtype of x
+ *      (real rows stay real); x and out follow `mem`.  Outputs beyond the full length ceil(((nsig - 1) up + ntaps) / down) are zero
+ *      by the definition, not an error.  The caller reduces up / down by their gcd.  No atomics, a fixed summation order: two calls
+ *      agree bitwise.  nout = 0 or batch = 0 returns 0 and launches nothing.
+ *      Limits of one launch: 1 <= up, down <= 256; 1 <= ntaps <= 8191; h finite; nsig >= 1; m0, nout >= 0;
+ *      (m0 + nout) down < 2^62; batch * ceil(nout / tile) fits 31 bits.
+ *      Anything else returns < 0 with sp_last_error() naming sp_upfirdn, before the device is touched, and leaves out untouched.
+ *      sp_upfirdn_tile: the outputs one workgroup produces for this shape (cplx != 0: complex64 rows), 0 outside the limits.
+ *      Host only. */
+int sp_upfirdn(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t batch, const float *h, int ntaps, int up, int down,
+               int64_t m0, int64_t nout, void *out, int on_device);
+int sp_upfirdn_tile(int up, int down, int ntaps, int cplx);
+
 /* ---- Polyphase filter-bank channelizer (weighted overlap-add DFT bank): every row of a batch split into M uniformly spaced
  *      bands under a prototype filter of ntaps = P*M real taps, longer than the transform.  For one row x[0:nsig], zero outside
  *      the row, and frame m = 0 .. nframes-1 with s = first + m*hop (first: the row index of frame 0's first sample, may be < 0):

@@ -43,3 +43,5 @@ from . import wavenumber as _wavenumber_mod                    # noqa: F401
 from .wavenumber import skf, skf_moments, dispersion, skf_plan   # noqa: F401
 from . import spod as _spod_mod                                # noqa: F401
 from .spod import spod, spod_energy, spod_reconstruct, spod_plan   # noqa: F401
+from . import resample as _resample_mod                        # noqa: F401
+from .resample import upfirdn, resample_poly, resample_rate, resample_plan   # noqa: F401

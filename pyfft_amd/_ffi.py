@@ -62,6 +62,8 @@ SIGNATURES = {
     "sp_czt_chirp": (_i, [_i64, _i64, _d, _d, _vp]),
     "sp_ddc": (_i, [_vp, _i, _i64, _i64, _i64, _d, _i64, _i, _vp, _i, _vp, _i]),
     "sp_ddc_tile": (_i, [_i]),
+    "sp_upfirdn": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _i, _i, _i, _i64, _i64, _vp, _i]),
+    "sp_upfirdn_tile": (_i, [_i, _i, _i, _i]),
     "sp_pfb": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _i, _i, _i, _i64, _i64, _i, _i, _i, _i, _d, _vp, _i]),
     "sp_pfb_synth": (_i, [_vp, _i, _i, _i64, _i64, _vp, _i, _i, _i, _i64, _i, _i, _d, _i64, _vp, _i]),
     "sp_pfb_synth_plan": (_i, [_i, _i64, _i64, _i, _i, _i, C.POINTER(_i64)]),

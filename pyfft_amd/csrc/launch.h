@@ -397,6 +397,68 @@ inline DdcGeom ddc_geom(int q, int ntaps) {
 int launch_ddc(LaunchCtx c, const void *x, bool cplx, int64_t x_ld, int64_t nsig, int64_t batch, const DdcGeom &g, uint64_t ph0,
                uint64_t dnu, const cf *tab, const float *taps, bool vec, cf *out);
 
+// rational resampler (k_upfirdn.hip): y[m] = sum_p h[phi + p up] x[i0 - p], i0 = floor(m down / up), phi = (m down) mod up; one
+// workgroup of 256 threads per tile of K consecutive outputs of a row.  Outputs a multiple of `up` apart share the taps row phi, and
+// their i0 lie that multiple of `down` apart: K = up NG R, and work item w < up NG is the R = SP_UPF_R outputs w, w + up NG, .. of the
+// tile.  The items are dealt to a thread grid of OT x SG: an item thread owns the R outputs of its item over the taps p = s, s + SG, ..
+// of its slice s.  Few items (heavy decimation: up = 1, K small) leave room for many slices, many items run in several rounds.
+// K is chosen so that a tile consumes about max(4096, 2 P) samples, P = ceil(ntaps / up), at most SP_UPF_MAXK outputs, and so that the
+// LDS image stays within SP_UPF_LDS_MAX.
+#ifndef SP_UPF_R           // -DSP_UPF_R=8 is the variant of profiles/resample_dropped_variants.txt
+#define SP_UPF_R 4
+#endif
+#define SP_UPF_MAXF 256
+#define SP_UPF_MAXTAPS 8191
+#define SP_UPF_MAXK 4096
+#define SP_UPF_LDS_MAX ((size_t)160 * 1024)
+struct UpfGeom {
+    int up, down, ntaps;
+    int P;             // taps per phase, ceil(ntaps / up)
+    int pitch;         // floats per phase row of the taps image [up][pitch]: P rounded up to odd
+    int NG, K;         // groups of R outputs per phase class; outputs per tile
+    int items;         // up NG
+    int sg, sg_log2;   // tap slices (a power of two), the fast index of the thread grid
+    int rounds;        // ceil(items / (256 / sg))
+    int NI;            // staged samples
+    int xlen;          // entries of the staged image (NI rounded up to even)
+    size_t lds;        // bytes: the staged samples, the partial sums [sg][K], the taps
+};
+inline UpfGeom upf_geom(int up, int down, int ntaps, bool cplx) {
+    UpfGeom g;
+    g.up = up;
+    g.down = down;
+    g.ntaps = ntaps;
+    g.P = (ntaps + up - 1) / up;
+    g.pitch = g.P | 1;
+    const size_t es = cplx ? 8 : 4;
+    const int64_t want = g.P > 2048 ? 2 * (int64_t)g.P : 4096;                     // samples a tile should consume
+    int64_t ng = want / ((int64_t)down * SP_UPF_R);
+    if (ng > SP_UPF_MAXK / (up * SP_UPF_R)) ng = SP_UPF_MAXK / (up * SP_UPF_R);
+    if (ng < 1) ng = 1;
+    for (;; --ng) {
+        g.NG = (int)ng;
+        g.K = up * g.NG * SP_UPF_R;
+        g.items = up * g.NG;
+        g.sg = 1;
+        g.sg_log2 = 0;
+        while (g.sg * 2 * g.items <= 256 && g.sg * 2 <= g.P) {
+            g.sg *= 2;
+            ++g.sg_log2;
+        }
+        const int ot = 256 / g.sg;
+        g.rounds = (g.items + ot - 1) / ot;
+        g.NI = g.P + (int)(((int64_t)(g.K - 1) * down) / up) + 2;
+        g.xlen = (g.NI + 1) & ~1;                                                // even: what follows stays 8-byte aligned
+        g.lds = es * (size_t)g.xlen + es * (size_t)g.sg * g.K + sizeof(float) * (size_t)up * g.pitch;
+        if (g.lds <= SP_UPF_LDS_MAX || ng == 1) break;
+    }
+    return g;
+}
+// x: rows of nsig samples (row stride x_ld) -> out[batch][nout] = y[m0 .. m0 + nout - 1] (float, or cf when cplx);
+// taps[phi][p] = h[phi + p up] or 0 past the last tap, row pitch g.pitch; vec: x is 16-byte aligned
+int launch_upfirdn(LaunchCtx c, const void *x, bool cplx, int64_t x_ld, int64_t nsig, int64_t batch, const UpfGeom &g,
+                   const float *taps, bool vec, int64_t m0, int64_t nout, void *out);
+
 // polyphase filter-bank channelizer (k_pfb.hip): frames m < nframes of every row, frame m = the L = P M samples from first + m hop on
 // (zero outside the row) folded to M under the taps and transformed; rp partitions the frames of ONE row, the grid is rp.blocks x batch
 // workgroups in one dimension.  out_kind 0: out = complex64 [batch][nframes][nb], nb = M (complex rows) or M/2 + 1 (real rows);

@@ -2765,6 +2765,71 @@ int sp_ddc(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t batch
     return 0;
 }
 
+// ---- rational resampler (k_upfirdn.hip) ------------------------------------------------------------
+static bool upf_admits(int up, int down, int ntaps) {
+    return up >= 1 && up <= SP_UPF_MAXF && down >= 1 && down <= SP_UPF_MAXF && ntaps >= 1 && ntaps <= SP_UPF_MAXTAPS;
+}
+
+int sp_upfirdn_tile(int up, int down, int ntaps, int cplx) {
+    if (!upf_admits(up, down, ntaps)) return 0;
+    const UpfGeom geom = upf_geom(up, down, ntaps, cplx != 0);
+    return geom.lds <= SP_UPF_LDS_MAX ? geom.K : 0;
+}
+
+int sp_upfirdn(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t batch, const float *h, int ntaps, int up, int down,
+               int64_t m0, int64_t nout, void *out, int mem) {
+    // every refusal comes before the device is touched
+    if (x_dtype != SP_DTYPE_F32 && x_dtype != SP_DTYPE_C64) return fail("sp_upfirdn: unknown dtype %d", x_dtype);
+    if (!upf_admits(up, down, ntaps))
+        return fail("sp_upfirdn: need up and down in 1 .. %d and ntaps in 1 .. %d, got up = %d, down = %d, ntaps = %d", SP_UPF_MAXF,
+                    SP_UPF_MAXTAPS, up, down, ntaps);
+    if (nsig < 1 || batch < 0 || x_ld < nsig) return fail("sp_upfirdn: need nsig >= 1, batch >= 0 and a row stride x_ld >= nsig");
+    if (m0 < 0 || nout < 0) return fail("sp_upfirdn: m0 = %lld and nout = %lld must not be negative", (long long)m0, (long long)nout);
+    const int64_t mmax = ((int64_t)1 << 62) / down;
+    if (m0 >= mmax || nout >= mmax - m0)
+        return fail("sp_upfirdn: (m0 + nout) down must stay below 2^62 (m0 = %lld, nout = %lld, down = %d)", (long long)m0,
+                    (long long)nout, down);
+    const bool cplx = x_dtype == SP_DTYPE_C64;
+    const UpfGeom geom = upf_geom(up, down, ntaps, cplx);
+    if (geom.lds > SP_UPF_LDS_MAX)
+        return fail("sp_upfirdn: up = %d, down = %d, ntaps = %d need %zu bytes of LDS", up, down, ntaps, geom.lds);
+    if (batch > 0 && (nout + geom.K - 1) / geom.K > INT_MAX / batch)
+        return fail("sp_upfirdn: %lld rows of %lld outputs are too many tiles for one launch", (long long)batch, (long long)nout);
+    if (nout == 0 || batch == 0) return 0;
+    if (!x || !h || !out) return fail("sp_upfirdn: x, h and out are required");
+    for (int j = 0; j < ntaps; ++j)
+        if (!isfinite(h[j])) return fail("sp_upfirdn: the taps must be finite");
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const size_t esz = cplx ? 8 : 4, in_elems = (size_t)((batch - 1) * x_ld + nsig), obytes = esz * (size_t)batch * (size_t)nout;
+    const void *xd = x;
+    void *od = out;
+    if (!mem) {
+        if (g.in0.ensure(esz * in_elems) || g.out0.ensure(obytes)) return -1;
+        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * in_elems, hipMemcpyHostToDevice, g.stream));
+        xd = g.in0.p;
+        od = g.out0.p;
+    }
+    // the taps, one row per phase: taps[phi][p] = h[phi + p up]
+    std::vector<float> tp((size_t)up * geom.pitch, 0.f);
+    for (int j = 0; j < ntaps; ++j) tp[(size_t)(j % up) * geom.pitch + j / up] = h[j];
+    void *taps_d = nullptr;
+    if (get_table(14, tp.data(), sizeof(float) * tp.size(), &taps_d, nullptr)) return -1;
+    {
+        ProfScope ps;
+        if (launch_upfirdn(lc(), xd, cplx, x_ld, nsig, batch, geom, (const float *)taps_d, ((uintptr_t)xd & 15) == 0, m0, nout, od) != 0)
+            return fail("sp_upfirdn: the launch was refused (up = %d, down = %d, ntaps = %d, %zu bytes of LDS)", up, down, ntaps,
+                        geom.lds);
+        HIPCHK(hipGetLastError());
+        g.last_kernel = "k_upfirdn";
+    }
+    if (!mem) {
+        HIPCHK(hipMemcpyAsync(out, od, obytes, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
 // ---- polyphase filter-bank channelizer (k_pfb.hip) ------------------------------------------------
 int sp_pfb(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t batch, const float *h, int ntaps, int M, int hop,
            int64_t first, int64_t nframes, int phase_ref, int r0, int out_kind, int out_major, double scale, void *out, int mem) {

@@ -690,6 +690,61 @@ def ddc(x, nu, q, h, n0=0):
     return out
 
 
+# ------------------------------------------------------------------------------------------ rational resampler
+def upfirdn_tile(up, down, ntaps, cplx):
+    """Outputs one workgroup of sp_upfirdn produces for this shape (cplx: complex64 rows).  Host only."""
+    k = int(lib().sp_upfirdn_tile(int(up), int(down), int(ntaps), 1 if cplx else 0))
+    if k <= 0:
+        raise ValueError("upfirdn_tile: up = %r, down = %r must lie in 1 .. 256 and ntaps = %r in 1 .. 8191" % (up, down, ntaps))
+    return k
+
+
+def upfirdn(x, h, up, down, m0=0, nout=None):
+    """Zero-stuff by up, filter with the real taps h and keep every down-th sample along the last axis (sp_upfirdn):
+    y[..., m] = sum_j h[j] xu[..., m down - j], xu[..., i up] = x[..., i]; returned are the outputs m0 .. m0 + nout - 1 (nout=None: up to
+    the full length ceil(((n - 1) up + T) / down); beyond it the outputs are zero).  The dtype of x is kept: float32 rows stay real.
+    up / down must be reduced.  numpy in -> numpy out, device tensor in -> device tensor on x's stream (rows of a 2-D tensor may be
+    strided)."""
+    up, down, m0 = int(up), int(down), int(m0)
+    if np.iscomplexobj(h):
+        raise ValueError("upfirdn: the taps must be real")
+    taps = np.ascontiguousarray(np.asarray(h), dtype=np.float32)
+    if taps.ndim != 1 or taps.size < 1:
+        raise ValueError("upfirdn: the taps must be one-dimensional and not empty")
+    if not (1 <= up <= 256 and 1 <= down <= 256):
+        raise ValueError("upfirdn: up = %d and down = %d must lie in 1 .. 256" % (up, down))
+    if taps.size > 8191:
+        raise ValueError("upfirdn: %d taps are beyond the 8191 one launch takes" % taps.size)
+    dev = _is_torch(x)
+    if dev:
+        _bind_stream(x)
+        if x.dtype not in (torch.float32, torch.complex64):
+            raise TypeError("device path takes float32 or complex64 samples, got %s" % x.dtype)
+    else:
+        x = _ffi.as_samples(x)
+    if (x.dim() if dev else x.ndim) < 1 or x.shape[-1] < 1:
+        raise ValueError("upfirdn: x must have at least one axis, and at least one sample along it")
+    n = int(x.shape[-1])
+    full = -(-((n - 1) * up + taps.size) // down)
+    nout = max(full - m0, 0) if nout is None else int(nout)
+    if m0 < 0 or nout < 0:
+        raise ValueError("upfirdn: m0 = %d and nout = %d must not be negative" % (m0, nout))
+    shape = tuple(x.shape[:-1]) + (nout,)
+    if dev:
+        if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= n and x.shape[0] >= 1:
+            xs, ld = x, int(x.stride(0))                      # a row-strided view goes through as it is
+        else:
+            xs, ld = x.contiguous(), n
+        out = torch.empty(shape, dtype=x.dtype, device=x.device)
+        check(lib().sp_upfirdn(ptr(xs.data_ptr()), _tcode(xs), n, ld, xs.numel() // n, ptr(taps), taps.size, up, down, m0, nout,
+                               ptr(out.data_ptr()), 1))
+        return out
+    out = np.empty(shape, dtype=x.dtype)
+    _ffi.init()
+    check(lib().sp_upfirdn(ptr(x), _ffi.dtype_code(x.dtype), n, n, x.size // n, ptr(taps), taps.size, up, down, m0, nout, ptr(out), 0))
+    return out
+
+
 def pfb(x, h, M, hop, first, nframes, phase_ref=0, r0=0, power=False, out_major=0, scale=1.0):
     """Polyphase filter bank along the last axis (sp_pfb): frame m holds the len(h) = P M samples from first + m hop on (zero outside the
     row), folded to M under the real taps h and transformed: X[..., m, k] = sum_n h[n] x[..., first + m hop + n] exp(-2 pi i k (n + rho_m) / M),
