@@ -444,6 +444,43 @@ int sp_skf(const void *x, const void *y, int dtype, int64_t nsig, const float *w
            int power, int b0, int nb, int nk, double scale, double *s_out, int mem);
 int sp_skf_plan(int cplx, int nfft, int nb, int nk, int64_t *out);
 
+/* ---- Time-resolved Welch spectra (build-defined; the reference's __init__.py tries to import CECE for this question): the PSD of x,
+ *      and with y the PSDs of nch records y_c (row c at y + c y_ld, y_ld >= nsig) and their cross spectra with x, over blocks of navg
+ *      consecutive frames, block after block along the record: the running spectra behind a coherogram and a running cross-phase.
+ *      Frame g < nframes is a_g = win (x[g hop : g hop + nfft] - m_g), b_g likewise from y_c, (nframes - 1) hop + nfft <= nsig; m_g is
+ *      the frame's own mean (SP_DETREND_SEGMEAN, scipy's detrend='constant') or 0 (SP_DETREND_NONE); win is a HOST float32 [nfft]
+ *      (device table cache) or NULL (boxcar); X_g, Y_g are the unnormalised forward transforms, nfft a power of two in
+ *      32 .. sp_max_wg_fft().  Block b < nblocks = (nframes - navg) / step + 1 holds the frames b step .. b step + navg - 1:
+ *        pxx[b][k]    = s_k / navg sum_g |X_g[k]|^2                 float32 [nblocks][nb]
+ *        pyy[c][b][k] = s_k / navg sum_g |Y_g[k]|^2                 float32 [nch][nblocks][nb]
+ *        pxy[c][b][k] = s_k / navg sum_g conj(X_g[k]) Y_g[k]        complex64 [nch][nblocks][nb]   (scipy.signal.csd's conjugation)
+ *      s_k = scale; for float32 records with doubled != 0 twice that on the bins 1 .. nfft/2 - 1.  float32 records give the bins
+ *      0 .. nfft/2 (nb = nfft/2 + 1), complex64 records the natural FFT order (nb = nfft), nothing doubled.  So block b is
+ *      scipy.signal.welch / csd of the samples b step hop .. b step hop + (navg - 1) hop + nfft - 1 with nperseg = nfft and
+ *      noverlap = nfft - hop.  step == navg: disjoint blocks; step < navg: overlapping blocks; step > navg: gaps.  Frames left over
+ *      behind the last block are not used.
+ *      One kernel forms the sums of runs of q frames inside its frame loop (q = navg for step >= navg, then it writes the outputs;
+ *      else q = gcd(navg, step), float32 run sums, and a second kernel adds the navg / q runs of every block in float64): every
+ *      frame is transformed once whatever the block overlap.  Every record has its own transform (float32 records as a + 0i), so a
+ *      channel 10^4 below the other keeps its own accuracy, a single frame's coherence is 1 to rounding, and pxx is bitwise the
+ *      same whatever y and nch are.  No atomics: every value has one writer and a
+ *      fixed order of additions that does not depend on where in the record the block lies -- two calls agree bitwise, and so does
+ *      a block with block 0 of the call on the record cut to start there.
+ *      x, y and the outputs follow `mem`.
+ *      Refused (< 0, sp_last_error() names sp_welch_blocks and the argument, the device is not touched, the outputs are untouched):
+ *      nfft not a power of two in 32 .. sp_max_wg_fft(); hop < 1 or hop > nfft; navg < 1; step < 1; nframes < navg; nsig shorter than
+ *      (nframes - 1) hop + nfft; with y: nch < 1, nch > 65535 or y_ld < nsig; a dtype other than float32 / complex64; a detrend
+ *      other than NONE / SEGMEAN; a scale that is not finite; x or pxx NULL; pyy or pxy NULL when y is given.
+ *      sp_welch_blocks_plan (host only; nch = 0: no y): out[8] = nblocks, nb, q, runs, transforms (frames transformed x 2 pairs, x and
+ *      y_c of every pair (x 4 pairs for complex64 pairs at 8192 points, whose bins two workgroups share), or x 1 without y; frames
+ *      transformed = runs x q = nframes when neither gaps nor leftovers exist), scratch bytes (the run
+ *      sums), workgroups, LDS bytes of a workgroup.  The CU count behind the workgroups is the device's once the library is
+ *      initialised and 256 before.  < 0 for a shape that sp_welch_blocks refuses, or out NULL. */
+int sp_welch_blocks(const void *x, const void *y, int dtype, int64_t nsig, int nch, int64_t y_ld, const float *win, int nfft, int hop,
+                    int64_t nframes, int navg, int step, int detrend, double scale, int doubled, float *pxx, float *pyy, void *pxy,
+                    int mem);
+int sp_welch_blocks_plan(int cplx, int nfft, int hop, int64_t nframes, int navg, int step, int nch, int64_t out[8]);
+
 /* ---- Batched Hermitian eigensolver (build-defined; the piece the reference's PCA.py takes from numpy.linalg.eigh): the
  *      eigendecomposition of `batch` matrices of order n, 1 <= n <= 64, e.g. the cross-spectral-density matrix of sp_csd_matrix at
  *      every bin (spectral POD).  a[batch][n][n] complex128 as (re, im) doubles, row-major.  Only the LOWER triangle (row >= column)

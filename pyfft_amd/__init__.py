@@ -45,3 +45,6 @@ from . import spod as _spod_mod                                # noqa: F401
 from .spod import spod, spod_energy, spod_reconstruct, spod_plan   # noqa: F401
 from . import resample as _resample_mod                        # noqa: F401
 from .resample import upfirdn, resample_poly, resample_rate, resample_plan   # noqa: F401
+from . import running as _running_mod                          # noqa: F401
+from .running import (running_psd, running_csd, running_coherence, running_spectra, running_plan,   # noqa: F401
+                      coherence_level)

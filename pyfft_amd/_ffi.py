@@ -76,6 +76,8 @@ SIGNATURES = {
     "sp_xcorr_frames_len": (_i, [_i, _i]),
     "sp_skf": (_i, [_vp, _vp, _i, _i64, _vp, _i, _i, _i64, _i, _i, _i, _i, _i, _d, _vp, _i]),
     "sp_skf_plan": (_i, [_i, _i, _i, _i, _vp]),
+    "sp_welch_blocks": (_i, [_vp, _vp, _i, _i64, _i, _i64, _vp, _i, _i, _i64, _i, _i, _i, _d, _i, _vp, _vp, _vp, _i]),
+    "sp_welch_blocks_plan": (_i, [_i, _i, _i, _i64, _i, _i, _i, _vp]),
     "sp_eigh": (_i, [_vp, _i, _i64, _i, _i, _vp, _vp, _vp, _i]),
     "sp_eigh_plan": (_i, [_i, _i, _i64, C.POINTER(_i64)]),
     "sp_fftfilt": (_i, [_vp, _i, _vp, _i64, _i, _vp, _i]),

@@ -545,6 +545,70 @@ struct SkfArgs {
 int launch_skf(LaunchCtx c, const SkfArgs &a, bool cplx, int L, const cf *tw, int64_t runs, const SkfPlan &pl, float *partial);
 int launch_skf_finish(LaunchCtx c, const float *partial, int64_t runs, int nb, int nk, double mult, double *s_out);
 
+// time-resolved Welch spectra (k_welch_blocks.hip): blocks of navg frames, step frames apart.  A run is q consecutive frames summed
+// once: q = navg and run r = block r = the frames from r step on when step >= navg (final: the kernel writes the outputs); else
+// q = gcd(navg, step), the runs tile the frames, and launch_block_sum forms block b from the navg / q runs from b step / q on.
+// A workgroup owns welch_blocks_teams(L) x rpt consecutive runs (teams: 256 / L below 256 points, else 1).
+struct WelchBlocksArgs {
+    const void *x, *y;                  // y null: the PSD alone; else pairs rows, y_ld samples apart
+    const float *win;                   // device table or null (boxcar)
+    int hop, segmean, q, rpt, planes;   // planes of the partials: 4 with y, else 1
+    int64_t y_ld, nframes, runs, rstride;      // rstride: frames from one run's first frame to the next one's
+    float mult, mult2;                  // final form: s / navg, and the same doubled (real records, bins 1 .. L/2 - 1) or not
+    float *partial;                     // [pairs][runs][planes][nb], or null: the final form ->
+    float *pxx, *pyy;                   // [runs][nb], [pairs][runs][nb]
+    cf *pxy;                            // [pairs][runs][nb]
+};
+struct WelchBlocksPlan {
+    int64_t nblocks, runs, rstride, wgs;
+    int nb, q, rpt, final_form, adv, nsum;      // block b = runs b adv .. b adv + nsum - 1
+    size_t lds_bytes, scratch_bytes;
+};
+inline int welch_blocks_teams(int L) { return L < 256 ? 256 / L : 1; }
+// a complex pair at 8192 points: the bins are split over two workgroups, each transforms the frames (registers; k_welch_blocks.hip)
+constexpr int welch_blocks_bin_split(bool cplx, bool pair, int L) { return cplx && pair && L >= 8192 ? 2 : 1; }
+// the transform images of a workgroup: two per group with y (X is parked while Y is made)
+inline size_t welch_blocks_lds_bytes(bool pair, int L) { return (size_t)fpw_of(L) * (size_t)(L + 16) * 8 * (pair ? 2 : 1); }
+// pairs = max(nch, 1); have_y = nch >= 1.  rpt: a team should run about four rounds of its groups, as long as that leaves the grid
+// about four workgroups per CU
+inline WelchBlocksPlan welch_blocks_plan_of(bool cplx, int L, int64_t nframes, int navg, int step, int nch, int ncu) {
+    WelchBlocksPlan p;
+    p.nb = cplx ? L : L / 2 + 1;
+    p.nblocks = (nframes - navg) / step + 1;
+    p.final_form = step >= navg ? 1 : 0;
+    if (p.final_form) {
+        p.q = navg;
+        p.runs = p.nblocks;
+        p.rstride = step;
+        p.adv = p.nsum = 1;
+    } else {
+        int g = navg, h = step;
+        while (h) {
+            const int r = g % h;
+            g = h;
+            h = r;
+        }
+        p.q = g;
+        p.runs = ((p.nblocks - 1) * step + navg) / g;
+        p.rstride = g;
+        p.adv = step / g;
+        p.nsum = navg / g;
+    }
+    const int teams = welch_blocks_teams(L), gpt = fpw_of(L) / teams, pairs = nch > 1 ? nch : 1;
+    int64_t rpt = ((int64_t)4 * gpt + p.q - 1) / p.q;
+    const int64_t room = p.runs * pairs / ((int64_t)teams * 4 * ncu);
+    if (rpt > room) rpt = room;
+    if (rpt < 1) rpt = 1;
+    p.rpt = (int)rpt;
+    p.wgs = (p.runs + teams * rpt - 1) / (teams * rpt);
+    p.lds_bytes = welch_blocks_lds_bytes(nch >= 1, L);
+    p.scratch_bytes = p.final_form ? 0 : sizeof(float) * (size_t)pairs * (size_t)p.runs * (nch >= 1 ? 4 : 1) * (size_t)p.nb;
+    return p;
+}
+int launch_welch_blocks(LaunchCtx c, const WelchBlocksArgs &a, bool cplx, int L, const cf *tw, int pairs, int64_t wgs);
+int launch_block_sum(LaunchCtx c, const float *partial, int64_t runs, int planes, int nb, int64_t nblocks, int adv, int nsum, bool dbl,
+                     int L, double mult, int pairs, float *pxx, float *pyy, cf *pxy);
+
 // batched Hermitian eigensolver (k_eigh.hip): a[batch][n][n] complex128, lower triangle -> w[batch][n] descending, the nvec leading
 // vectors v[batch][n][nvec] and the sweeps used; parallel cyclic Jacobi, one matrix per workgroup, A (and V, if nvec > 0) in LDS at the
 // padded order NP.  The grid walks the batch: at most workgroups-per-CU x CUs workgroups.

@@ -3354,6 +3354,111 @@ int sp_skf(const void *x, const void *y, int dtype, int64_t nsig, const float *w
     return 0;
 }
 
+// ---- time-resolved Welch spectra (k_welch_blocks.hip) ---------------------------------------------
+// the shape checks sp_welch_blocks and its plan share; 0 or the message's tail
+static const char *welch_blocks_shape(int nfft, int hop, int64_t nframes, int navg, int step) {
+    if (nfft < 32 || nfft > SP_MAX_WG_FFT || !is_pow2(nfft)) return "nfft must be a power of two from 32 to 8192";
+    if (hop < 1 || hop > nfft) return "hop must lie in 1 .. nfft";
+    if (navg < 1) return "navg must be at least 1";
+    if (step < 1) return "step must be at least 1";
+    if (nframes < navg) return "nframes must be at least navg";
+    if (nframes > ((int64_t)1 << 40) / hop) return "nframes: too many frames";
+    return nullptr;
+}
+
+int sp_welch_blocks_plan(int cplx, int nfft, int hop, int64_t nframes, int navg, int step, int nch, int64_t out[8]) {
+    if (welch_blocks_shape(nfft, hop, nframes, navg, step) || nch < 0 || nch > 65535 || !out) return -1;
+    const WelchBlocksPlan p = welch_blocks_plan_of(cplx != 0, nfft, nframes, navg, step, nch, g.ncu);
+    out[0] = p.nblocks;
+    out[1] = p.nb;
+    out[2] = p.q;
+    out[3] = p.runs;
+    // every record of every pair has its own transform; twice where the bins are split over two workgroups
+    out[4] = p.runs * p.q * (nch < 1 ? 1 : 2 * (int64_t)nch) * welch_blocks_bin_split(cplx != 0, nch >= 1, nfft);
+    out[5] = (int64_t)p.scratch_bytes;
+    out[6] = p.wgs;
+    out[7] = (int64_t)p.lds_bytes;
+    return 0;
+}
+
+int sp_welch_blocks(const void *x, const void *y, int dtype, int64_t nsig, int nch, int64_t y_ld, const float *win, int nfft, int hop,
+                    int64_t nframes, int navg, int step, int detrend, double scale, int doubled, float *pxx, float *pyy, void *pxy,
+                    int mem) {
+    // every refusal comes before the device is touched
+    if (const char *why = welch_blocks_shape(nfft, hop, nframes, navg, step))
+        return fail("sp_welch_blocks: %s (nfft %d, hop %d, nframes %lld, navg %d, step %d)", why, nfft, hop, (long long)nframes, navg,
+                    step);
+    if (nsig < nfft || (nframes - 1) > (nsig - nfft) / hop)
+        return fail("sp_welch_blocks: nsig = %lld is shorter than the %lld frames of %d with hop %d", (long long)nsig, (long long)nframes,
+                    nfft, hop);
+    if (dtype != SP_DTYPE_F32 && dtype != SP_DTYPE_C64) return fail("sp_welch_blocks: dtype must be float32 or complex64, got %d", dtype);
+    if (y && (nch < 1 || nch > 65535)) return fail("sp_welch_blocks: nch = %d outside 1 .. 65535", nch);
+    if (y && y_ld < nsig) return fail("sp_welch_blocks: y_ld = %lld is below nsig = %lld", (long long)y_ld, (long long)nsig);
+    if (detrend != SP_DETREND_NONE && detrend != SP_DETREND_SEGMEAN)
+        return fail("sp_welch_blocks: detrend must be SP_DETREND_NONE or SP_DETREND_SEGMEAN, got %d", detrend);
+    if (!isfinite(scale)) return fail("sp_welch_blocks: scale must be finite");
+    if (!x) return fail("sp_welch_blocks: x is required");
+    if (!pxx) return fail("sp_welch_blocks: pxx is required");
+    if (y && !pyy) return fail("sp_welch_blocks: pyy is required when y is given");
+    if (y && !pxy) return fail("sp_welch_blocks: pxy is required when y is given");
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const bool cplx = dtype == SP_DTYPE_C64, dbl = !cplx && doubled != 0;
+    const int pairs = y ? nch : 1;
+    const WelchBlocksPlan pl = welch_blocks_plan_of(cplx, nfft, nframes, navg, step, y ? nch : 0, g.ncu);
+    const size_t esz = cplx ? 8 : 4, cells = (size_t)pl.nblocks * (size_t)pl.nb;
+    const size_t xxb = sizeof(float) * cells, yyb = y ? sizeof(float) * cells * (size_t)nch : 0, xyb = 2 * yyb;
+    const size_t yoff = (xxb + 255) & ~(size_t)255, xyoff = yoff + ((yyb + 255) & ~(size_t)255);
+    const void *xd = x, *yd = y;
+    float *pxx_d = pxx, *pyy_d = pyy;
+    cf *pxy_d = (cf *)pxy;
+    if (!mem) {
+        if (g.in0.ensure(esz * (size_t)nsig)) return -1;
+        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
+        xd = g.in0.p;
+        if (y) {
+            const size_t yb = esz * ((size_t)(nch - 1) * (size_t)y_ld + (size_t)nsig);
+            if (g.in1.ensure(yb)) return -1;
+            HIPCHK(hipMemcpyAsync(g.in1.p, y, yb, hipMemcpyHostToDevice, g.stream));
+            yd = g.in1.p;
+        }
+        if (g.out0.ensure(xyoff + xyb)) return -1;       // staged outputs: [pxx | pyy | pxy], each piece 256-byte aligned
+        pxx_d = (float *)g.out0.p;
+        pyy_d = y ? (float *)((char *)g.out0.p + yoff) : nullptr;
+        pxy_d = y ? (cf *)((char *)g.out0.p + xyoff) : nullptr;
+    }
+    void *win_d = nullptr;
+    if (win && get_table(1, win, sizeof(float) * (size_t)nfft, &win_d, nullptr)) return -1;
+    const cf *tw;
+    if (get_twiddles(nfft, &tw)) return -1;
+    float *partial = nullptr;
+    if (!pl.final_form) {
+        if (g.work.ensure(pl.scratch_bytes)) return -1;
+        partial = (float *)g.work.p;
+    }
+    const double mult = scale / (double)navg;
+    const WelchBlocksArgs a{xd, yd, (const float *)win_d, hop, detrend == SP_DETREND_SEGMEAN ? 1 : 0, pl.q, pl.rpt, y ? 4 : 1,
+                            y_ld, nframes, pl.runs, pl.rstride, (float)mult, (float)(dbl ? 2.0 * mult : mult), partial,
+                            pxx_d, pyy_d, pxy_d};
+    {
+        ProfScope ps;
+        LAUNCHCHK(launch_welch_blocks(lc(), a, cplx, nfft, tw, pairs, pl.wgs));
+        g.last_kernel = "k_welch_blocks";
+    }
+    if (!pl.final_form)
+        LAUNCHCHK(launch_block_sum(lc(), partial, pl.runs, y ? 4 : 1, pl.nb, pl.nblocks, pl.adv, pl.nsum, dbl, nfft, mult, pairs, pxx_d,
+                                   pyy_d, pxy_d));
+    if (!mem) {
+        HIPCHK(hipMemcpyAsync(pxx, pxx_d, xxb, hipMemcpyDeviceToHost, g.stream));
+        if (y) {
+            HIPCHK(hipMemcpyAsync(pyy, pyy_d, yyb, hipMemcpyDeviceToHost, g.stream));
+            HIPCHK(hipMemcpyAsync(pxy, pxy_d, xyb, hipMemcpyDeviceToHost, g.stream));
+        }
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
 // ---- batched Hermitian eigensolver (k_eigh.hip) --------------------------------------------------
 int sp_eigh_plan(int n, int nvec, int64_t batch, int64_t out[4]) {
     if (n < 1 || n > SP_EIGH_MAX_N || nvec < 0 || nvec > n || batch < 0 || !out) return -1;

@@ -1050,6 +1050,125 @@ def skf(x, y, nfft, hop, nframes, b0, nb, nk, win=None, segmean=True, cross=Fals
     return out
 
 
+WELCH_BLOCKS_MIN_NFFT, WELCH_BLOCKS_MAX_NFFT = 32, 8192
+
+
+class WelchBlocksRefused(ValueError, NotImplementedError):
+    """A shape welch_blocks does not take: outside the limits, and a path that is not built (segments that are no power of two or
+    longer than one workgroup transform, detrend modes other than the segment's own mean, zero padding)."""
+
+
+def welch_blocks_check(who, nsig, nfft, hop, nframes, navg, step, detrend, nch=None, y_ld=None):
+    """Every refusal of sp_welch_blocks, before the library is touched -> the detrend code."""
+    if nfft < WELCH_BLOCKS_MIN_NFFT or nfft > WELCH_BLOCKS_MAX_NFFT or nfft & (nfft - 1):
+        raise WelchBlocksRefused("%s: nfft = %d must be a power of two from %d to %d"
+                                 % (who, nfft, WELCH_BLOCKS_MIN_NFFT, WELCH_BLOCKS_MAX_NFFT))
+    if hop < 1 or hop > nfft:
+        raise WelchBlocksRefused("%s: hop = %d must lie in 1 .. nfft = %d" % (who, hop, nfft))
+    if navg < 1:
+        raise WelchBlocksRefused("%s: navg = %d must be at least 1" % (who, navg))
+    if step < 1:
+        raise WelchBlocksRefused("%s: step = %d must be at least 1" % (who, step))
+    if nframes < navg:
+        raise WelchBlocksRefused("%s: nframes = %d must be at least navg = %d" % (who, nframes, navg))
+    if nsig < (nframes - 1) * hop + nfft:
+        raise WelchBlocksRefused("%s: the record (%d samples) is shorter than %d frames of %d with hop %d"
+                                 % (who, nsig, nframes, nfft, hop))
+    if nch is not None and (nch < 1 or nch > 65535):
+        raise WelchBlocksRefused("%s: nch = %d outside 1 .. 65535" % (who, nch))
+    if y_ld is not None and y_ld < nsig:
+        raise WelchBlocksRefused("%s: the rows of y (%d samples) are shorter than x (%d)" % (who, y_ld, nsig))
+    if detrend is True or (isinstance(detrend, str) and detrend in ("constant", "segmean")):
+        return _ffi.DETREND_SEGMEAN
+    if detrend is None or detrend is False or (isinstance(detrend, str) and detrend == "none"):
+        return _ffi.DETREND_NONE
+    raise WelchBlocksRefused("%s: detrend must be 'constant' (every segment's own mean) or False, got %r" % (who, detrend))
+
+
+def welch_blocks(x, win, hop, nframes, navg, step=None, y=None, detrend=True, scale=1.0, doubled=False, nfft=None):
+    """Time-resolved Welch spectra (sp_welch_blocks): block b holds the frames b*step .. b*step + navg - 1 of the nframes frames
+    x[g*hop : g*hop + nfft] (every frame's own mean removed when detrend is True / 'constant', tapered by win[nfft]; win=None: boxcar,
+    then nfft is required), nblocks = (nframes - navg) // step + 1, step = navg by default.
+    -> (Pxx, Pyy, Pxy): Pxx float32 [nblocks, nb] = scale / navg * sum |X|^2; with y (x's dtype; [nsig] or [nch, >= nsig]) Pyy float32
+    and Pxy complex64 = scale / navg * sum conj(X) Y, [nblocks, nb] or [nch, nblocks, nb], else None.  float32 records: nb = nfft/2 + 1,
+    the bins 1 .. nfft/2 - 1 doubled when `doubled`; complex64 records: nb = nfft in FFT order.  Every frame is transformed once
+    whatever the overlap of the blocks.  numpy in -> numpy out; device tensors in -> device tensors on x's stream."""
+    w = None if win is None else _win32(win)
+    if w is None and nfft is None:
+        raise ValueError("welch_blocks: nfft is required when win is None")
+    nfft = int(w.size if nfft is None else nfft)
+    if w is not None and w.shape != (nfft,):
+        raise ValueError("welch_blocks: win must hold nfft = %d values" % nfft)
+    hop, nframes, navg = int(hop), int(nframes), int(navg)
+    step = navg if step is None else int(step)
+    dev = _is_torch(x)
+    if dev:
+        xs = _torch_samples(x)
+        cplx = xs.dtype == torch.complex64
+        ys = None
+        if y is not None:
+            if not _is_torch(y):
+                raise TypeError("welch_blocks: x is a device tensor, y must be one too")
+            ys = _torch_samples(y)
+            if ys.dtype != xs.dtype or ys.device != xs.device:
+                raise ValueError("welch_blocks: y must have x's dtype and device")
+    else:
+        xs = _ffi.as_samples(x)
+        ys = None if y is None else np.asarray(y)
+        if ys is not None and (np.iscomplexobj(ys) or xs.dtype == np.complex64):
+            xs = np.ascontiguousarray(xs, dtype=np.complex64)
+        cplx = xs.dtype == np.complex64
+        if ys is not None:
+            ys = np.ascontiguousarray(ys, dtype=xs.dtype)
+    if xs.ndim != 1 or (ys is not None and ys.ndim not in (1, 2)):
+        raise ValueError("welch_blocks: x[nsig] against y[nsig] or y[nch, >= nsig]")
+    nsig = int(xs.shape[0])
+    squeeze = ys is not None and ys.ndim == 1
+    if squeeze:
+        ys = ys[None, :]
+    nch, ld = (None, None) if ys is None else (int(ys.shape[0]), int(ys.shape[1]))
+    code = welch_blocks_check("welch_blocks", nsig, nfft, hop, nframes, navg, step, detrend, nch, ld)
+    scale = float(scale)
+    if not np.isfinite(scale):
+        raise ValueError("welch_blocks: scale must be finite")
+    nblocks, nb = (nframes - navg) // step + 1, nfft if cplx else nfft // 2 + 1
+    if dev:
+        _bind_stream(xs)
+
+        def new(shape, dt):
+            return torch.empty(shape, dtype=getattr(torch, dt), device=xs.device)
+
+        def addr(a):
+            return None if a is None else ptr(a.data_ptr())
+        dcode = _tcode(xs)
+    else:
+        def new(shape, dt):
+            return np.empty(shape, dtype=getattr(np, dt))
+        addr = ptr
+        dcode = _ffi.dtype_code(xs.dtype)
+        _ffi.init()
+    pxx = new((nblocks, nb), "float32")
+    pyy = None if ys is None else new((nch, nblocks, nb), "float32")
+    pxy = None if ys is None else new((nch, nblocks, nb), "complex64")
+    check(lib().sp_welch_blocks(addr(xs), addr(ys), dcode, nsig, nch or 0, ld or 0, ptr(w), nfft, hop, nframes, navg, step, code, scale,
+                                1 if doubled else 0, addr(pxx), addr(pyy), addr(pxy), 1 if dev else 0))
+    if squeeze:
+        pyy, pxy = pyy[0], pxy[0]
+    return pxx, pyy, pxy
+
+
+def welch_blocks_plan(nfft, hop, nframes, navg, step=None, nch=1, cplx=False):
+    """sp_welch_blocks_plan as a dict (host only; nch = 0: no y): nblocks, nb, q (frames of a run), runs, transforms, scratch (bytes of
+    run sums), workgroups, lds_bytes."""
+    nfft, hop, nframes, navg, nch = int(nfft), int(hop), int(nframes), int(navg), int(nch)
+    step = navg if step is None else int(step)
+    welch_blocks_check("welch_blocks_plan", (nframes - 1) * hop + nfft, nfft, hop, nframes, navg, step, False, nch if nch else None)
+    out = np.zeros(8, dtype=np.int64)
+    if lib().sp_welch_blocks_plan(1 if cplx else 0, nfft, hop, nframes, navg, step, nch, ptr(out)) != 0:
+        raise WelchBlocksRefused("welch_blocks_plan: the shape is refused")
+    return dict(zip(("nblocks", "nb", "q", "runs", "transforms", "scratch", "workgroups", "lds_bytes"), (int(v) for v in out)))
+
+
 EIGH_MAX_N = 64
 
 
