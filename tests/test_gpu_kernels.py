@@ -9,6 +9,7 @@ from conftest import load_golden
 pytestmark = pytest.mark.gpu
 
 from oracle import cpu_ref as O
+from dynrange_ref import coloured_record_256 as _coloured_record, csd_excess, csd_matrix32
 
 
 @pytest.fixture(scope="module")
@@ -423,40 +424,23 @@ def _csd_per_bin_excess(G, ref, rtol=2e-4, atol_rel=1e-6):
     return float(np.max(np.abs(G - ref) / allow))
 
 
-def _coloured_record(nch, nsig, seed, line_db=None, weak_pair=(3, 7), weak_gamma2=0.01):
-    """real multi-channel record for the cfg5 parity tests: every channel an independent AR(1) ("red", ~45 dB between the
-    spectrum's ends) floor; one pair shares a weak common component (mean-squared coherence weak_gamma2); optionally a line
-    `line_db` dB above the floor in every channel (a different amplitude and phase per channel), a fraction of a bin off
-    centre so that it leaks"""
-    from scipy.signal import lfilter
-    rng = np.random.default_rng(seed)
-    x = np.empty((nch, nsig))
-    for c in range(nch):
-        x[c] = lfilter([1.0], [1.0, -0.97], rng.standard_normal(nsig))
-    a2 = np.sqrt(weak_gamma2) / (1.0 - np.sqrt(weak_gamma2))                 # gamma^2 = (a2 / (1 + a2))^2
-    common = lfilter([1.0], [1.0, -0.97], rng.standard_normal(nsig)) * np.sqrt(a2)
-    for c in weak_pair:
-        x[c] += common
-    if line_db is not None:
-        k = np.arange(nsig)
-        # floor PSD of the AR(1) process at f = 0.237: 1 / |1 - 0.97 e^{-i w}|^2; a sinusoid of amplitude A in a Hann-windowed
-        # periodogram stands A^2 S1^2 / (4 S2) over a floor of that height
-        w = 2 * np.pi * 0.237
-        floor = 1.0 / abs(1.0 - 0.97 * np.exp(-1j * w)) ** 2
-        for c in range(nch):
-            amp = np.sqrt(floor * 10.0 ** (line_db / 10.0) * 4.0 * 1.5 / 256.0) * (1.0 + 0.1 * c)   # (nfft 256: S1^2/S2 = N/1.5)
-            x[c] += amp * np.cos(w * k + 0.4 * c)
-        x += 0.3
-    return x.astype(np.float32)
-
-
 @pytest.mark.parametrize("line_db", [None, 80.0])
 @pytest.mark.parametrize("nch", [16, 64])
 def test_csd_matrix_per_bin_parity_dynamic_range(E, nch, line_db):
-    """cfg5 parity per bin and pair: coloured floor, a weakly coherent pair (gamma^2 ~ 0.01), with and
-    without a line 80 dB above the floor, 2200 frames = 1100 frame pairs so that the TWO-piece bf16 contraction
-    (k_csdm_bf16<4>, operands rounded to 16 significant bits) is the one that runs; against oracle.csd_matrix (float64,
-    generalises fft_analysis.py:387-393).  Also forced three-piece and float32-MFMA forms."""
+    """cfg5 parity per bin and pair at nfft 256 (k_stft_rp spectra, no mirror fold; the shipped nfft-4096 path
+    is held the same way in test_gpu_dynamic_range.py): coloured floor, a weakly coherent pair (gamma^2 ~ 0.01), with and without
+    a line 80 dB above the floor, 2200 frames = 1100 frame pairs so that the TWO-piece bf16 contraction (k_csdm_bf16<4>,
+    operands rounded to 16 significant bits) is the one that runs; against oracle.csd_matrix (float64, generalises
+    fft_analysis.py:387-393).  Also forced three-piece and float32-MFMA forms.  Asserted: every bin and pair within
+    2e-4 sqrt(G_ii G_jj) + 1e-6 max_k sqrt(G_ii G_jj) (_csd_per_bin_excess: on the 80 dB record the second term is 100 x the
+    floor, so alone it says little about the quiet bins) and, on the 80 dB record, within 2e-4 sqrt(G_ii G_jj) with no absolute
+    term (dynrange_ref.csd_excess).  The line's amplitude grows as 1 + 0.1 c with the channel: at 16 channels the record spans
+    82 dB and float32 arithmetic itself (dynrange_ref.csd_matrix32, window, mean and transform in float32) loses 0.82 of that
+    bound, at 64 channels the last channels span 97 - 100 dB and float32 loses 2.7 bounds (5.4e-4 of the quietest bins' level), so
+    no float32 kernel can hold 2e-4 there: where the restatement misses the bound, the kernels get 4 x the restatement's loss
+    (measured on an MI355X: 0.84 at 16 channels, 4.03 at 64, the same to three digits in all three contraction forms), and the
+    first 16 channels of either record, whose lines are at most 2.5 x channel 0's (the restatement loses 0.77 .. 0.82 of the bound
+    there), are held to 2e-4 all the same."""
     import os
     nfft, hop, M = 256, 128, 2200
     nsig = (M - 1) * hop + nfft
@@ -469,7 +453,7 @@ def test_csd_matrix_per_bin_parity_dynamic_range(E, nch, line_db):
     g2 = np.abs(ref[:, 3, 7]) ** 2 / (d[:, 3] * d[:, 7])
     if line_db is None:
         assert 0.003 < np.median(g2) < 0.03                                  # the weak pair is weak (and not lost)
-    worst = {}
+    worst, strict, first16 = {}, {}, {}
     for tag, env in (("two_piece", {}), ("three_piece", {"SP_CSDM_SPLIT3": "1"}), ("fp32_mfma", {"SP_CSDM_FP32": "1"})):
         os.environ.update(env)
         try:
@@ -478,7 +462,18 @@ def test_csd_matrix_per_bin_parity_dynamic_range(E, nch, line_db):
             for k in env:
                 del os.environ[k]
         worst[tag] = _csd_per_bin_excess(G, ref)
+        if line_db is not None:
+            strict[tag], at = csd_excess(G, ref)
+            first16[tag] = csd_excess(G[:, :16, :16], ref[:, :16, :16])[0]
+            print("csd_matrix nfft 256, %d channels, %s: per-bin excess %.3f at (bin, i, j) = %s, %.3f among the first 16 channels"
+                  % (nch, tag, strict[tag], at, first16[tag]))
     assert max(worst.values()) <= 1.0, worst
+    if line_db is not None:
+        loss32 = csd_excess(csd_matrix32(x, win, hop, M), ref)[0]                    # (scale 1, like ref)
+        bound = 1.0 if loss32 <= 1.0 else 4.0 * loss32
+        print("csd_matrix nfft 256, %d channels: the float32 restatement loses %.3f of the bound, the kernels get %.3f" % (nch, loss32, bound))
+        assert max(strict.values()) <= bound, (strict, loss32)
+        assert max(first16.values()) <= 1.0, first16                         # (lines <= 2.5 x channel 0's: within float32's reach)
 
 
 @pytest.mark.parametrize("nch,nfft,hop,nsig", [(5, 256, 128, 6000), (64, 1024, 512, 20000), (70, 512, 256, 9000),

@@ -430,3 +430,30 @@ def test_class_crosscorr_against_reference_fixture(onesided):
         close(np.asarray(c[k]).reshape(ref.shape), ref, rtol=1e-9, atol=1e-12 * float(np.abs(ref).max()))
     # the reference's own last line fails for 1-D signals (self.nch is never set): recorded, not reproduced
     assert str(g["err_stft_" + tag]) == "AttributeError" and str(g["err_avg_" + tag]) == "AttributeError"
+
+
+# ------------------------------------------------------------------ multi-channel CSD matrix (cfg5)
+def test_csd_matrix_is_the_reference_pwelch_over_all_pairs():
+    """oracle.csd_matrix against the reference's own fft_pwelch looped over all ordered pairs of 4 channels
+    (tests/golden/make_golden_csdm.py; nfft 256, Hann, 50 % overlap, mean detrend, no reflection).  Conjugation: the function
+    path returns Pxy = Y conj(X) (fft_analysis.py:393), so fft_pwelch(x = channel i, y = channel j) is X_j conj(X_i), which in
+    the oracle's convention G[k, i, j] = X_i conj(X_j) is G[k, j, i] = conj(G[k, i, j]); the diagonal is Pxx."""
+    g = load_golden("csd_matrix_4ch")
+    x = g["x"]
+    i0, i1 = [int(v) for v in g["ibnds"]]
+    nfft, nov, M, Fs = int(g["nwins"][0]), int(g["noverlap"][0]), int(g["Navr"][0]), float(g["Fs"][0])
+    assert (i0, i1) == (0, x.shape[0] - 1) and nfft == 256                   # one sample short of the record: not reflected
+    win = O.windows("Hanning", nwins=nfft)
+    assert abs(np.sum(win ** 2) - float(g["S2"][0])) < 1e-12
+    G = O.csd_matrix(x[i0:i1].T, win, nfft, nfft - nov, M, Fs)
+    nch = x.shape[1]
+    assert G.shape == (nfft // 2 + 1, nch, nch)
+    P = np.fft.ifftshift(g["Pxy"], axes=-1)                                  # [i, j, nfft], natural bin order
+    peak = np.abs(P).max()
+    for i in range(nch):
+        for j in range(nch):
+            assert np.max(np.abs(G[:, j, i] - P[i, j, : nfft // 2 + 1])) <= 1e-10 * peak, (i, j)
+            # real channels: the negative frequencies are the mirror image
+            assert np.max(np.abs(np.conj(G[1:nfft // 2, j, i])[::-1] - P[i, j, nfft // 2 + 1:])) <= 1e-10 * peak, (i, j)
+    assert np.max(np.abs(G[:, 0, 1])) > 0.01 * peak                          # (the cross terms are not small: the check has teeth)
+    assert np.max(np.abs(G[:, 0, 1].imag)) > 0.01 * peak                     # (and complex: a lost conjugation would show)
