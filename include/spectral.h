@@ -481,6 +481,42 @@ int sp_welch_blocks(const void *x, const void *y, int dtype, int64_t nsig, int n
                     int mem);
 int sp_welch_blocks_plan(int cplx, int nfft, int hop, int64_t nframes, int navg, int step, int nch, int64_t out[8]);
 
+/* ---- Continuous wavelet transform by overlap-save (Torrence & Compo 1998, analytic wavelets): for every row of a batch and every scale
+ *      s' (in samples)
+ *        W[s][n] = sum_m g_s[m] x[n - m]  over the zero-extended row (a linear convolution, no wrap-around),  g_s = IDFT(H_s),
+ *        H_s[k]  = sqrt(2 pi s') psi0^(s' w_k),  w_k = 2 pi k / L for 0 < k <= L/2,  0 at k = 0 and k > L/2
+ *        family SP_CWT_MORLET (p0 = w0 > 0):   psi0^(u) = pi^(-1/4) exp(-(u - w0)^2 / 2)
+ *        family SP_CWT_PAUL   (p0 = m >= 1):   psi0^(u) = 2^m / sqrt(m Gamma(2m)) u^m exp(-u);   p1 is reserved and must be 0.
+ *      Frames of L samples, L a power of two in 256 .. 8192; frame g covers the samples [g hop - M, g hop - M + L), hop = L - 2 M, and
+ *      yields the samples g hop .. g hop + hop - 1: the caller chooses the margin M so that |g_s| beyond +-M is negligible for every scale
+ *      of the call.  One forward transform per frame (and scale chunk), one filtered inverse transform per scale, the filter evaluated
+ *      on the fly.  x: float32 or complex64 rows of nsig samples, row stride x_ld >= nsig (float32 rows run as x + 0i); scales: HOST
+ *      float64 [nscales].  Outputs, any combination, NULL skips one (at least one is required):
+ *        W        complex64 [batch][nscales][nsig]
+ *        gws      float64   [batch][nscales]   sum_n |W[s][n]|^2: float32 sums per frame, added in float64 in frame order
+ *        recon    complex64 [batch][nsig]      sum_s wrec[s] W[s][n]        (wrec: HOST float32 [nscales], required with recon)
+ *        bandpow  float32   [batch][nsig]      sum_s wband[s] |W[s][n]|^2   (wband: HOST float32 [nscales], required with bandpow)
+ *      recon and bandpow are accumulated in registers across the scale loop and written once: W is never formed.  No atomics, a fixed
+ *      order of additions: two calls agree bitwise, and W does not depend on how the scales are dealt to workgroups.
+ *      x and the outputs follow `mem`; a device-resident x needs only its natural alignment.
+ *      Refused (< 0, sp_last_error() names sp_cwt, the device is not touched, the outputs are untouched): L not a power of two in
+ *      256 .. 8192; M < 0, 2 M >= L or hop < L / 4; nscales < 1; a scale that is not positive or not finite; an unknown family or a
+ *      parameter outside its range; an unknown dtype; nsig < 1, batch < 0, batch > 65535, x_ld < nsig; no output; recon without wrec or
+ *      bandpow without wband, or weights that are not finite; x or scales NULL.  batch == 0 returns 0 and launches nothing.
+ *      sp_cwt_plan (host only, never touches the device; outputs: bit 0 W, 1 gws, 2 recon, 3 bandpow): out[5] = hop, frames per row,
+ *      scales per workgroup (the whole set with recon or bandpow; else as few as bring the grid to about four workgroups per CU),
+ *      workgroups launched, scratch bytes (the per-frame sums behind gws).  The CU count is the device's once the library is
+ *      initialised and 256 before.  < 0 for a shape sp_cwt refuses, or out NULL.
+ *      sp_icwt: out[b][n] = sum_s w[s] W[b][s][n], ascending s (w: HOST float32 [nscales]; W, out follow `mem`): the sum behind the
+ *      reconstruction (T&C eq. 11) from a materialised W.  Refused: nscales < 1, nsig < 1, batch < 0 or > 65535, NULL pointers,
+ *      weights that are not finite. */
+#define SP_CWT_MORLET 0
+#define SP_CWT_PAUL 1
+int sp_cwt(const void *x, int dtype, int64_t nsig, int64_t x_ld, int64_t batch, const double *scales, int nscales, int family, double p0,
+           double p1, int L, int M, const float *wrec, const float *wband, void *W, double *gws, void *recon, float *bandpow, int mem);
+int sp_cwt_plan(int64_t nsig, int nscales, int64_t batch, int L, int M, int outputs, int64_t out[5]);
+int sp_icwt(const void *W, int64_t nsig, int nscales, int64_t batch, const float *w, void *out, int mem);
+
 /* ---- Batched Hermitian eigensolver (build-defined; the piece the reference's PCA.py takes from numpy.linalg.eigh): the
  *      eigendecomposition of `batch` matrices of order n, 1 <= n <= 64, e.g. the cross-spectral-density matrix of sp_csd_matrix at
  *      every bin (spectral POD).  a[batch][n][n] complex128 as (re, im) doubles, row-major.  Only the LOWER triangle (row >= column)

@@ -48,3 +48,5 @@ from .resample import upfirdn, resample_poly, resample_rate, resample_plan   # n
 from . import running as _running_mod                          # noqa: F401
 from .running import (running_psd, running_csd, running_coherence, running_spectra, running_plan,   # noqa: F401
                       coherence_level)
+from . import wavelet as _wavelet_mod                          # noqa: F401
+from .wavelet import Morlet, Paul, cwt_scales, cwt, icwt, cwt_power, cwt_filter, cwt_plan   # noqa: F401

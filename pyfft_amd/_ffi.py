@@ -18,6 +18,7 @@ DETREND_CONST, DETREND_MEAN, DETREND_LINEAR, DETREND_SEGMEAN, DETREND_SEGLINEAR 
 XC_RAW, XC_COEFF = 0, 1
 DETREND_NONE = 0
 SKF_MEAN, SKF_CROSS = 0, 1
+CWT_MORLET, CWT_PAUL = 0, 1
 
 _lib = None
 
@@ -78,6 +79,9 @@ SIGNATURES = {
     "sp_skf_plan": (_i, [_i, _i, _i, _i, _vp]),
     "sp_welch_blocks": (_i, [_vp, _vp, _i, _i64, _i, _i64, _vp, _i, _i, _i64, _i, _i, _i, _d, _i, _vp, _vp, _vp, _i]),
     "sp_welch_blocks_plan": (_i, [_i, _i, _i, _i64, _i, _i, _i, _vp]),
+    "sp_cwt": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _i, _i, _d, _d, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "sp_cwt_plan": (_i, [_i64, _i, _i64, _i, _i, _i, _vp]),
+    "sp_icwt": (_i, [_vp, _i64, _i, _i64, _vp, _vp, _i]),
     "sp_eigh": (_i, [_vp, _i, _i64, _i, _i, _vp, _vp, _vp, _i]),
     "sp_eigh_plan": (_i, [_i, _i, _i64, C.POINTER(_i64)]),
     "sp_fftfilt": (_i, [_vp, _i, _vp, _i64, _i, _vp, _i]),

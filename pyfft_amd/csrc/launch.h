@@ -1,5 +1,6 @@
 // launch.h -- host-side launchers, one translation unit per kernel family so they compile in parallel.
 #pragma once
+#include <limits.h>
 #include <stdlib.h>
 #include "kernels.h"
 #include <hip/hip_runtime.h>
@@ -23,6 +24,7 @@ namespace sp {
 //   SP_XCF_FPG (int: the short-time correlation's frames per run)
 //   SP_SKF_FPG, SP_SKF_CELLS (int: the wavenumber-frequency histogram's frames per run; a cap on the cells nk x bins of a tile)
 //   SP_EIGH_GRID (int: the eigensolver's workgroups, so that a small batch walks the batch loop)
+//   SP_CWT_CHUNK (int: the wavelet transform's scales per workgroup, where no output needs the whole scale set in one)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
     return v && v[0] && v[0] != '0';
@@ -643,6 +645,58 @@ inline EighPlan eigh_plan_of(int n, bool vec, int64_t batch, int ncu, int grid_c
 }
 int launch_eigh(LaunchCtx c, const double *a, int n, int64_t batch, int nvec, int max_sweeps, double *w, double *v, int32_t *sweeps,
                 const EighPlan &pl);
+
+// continuous wavelet transform by overlap-save (k_cwt.hip): frame g = the L samples from g hop - M on (zero outside the row), hop = L - 2 M,
+// every scale's filter H_s[k] = exp(c_s + p ln u - a d^2 - b d), u = k step_s, d = u - u0, on the bins 0 < k <= L / 2; sc[s] = (step_s, c_s)
+// is a device table, c_s includes the 1 / L of the inverse transform.  Any of the outputs may be null: W [rows][S][nsig], gpart
+// [rows][S][nframes] (summed by launch_cwt_gws_finish into float64 gws[rows][S]), recon [rows][nsig] = sum_s wr[s] W, bandpow
+// [rows][nsig] = sum_s wb[s] |W|^2 (wr, wb: device tables [S]; with either the chunk must be the whole scale set).
+#define SP_CWT_MIN_L 256
+#define SP_CWT_MAX_L 8192
+struct CwtArgs {
+    const void *x;
+    int cplx;
+    int64_t nsig, x_ld, nframes;
+    const float *sc;
+    float p, a, b, u0;
+    int S, chunk, M, hop;
+    const float *wr, *wb;
+    cf *W;
+    float *gpart;
+    cf *recon;
+    float *bandpow;
+};
+struct CwtPlan {
+    int hop, chunk, nchunks;
+    int64_t frames, blocks_x, grid;
+    size_t scratch_bytes;
+};
+// whole: an output needs every scale of a frame in one workgroup (recon, bandpow).  Otherwise the scales are cut into as many chunks as
+// bring the grid to about four workgroups per CU (every chunk repeats the forward transform); chunk_force > 0 sets the chunk (test hook)
+inline CwtPlan cwt_plan_of(int L, int M, int64_t nsig, int S, int64_t rows, bool whole, bool gws, int ncu, int chunk_force) {
+    CwtPlan p;
+    p.hop = L - 2 * M;
+    p.frames = (nsig + p.hop - 1) / p.hop;
+    const int fpw = fpw_of(L);
+    p.blocks_x = (p.frames + fpw - 1) / fpw;
+    int64_t nch = 1;
+    if (!whole) {
+        const int64_t wg = p.blocks_x * (rows > 0 ? rows : 1);
+        nch = ((int64_t)4 * ncu + wg - 1) / wg;
+        if (nch > S) nch = S;
+        if (nch < 1) nch = 1;
+    }
+    p.chunk = (int)((S + nch - 1) / nch);
+    if (!whole && chunk_force > 0) p.chunk = chunk_force < S ? chunk_force : S;
+    p.nchunks = (S + p.chunk - 1) / p.chunk;
+    p.grid = p.blocks_x * p.nchunks * rows;
+    p.scratch_bytes = gws ? sizeof(float) * (size_t)rows * (size_t)S * (size_t)p.frames : 0;
+    return p;
+}
+int launch_cwt(LaunchCtx c, const CwtArgs &a, int L, const cf *tw, const CwtPlan &pl, int64_t rows);
+int launch_cwt_gws_finish(LaunchCtx c, const float *gpart, int64_t rows_x_scales, int64_t nframes, double *gws);
+// out[row][n] = sum_s w[s] W[row][s][n] (w: device table)
+int launch_icwt(LaunchCtx c, const cf *W, const float *w, int S, int64_t N, int64_t rows, cf *out);
 
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;

@@ -3459,6 +3459,166 @@ int sp_welch_blocks(const void *x, const void *y, int dtype, int64_t nsig, int n
     return 0;
 }
 
+// ---- continuous wavelet transform (k_cwt.hip) ------------------------------------------------------
+// the shape checks sp_cwt and its plan share; 0 or the message's tail
+static const char *cwt_shape(int64_t nsig, int nscales, int64_t batch, int L, int M) {
+    if (L < SP_CWT_MIN_L || L > SP_CWT_MAX_L || !is_pow2(L)) return "L must be a power of two from 256 to 8192";
+    if (M < 0 || 2 * (int64_t)M >= L) return "M must lie in 0 .. L / 2 - 1";
+    if (L - 2 * M < L / 4) return "M leaves hop = L - 2 M below L / 4";
+    if (nscales < 1) return "nscales must be at least 1";
+    if (nsig < 1) return "nsig must be at least 1";
+    if (batch < 0 || batch > 65535) return "batch must lie in 0 .. 65535";
+    return nullptr;
+}
+
+int sp_cwt_plan(int64_t nsig, int nscales, int64_t batch, int L, int M, int outputs, int64_t out[5]) {
+    if (cwt_shape(nsig, nscales, batch, L, M) || !out || (outputs & 15) == 0 || (outputs & ~15) != 0) return -1;
+    const CwtPlan p = cwt_plan_of(L, M, nsig, nscales, batch, (outputs & 12) != 0, (outputs & 2) != 0, g.ncu, env_int("SP_CWT_CHUNK", 0));
+    out[0] = p.hop;
+    out[1] = p.frames;
+    out[2] = p.chunk;
+    out[3] = p.grid;
+    out[4] = (int64_t)p.scratch_bytes;
+    return 0;
+}
+
+int sp_cwt(const void *x, int dtype, int64_t nsig, int64_t x_ld, int64_t batch, const double *scales, int nscales, int family, double p0,
+           double p1, int L, int M, const float *wrec, const float *wband, void *W, double *gws, void *recon, float *bandpow, int mem) {
+    // every refusal comes before the device is touched
+    if (const char *why = cwt_shape(nsig, nscales, batch, L, M))
+        return fail("sp_cwt: %s (L %d, M %d, nscales %d, nsig %lld, batch %lld)", why, L, M, nscales, (long long)nsig, (long long)batch);
+    if (dtype != SP_DTYPE_F32 && dtype != SP_DTYPE_C64) return fail("sp_cwt: dtype must be float32 or complex64, got %d", dtype);
+    if (x_ld < nsig) return fail("sp_cwt: x_ld = %lld is below nsig = %lld", (long long)x_ld, (long long)nsig);
+    if (family != SP_CWT_MORLET && family != SP_CWT_PAUL) return fail("sp_cwt: family %d is neither SP_CWT_MORLET nor SP_CWT_PAUL", family);
+    if (!isfinite(p0) || !(p0 > 0.0) || p0 > 64.0 || (family == SP_CWT_PAUL && p0 < 1.0) || p1 != 0.0)
+        return fail("sp_cwt: parameter p0 = %g must lie in (0, 64] (Morlet's w0) or [1, 64] (Paul's m), and p1 = %g must be 0", p0, p1);
+    if (!scales) return fail("sp_cwt: scales is required");
+    for (int s = 0; s < nscales; ++s)
+        if (!isfinite(scales[s]) || !(scales[s] > 0.0) || scales[s] > 1e9)
+            return fail("sp_cwt: scales[%d] = %g must be positive and finite", s, scales[s]);
+    if (!W && !gws && !recon && !bandpow) return fail("sp_cwt: an output is required: W, gws, recon or bandpow");
+    if (recon && !wrec) return fail("sp_cwt: wrec is required with recon");
+    if (bandpow && !wband) return fail("sp_cwt: wband is required with bandpow");
+    for (int s = 0; s < nscales; ++s)
+        if ((recon && !isfinite(wrec[s])) || (bandpow && !isfinite(wband[s]))) return fail("sp_cwt: weights must be finite (scale %d)", s);
+    if (batch == 0) return 0;
+    if (!x) return fail("sp_cwt: x is required");
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const bool cplx = dtype == SP_DTYPE_C64, whole = recon || bandpow;
+    const CwtPlan pl = cwt_plan_of(L, M, nsig, nscales, batch, whole, gws != nullptr, g.ncu, env_int("SP_CWT_CHUNK", 0));
+    if (pl.blocks_x > INT_MAX) return fail("sp_cwt: nsig = %lld is too many frames for one launch", (long long)nsig);
+    const size_t esz = cplx ? 8 : 4, in_elems = (size_t)((batch - 1) * x_ld + nsig), S = (size_t)nscales, rows = (size_t)batch;
+    // the scales' filter constants: step = 2 pi s' / L, c = ln(norm sqrt(2 pi s') / L)
+    const double lognorm = family == SP_CWT_MORLET ? -0.25 * log(M_PI) : p0 * log(2.0) - 0.5 * (log(p0) + lgamma(2.0 * p0));
+    std::vector<float> sc(2 * S);
+    for (size_t s = 0; s < S; ++s) {
+        sc[2 * s] = (float)(2.0 * M_PI * scales[s] / (double)L);
+        sc[2 * s + 1] = (float)(lognorm + 0.5 * log(2.0 * M_PI * scales[s]) - log((double)L));
+    }
+    void *sc_d = nullptr, *wr_d = nullptr, *wb_d = nullptr;
+    if (get_table(15, sc.data(), sizeof(float) * sc.size(), &sc_d, nullptr)) return -1;
+    if (recon && get_table(16, wrec, sizeof(float) * S, &wr_d, nullptr)) return -1;
+    if (bandpow && get_table(17, wband, sizeof(float) * S, &wb_d, nullptr)) return -1;
+    const cf *tw;
+    if (get_twiddles(L, &tw)) return -1;
+    // outputs staged for host callers: [W | gws | recon | bandpow], each piece 256-byte aligned
+    const size_t wbytes = W ? sizeof(cf) * rows * S * (size_t)nsig : 0, gbytes = gws ? sizeof(double) * rows * S : 0;
+    const size_t rbytes = recon ? sizeof(cf) * rows * (size_t)nsig : 0, bbytes = bandpow ? sizeof(float) * rows * (size_t)nsig : 0;
+    const size_t goff = (wbytes + 255) & ~(size_t)255, roff = goff + ((gbytes + 255) & ~(size_t)255);
+    const size_t boff = roff + ((rbytes + 255) & ~(size_t)255);
+    const void *xd = x;
+    cf *W_d = (cf *)W, *rec_d = (cf *)recon;
+    double *gws_d = gws;
+    float *bp_d = bandpow;
+    if (!mem) {
+        if (g.in0.ensure(esz * in_elems) || g.out0.ensure(boff + bbytes)) return -1;
+        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * in_elems, hipMemcpyHostToDevice, g.stream));
+        xd = g.in0.p;
+        W_d = W ? (cf *)g.out0.p : nullptr;
+        gws_d = gws ? (double *)((char *)g.out0.p + goff) : nullptr;
+        rec_d = recon ? (cf *)((char *)g.out0.p + roff) : nullptr;
+        bp_d = bandpow ? (float *)((char *)g.out0.p + boff) : nullptr;
+    }
+    float *gpart = nullptr;
+    if (gws) {
+        if (g.work.ensure(pl.scratch_bytes)) return -1;
+        gpart = (float *)g.work.p;
+    }
+    CwtArgs a;
+    a.x = xd;
+    a.cplx = cplx ? 1 : 0;
+    a.nsig = nsig;
+    a.x_ld = x_ld;
+    a.nframes = pl.frames;
+    a.sc = (const float *)sc_d;
+    a.p = family == SP_CWT_PAUL ? (float)p0 : 0.f;
+    a.a = family == SP_CWT_MORLET ? 0.5f : 0.f;
+    a.b = family == SP_CWT_PAUL ? 1.f : 0.f;
+    a.u0 = family == SP_CWT_MORLET ? (float)p0 : 0.f;
+    a.S = nscales;
+    a.chunk = pl.chunk;
+    a.M = M;
+    a.hop = pl.hop;
+    a.wr = (const float *)wr_d;
+    a.wb = (const float *)wb_d;
+    a.W = W_d;
+    a.gpart = gpart;
+    a.recon = rec_d;
+    a.bandpow = bp_d;
+    {
+        ProfScope ps;
+        if (launch_cwt(lc(), a, L, tw, pl, batch) != 0)
+            return fail("sp_cwt: the launch was refused (L %d, M %d, nscales %d, %lld rows)", L, M, nscales, (long long)batch);
+        HIPCHK(hipGetLastError());
+        g.last_kernel = "k_cwt";
+    }
+    if (gws) LAUNCHCHK(launch_cwt_gws_finish(lc(), gpart, (int64_t)(rows * S), pl.frames, gws_d));
+    if (!mem) {
+        if (W) HIPCHK(hipMemcpyAsync(W, W_d, wbytes, hipMemcpyDeviceToHost, g.stream));
+        if (gws) HIPCHK(hipMemcpyAsync(gws, gws_d, gbytes, hipMemcpyDeviceToHost, g.stream));
+        if (recon) HIPCHK(hipMemcpyAsync(recon, rec_d, rbytes, hipMemcpyDeviceToHost, g.stream));
+        if (bandpow) HIPCHK(hipMemcpyAsync(bandpow, bp_d, bbytes, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
+int sp_icwt(const void *W, int64_t nsig, int nscales, int64_t batch, const float *w, void *out, int mem) {
+    // every refusal comes before the device is touched
+    if (nscales < 1) return fail("sp_icwt: nscales must be at least 1");
+    if (nsig < 1) return fail("sp_icwt: nsig must be at least 1");
+    if (batch < 0 || batch > 65535) return fail("sp_icwt: batch must lie in 0 .. 65535");
+    if (!w) return fail("sp_icwt: w is required");
+    for (int s = 0; s < nscales; ++s)
+        if (!isfinite(w[s])) return fail("sp_icwt: weights must be finite (scale %d)", s);
+    if (batch == 0) return 0;
+    if (!W || !out) return fail("sp_icwt: W and out are required");
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const size_t ibytes = sizeof(cf) * (size_t)batch * (size_t)nscales * (size_t)nsig, obytes = sizeof(cf) * (size_t)batch * (size_t)nsig;
+    const void *Wd = W;
+    void *od = out;
+    if (!mem) {
+        if (g.in0.ensure(ibytes) || g.out0.ensure(obytes)) return -1;
+        HIPCHK(hipMemcpyAsync(g.in0.p, W, ibytes, hipMemcpyHostToDevice, g.stream));
+        Wd = g.in0.p;
+        od = g.out0.p;
+    }
+    void *w_d = nullptr;
+    if (get_table(16, w, sizeof(float) * (size_t)nscales, &w_d, nullptr)) return -1;
+    {
+        ProfScope ps;
+        LAUNCHCHK(launch_icwt(lc(), (const cf *)Wd, (const float *)w_d, nscales, nsig, batch, (cf *)od));
+        g.last_kernel = "k_icwt";
+    }
+    if (!mem) {
+        HIPCHK(hipMemcpyAsync(out, od, obytes, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
 // ---- batched Hermitian eigensolver (k_eigh.hip) --------------------------------------------------
 int sp_eigh_plan(int n, int nvec, int64_t batch, int64_t out[4]) {
     if (n < 1 || n > SP_EIGH_MAX_N || nvec < 0 || nvec > n || batch < 0 || !out) return -1;

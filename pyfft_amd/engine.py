@@ -1169,6 +1169,143 @@ def welch_blocks_plan(nfft, hop, nframes, navg, step=None, nch=1, cplx=False):
     return dict(zip(("nblocks", "nb", "q", "runs", "transforms", "scratch", "workgroups", "lds_bytes"), (int(v) for v in out)))
 
 
+CWT_MIN_L, CWT_MAX_L, CWT_MAX_ROWS = 256, 8192, 65535
+CWT_FAMILIES = {"morlet": _ffi.CWT_MORLET, "paul": _ffi.CWT_PAUL}
+
+
+class CwtRefused(ValueError, NotImplementedError):
+    """A shape the fused wavelet transform does not take: outside the limits, and a path that is not built (frames that are no power
+    of two or longer than one workgroup transform, margins that leave less than a quarter of a frame, wavelets that are not analytic)."""
+
+
+def cwt_check(who, nsig, scales, family, param, L, M, rows=1):
+    """Every refusal of sp_cwt's shape, before the library is touched -> (scales float64, family code, param)."""
+    L, M = int(L), int(M)
+    if L < CWT_MIN_L or L > CWT_MAX_L or L & (L - 1):
+        raise CwtRefused("%s: L = %d must be a power of two from %d to %d" % (who, L, CWT_MIN_L, CWT_MAX_L))
+    if M < 0 or 2 * M >= L:
+        raise CwtRefused("%s: M = %d must lie in 0 .. L / 2 - 1 = %d" % (who, M, L // 2 - 1))
+    if L - 2 * M < L // 4:
+        raise CwtRefused("%s: M = %d leaves hop = L - 2 M = %d below L / 4 = %d" % (who, M, L - 2 * M, L // 4))
+    sc = np.ascontiguousarray(np.asarray(scales, dtype=np.float64))
+    if sc.ndim != 1 or sc.size < 1:
+        raise CwtRefused("%s: scales must be one-dimensional and hold at least one scale" % who)
+    if not np.all(np.isfinite(sc)) or not np.all(sc > 0) or np.any(sc > 1e9):
+        raise CwtRefused("%s: every scale must be positive and finite" % who)
+    if not isinstance(family, str) or family.lower() not in CWT_FAMILIES:
+        raise CwtRefused("%s: family %r is not built: 'morlet' or 'paul' (analytic wavelets)" % (who, family))
+    param = float(param)
+    code = CWT_FAMILIES[family.lower()]
+    if not np.isfinite(param) or not (0.0 < param <= 64.0) or (code == _ffi.CWT_PAUL and param < 1.0):
+        raise CwtRefused("%s: the %s parameter %r is outside (0, 64] (Morlet's w0) or [1, 64] (Paul's m)" % (who, family, param))
+    if nsig < 1:
+        raise CwtRefused("%s: the record must hold at least one sample" % who)
+    if rows < 1 or rows > CWT_MAX_ROWS:
+        raise CwtRefused("%s: %d rows are outside 1 .. %d" % (who, rows, CWT_MAX_ROWS))
+    return sc, code, param
+
+
+def _cwt_weights(who, w, S, name):
+    if w is None:
+        return None
+    w = np.ascontiguousarray(np.asarray(w), dtype=np.float32)
+    if w.shape != (S,) or not np.all(np.isfinite(w)):
+        raise CwtRefused("%s: %s must hold one finite weight per scale (%d)" % (who, name, S))
+    return w
+
+
+def cwt(x, scales, family, param, L, M, W=True, gws=False, recon=None, bandpow=None):
+    """Continuous wavelet transform along the last axis by overlap-save (sp_cwt): scales in samples, family 'morlet' (param = w0) or
+    'paul' (param = m), frames of L samples with margin M on either side (hop = L - 2 M).  Outputs, any combination, as a dict:
+    'W' complex64 [..., S, N] (W=True), 'gws' float64 [..., S] = sum_n |W|^2 (gws=True), 'recon' complex64 [..., N] = sum_s recon[s] W
+    and 'bandpow' float32 [..., N] = sum_s bandpow[s] |W|^2 (weights, one per scale; neither forms W).  float32 records run as x + 0i.
+    numpy in -> numpy out; device tensor in -> device tensors on x's stream (rows of a 2-D tensor may be strided)."""
+    dev = _is_torch(x)
+    if dev:
+        if x.dtype not in (torch.float32, torch.complex64):
+            raise TypeError("device path takes float32 or complex64 samples, got %s" % x.dtype)
+    else:
+        x = _ffi.as_samples(x)
+    if (x.dim() if dev else x.ndim) < 1:
+        raise CwtRefused("cwt: x must have at least one axis")
+    n = int(x.shape[-1])
+    rows = 1
+    for d in x.shape[:-1]:
+        rows *= int(d)
+    sc, code, param = cwt_check("cwt", n, scales, family, param, L, M, rows)
+    S = sc.size
+    wr, wb = _cwt_weights("cwt", recon, S, "recon"), _cwt_weights("cwt", bandpow, S, "bandpow")
+    if not W and not gws and wr is None and wb is None:
+        raise CwtRefused("cwt: an output is required: W, gws, recon or bandpow")
+    lead = tuple(x.shape[:-1])
+    shapes = {"W": (lead + (S, n), "complex64"), "gws": (lead + (S,), "float64"), "recon": (lead + (n,), "complex64"),
+              "bandpow": (lead + (n,), "float32")}
+    want = {"W": bool(W), "gws": bool(gws), "recon": wr is not None, "bandpow": wb is not None}
+    if dev:
+        _bind_stream(x)
+        if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= n:
+            xs, ld = x, int(x.stride(0))                      # a row-strided view goes through as it is
+        else:
+            xs, ld = x.contiguous(), n
+        out = {k: torch.empty(sh, dtype=getattr(torch, dt), device=x.device) for k, (sh, dt) in shapes.items() if want[k]}
+        addr = {k: ptr(v.data_ptr()) for k, v in out.items()}
+        xp, dcode = ptr(xs.data_ptr()), _tcode(xs)
+    else:
+        xs, ld = x, n
+        out = {k: np.empty(sh, dtype=getattr(np, dt)) for k, (sh, dt) in shapes.items() if want[k]}
+        addr = {k: ptr(v) for k, v in out.items()}
+        xp, dcode = ptr(xs), _ffi.dtype_code(xs.dtype)
+        _ffi.init()
+    check(lib().sp_cwt(xp, dcode, n, ld, rows, ptr(sc), S, code, param, 0.0, int(L), int(M), ptr(wr), ptr(wb), addr.get("W"),
+                       addr.get("gws"), addr.get("recon"), addr.get("bandpow"), 1 if dev else 0))
+    return out
+
+
+def cwt_plan(nsig, nscales, L, M, rows=1, W=True, gws=False, recon=False, bandpow=False):
+    """sp_cwt_plan as a dict (host only): hop, frames (per row), chunk (scales per workgroup), workgroups, scratch (bytes)."""
+    cwt_check("cwt_plan", int(nsig), np.ones(max(int(nscales), 0)), "morlet", 6.0, L, M, int(rows))
+    bits = (1 if W else 0) | (2 if gws else 0) | (4 if recon else 0) | (8 if bandpow else 0)
+    if not bits:
+        raise CwtRefused("cwt_plan: an output is required: W, gws, recon or bandpow")
+    out = np.zeros(5, dtype=np.int64)
+    if lib().sp_cwt_plan(int(nsig), int(nscales), int(rows), int(L), int(M), bits, ptr(out)) != 0:
+        raise CwtRefused("cwt_plan: the shape is refused")
+    return dict(zip(("hop", "frames", "chunk", "workgroups", "scratch"), (int(v) for v in out)))
+
+
+def icwt_sum(W, weights):
+    """out[..., n] = sum_s weights[s] W[..., s, n] (sp_icwt): the sum behind the wavelet reconstruction, from a materialised W (complex64
+    [..., S, N]).  numpy in -> numpy out; device tensor in -> device tensor on W's stream."""
+    dev = _is_torch(W)
+    if dev:
+        if W.dtype != torch.complex64:
+            raise TypeError("icwt_sum: W must be complex64, got %s" % W.dtype)
+    else:
+        W = np.ascontiguousarray(np.asarray(W), dtype=np.complex64)
+    if (W.dim() if dev else W.ndim) < 2 or W.shape[-1] < 1 or W.shape[-2] < 1:
+        raise CwtRefused("icwt_sum: W must be [..., S, N] with S, N >= 1")
+    S, n = int(W.shape[-2]), int(W.shape[-1])
+    w = _cwt_weights("icwt_sum", weights, S, "weights")
+    if w is None:
+        raise CwtRefused("icwt_sum: weights are required")
+    lead = tuple(W.shape[:-2])
+    rows = 1
+    for d in lead:
+        rows *= int(d)
+    if rows < 1 or rows > CWT_MAX_ROWS:
+        raise CwtRefused("icwt_sum: %d rows are outside 1 .. %d" % (rows, CWT_MAX_ROWS))
+    if dev:
+        _bind_stream(W)
+        Wc = W.contiguous()
+        out = torch.empty(lead + (n,), dtype=torch.complex64, device=W.device)
+        check(lib().sp_icwt(ptr(Wc.data_ptr()), n, S, rows, ptr(w), ptr(out.data_ptr()), 1))
+        return out
+    out = np.empty(lead + (n,), dtype=np.complex64)
+    _ffi.init()
+    check(lib().sp_icwt(ptr(W), n, S, rows, ptr(w), ptr(out), 0))
+    return out
+
+
 EIGH_MAX_N = 64
 
 
