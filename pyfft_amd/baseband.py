@@ -13,6 +13,7 @@ import math
 
 import numpy as np
 
+from .engine import _is_torch
 from .windows import get_window
 
 MAX_Q = 64                          # one launch decimates by at most this
@@ -22,10 +23,6 @@ MAX_WG_FFT = 8192                   # the longest one-workgroup transform (sp_ma
 
 class Unsupported(ValueError, NotImplementedError):
     """A decimation or a filter outside the limits of the kernel: a path that is not built."""
-
-
-def _is_torch(v):
-    return type(v).__module__.startswith("torch")
 
 
 def _factor(q):

@@ -13,6 +13,7 @@ import math
 import numpy as np
 
 from . import engine as _E
+from .engine import _is_torch
 from .windows import get_window
 
 MAX_L = 8192                        # one workgroup transform
@@ -32,10 +33,6 @@ def ccf(x1, x2, fs):
     tau = -lags / float(fs)
     co = _E.xcorr_normalised(x1, x2).astype(np.float64)
     return tau, co
-
-
-def _is_torch(v):
-    return type(v).__module__.startswith("torch")
 
 
 def _xc_len(who, nav, maxlag):

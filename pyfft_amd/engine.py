@@ -1,13 +1,17 @@
 """Array-level entry points over the C ABI (libspectral.so).
 
-Two calling modes, chosen by the type of the sample array:
-  * numpy arrays  -> `mem=0`: the library stages host buffers through its own device scratch and returns
+Two calling modes, chosen once per call from the type of the sample array by `_mode(x)`, or by `_enter(x)`, which binds the stream first:
+  * numpy arrays  -> `_HOST` (`mem=0`): the library stages host buffers through its own device scratch and returns
                      numpy results (synchronous).  This is what the drop-in modules use.
-  * torch CUDA tensors -> `mem=1`: device pointers are passed straight through, work is enqueued on
+  * torch CUDA tensors -> `_DEV` (`mem=1`): device pointers are passed straight through, work is enqueued on
                      torch's current stream, results are torch tensors on the same device (asynchronous).
                      PyTorch is only the allocator / stream owner here.
-There is no CPU implementation behind these functions.
+The mode object holds what the two differ in (casting the samples, allocating results, taking addresses, the prologue of the call and the
+trailing `mem`), so every entry point below assembles the argument list of its sp_* entry once; where the modes differ in substance
+the function says so with an `if md.dev:`.  There is no CPU implementation behind these functions.
 """
+import operator
+
 import numpy as np
 
 from . import _ffi
@@ -35,6 +39,13 @@ def _torch_samples(x):
     if x.dtype not in (torch.float32, torch.complex64):
         raise TypeError("device path takes float32 or complex64 samples, got %s" % x.dtype)
     return x.contiguous()
+
+
+def _torch_checked(x):
+    """_torch_samples without the copy: the strided-rows rule decides about that (the streamed step keeps the one above as it was)"""
+    if x.dtype not in (torch.float32, torch.complex64):
+        raise TypeError("device path takes float32 or complex64 samples, got %s" % x.dtype)
+    return x
 
 
 def _tcode(x):
@@ -72,6 +83,102 @@ def _detrend_args(detrend, mean_value):
     return _ffi.DETREND_MEAN, 0j
 
 
+def _ncode(x):
+    return _ffi.DTYPE_C64 if x.dtype == np.complex64 else _ffi.DTYPE_F32
+
+
+class _HostMode:
+    """numpy arrays in host memory, `mem=0`: what the two calling modes differ in and nothing else (see the module docstring).  dtype
+    names are strings ("float64"); `like` is an array of the call, which only the device mode looks at.  Every call pays for these, so
+    they are the functions themselves wherever the signatures allow it, and the instances hold no state."""
+    dev, mem = False, 0
+    ALIKE = "length and dtype"              # what a second signal must share with the first, for the refusals
+
+    checked = staticmethod(_ffi.as_samples)             # samples as float32 / complex64: contiguous here, as they came on the device
+    samples = staticmethod(_ffi.as_samples)             # ... and contiguous in both
+    addr = staticmethod(ptr)                            # the address of an array, or None
+    code = staticmethod(_ncode)                         # the dtype code of samples
+    count = staticmethod(operator.attrgetter("size"))   # the number of elements
+
+    def bind(self, x):
+        pass
+
+    def cast(self, x, dt):
+        return np.ascontiguousarray(x, dtype=dt)
+
+    def rows(self, x):
+        """checked samples -> (contiguous rows, their pitch)"""
+        return x, int(x.shape[-1])
+
+    def empty(self, shape, dt, like):
+        return np.empty(shape, dt)
+
+    def alike(self, a, b):
+        return a.dtype == b.dtype and a.size == b.size
+
+    def init(self):
+        _ffi.init()
+
+    def call(self, entry, *args):
+        """_ffi.init() immediately before the library call that needs the device, `mem` behind its arguments"""
+        _ffi.init()
+        check(entry(*args, 0))
+
+
+class _DeviceMode:
+    """torch tensors in device memory, `mem=1`, on torch's current stream: bind(), then as _HostMode"""
+    dev, mem = True, 1
+    ALIKE = "length, dtype and device"
+
+    checked = staticmethod(_torch_checked)
+    samples = staticmethod(_torch_samples)
+    code = staticmethod(_tcode)
+    count = staticmethod(operator.methodcaller("numel"))
+
+    def bind(self, x):
+        _bind_stream(x)
+
+    def addr(self, a):
+        return None if a is None else ptr(a.data_ptr())
+
+    def cast(self, x, dt):
+        return x.to(getattr(torch, dt)).contiguous()
+
+    def rows(self, x):
+        n = int(x.shape[-1])
+        if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= n and x.shape[0] >= 1:
+            return x, int(x.stride(0))                        # a row-strided view goes through as it is
+        return x.contiguous(), n
+
+    def empty(self, shape, dt, like):
+        return torch.empty(shape, dtype=getattr(torch, dt), device=like.device)
+
+    def alike(self, a, b):
+        return a.dtype == b.dtype and a.numel() == b.numel() and a.device == b.device
+
+    def init(self):
+        pass                                # bind() brought the library up on the tensor's device
+
+    def call(self, entry, *args):
+        check(entry(*args, 1))
+
+
+_HOST, _DEV = _HostMode(), _DeviceMode()
+
+
+def _mode(x):
+    """the calling mode of a call, from its sample array"""
+    return _DEV if _is_torch(x) else _HOST
+
+
+def _enter(x):
+    """_mode(x) with the stream bound first when x is a device tensor: most entries bind before they look at their arguments"""
+    if torch is not None and isinstance(x, torch.Tensor):
+        _bind_stream(x)
+        return _DEV
+    return _HOST
+
+
 def max_wg_fft():
     return int(lib().sp_max_wg_fft())
 
@@ -79,29 +186,24 @@ def max_wg_fft():
 # ------------------------------------------------------------------------------------------ A7
 def fft(x, n=None, axis=-1, inverse=False):
     """np.fft.fft / ifft semantics (forward unnormalised, inverse 1/n) on the GPU, complex64 math."""
-    if _is_torch(x):
-        _bind_stream(x)
+    md = _enter(x)
+    if md.dev:
         if axis not in (-1, x.dim() - 1) or (n is not None and n != x.shape[-1]):
             raise NotImplementedError("device-tensor fft: last axis, n == length")
-        xc = x.to(torch.complex64).contiguous()
-        out = torch.empty_like(xc)
-        nn = xc.shape[-1]
-        check(lib().sp_fft_c2c(ptr(xc.data_ptr()), ptr(out.data_ptr()), nn, xc.numel() // nn, 1 if inverse else -1, 1))
-        return out
-    a = np.asarray(x)
-    a = np.moveaxis(a, axis, -1)
-    if n is not None and n != a.shape[-1]:
-        if n < a.shape[-1]:
-            a = a[..., :n]
-        else:
-            pad = [(0, 0)] * (a.ndim - 1) + [(0, n - a.shape[-1])]
-            a = np.pad(a, pad)
-    a = np.ascontiguousarray(a, dtype=np.complex64)
-    out = np.empty_like(a)
+        a = x
+    else:                                   # any axis and any n: moved, cropped or padded on the host
+        a = np.moveaxis(np.asarray(x), axis, -1)
+        if n is not None and n != a.shape[-1]:
+            if n < a.shape[-1]:
+                a = a[..., :n]
+            else:
+                pad = [(0, 0)] * (a.ndim - 1) + [(0, n - a.shape[-1])]
+                a = np.pad(a, pad)
+    a = md.cast(a, "complex64")
+    out = md.empty(a.shape, "complex64", a)
     nn = a.shape[-1]
-    _ffi.init()
-    check(lib().sp_fft_c2c(ptr(a), ptr(out), nn, a.size // nn if nn else 0, 1 if inverse else -1, 0))
-    return np.moveaxis(out, -1, axis)
+    md.call(lib().sp_fft_c2c, md.addr(a), md.addr(out), nn, md.count(a) // nn if nn else 0, 1 if inverse else -1)
+    return out if md.dev else np.moveaxis(out, -1, axis)
 
 
 def ifft(x, n=None, axis=-1):
@@ -112,17 +214,10 @@ def ifft(x, n=None, axis=-1):
 def mean(x):
     """Mean of a float32/complex64 vector accumulated in double on the device (python float / complex)."""
     out = (_ffi.C.c_double * 2)()
-    if _is_torch(x):
-        _bind_stream(x)
-        xs = _torch_samples(x)
-        cplx = xs.is_complex()
-        check(lib().sp_mean(ptr(xs.data_ptr()), _tcode(xs), xs.numel(), out, 1))
-    else:
-        xs = _ffi.as_samples(x)
-        cplx = xs.dtype == np.complex64
-        _ffi.init()
-        check(lib().sp_mean(ptr(xs), _ffi.dtype_code(xs.dtype), xs.size, out, 0))
-    return complex(out[0], out[1]) if cplx else float(out[0])
+    md = _enter(x)
+    xs = md.samples(x)
+    md.call(lib().sp_mean, md.addr(xs), md.code(xs), md.count(xs), out)
+    return complex(out[0], out[1]) if md.code(xs) == _ffi.DTYPE_C64 else float(out[0])
 
 
 def profile_enable(on=True):
@@ -148,18 +243,11 @@ def welch_psd(x, win, hop, nframes, detrend=True, sided=SIDED_TWO, scale=1.0, me
     nfft = w.size
     nb = nbins(nfft, sided)
     want, mv = _detrend_args(detrend, mean_value)
-    if _is_torch(x):
-        _bind_stream(x)
-        xs = _torch_samples(x)
-        out = torch.empty(nb, dtype=torch.float64, device=xs.device)
-        check(lib().sp_welch_psd(ptr(xs.data_ptr()), _tcode(xs), xs.numel(), ptr(w), nfft, int(hop), int(nframes), want,
-                                 mv.real, mv.imag, sided, float(scale), ptr(out.data_ptr()), 1))
-        return out
-    xs = _ffi.as_samples(x)
-    out = np.empty(nb, dtype=np.float64)
-    _ffi.init()
-    check(lib().sp_welch_psd(ptr(xs), _ffi.dtype_code(xs.dtype), xs.size, ptr(w), nfft, int(hop), int(nframes), want,
-                             mv.real, mv.imag, sided, float(scale), ptr(out), 0))
+    md = _enter(x)
+    xs = md.samples(x)
+    out = md.empty(nb, "float64", xs)
+    md.call(lib().sp_welch_psd, md.addr(xs), md.code(xs), md.count(xs), ptr(w), nfft, int(hop), int(nframes), want, mv.real, mv.imag,
+            sided, float(scale), md.addr(out))
     return out
 
 
@@ -168,20 +256,11 @@ def welch_accum(x, win, hop, nframes, nmean=None):
     against a local mean estimate.  Returns sum(x[0:nmean]) as a (2,) float64 (torch tensor on the device for device
     input, numpy otherwise) for the cross-shard all-reduce."""
     w = _win32(win)
-    if _is_torch(x):
-        _bind_stream(x)
-        xs = _torch_samples(x)
-        nm = xs.numel() if nmean is None else int(nmean)
-        out = torch.empty(2, dtype=torch.float64, device=xs.device)
-        check(lib().sp_welch_accum(ptr(xs.data_ptr()), _tcode(xs), xs.numel(), ptr(w), w.size, int(hop), int(nframes), nm,
-                                   ptr(out.data_ptr()), 1))
-        return out
-    xs = _ffi.as_samples(x)
-    nm = xs.size if nmean is None else int(nmean)
-    out = np.empty(2, dtype=np.float64)
-    _ffi.init()
-    check(lib().sp_welch_accum(ptr(xs), _ffi.dtype_code(xs.dtype), xs.size, ptr(w), w.size, int(hop), int(nframes), nm,
-                               ptr(out), 0))
+    md = _enter(x)
+    xs = md.samples(x)
+    nm = md.count(xs) if nmean is None else int(nmean)
+    out = md.empty(2, "float64", xs)
+    md.call(lib().sp_welch_accum, md.addr(xs), md.code(xs), md.count(xs), ptr(w), w.size, int(hop), int(nframes), nm, md.addr(out))
     return out
 
 
@@ -190,20 +269,11 @@ def welch_export(x, win, hop, nframes, nmean=None):
     float64[5*nfft + 8] (torch tensor on the device for device input).  Sum the states of all shards, then welch_apply."""
     w = _win32(win)
     n = 5 * w.size + 8
-    if _is_torch(x):
-        _bind_stream(x)
-        xs = _torch_samples(x)
-        nm = xs.numel() if nmean is None else int(nmean)
-        out = torch.empty(n, dtype=torch.float64, device=xs.device)
-        check(lib().sp_welch_export(ptr(xs.data_ptr()), _tcode(xs), xs.numel(), ptr(w), w.size, int(hop), int(nframes), nm,
-                                    ptr(out.data_ptr()), 1))
-        return out
-    xs = _ffi.as_samples(x)
-    nm = xs.size if nmean is None else int(nmean)
-    out = np.empty(n, dtype=np.float64)
-    _ffi.init()
-    check(lib().sp_welch_export(ptr(xs), _ffi.dtype_code(xs.dtype), xs.size, ptr(w), w.size, int(hop), int(nframes), nm,
-                                ptr(out), 0))
+    md = _enter(x)
+    xs = md.samples(x)
+    nm = md.count(xs) if nmean is None else int(nmean)
+    out = md.empty(n, "float64", xs)
+    md.call(lib().sp_welch_export, md.addr(xs), md.code(xs), md.count(xs), ptr(w), w.size, int(hop), int(nframes), nm, md.addr(out))
     return out
 
 
@@ -211,17 +281,10 @@ def welch_apply(state, win, frames_total, sided=SIDED_TWO, scale=1.0):
     """PSD of the whole stream (global-mean detrend) from the summed shard states: float64[nbins]."""
     w = _win32(win)
     nb = nbins(w.size, sided)
-    if _is_torch(state):
-        _bind_stream(state)
-        st = state.to(torch.float64).contiguous()
-        out = torch.empty(nb, dtype=torch.float64, device=st.device)
-        check(lib().sp_welch_apply(ptr(st.data_ptr()), ptr(w), w.size, int(frames_total), sided, float(scale),
-                                   ptr(out.data_ptr()), 1))
-        return out
-    st = np.ascontiguousarray(state, dtype=np.float64)
-    out = np.empty(nb, dtype=np.float64)
-    _ffi.init()
-    check(lib().sp_welch_apply(ptr(st), ptr(w), w.size, int(frames_total), sided, float(scale), ptr(out), 0))
+    md = _enter(state)
+    st = md.cast(state, "float64")
+    out = md.empty(nb, "float64", st)
+    md.call(lib().sp_welch_apply, md.addr(st), ptr(w), w.size, int(frames_total), sided, float(scale), md.addr(out))
     return out
 
 
@@ -277,18 +340,13 @@ def welch_finish(nfft, mean, frames_total, sided=SIDED_TWO, scale=1.0, like=None
     """Second half: apply the (global) mean -- (2,) float64 [re, im], same kind of array welch_accum returned, or None
     for the shard's own mean -- and return scale/frames_total * sum_{local frames} |X|^2 as float64 [nbins]."""
     nb = nbins(nfft, sided)
-    if _is_torch(like) or _is_torch(mean):
-        dev = (mean if _is_torch(mean) else like).device
-        out = torch.empty(nb, dtype=torch.float64, device=dev)
-        mp = None
-        if mean is not None:
-            mean = mean.to(torch.float64).contiguous()
-            mp = ptr(mean.data_ptr())
-        check(lib().sp_welch_finish(mp, int(frames_total), sided, float(scale), ptr(out.data_ptr()), 1))
-        return out
-    out = np.empty(nb, dtype=np.float64)
-    m = None if mean is None else np.ascontiguousarray(mean, dtype=np.float64)
-    check(lib().sp_welch_finish(ptr(m), int(frames_total), sided, float(scale), ptr(out), 0))
+    like = mean if _is_torch(mean) else like
+    md = _mode(like)
+    out = md.empty(nb, "float64", like)
+    if mean is not None:
+        mean = md.cast(mean, "float64")
+    # no prologue of its own: welch_accum's call brought the library up and bound the stream
+    check(lib().sp_welch_finish(md.addr(mean), int(frames_total), sided, float(scale), md.addr(out), md.mem))
     return out
 
 
@@ -299,9 +357,9 @@ def welch_csd(x, y, win, hop, nframes, detrend=True, sided=SIDED_ONE, scale=1.0)
     w = _win32(win)
     nfft = w.size
     nb = nbins(nfft, sided)
-    if _is_torch(x):
-        _bind_stream(x)
-        xs = _torch_samples(x)
+    md = _enter(x)
+    xs = md.samples(x)
+    if md.dev:                               # the tensors must agree as they come
         if not _is_torch(y):
             raise TypeError("welch_csd: x is a device tensor, y must be one too")
         ys = _torch_samples(y)
@@ -313,30 +371,20 @@ def welch_csd(x, y, win, hop, nframes, detrend=True, sided=SIDED_ONE, scale=1.0)
             raise ValueError("welch_csd: x and y live on different devices")
         if xs.dim() != 1 or ys.dim() != 2 or ys.shape[1] < xs.numel():
             raise ValueError("welch_csd: x[nsig] against y[nch, >= nsig]")
-        nch, ld = ys.shape
-        pxx = torch.empty(nb, dtype=torch.float64, device=xs.device)
-        pyy = torch.empty((nch, nb), dtype=torch.float64, device=xs.device)
-        pxy = torch.empty((nch, nb), dtype=torch.complex128, device=xs.device)
-        check(lib().sp_welch_csd(ptr(xs.data_ptr()), ptr(ys.data_ptr()), _tcode(xs), xs.numel(), nch, ld, ptr(w), nfft,
-                                 int(hop), int(nframes), _detrend_args(detrend, None)[0], None, None, sided,
-                                 float(scale), ptr(pxx.data_ptr()), ptr(pyy.data_ptr()), ptr(pxy.data_ptr()), 1))
-        return pxx, pyy, pxy
-    xs = _ffi.as_samples(x)
-    ys = np.asarray(y)
-    if ys.ndim == 1:
-        ys = ys[None, :]
-    ys = np.ascontiguousarray(ys, dtype=xs.dtype)
-    if np.iscomplexobj(y) and xs.dtype != np.complex64:
-        xs = xs.astype(np.complex64)
-        ys = np.ascontiguousarray(y, dtype=np.complex64).reshape(ys.shape)
+    else:                                   # y is cast to x's dtype; a real x beside a complex y is promoted
+        ys = np.asarray(y)
+        if ys.ndim == 1:
+            ys = ys[None, :]
+        ys = np.ascontiguousarray(ys, dtype=xs.dtype)
+        if np.iscomplexobj(y) and xs.dtype != np.complex64:
+            xs = xs.astype(np.complex64)
+            ys = np.ascontiguousarray(y, dtype=np.complex64).reshape(ys.shape)
     nch, ld = ys.shape
-    pxx = np.empty(nb, dtype=np.float64)
-    pyy = np.empty((nch, nb), dtype=np.float64)
-    pxy = np.empty((nch, nb), dtype=np.complex128)
-    _ffi.init()
-    check(lib().sp_welch_csd(ptr(xs), ptr(ys), _ffi.dtype_code(xs.dtype), xs.size, nch, ld, ptr(w), nfft, int(hop),
-                             int(nframes), _detrend_args(detrend, None)[0], None, None, sided, float(scale), ptr(pxx),
-                             ptr(pyy), ptr(pxy), 0))
+    pxx = md.empty(nb, "float64", xs)
+    pyy = md.empty((nch, nb), "float64", xs)
+    pxy = md.empty((nch, nb), "complex128", xs)
+    md.call(lib().sp_welch_csd, md.addr(xs), md.addr(ys), md.code(xs), md.count(xs), nch, ld, ptr(w), nfft, int(hop), int(nframes),
+            _detrend_args(detrend, None)[0], None, None, sided, float(scale), md.addr(pxx), md.addr(pyy), md.addr(pxy))
     return pxx, pyy, pxy
 
 
@@ -352,50 +400,30 @@ def csd_matrix(x, win, hop, nframes, detrend=True, scale=1.0, means=None):
     mh = None
     if means is not None:
         mh = np.ascontiguousarray(means.detach().cpu().numpy() if _is_torch(means) else means, dtype=np.float64).ravel()
-    if _is_torch(x):
-        _bind_stream(x)
-        xs = x.to(torch.float32).contiguous()
-        nch, ld = xs.shape
-        out = torch.empty((nb, nch, nch), dtype=torch.complex128, device=xs.device)
-        if mh is not None:
-            if mh.size != nch:
-                raise ValueError("means must have one value per channel")
-            check(lib().sp_csd_matrix_means(ptr(xs.data_ptr()), nch, ld, ld, ptr(w), nfft, int(hop), int(nframes), ptr(mh),
-                                            float(scale), ptr(out.data_ptr()), 1))
-        else:
-            check(lib().sp_csd_matrix(ptr(xs.data_ptr()), nch, ld, ld, ptr(w), nfft, int(hop), int(nframes), want,
-                                      float(scale), ptr(out.data_ptr()), 1))
-        return out
-    xs = np.ascontiguousarray(x, dtype=np.float32)
+    md = _enter(x)
+    xs = md.cast(x, "float32")
     nch, ld = xs.shape
-    out = np.empty((nb, nch, nch), dtype=np.complex128)
-    _ffi.init()
+    out = md.empty((nb, nch, nch), "complex128", xs)
+    md.init()
     if mh is not None:
         if mh.size != nch:
             raise ValueError("means must have one value per channel")
-        check(lib().sp_csd_matrix_means(ptr(xs), nch, ld, ld, ptr(w), nfft, int(hop), int(nframes), ptr(mh), float(scale),
-                                        ptr(out), 0))
+        check(lib().sp_csd_matrix_means(md.addr(xs), nch, ld, ld, ptr(w), nfft, int(hop), int(nframes), ptr(mh), float(scale),
+                                        md.addr(out), md.mem))
     else:
-        check(lib().sp_csd_matrix(ptr(xs), nch, ld, ld, ptr(w), nfft, int(hop), int(nframes), want, float(scale), ptr(out), 0))
+        check(lib().sp_csd_matrix(md.addr(xs), nch, ld, ld, ptr(w), nfft, int(hop), int(nframes), want, float(scale), md.addr(out),
+                                  md.mem))
     return out
 
 
 def channel_means(x, nsamples=None):
     """Mean of the first `nsamples` samples of every row of x[nch, nsig] (float32 channels), float64[nch]."""
-    if _is_torch(x):
-        _bind_stream(x)
-        xs = x.to(torch.float32).contiguous()
-        nch, ld = xs.shape
-        n = ld if nsamples is None else int(nsamples)
-        out = torch.empty(nch, dtype=torch.float64, device=xs.device)
-        check(lib().sp_channel_means(ptr(xs.data_ptr()), nch, n, ld, ptr(out.data_ptr()), 1))
-        return out
-    xs = np.ascontiguousarray(x, dtype=np.float32)
+    md = _enter(x)
+    xs = md.cast(x, "float32")
     nch, ld = xs.shape
     n = ld if nsamples is None else int(nsamples)
-    out = np.empty(nch, dtype=np.float64)
-    _ffi.init()
-    check(lib().sp_channel_means(ptr(xs), nch, n, ld, ptr(out), 0))
+    out = md.empty(nch, "float64", xs)
+    md.call(lib().sp_channel_means, md.addr(xs), nch, n, ld, md.addr(out))
     return out
 
 
@@ -409,22 +437,12 @@ def stft_frames(x, win, hop, nframes, detrend=True, sided=SIDED_ONE, amp_scale=1
     nb = nbins(nfft, sided)
     want, mv = _detrend_args(detrend, mean_value)
     shape = (nb, int(nframes)) if bin_major else (int(nframes), nb)
-    if _is_torch(x):
-        _bind_stream(x)
-        xs = _torch_samples(x)
-        out = torch.empty(shape, dtype=torch.float32 if power else torch.complex64, device=xs.device)
-        pseg = torch.empty(int(nframes), dtype=torch.float64, device=xs.device) if want_pseg else None
-        check(lib().sp_stft(ptr(xs.data_ptr()), _tcode(xs), xs.numel(), ptr(w), nfft, int(hop), int(nframes), want,
-                            mv.real, mv.imag, sided, float(amp_scale), 1 if power else 0, 1 if bin_major else 0,
-                            ptr(out.data_ptr()), ptr(pseg.data_ptr()) if want_pseg else None, 1))
-        return out, pseg
-    xs = _ffi.as_samples(x)
-    out = np.empty(shape, dtype=np.float32 if power else np.complex64)
-    pseg = np.empty(int(nframes), dtype=np.float64) if want_pseg else None
-    _ffi.init()
-    check(lib().sp_stft(ptr(xs), _ffi.dtype_code(xs.dtype), xs.size, ptr(w), nfft, int(hop), int(nframes), want,
-                        mv.real, mv.imag, sided, float(amp_scale), 1 if power else 0, 1 if bin_major else 0, ptr(out),
-                        ptr(pseg), 0))
+    md = _enter(x)
+    xs = md.samples(x)
+    out = md.empty(shape, "float32" if power else "complex64", xs)
+    pseg = md.empty(int(nframes), "float64", xs) if want_pseg else None
+    md.call(lib().sp_stft, md.addr(xs), md.code(xs), md.count(xs), ptr(w), nfft, int(hop), int(nframes), want, mv.real, mv.imag, sided,
+            float(amp_scale), 1 if power else 0, 1 if bin_major else 0, md.addr(out), md.addr(pseg))
     return out, pseg
 
 
@@ -452,19 +470,12 @@ def istft_frames(Z, win, hop, sided=SIDED_HALF, scale=None, bin_major=False, ski
     sc = float(np.sum(np.asarray(win, dtype=np.float64))) if scale is None else float(scale)
     lead = tuple(int(d) for d in Z.shape[:-2])
     nch = int(np.prod(lead)) if lead else 1
-    if _is_torch(Z):
-        _bind_stream(Z)
-        if Z.dtype != torch.complex64:
-            raise TypeError("device path takes complex64 spectra, got %s" % Z.dtype)
-        zs = Z.contiguous()
-        y = torch.empty(lead + (max(nout, 0),), dtype=torch.complex64 if sided == SIDED_RAW else torch.float32, device=zs.device)
-        check(lib().sp_istft(ptr(zs.data_ptr()), sided, 1 if bin_major else 0, nch, M, ptr(w), nfft, hop, sc, skip, nout,
-                             ptr(y.data_ptr()), 1))
-        return y
-    zs = np.ascontiguousarray(Z, dtype=np.complex64)
-    y = np.empty(lead + (max(nout, 0),), dtype=np.complex64 if sided == SIDED_RAW else np.float32)
-    _ffi.init()
-    check(lib().sp_istft(ptr(zs), sided, 1 if bin_major else 0, nch, M, ptr(w), nfft, hop, sc, skip, nout, ptr(y), 0))
+    md = _enter(Z)
+    if md.dev and Z.dtype != torch.complex64:            # (host spectra are cast)
+        raise TypeError("device path takes complex64 spectra, got %s" % Z.dtype)
+    zs = md.cast(Z, "complex64")
+    y = md.empty(lead + (max(nout, 0),), "complex64" if sided == SIDED_RAW else "float32", zs)
+    md.call(lib().sp_istft, md.addr(zs), sided, 1 if bin_major else 0, nch, M, ptr(w), nfft, hop, sc, skip, nout, md.addr(y))
     return y
 
 
@@ -479,33 +490,18 @@ def bispectrum(x, win, hop, nframes, y=None, z=None, detrend=True, mean_value=No
     want, mv = _detrend_args(detrend, mean_value)
     if want not in (_ffi.DETREND_CONST, _ffi.DETREND_MEAN, _ffi.DETREND_LINEAR):
         raise ValueError("bispectrum: detrend must be none, mean or linear over the whole record")
-    if _is_torch(x):
-        _bind_stream(x)
-        xs = _torch_samples(x)
-        others = [None if v is None else _torch_samples(v) for v in (y, z)]
-        for v in others:
-            if v is not None and (v.dtype != xs.dtype or v.numel() != xs.numel() or v.device != xs.device):
-                raise ValueError("bispectrum: y and z must match x's length, dtype and device")
-        nb = nfft if xs.dtype == torch.complex64 else nfft // 2 + 1
-        B = torch.empty((nb, nb), dtype=torch.complex128, device=xs.device)
-        b2 = torch.empty((nb, nb), dtype=torch.float64, device=xs.device)
-        pzz = torch.empty(nb, dtype=torch.float64, device=xs.device)
-        yp, zp = (None if v is None else ptr(v.data_ptr()) for v in others)
-        check(lib().sp_bispectrum(ptr(xs.data_ptr()), yp, zp, _tcode(xs), xs.numel(), ptr(w), nfft, int(hop), int(nframes), want,
-                                  mv.real, mv.imag, ptr(B.data_ptr()), ptr(b2.data_ptr()), ptr(pzz.data_ptr()), 1))
-        return B, b2, pzz
-    xs = _ffi.as_samples(x)
-    others = [None if v is None else _ffi.as_samples(v) for v in (y, z)]
-    for v in others:
-        if v is not None and (v.dtype != xs.dtype or v.size != xs.size):
-            raise ValueError("bispectrum: y and z must match x's length and dtype")
-    nb = nfft if xs.dtype == np.complex64 else nfft // 2 + 1
-    B = np.empty((nb, nb), dtype=np.complex128)
-    b2 = np.empty((nb, nb), dtype=np.float64)
-    pzz = np.empty(nb, dtype=np.float64)
-    _ffi.init()
-    check(lib().sp_bispectrum(ptr(xs), ptr(others[0]), ptr(others[1]), _ffi.dtype_code(xs.dtype), xs.size, ptr(w), nfft, int(hop),
-                              int(nframes), want, mv.real, mv.imag, ptr(B), ptr(b2), ptr(pzz), 0))
+    md = _enter(x)
+    xs = md.samples(x)
+    ys, zs = [None if v is None else md.samples(v) for v in (y, z)]
+    for v in (ys, zs):
+        if v is not None and not md.alike(v, xs):
+            raise ValueError("bispectrum: y and z must match x's %s" % md.ALIKE)
+    nb = nfft if md.code(xs) == _ffi.DTYPE_C64 else nfft // 2 + 1
+    B = md.empty((nb, nb), "complex128", xs)
+    b2 = md.empty((nb, nb), "float64", xs)
+    pzz = md.empty(nb, "float64", xs)
+    md.call(lib().sp_bispectrum, md.addr(xs), md.addr(ys), md.addr(zs), md.code(xs), md.count(xs), ptr(w), nfft, int(hop), int(nframes),
+            want, mv.real, mv.imag, md.addr(B), md.addr(b2), md.addr(pzz))
     return B, b2, pzz
 
 
@@ -529,39 +525,18 @@ def multitaper(x, tapers, hop, nframes, y=None, detrend=True, mean_value=None, w
     if wt is not None and wt.shape != (K,):
         raise ValueError("multitaper: weights must hold one number per taper")
     cross, eigen = y is not None, wt is not None
-    dev = _is_torch(x)
-    if dev:
-        _bind_stream(x)
-        xs = _torch_samples(x)
-        ys = _torch_samples(y) if cross else None
-        if cross and (ys.dtype != xs.dtype or ys.numel() != xs.numel() or ys.device != xs.device):
-            raise ValueError("multitaper: y must match x's length, dtype and device")
-        cplx, nsig, code = xs.dtype == torch.complex64, xs.numel(), _tcode(xs)
-
-        def new(shape, dt=torch.float64):
-            return torch.empty(shape, dtype=dt, device=xs.device)
-
-        def addr(a):
-            return None if a is None else ptr(a.data_ptr())
-    else:
-        xs = _ffi.as_samples(x)
-        ys = _ffi.as_samples(y) if cross else None
-        if cross and (ys.dtype != xs.dtype or ys.size != xs.size):
-            raise ValueError("multitaper: y must match x's length and dtype")
-        cplx, nsig, code = xs.dtype == np.complex64, xs.size, _ffi.dtype_code(xs.dtype)
-
-        def new(shape, dt=np.float64):
-            return np.empty(shape, dtype=dt)
-        addr = ptr
-        _ffi.init()
-    nb = nfft if cplx else nfft // 2 + 1
-    c128 = torch.complex128 if dev else np.complex128
-    pxx = new(nb)
-    pyy, pxy = (new(nb), new(nb, c128)) if cross else (None, None)
-    skx = new((K, nb)) if eigen else None
-    sky = new((K, nb)) if eigen and cross else None
-    check(lib().sp_multitaper(addr(xs), addr(ys), code, nsig, ptr(tp), K, nfft, int(hop), int(nframes), want, ptr(mean), ptr(mean),
-                              ptr(wt), float(scale), addr(pxx), addr(pyy), addr(pxy), addr(skx), addr(sky), 1 if dev else 0))
+    md = _enter(x)
+    xs = md.samples(x)
+    ys = md.samples(y) if cross else None
+    if cross and not md.alike(ys, xs):
+        raise ValueError("multitaper: y must match x's %s" % md.ALIKE)
+    nb = nfft if md.code(xs) == _ffi.DTYPE_C64 else nfft // 2 + 1
+    pxx = md.empty(nb, "float64", xs)
+    pyy, pxy = (md.empty(nb, "float64", xs), md.empty(nb, "complex128", xs)) if cross else (None, None)
+    skx = md.empty((K, nb), "float64", xs) if eigen else None
+    sky = md.empty((K, nb), "float64", xs) if eigen and cross else None
+    md.call(lib().sp_multitaper, md.addr(xs), md.addr(ys), md.code(xs), md.count(xs), ptr(tp), K, nfft, int(hop), int(nframes), want,
+            ptr(mean), ptr(mean), ptr(wt), float(scale), md.addr(pxx), md.addr(pyy), md.addr(pxy), md.addr(skx), md.addr(sky))
     return pxx, pyy, pxy, skx, sky
 
 
@@ -571,28 +546,14 @@ def czt(x, m, start, step):
     start and step in cycles per sample.  complex64 [..., m]; numpy in -> numpy out, device tensor in -> device tensor on x's
     stream (rows of a 2-D tensor may be strided)."""
     m, start, step = int(m), float(start), float(step)
-    if _is_torch(x):
-        _bind_stream(x)
-        if x.dtype not in (torch.float32, torch.complex64):
-            raise TypeError("device path takes float32 or complex64 samples, got %s" % x.dtype)
-        if x.dim() < 1:
-            raise ValueError("czt: x must have at least one axis")
-        n = int(x.shape[-1])
-        if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= n and x.shape[0] >= 1:
-            xs, ld = x, int(x.stride(0))                      # a row-strided view goes through as it is
-        else:
-            xs, ld = x.contiguous(), n
-        batch = xs.numel() // n if n else 0
-        out = torch.empty(tuple(x.shape[:-1]) + (max(m, 0),), dtype=torch.complex64, device=x.device)
-        check(lib().sp_czt(ptr(xs.data_ptr()), _tcode(xs), n, ld, batch, m, start, step, ptr(out.data_ptr()), 1))
-        return out
-    xs = _ffi.as_samples(x)
-    if xs.ndim < 1:
+    md = _enter(x)
+    x = md.checked(x)
+    if x.ndim < 1:
         raise ValueError("czt: x must have at least one axis")
-    n = xs.shape[-1]
-    out = np.empty(xs.shape[:-1] + (max(m, 0),), dtype=np.complex64)
-    _ffi.init()
-    check(lib().sp_czt(ptr(xs), _ffi.dtype_code(xs.dtype), n, n, xs.size // n if n else 0, m, start, step, ptr(out), 0))
+    xs, ld = md.rows(x)
+    n = int(x.shape[-1])
+    out = md.empty(tuple(x.shape[:-1]) + (max(m, 0),), "complex64", x)
+    md.call(lib().sp_czt, md.addr(xs), md.code(xs), n, ld, md.count(xs) // n if n else 0, m, start, step, md.addr(out))
     return out
 
 
@@ -610,37 +571,17 @@ def zoom_welch(x, win, hop, nframes, m, start, step, y=None, detrend=False, mean
         raise ValueError("zoom_welch: frames=True takes one signal")
     mean = np.array([mv.real, mv.imag], dtype=np.float64)
     cross = y is not None
-    dev = _is_torch(x)
-    if dev:
-        _bind_stream(x)
-        xs = _torch_samples(x)
-        ys = _torch_samples(y) if cross else None
-        if cross and (ys.dtype != xs.dtype or ys.numel() != xs.numel() or ys.device != xs.device):
-            raise ValueError("zoom_welch: y must match x's length, dtype and device")
-        nsig, code = xs.numel(), _tcode(xs)
-
-        def new(shape, dt=torch.float64):
-            return torch.empty(shape, dtype=dt, device=xs.device)
-
-        def addr(a):
-            return None if a is None else ptr(a.data_ptr())
-    else:
-        xs = _ffi.as_samples(x)
-        ys = _ffi.as_samples(y) if cross else None
-        if cross and (ys.dtype != xs.dtype or ys.size != xs.size):
-            raise ValueError("zoom_welch: y must match x's length and dtype")
-        nsig, code = xs.size, _ffi.dtype_code(xs.dtype)
-
-        def new(shape, dt=np.float64):
-            return np.empty(shape, dtype=dt)
-        addr = ptr
-        _ffi.init()
+    md = _enter(x)
+    xs = md.samples(x)
+    ys = md.samples(y) if cross else None
+    if cross and not md.alike(ys, xs):
+        raise ValueError("zoom_welch: y must match x's %s" % md.ALIKE)
     mm = max(m, 0)
-    fr = new((max(int(nframes), 0), mm), torch.complex64 if dev else np.complex64) if frames else None
-    pxx = None if frames else new(mm)
-    pyy, pxy = (new(mm), new(mm, torch.complex128 if dev else np.complex128)) if cross else (None, None)
-    check(lib().sp_zoom_welch(addr(xs), addr(ys), code, nsig, ptr(w), nfft, int(hop), int(nframes), want, ptr(mean), ptr(mean), m,
-                              float(start), float(step), float(scale), addr(pxx), addr(pyy), addr(pxy), addr(fr), 1 if dev else 0))
+    fr = md.empty((max(int(nframes), 0), mm), "complex64", xs) if frames else None
+    pxx = None if frames else md.empty(mm, "float64", xs)
+    pyy, pxy = (md.empty(mm, "float64", xs), md.empty(mm, "complex128", xs)) if cross else (None, None)
+    md.call(lib().sp_zoom_welch, md.addr(xs), md.addr(ys), md.code(xs), md.count(xs), ptr(w), nfft, int(hop), int(nframes), want,
+            ptr(mean), ptr(mean), m, float(start), float(step), float(scale), md.addr(pxx), md.addr(pyy), md.addr(pxy), md.addr(fr))
     return fr if frames else (pxx, pyy, pxy)
 
 
@@ -665,28 +606,14 @@ def ddc(x, nu, q, h, n0=0):
         raise ValueError("ddc: the taps must be one-dimensional")
     if not 1 <= q <= 64:
         raise ValueError("ddc: q = %d is outside 1 .. 64" % q)
-    if _is_torch(x):
-        _bind_stream(x)
-        if x.dtype not in (torch.float32, torch.complex64):
-            raise TypeError("device path takes float32 or complex64 samples, got %s" % x.dtype)
-        if x.dim() < 1:
-            raise ValueError("ddc: x must have at least one axis")
-        n = int(x.shape[-1])
-        if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= n and x.shape[0] >= 1:
-            xs, ld = x, int(x.stride(0))                      # a row-strided view goes through as it is
-        else:
-            xs, ld = x.contiguous(), n
-        batch = xs.numel() // n if n else 0
-        out = torch.empty(tuple(x.shape[:-1]) + (-(-n // q),), dtype=torch.complex64, device=x.device)
-        check(lib().sp_ddc(ptr(xs.data_ptr()), _tcode(xs), n, ld, batch, nu, n0, q, ptr(taps), taps.size, ptr(out.data_ptr()), 1))
-        return out
-    xs = _ffi.as_samples(x)
-    if xs.ndim < 1:
+    md = _enter(x)
+    x = md.checked(x)
+    if x.ndim < 1:
         raise ValueError("ddc: x must have at least one axis")
-    n = xs.shape[-1]
-    out = np.empty(xs.shape[:-1] + (-(-n // q),), dtype=np.complex64)
-    _ffi.init()
-    check(lib().sp_ddc(ptr(xs), _ffi.dtype_code(xs.dtype), n, n, xs.size // n if n else 0, nu, n0, q, ptr(taps), taps.size, ptr(out), 0))
+    xs, ld = md.rows(x)
+    n = int(x.shape[-1])
+    out = md.empty(tuple(x.shape[:-1]) + (-(-n // q),), "complex64", x)
+    md.call(lib().sp_ddc, md.addr(xs), md.code(xs), n, ld, md.count(xs) // n if n else 0, nu, n0, q, ptr(taps), taps.size, md.addr(out))
     return out
 
 
@@ -715,33 +642,19 @@ def upfirdn(x, h, up, down, m0=0, nout=None):
         raise ValueError("upfirdn: up = %d and down = %d must lie in 1 .. 256" % (up, down))
     if taps.size > 8191:
         raise ValueError("upfirdn: %d taps are beyond the 8191 one launch takes" % taps.size)
-    dev = _is_torch(x)
-    if dev:
-        _bind_stream(x)
-        if x.dtype not in (torch.float32, torch.complex64):
-            raise TypeError("device path takes float32 or complex64 samples, got %s" % x.dtype)
-    else:
-        x = _ffi.as_samples(x)
-    if (x.dim() if dev else x.ndim) < 1 or x.shape[-1] < 1:
+    md = _enter(x)
+    x = md.checked(x)
+    if x.ndim < 1 or x.shape[-1] < 1:
         raise ValueError("upfirdn: x must have at least one axis, and at least one sample along it")
     n = int(x.shape[-1])
     full = -(-((n - 1) * up + taps.size) // down)
     nout = max(full - m0, 0) if nout is None else int(nout)
     if m0 < 0 or nout < 0:
         raise ValueError("upfirdn: m0 = %d and nout = %d must not be negative" % (m0, nout))
-    shape = tuple(x.shape[:-1]) + (nout,)
-    if dev:
-        if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= n and x.shape[0] >= 1:
-            xs, ld = x, int(x.stride(0))                      # a row-strided view goes through as it is
-        else:
-            xs, ld = x.contiguous(), n
-        out = torch.empty(shape, dtype=x.dtype, device=x.device)
-        check(lib().sp_upfirdn(ptr(xs.data_ptr()), _tcode(xs), n, ld, xs.numel() // n, ptr(taps), taps.size, up, down, m0, nout,
-                               ptr(out.data_ptr()), 1))
-        return out
-    out = np.empty(shape, dtype=x.dtype)
-    _ffi.init()
-    check(lib().sp_upfirdn(ptr(x), _ffi.dtype_code(x.dtype), n, n, x.size // n, ptr(taps), taps.size, up, down, m0, nout, ptr(out), 0))
+    xs, ld = md.rows(x)
+    cplx = md.code(xs) == _ffi.DTYPE_C64
+    out = md.empty(tuple(x.shape[:-1]) + (nout,), "complex64" if cplx else "float32", x)
+    md.call(lib().sp_upfirdn, md.addr(xs), md.code(xs), n, ld, md.count(xs) // n, ptr(taps), taps.size, up, down, m0, nout, md.addr(out))
     return out
 
 
@@ -766,31 +679,16 @@ def pfb(x, h, M, hop, first, nframes, phase_ref=0, r0=0, power=False, out_major=
         if power:
             return tuple(lead) + (nb,)
         return tuple(lead) + ((nb, nframes) if major == 1 else (nframes, nb))
-    if _is_torch(x):
-        _bind_stream(x)
-        if x.dtype not in (torch.float32, torch.complex64):
-            raise TypeError("device path takes float32 or complex64 samples, got %s" % x.dtype)
-        if x.dim() < 1 or x.shape[-1] < 1:
-            raise ValueError("pfb: x must have at least one axis, with at least one sample")
-        n = int(x.shape[-1])
-        if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= n and x.shape[0] >= 1:
-            xs, ld = x, int(x.stride(0))                      # a row-strided view goes through as it is
-        else:
-            xs, ld = x.contiguous(), n
-        nb = M if xs.is_complex() else M // 2 + 1
-        out = torch.empty(oshape(x.shape[:-1], nb), dtype=torch.float64 if power else torch.complex64, device=x.device)
-        check(lib().sp_pfb(ptr(xs.data_ptr()), _tcode(xs), n, ld, xs.numel() // n, ptr(taps), taps.size, M, hop, first, nframes,
-                           int(phase_ref), r0, kind, major, float(scale), ptr(out.data_ptr()), 1))
-        return out
-    xs = _ffi.as_samples(x)
-    if xs.ndim < 1 or xs.shape[-1] < 1:
+    md = _enter(x)
+    x = md.checked(x)
+    if x.ndim < 1 or x.shape[-1] < 1:
         raise ValueError("pfb: x must have at least one axis, with at least one sample")
-    n = xs.shape[-1]
-    nb = M if np.iscomplexobj(xs) else M // 2 + 1
-    out = np.empty(oshape(xs.shape[:-1], nb), dtype=np.float64 if power else np.complex64)
-    _ffi.init()
-    check(lib().sp_pfb(ptr(xs), _ffi.dtype_code(xs.dtype), n, n, xs.size // n, ptr(taps), taps.size, M, hop, first, nframes,
-                       int(phase_ref), r0, kind, major, float(scale), ptr(out), 0))
+    xs, ld = md.rows(x)
+    n = int(x.shape[-1])
+    nb = M if md.code(xs) == _ffi.DTYPE_C64 else M // 2 + 1
+    out = md.empty(oshape(x.shape[:-1], nb), "float64" if power else "complex64", x)
+    md.call(lib().sp_pfb, md.addr(xs), md.code(xs), n, ld, md.count(xs) // n, ptr(taps), taps.size, M, hop, first, nframes,
+            int(phase_ref), r0, kind, major, float(scale), md.addr(out))
     return out
 
 
@@ -822,20 +720,13 @@ def pfb_synth(X, g, M, hop, first, nout, phase_ref=0, r0=0, onesided=True, in_ma
     sided = SIDED_HALF if onesided else SIDED_RAW
     lead = tuple(int(d) for d in X.shape[:-2])
     batch = int(np.prod(lead)) if lead else 1
-    if _is_torch(X):
-        _bind_stream(X)
-        if X.dtype != torch.complex64:
-            raise TypeError("device path takes complex64 frames, got %s" % X.dtype)
-        xs = X.contiguous()
-        y = torch.empty(lead + (nout,), dtype=torch.float32 if onesided else torch.complex64, device=xs.device)
-        check(lib().sp_pfb_synth(ptr(xs.data_ptr()), sided, major, batch, nframes, ptr(taps), taps.size, M, hop, first, int(phase_ref),
-                                 r0, float(scale), nout, ptr(y.data_ptr()), 1))
-        return y
-    xs = np.ascontiguousarray(X, dtype=np.complex64)
-    y = np.empty(lead + (nout,), dtype=np.float32 if onesided else np.complex64)
-    _ffi.init()
-    check(lib().sp_pfb_synth(ptr(xs), sided, major, batch, nframes, ptr(taps), taps.size, M, hop, first, int(phase_ref), r0,
-                             float(scale), nout, ptr(y), 0))
+    md = _enter(X)
+    if md.dev and X.dtype != torch.complex64:           # (host frames are cast)
+        raise TypeError("device path takes complex64 frames, got %s" % X.dtype)
+    xs = md.cast(X, "complex64")
+    y = md.empty(lead + (nout,), "float32" if onesided else "complex64", xs)
+    md.call(lib().sp_pfb_synth, md.addr(xs), sided, major, batch, nframes, ptr(taps), taps.size, M, hop, first, int(phase_ref), r0,
+            float(scale), nout, md.addr(y))
     return y
 
 
@@ -856,36 +747,22 @@ def stft_cog(x, win, hop, nframes, fs, fmin=0.0, fmax=None, detrend=False, mean_
     nfft = w.size
     want, mv = _detrend_args(detrend, mean_value)
     fmax = float(fs) if fmax is None else float(fmax)
-    if _is_torch(x):
-        _bind_stream(x)
-        xs = _torch_samples(x)
-        out = torch.empty(int(nframes), dtype=torch.float64, device=xs.device)
-        check(lib().sp_stft_cog(ptr(xs.data_ptr()), _tcode(xs), xs.numel(), ptr(w), nfft, int(hop), int(nframes), want,
-                                mv.real, mv.imag, float(fs), float(fmin), fmax, ptr(out.data_ptr()), 1))
-        return out
-    xs = _ffi.as_samples(x)
-    out = np.empty(int(nframes), dtype=np.float64)
-    _ffi.init()
-    check(lib().sp_stft_cog(ptr(xs), _ffi.dtype_code(xs.dtype), xs.size, ptr(w), nfft, int(hop), int(nframes), want,
-                            mv.real, mv.imag, float(fs), float(fmin), fmax, ptr(out), 0))
+    md = _enter(x)
+    xs = md.samples(x)
+    out = md.empty(int(nframes), "float64", xs)
+    md.call(lib().sp_stft_cog, md.addr(xs), md.code(xs), md.count(xs), ptr(w), nfft, int(hop), int(nframes), want, mv.real, mv.imag,
+            float(fs), float(fmin), fmax, md.addr(out))
     return out
 
 
 # ------------------------------------------------------------------------------------------ A10
 def hilbert_rows(x2d, nfft):
     """Analytic signal of each row of a real [batch, n_in] array, transform length nfft -> complex64 [batch, nfft]."""
-    if _is_torch(x2d):
-        _bind_stream(x2d)
-        xs = x2d.to(torch.float32).contiguous()
-        batch, n_in = xs.shape
-        out = torch.empty((batch, nfft), dtype=torch.complex64, device=xs.device)
-        check(lib().sp_hilbert(ptr(xs.data_ptr()), n_in, n_in, int(nfft), batch, ptr(out.data_ptr()), 1))
-        return out
-    xs = np.ascontiguousarray(x2d, dtype=np.float32)
+    md = _enter(x2d)
+    xs = md.cast(x2d, "float32")
     batch, n_in = xs.shape
-    out = np.empty((batch, nfft), dtype=np.complex64)
-    _ffi.init()
-    check(lib().sp_hilbert(ptr(xs), n_in, n_in, int(nfft), batch, ptr(out), 0))
+    out = md.empty((batch, nfft), "complex64", xs)
+    md.call(lib().sp_hilbert, md.addr(xs), n_in, n_in, int(nfft), batch, md.addr(out))
     return out
 
 
@@ -896,23 +773,15 @@ def frame_sum(y2d, nfft, hop, nframes, detrend=True):
     want, _ = _detrend_args(detrend, None)
     if want not in (_ffi.DETREND_CONST, _ffi.DETREND_MEAN, _ffi.DETREND_LINEAR):
         raise ValueError("frame_sum: detrend must be none, mean or linear")
-    if _is_torch(y2d):
-        _bind_stream(y2d)
-        ys = y2d.contiguous()
-        ys = ys.to(torch.complex64) if ys.is_complex() else ys.to(torch.float32)
-        nch, nsig = ys.shape
-        out = torch.empty((nch, int(nfft), 2), dtype=torch.float64, device=ys.device)
-        check(lib().sp_frame_sum(ptr(ys.data_ptr()), _tcode(ys), nsig, nch, nsig, int(nfft), int(hop), int(nframes), want,
-                                 ptr(out.data_ptr()), 1))
-        return torch.view_as_complex(out) if ys.is_complex() else out[..., 0]
-    a = np.asarray(y2d)
-    ys = np.ascontiguousarray(a, dtype=np.complex64 if np.iscomplexobj(a) else np.float32)
+    md = _enter(y2d)
+    cplx = y2d.is_complex() if md.dev else np.iscomplexobj(y2d)
+    ys = md.cast(y2d, "complex64" if cplx else "float32")
     nch, nsig = ys.shape
-    out = np.empty((nch, int(nfft), 2), dtype=np.float64)
-    _ffi.init()
-    check(lib().sp_frame_sum(ptr(ys), _ffi.dtype_code(ys.dtype), nsig, nch, nsig, int(nfft), int(hop), int(nframes), want,
-                             ptr(out), 0))
-    return out.view(np.complex128)[..., 0] if np.iscomplexobj(ys) else out[..., 0].copy()
+    out = md.empty((nch, int(nfft), 2), "float64", ys)
+    md.call(lib().sp_frame_sum, md.addr(ys), md.code(ys), nsig, nch, nsig, int(nfft), int(hop), int(nframes), want, md.addr(out))
+    if md.dev:                              # (re, im) pairs -> a complex view, or the real parts as a view
+        return torch.view_as_complex(out) if cplx else out[..., 0]
+    return out.view(np.complex128)[..., 0] if cplx else out[..., 0].copy()
 
 
 # ------------------------------------------------------------------------------------------ N4
@@ -920,48 +789,33 @@ def spectral_filter_rows(x2d, H):
     """IFFT(H * FFT(row)) for each real row of [batch, n]; H complex [n] (host table).  complex64 [batch, n]."""
     Hc = np.ascontiguousarray(H, dtype=np.complex64)
     nfft = Hc.size
-    if _is_torch(x2d):
-        _bind_stream(x2d)
-        xs = x2d.to(torch.float32).contiguous()
-        batch, n_in = xs.shape
-        out = torch.empty((batch, nfft), dtype=torch.complex64, device=xs.device)
-        check(lib().sp_spectral_filter(ptr(xs.data_ptr()), n_in, n_in, nfft, batch, ptr(Hc), ptr(out.data_ptr()), 1))
-        return out
-    xs = np.ascontiguousarray(x2d, dtype=np.float32)
+    md = _enter(x2d)
+    xs = md.cast(x2d, "float32")
     batch, n_in = xs.shape
-    out = np.empty((batch, nfft), dtype=np.complex64)
-    _ffi.init()
-    check(lib().sp_spectral_filter(ptr(xs), n_in, n_in, nfft, batch, ptr(Hc), ptr(out), 0))
+    out = md.empty((batch, nfft), "complex64", xs)
+    md.call(lib().sp_spectral_filter, md.addr(xs), n_in, n_in, nfft, batch, ptr(Hc), md.addr(out))
     return out
 
 
 # ------------------------------------------------------------------------------------------ A11
 def xcorr_normalised(x1, x2):
     """co[2n-1] = correlate(x1-m1, x2-m2, 'full') / (n std1 std2), float32."""
-    if _is_torch(x1):
-        _bind_stream(x1)
+    md = _enter(x1)
+    if md.dev:                              # the tensors are judged as they come, the host arrays after the cast
         if not _is_torch(x2) or x2.device != x1.device:
             raise ValueError("xcorr: both signals must be tensors on the same device")
         if x1.dim() != 1 or x2.shape != x1.shape:
             raise ValueError("xcorr: two 1-D signals of equal length")
         if x1.is_complex() or x2.is_complex():
             raise TypeError("xcorr: real signals")
-        a = x1.to(torch.float32).contiguous()
-        b = x2.to(torch.float32).contiguous()
-        n = a.numel()
-        out = torch.empty(2 * n - 1, dtype=torch.float32, device=a.device)
-        check(lib().sp_xcorr(ptr(a.data_ptr()), ptr(b.data_ptr()), n, ptr(out.data_ptr()), 1))
-        return out
-    if np.iscomplexobj(x1) or np.iscomplexobj(x2):
+    elif np.iscomplexobj(x1) or np.iscomplexobj(x2):
         raise TypeError("xcorr: real signals")
-    a = np.ascontiguousarray(x1, dtype=np.float32)
-    b = np.ascontiguousarray(x2, dtype=np.float32)
+    a, b = md.cast(x1, "float32"), md.cast(x2, "float32")
     if a.shape != b.shape or a.ndim != 1:
         raise ValueError("xcorr: two 1-D signals of equal length")
-    n = a.size
-    out = np.empty(2 * n - 1, dtype=np.float32)
-    _ffi.init()
-    check(lib().sp_xcorr(ptr(a), ptr(b), n, ptr(out), 0))
+    n = md.count(a)
+    out = md.empty(2 * n - 1, "float32", a)
+    md.call(lib().sp_xcorr, md.addr(a), md.addr(b), n, md.addr(out))
     return out
 
 
@@ -983,36 +837,18 @@ def xcorr_frames(x, y, nw, hop, nframes, maxlag, win=None, segmean=True, coeff=T
         raise ValueError("xcorr_frames: weight must hold sp_xcorr_frames_len(nw, maxlag) values")
     if not (frames or avg or peak):
         raise ValueError("xcorr_frames: ask for at least one of frames, avg, peak")
-    dev = _is_torch(x)
-    if dev:
-        _bind_stream(x)
-        xs, ys = _torch_samples(x), _torch_samples(y) if _is_torch(y) else None
-        if ys is None or ys.dtype != xs.dtype or ys.numel() != xs.numel() or ys.device != xs.device:
-            raise ValueError("xcorr_frames: y must be a tensor of x's length, dtype and device")
-        nsig, code, cplx = xs.numel(), _tcode(xs), xs.dtype == torch.complex64
-
-        def new(shape, dt):
-            return torch.empty(shape, dtype=getattr(torch, dt), device=xs.device)
-
-        def addr(a):
-            return None if a is None else ptr(a.data_ptr())
-    else:
-        xs, ys = _ffi.as_samples(x), _ffi.as_samples(y)
-        if ys.dtype != xs.dtype or ys.size != xs.size:
-            raise ValueError("xcorr_frames: y must match x's length and dtype")
-        nsig, code, cplx = xs.size, _ffi.dtype_code(xs.dtype), xs.dtype == np.complex64
-
-        def new(shape, dt):
-            return np.empty(shape, dtype=getattr(np, dt))
-        addr = ptr
-        _ffi.init()
+    md = _enter(x)
+    xs, ys = md.samples(x), md.samples(y) if _is_torch(y) or not md.dev else None
+    if ys is None or not md.alike(ys, xs):
+        raise ValueError("xcorr_frames: y must %s x's %s" % ("be a tensor of" if md.dev else "match", md.ALIKE))
+    cplx = md.code(xs) == _ffi.DTYPE_C64
     nl, m = 2 * max(maxlag, 0) + 1, max(nframes, 0)
-    fr = new((m, nl), "complex64" if cplx else "float32") if frames else None
-    av = new((nl,), "complex128" if cplx else "float64") if avg else None
-    pk = new((m, 2), "float32") if peak else None
-    check(lib().sp_xcorr_frames(addr(xs), addr(ys), code, nsig, ptr(w), nw, hop, nframes, maxlag,
-                                _ffi.DETREND_SEGMEAN if segmean else _ffi.DETREND_CONST, _ffi.XC_COEFF if coeff else _ffi.XC_RAW,
-                                float(beta), ptr(wt), addr(fr), addr(av), addr(pk), 1 if dev else 0))
+    fr = md.empty((m, nl), "complex64" if cplx else "float32", xs) if frames else None
+    av = md.empty((nl,), "complex128" if cplx else "float64", xs) if avg else None
+    pk = md.empty((m, 2), "float32", xs) if peak else None
+    md.call(lib().sp_xcorr_frames, md.addr(xs), md.addr(ys), md.code(xs), md.count(xs), ptr(w), nw, hop, nframes, maxlag,
+            _ffi.DETREND_SEGMEAN if segmean else _ffi.DETREND_CONST, _ffi.XC_COEFF if coeff else _ffi.XC_RAW, float(beta), ptr(wt),
+            md.addr(fr), md.addr(av), md.addr(pk))
     return fr, av, pk
 
 
@@ -1026,27 +862,14 @@ def skf(x, y, nfft, hop, nframes, b0, nb, nk, win=None, segmean=True, cross=Fals
     w = None if win is None else _win32(win)
     if w is not None and w.shape != (nfft,):
         raise ValueError("skf: win must hold nfft = %d values" % nfft)
-    dev = _is_torch(x)
-    shape = (max(nb, 0), max(nk, 0))
-    if dev:
-        _bind_stream(x)
-        xs, ys = _torch_samples(x), _torch_samples(y) if _is_torch(y) else None
-        if ys is None or ys.dtype != xs.dtype or ys.numel() != xs.numel() or ys.device != xs.device:
-            raise ValueError("skf: y must be a tensor of x's length, dtype and device")
-        nsig, code = xs.numel(), _tcode(xs)
-        out = torch.empty(shape, dtype=torch.float64, device=xs.device)
-        check(lib().sp_skf(ptr(xs.data_ptr()), ptr(ys.data_ptr()), code, nsig, ptr(w), nfft, hop, nframes,
-                           _ffi.DETREND_SEGMEAN if segmean else _ffi.DETREND_NONE, _ffi.SKF_CROSS if cross else _ffi.SKF_MEAN, b0, nb,
-                           nk, float(scale), ptr(out.data_ptr()), 1))
-        return out
-    xs, ys = _ffi.as_samples(x), _ffi.as_samples(y)
-    if ys.dtype != xs.dtype or ys.size != xs.size:
-        raise ValueError("skf: y must match x's length and dtype")
-    _ffi.init()
-    out = np.empty(shape, dtype=np.float64)
-    check(lib().sp_skf(ptr(xs), ptr(ys), _ffi.dtype_code(xs.dtype), xs.size, ptr(w), nfft, hop, nframes,
-                       _ffi.DETREND_SEGMEAN if segmean else _ffi.DETREND_NONE, _ffi.SKF_CROSS if cross else _ffi.SKF_MEAN, b0, nb, nk,
-                       float(scale), ptr(out), 0))
+    md = _enter(x)
+    xs, ys = md.samples(x), md.samples(y) if _is_torch(y) or not md.dev else None
+    if ys is None or not md.alike(ys, xs):
+        raise ValueError("skf: y must %s x's %s" % ("be a tensor of" if md.dev else "match", md.ALIKE))
+    out = md.empty((max(nb, 0), max(nk, 0)), "float64", xs)
+    md.call(lib().sp_skf, md.addr(xs), md.addr(ys), md.code(xs), md.count(xs), ptr(w), nfft, hop, nframes,
+            _ffi.DETREND_SEGMEAN if segmean else _ffi.DETREND_NONE, _ffi.SKF_CROSS if cross else _ffi.SKF_MEAN, b0, nb, nk,
+            float(scale), md.addr(out))
     return out
 
 
@@ -1101,25 +924,23 @@ def welch_blocks(x, win, hop, nframes, navg, step=None, y=None, detrend=True, sc
         raise ValueError("welch_blocks: win must hold nfft = %d values" % nfft)
     hop, nframes, navg = int(hop), int(nframes), int(navg)
     step = navg if step is None else int(step)
-    dev = _is_torch(x)
-    if dev:
-        xs = _torch_samples(x)
-        cplx = xs.dtype == torch.complex64
+    md = _mode(x)
+    xs = md.samples(x)
+    if md.dev:                              # the tensors must agree as they come
         ys = None
         if y is not None:
             if not _is_torch(y):
                 raise TypeError("welch_blocks: x is a device tensor, y must be one too")
-            ys = _torch_samples(y)
+            ys = md.samples(y)
             if ys.dtype != xs.dtype or ys.device != xs.device:
                 raise ValueError("welch_blocks: y must have x's dtype and device")
-    else:
-        xs = _ffi.as_samples(x)
+    else:                                   # y is cast to x's dtype; a real x beside a complex y is promoted
         ys = None if y is None else np.asarray(y)
         if ys is not None and (np.iscomplexobj(ys) or xs.dtype == np.complex64):
             xs = np.ascontiguousarray(xs, dtype=np.complex64)
-        cplx = xs.dtype == np.complex64
         if ys is not None:
             ys = np.ascontiguousarray(ys, dtype=xs.dtype)
+    cplx = md.code(xs) == _ffi.DTYPE_C64
     if xs.ndim != 1 or (ys is not None and ys.ndim not in (1, 2)):
         raise ValueError("welch_blocks: x[nsig] against y[nsig] or y[nch, >= nsig]")
     nsig = int(xs.shape[0])
@@ -1132,26 +953,12 @@ def welch_blocks(x, win, hop, nframes, navg, step=None, y=None, detrend=True, sc
     if not np.isfinite(scale):
         raise ValueError("welch_blocks: scale must be finite")
     nblocks, nb = (nframes - navg) // step + 1, nfft if cplx else nfft // 2 + 1
-    if dev:
-        _bind_stream(xs)
-
-        def new(shape, dt):
-            return torch.empty(shape, dtype=getattr(torch, dt), device=xs.device)
-
-        def addr(a):
-            return None if a is None else ptr(a.data_ptr())
-        dcode = _tcode(xs)
-    else:
-        def new(shape, dt):
-            return np.empty(shape, dtype=getattr(np, dt))
-        addr = ptr
-        dcode = _ffi.dtype_code(xs.dtype)
-        _ffi.init()
-    pxx = new((nblocks, nb), "float32")
-    pyy = None if ys is None else new((nch, nblocks, nb), "float32")
-    pxy = None if ys is None else new((nch, nblocks, nb), "complex64")
-    check(lib().sp_welch_blocks(addr(xs), addr(ys), dcode, nsig, nch or 0, ld or 0, ptr(w), nfft, hop, nframes, navg, step, code, scale,
-                                1 if doubled else 0, addr(pxx), addr(pyy), addr(pxy), 1 if dev else 0))
+    md.bind(xs)
+    pxx = md.empty((nblocks, nb), "float32", xs)
+    pyy = None if ys is None else md.empty((nch, nblocks, nb), "float32", xs)
+    pxy = None if ys is None else md.empty((nch, nblocks, nb), "complex64", xs)
+    md.call(lib().sp_welch_blocks, md.addr(xs), md.addr(ys), md.code(xs), nsig, nch or 0, ld or 0, ptr(w), nfft, hop, nframes, navg,
+            step, code, scale, 1 if doubled else 0, md.addr(pxx), md.addr(pyy), md.addr(pxy))
     if squeeze:
         pyy, pxy = pyy[0], pxy[0]
     return pxx, pyy, pxy
@@ -1220,13 +1027,9 @@ def cwt(x, scales, family, param, L, M, W=True, gws=False, recon=None, bandpow=N
     'W' complex64 [..., S, N] (W=True), 'gws' float64 [..., S] = sum_n |W|^2 (gws=True), 'recon' complex64 [..., N] = sum_s recon[s] W
     and 'bandpow' float32 [..., N] = sum_s bandpow[s] |W|^2 (weights, one per scale; neither forms W).  float32 records run as x + 0i.
     numpy in -> numpy out; device tensor in -> device tensors on x's stream (rows of a 2-D tensor may be strided)."""
-    dev = _is_torch(x)
-    if dev:
-        if x.dtype not in (torch.float32, torch.complex64):
-            raise TypeError("device path takes float32 or complex64 samples, got %s" % x.dtype)
-    else:
-        x = _ffi.as_samples(x)
-    if (x.dim() if dev else x.ndim) < 1:
+    md = _mode(x)
+    x = md.checked(x)
+    if x.ndim < 1:
         raise CwtRefused("cwt: x must have at least one axis")
     n = int(x.shape[-1])
     rows = 1
@@ -1241,23 +1044,11 @@ def cwt(x, scales, family, param, L, M, W=True, gws=False, recon=None, bandpow=N
     shapes = {"W": (lead + (S, n), "complex64"), "gws": (lead + (S,), "float64"), "recon": (lead + (n,), "complex64"),
               "bandpow": (lead + (n,), "float32")}
     want = {"W": bool(W), "gws": bool(gws), "recon": wr is not None, "bandpow": wb is not None}
-    if dev:
-        _bind_stream(x)
-        if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= n:
-            xs, ld = x, int(x.stride(0))                      # a row-strided view goes through as it is
-        else:
-            xs, ld = x.contiguous(), n
-        out = {k: torch.empty(sh, dtype=getattr(torch, dt), device=x.device) for k, (sh, dt) in shapes.items() if want[k]}
-        addr = {k: ptr(v.data_ptr()) for k, v in out.items()}
-        xp, dcode = ptr(xs.data_ptr()), _tcode(xs)
-    else:
-        xs, ld = x, n
-        out = {k: np.empty(sh, dtype=getattr(np, dt)) for k, (sh, dt) in shapes.items() if want[k]}
-        addr = {k: ptr(v) for k, v in out.items()}
-        xp, dcode = ptr(xs), _ffi.dtype_code(xs.dtype)
-        _ffi.init()
-    check(lib().sp_cwt(xp, dcode, n, ld, rows, ptr(sc), S, code, param, 0.0, int(L), int(M), ptr(wr), ptr(wb), addr.get("W"),
-                       addr.get("gws"), addr.get("recon"), addr.get("bandpow"), 1 if dev else 0))
+    md.bind(x)
+    xs, ld = md.rows(x)
+    out = {k: md.empty(sh, dt, x) for k, (sh, dt) in shapes.items() if want[k]}
+    md.call(lib().sp_cwt, md.addr(xs), md.code(xs), n, ld, rows, ptr(sc), S, code, param, 0.0, int(L), int(M), ptr(wr), ptr(wb),
+            md.addr(out.get("W")), md.addr(out.get("gws")), md.addr(out.get("recon")), md.addr(out.get("bandpow")))
     return out
 
 
@@ -1276,13 +1067,13 @@ def cwt_plan(nsig, nscales, L, M, rows=1, W=True, gws=False, recon=False, bandpo
 def icwt_sum(W, weights):
     """out[..., n] = sum_s weights[s] W[..., s, n] (sp_icwt): the sum behind the wavelet reconstruction, from a materialised W (complex64
     [..., S, N]).  numpy in -> numpy out; device tensor in -> device tensor on W's stream."""
-    dev = _is_torch(W)
-    if dev:
+    md = _mode(W)
+    if md.dev:
         if W.dtype != torch.complex64:
             raise TypeError("icwt_sum: W must be complex64, got %s" % W.dtype)
-    else:
-        W = np.ascontiguousarray(np.asarray(W), dtype=np.complex64)
-    if (W.dim() if dev else W.ndim) < 2 or W.shape[-1] < 1 or W.shape[-2] < 1:
+    else:                                   # (cast before the shape is judged: a list of rows will do)
+        W = md.cast(np.asarray(W), "complex64")
+    if W.ndim < 2 or W.shape[-1] < 1 or W.shape[-2] < 1:
         raise CwtRefused("icwt_sum: W must be [..., S, N] with S, N >= 1")
     S, n = int(W.shape[-2]), int(W.shape[-1])
     w = _cwt_weights("icwt_sum", weights, S, "weights")
@@ -1294,15 +1085,10 @@ def icwt_sum(W, weights):
         rows *= int(d)
     if rows < 1 or rows > CWT_MAX_ROWS:
         raise CwtRefused("icwt_sum: %d rows are outside 1 .. %d" % (rows, CWT_MAX_ROWS))
-    if dev:
-        _bind_stream(W)
-        Wc = W.contiguous()
-        out = torch.empty(lead + (n,), dtype=torch.complex64, device=W.device)
-        check(lib().sp_icwt(ptr(Wc.data_ptr()), n, S, rows, ptr(w), ptr(out.data_ptr()), 1))
-        return out
-    out = np.empty(lead + (n,), dtype=np.complex64)
-    _ffi.init()
-    check(lib().sp_icwt(ptr(W), n, S, rows, ptr(w), ptr(out), 0))
+    md.bind(W)
+    Wc = md.cast(W, "complex64")
+    out = md.empty(lead + (n,), "complex64", W)
+    md.call(lib().sp_icwt, md.addr(Wc), n, S, rows, ptr(w), md.addr(out))
     return out
 
 
@@ -1325,7 +1111,6 @@ def eigh(A, nvec=None, max_sweeps=30, check=True):
     complex64, float32 and float64 are cast.  check=True reads sweeps back and raises numpy.linalg.LinAlgError naming the first
     matrix that did not converge; check=False leaves the judgement (and, for device tensors, the asynchrony) to the caller.
     numpy in -> numpy out; a device tensor in -> device tensors out on the same device and on torch's current stream."""
-    dev = _is_torch(A)
     shape = tuple(A.shape)
     if len(shape) < 2 or shape[-1] != shape[-2]:
         raise ValueError("eigh: A must be [..., n, n], got %s" % (shape,))
@@ -1345,23 +1130,15 @@ def eigh(A, nvec=None, max_sweeps=30, check=True):
     batch = 1
     for d in lead:
         batch *= int(d)
-    if dev:
-        _bind_stream(A)
-        a = A.to(torch.complex128).contiguous()
-        w = torch.empty(lead + (n,), dtype=torch.float64, device=a.device)
-        V = torch.empty(lead + (n, nvec), dtype=torch.complex128, device=a.device)
-        sw = torch.empty(lead, dtype=torch.int32, device=a.device)
-        _ffi.check(lib().sp_eigh(ptr(a.data_ptr()), n, batch, nvec, max_sweeps, ptr(w.data_ptr()),
-                             ptr(V.data_ptr()) if nvec > 0 and batch > 0 else None, ptr(sw.data_ptr()), 1))
-        bad = sw.reshape(-1).cpu().numpy() > max_sweeps if check else None
-    else:
-        a = np.ascontiguousarray(A, dtype=np.complex128)
-        _ffi.init()
-        w = np.empty(lead + (n,), dtype=np.float64)
-        V = np.empty(lead + (n, nvec), dtype=np.complex128)
-        sw = np.empty(lead, dtype=np.int32)
-        _ffi.check(lib().sp_eigh(ptr(a), n, batch, nvec, max_sweeps, ptr(w), ptr(V) if nvec > 0 and batch > 0 else None, ptr(sw), 0))
-        bad = sw.reshape(-1) > max_sweeps if check else None
+    md = _enter(A)
+    a = md.cast(A, "complex128")
+    w = md.empty(lead + (n,), "float64", a)
+    V = md.empty(lead + (n, nvec), "complex128", a)
+    sw = md.empty(lead, "int32", a)
+    md.call(lib().sp_eigh, md.addr(a), n, batch, nvec, max_sweeps, md.addr(w), md.addr(V) if nvec > 0 and batch > 0 else None,
+            md.addr(sw))
+    if check:                               # (the read-back of a device tensor waits for the stream)
+        bad = (sw.reshape(-1).cpu().numpy() if md.dev else sw.reshape(-1)) > max_sweeps
     if check and bad.any():
         first = int(np.argmax(bad))
         raise np.linalg.LinAlgError("eigh: matrix %s (flat index %d) did not converge in %d sweeps (non-finite input?)"
@@ -1373,16 +1150,10 @@ def eigh(A, nvec=None, max_sweeps=30, check=True):
 def fir_filter(h, x, nfft=0):
     """Causal FIR y = lfilter(h, 1, x) (float32) by overlap-save on the GPU."""
     taps = np.ascontiguousarray(h, dtype=np.float32)
-    if _is_torch(x):
-        _bind_stream(x)
-        xs = x.to(torch.float32).contiguous()
-        out = torch.empty_like(xs)
-        check(lib().sp_fftfilt(ptr(taps), taps.size, ptr(xs.data_ptr()), xs.numel(), int(nfft), ptr(out.data_ptr()), 1))
-        return out
-    xs = np.ascontiguousarray(x, dtype=np.float32)
-    out = np.empty_like(xs)
-    _ffi.init()
-    check(lib().sp_fftfilt(ptr(taps), taps.size, ptr(xs), xs.size, int(nfft), ptr(out), 0))
+    md = _enter(x)
+    xs = md.cast(x, "float32")
+    out = md.empty(xs.shape, "float32", xs)
+    md.call(lib().sp_fftfilt, ptr(taps), taps.size, md.addr(xs), md.count(xs), int(nfft), md.addr(out))
     return out
 
 
@@ -1402,20 +1173,12 @@ def biquad_filter(b, a, x):
     if rts.size and float(np.max(np.abs(rts))) > 1.0 + 1e-12:
         # (the device scan raises the state map to powers up to len(x): an unstable section would overflow them to inf / NaN)
         raise ValueError("biquad_filter: unstable section (pole radius %.9g > 1)" % float(np.max(np.abs(rts))))
-    if _is_torch(x):
-        _bind_stream(x)
-        if x.is_complex() or x.dim() != 1:
-            raise TypeError("biquad_filter: one real 1-D signal")
-        xs = x.to(torch.float32).contiguous()
-        out = torch.empty_like(xs)
-        check(lib().sp_biquad(ptr(bb), ptr(aa), ptr(xs.data_ptr()), xs.numel(), ptr(out.data_ptr()), 1))
-        return out
-    if np.iscomplexobj(x) or np.ndim(x) != 1:
+    md = _enter(x)
+    if (x.is_complex() if md.dev else np.iscomplexobj(x)) or np.ndim(x) != 1:
         raise TypeError("biquad_filter: one real 1-D signal")
-    xs = np.ascontiguousarray(x, dtype=np.float32)
-    out = np.empty_like(xs)
-    _ffi.init()
-    check(lib().sp_biquad(ptr(bb), ptr(aa), ptr(xs), xs.size, ptr(out), 0))
+    xs = md.cast(x, "float32")
+    out = md.empty(xs.shape, "float32", xs)
+    md.call(lib().sp_biquad, ptr(bb), ptr(aa), md.addr(xs), md.count(xs), md.addr(out))
     return out
 
 
@@ -1482,7 +1245,7 @@ def sos_filter(sos, x, zi=None):
     current stream).  zi (or None): scipy's shape (n_sections, ...lead, 2); with zi, returns (y, zf) of the same shapes."""
     s = sos_array(sos)
     nsec = s.shape[0]
-    if (x.dim() if _is_torch(x) else np.ndim(x)) < 1 or x.shape[-1] < 1:
+    if np.ndim(x) < 1 or x.shape[-1] < 1:
         raise ValueError("sos_filter: empty signal")
     rows, lead, cplx = _sos_rows(x)
     R, n = rows.shape
@@ -1491,29 +1254,22 @@ def sos_filter(sos, x, zi=None):
         want = (nsec,) + tuple(lead) + (2,)
         if tuple(zi.shape) != want:
             raise ValueError("sos_filter: zi must have shape %s, got %s" % (want, tuple(zi.shape)))
-    if _is_torch(x):
-        _bind_stream(x)
-        if zi is not None:
-            z = torch.as_tensor(zi, device=x.device)
-            z = z.reshape(nsec, -1, 2)
+    md = _enter(x)
+    if zi is not None:
+        if md.dev:
+            z = torch.as_tensor(zi, device=x.device).reshape(nsec, -1, 2)
             if cplx:                          # a real zi is the real parts' state; the imaginary parts start from rest
                 z = torch.cat([z.real, z.imag if z.is_complex() else torch.zeros_like(z)], 1)
             elif z.is_complex():
                 z = z.real
-            zr = z.permute(1, 0, 2).to(torch.float64).contiguous()
-        y = torch.empty_like(rows)
-        zf = torch.empty_like(zr) if zr is not None else None
-        check(lib().sp_sosfilt(ptr(s), nsec, ptr(rows.data_ptr()), R, n, ptr(zr.data_ptr()) if zr is not None else None,
-                               ptr(y.data_ptr()), ptr(zf.data_ptr()) if zf is not None else None, 1))
-    else:
-        if zi is not None:
+            zr = md.cast(z.permute(1, 0, 2), "float64")
+        else:
             z = np.asarray(zi).reshape(nsec, -1, 2)
             z = np.concatenate([z.real, z.imag], 1) if cplx else np.real(z)
-            zr = np.ascontiguousarray(z.transpose(1, 0, 2), dtype=np.float64)
-        y = np.empty_like(rows)
-        zf = np.empty_like(zr) if zr is not None else None
-        _ffi.init()
-        check(lib().sp_sosfilt(ptr(s), nsec, ptr(rows), R, n, ptr(zr), ptr(y), ptr(zf), 0))
+            zr = md.cast(z.transpose(1, 0, 2), "float64")
+    y = md.empty(rows.shape, "float32", rows)
+    zf = md.empty(zr.shape, "float64", zr) if zr is not None else None
+    md.call(lib().sp_sosfilt, ptr(s), nsec, md.addr(rows), R, n, md.addr(zr), md.addr(y), md.addr(zf))
     out = _sos_out(y, x, lead, cplx)
     if zi is None:
         return out
@@ -1536,7 +1292,7 @@ def sos_filtfilt(sos, x, padtype="odd", padlen=0):
     padlen = 0 if pt == 0 else int(padlen)
     if padlen < 0:
         raise ValueError("padlen must not be negative")
-    if (x.dim() if _is_torch(x) else np.ndim(x)) < 1 or x.shape[-1] < 1:
+    if np.ndim(x) < 1 or x.shape[-1] < 1:
         raise ValueError("sos_filtfilt: empty signal")
     n = int(x.shape[-1])
     if padlen > 0 and n <= padlen:
@@ -1545,14 +1301,9 @@ def sos_filtfilt(sos, x, padtype="odd", padlen=0):
         raise ValueError("sos_filtfilt: a section with a pole at z = 1 has no steady state")
     rows, lead, cplx = _sos_rows(x)
     R = rows.shape[0]
-    if _is_torch(x):
-        _bind_stream(x)
-        y = torch.empty_like(rows)
-        check(lib().sp_sosfiltfilt(ptr(s), nsec, ptr(rows.data_ptr()), R, n, pt, padlen, ptr(y.data_ptr()), 1))
-    else:
-        y = np.empty_like(rows)
-        _ffi.init()
-        check(lib().sp_sosfiltfilt(ptr(s), nsec, ptr(rows), R, n, pt, padlen, ptr(y), 0))
+    md = _enter(x)
+    y = md.empty(rows.shape, "float32", rows)
+    md.call(lib().sp_sosfiltfilt, ptr(s), nsec, md.addr(rows), R, n, pt, padlen, md.addr(y))
     return _sos_out(y, x, lead, cplx)
 
 
@@ -1563,32 +1314,19 @@ def csd_epilogue(pxx, pyy, pxy, nfft, onesided, enbw):
     channel-major arrays: Cxy[nch, nb] complex, Cxy2, phi, Lyy, Lxy [nch, nb], Lxx[nb], and the fftshifted correlations
     Rxx[nfft], Ryy / Rxy / iCxy / corrcoef [nch, nfft] (real for one-sided input, complex otherwise), Ex, Ey[nch]."""
     nfft, onesided = int(nfft), bool(onesided)
-    dev = _is_torch(pxx)
-    if dev:
-        _bind_stream(pxx)
-        a = pxx.to(torch.float64).contiguous() if not pxx.is_complex() else pxx.real.to(torch.float64).contiguous()
-        b = (pyy if not pyy.is_complex() else pyy.real).to(torch.float64).contiguous()
-        c = pxy.to(torch.complex128).contiguous()
-        if b.dim() == 1:
-            b, c = b[None, :], c[None, :]
-        nch, nb = b.shape
-        n_out = int(lib().sp_csd_epilogue_doubles(nch, nb, nfft))
-        out = torch.empty(n_out, dtype=torch.float64, device=a.device)
-        check(lib().sp_csd_epilogue(ptr(a.data_ptr()), ptr(b.data_ptr()), ptr(c.data_ptr()), nch, nb, nfft, 1 if onesided else 0,
-                                    float(enbw), ptr(out.data_ptr()), 1))
+    md = _enter(pxx)
+    if md.dev:                              # the real parts of the powers; (re, im) pairs of the result -> complex
+        a, b = (v.real if v.is_complex() else v for v in (pxx, pyy))
         cplx = lambda v: torch.complex(v[..., 0], v[..., 1])          # noqa: E731  (slices of `out` may start at odd offsets)
     else:
-        a = np.ascontiguousarray(np.real(pxx), dtype=np.float64)
-        b = np.ascontiguousarray(np.real(pyy), dtype=np.float64)
-        c = np.ascontiguousarray(pxy, dtype=np.complex128)
-        if b.ndim == 1:
-            b, c = b[None, :], c[None, :]
-        nch, nb = b.shape
-        _ffi.init()
-        n_out = int(lib().sp_csd_epilogue_doubles(nch, nb, nfft))
-        out = np.empty(n_out, dtype=np.float64)
-        check(lib().sp_csd_epilogue(ptr(a), ptr(b), ptr(c), nch, nb, nfft, 1 if onesided else 0, float(enbw), ptr(out), 0))
+        a, b = np.real(pxx), np.real(pyy)
         cplx = lambda v: v[..., 0] + 1j * v[..., 1]                     # noqa: E731
+    a, b, c = md.cast(a, "float64"), md.cast(b, "float64"), md.cast(pxy, "complex128")
+    if b.ndim == 1:
+        b, c = b[None, :], c[None, :]
+    nch, nb = b.shape
+    out = md.empty(int(lib().sp_csd_epilogue_doubles(nch, nb, nfft)), "float64", a)
+    md.call(lib().sp_csd_epilogue, md.addr(a), md.addr(b), md.addr(c), nch, nb, nfft, 1 if onesided else 0, float(enbw), md.addr(out))
     pos = [0]
 
     def take(*shape):

@@ -8,6 +8,7 @@ import numpy as np
 import scipy.signal as _dsp
 
 from . import engine as _E
+from .engine import _is_torch
 from .notch_filter import apply_notch  # noqa: F401  (notch application lives with the design)
 
 
@@ -39,10 +40,6 @@ def smooth(x, window_len=11, window="hanning"):
 
 
 # ------------------------------------------------------------------------------------------ IIR (F3)
-def _is_torch(x):
-    return _E._is_torch(x)
-
-
 def _to_last(x, axis):
     return _E.torch.movedim(x, axis, -1) if _is_torch(x) else np.moveaxis(np.asarray(x), axis, -1)
 

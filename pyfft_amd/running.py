@@ -24,13 +24,9 @@ import numpy as np
 
 from .windows import get_window
 from . import engine as _engine
-from .engine import WelchBlocksRefused
+from .engine import WelchBlocksRefused, _is_torch
 
 MIN_NFFT, MAX_NFFT = _engine.WELCH_BLOCKS_MIN_NFFT, _engine.WELCH_BLOCKS_MAX_NFFT
-
-
-def _is_torch(v):
-    return type(v).__module__.startswith("torch")
 
 
 class RunningSpectra(object):

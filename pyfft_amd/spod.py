@@ -15,13 +15,10 @@ import ctypes as C
 
 import numpy as np
 
+from .engine import _is_torch
 from .windows import get_window
 
 MAX_CHANNELS = 64
-
-
-def _is_torch(v):
-    return type(v).__module__.startswith("torch")
 
 
 def _too_many(who, nch):

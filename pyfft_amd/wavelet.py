@@ -21,7 +21,7 @@ import math
 import numpy as np
 
 from . import engine as E
-from .engine import CwtRefused
+from .engine import CwtRefused, _is_torch
 
 try:
     import torch
@@ -224,10 +224,6 @@ def cwt_plan(n, dt=1.0, dj=1.0 / 12, s0=None, J=None, wavelet=None, scales=None,
                              % (int((~fused).sum()), FUSED_MAX_MARGIN, n_full))
         plan["n_full"] = n_full
     return plan
-
-
-def _is_torch(x):
-    return torch is not None and isinstance(x, torch.Tensor)
 
 
 def _prep(x):

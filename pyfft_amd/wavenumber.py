@@ -17,6 +17,7 @@ import os
 
 import numpy as np
 
+from .engine import _is_torch
 from .windows import get_window
 
 MIN_NFFT, MAX_NFFT, MAX_NK = 32, 4096, 1024
@@ -26,10 +27,6 @@ _POWERS = {"mean": 0, "cross": 1}
 
 class SegmentNotBuilt(ValueError, NotImplementedError):
     """nperseg that is not a power of two in 32 .. 4096: outside the limits, and a path that is not built."""
-
-
-def _is_torch(v):
-    return type(v).__module__.startswith("torch")
 
 
 def _check_shape(who, nperseg, nk):

@@ -15,6 +15,7 @@ import math
 
 import numpy as np
 
+from .engine import _is_torch
 from .windows import get_window
 
 _DETRENDS = {False: 0, None: 0, "none": 0, "constant": 1, "mean": 1, "linear": 2}
@@ -27,10 +28,6 @@ class OffCircle(ValueError, NotImplementedError):
 
 class TooLong(ValueError, NotImplementedError):
     """n + m - 1 beyond the longest multi-pass transform."""
-
-
-def _is_torch(v):
-    return type(v).__module__.startswith("torch")
 
 
 def _check_len(who, n, m):

@@ -1,0 +1,508 @@
+"""What pyfft_amd.engine hands to the C ABI, recorded without a GPU: a stand-in for libspectral.so that logs every call, and a table
+of calls that drives each entry point of the engine in both calling modes (numpy arrays; torch tensors, here on the CPU) through every
+branch that changes what reaches the library or what comes back.  tests/golden/make_golden_engine_trace.py wrote the trace of this
+table once; tests/test_host_engine_trace.py replays it.  A plain module: nothing here is collected by pytest.
+
+One argument of a recorded call becomes: an int or a float as it is; None (or a null pointer) null; a c_void_p ["in", k, byte offset]
+when it points into the k-th array the case made, ["out", k, byte offset] when it points into the k-th array the call returned (looked
+up after the call), "tmp" otherwise (the engine's own copies, windows, taps); any other ctypes object the name of its type."""
+import ctypes
+
+import numpy as np
+
+from pyfft_amd import _ffi, engine
+
+try:
+    import torch
+except Exception:                       # pragma: no cover
+    torch = None
+
+# entries whose result the engine reads: answered by the built library, which needs no GPU for them; not recorded
+HOST_ARITHMETIC = ("sp_xcorr_frames_len", "sp_csd_epilogue_doubles", "sp_ddc_tile", "sp_upfirdn_tile", "sp_pfb_synth_plan", "sp_skf_plan",
+                   "sp_welch_blocks_plan", "sp_cwt_plan", "sp_eigh_plan", "sp_version", "sp_max_wg_fft")
+REFUSAL_TYPES = (ValueError, TypeError, NotImplementedError)
+MODES = ("host", "dev")
+
+_INTS, _FLOATS = (int, np.integer), (float, np.floating)
+
+
+class StandIn:
+    """Looks like the loaded library to the engine: every declared name is callable, checks its arguments the way ctypes would (their
+    number; no float where an integer is declared) and logs them."""
+
+    def __init__(self, events):
+        self._events = events
+        self._real = None
+
+    def _delegate(self, name):
+        if self._real is None:
+            self._real = ctypes.CDLL(_ffi.LIB_PATH)
+        fn = getattr(self._real, name)
+        fn.restype, fn.argtypes = _ffi.SIGNATURES[name]
+        return fn
+
+    def __getattr__(self, name):
+        if name not in _ffi.SIGNATURES:
+            raise AttributeError(name)
+        if name in HOST_ARITHMETIC:
+            return self._delegate(name)
+        argtypes = _ffi.SIGNATURES[name][1]
+
+        def record(*args):
+            if len(args) != len(argtypes):
+                raise TypeError("%s takes %d arguments, got %d" % (name, len(argtypes), len(args)))
+            for k, (a, t) in enumerate(zip(args, argtypes)):
+                if t in (ctypes.c_int, ctypes.c_int64) and not isinstance(a, _INTS):
+                    raise TypeError("%s: argument %d must be an integer, got %r" % (name, k, a))
+                if t is ctypes.c_double and not isinstance(a, _INTS + _FLOATS):
+                    raise TypeError("%s: argument %d must be a number, got %r" % (name, k, a))
+            self._events.append((name, args))
+            return 0
+        return record
+
+
+def install(monkeypatch, events):
+    """engine.lib / _ffi.lib -> a stand-in, _ffi.init and engine._bind_stream -> recorders, all logging into `events`."""
+    standin = StandIn(events)
+    monkeypatch.setattr(engine, "lib", lambda: standin)
+    monkeypatch.setattr(_ffi, "lib", lambda: standin)
+    monkeypatch.setattr(_ffi, "init", lambda device=-1: events.append(("init", device)))
+    monkeypatch.setattr(engine, "_bind_stream", lambda x: events.append(("bind",)))
+    return standin
+
+
+def _is_tensor(a):
+    return torch is not None and isinstance(a, torch.Tensor)
+
+
+def _span(a):
+    """(first byte, one past the last byte) of the memory an array's elements lie in"""
+    if _is_tensor(a):
+        if a.numel() == 0:
+            return 0, 0
+        reach = 1 + sum((int(d) - 1) * int(s) for d, s in zip(a.shape, a.stride()))
+        return int(a.data_ptr()), int(a.data_ptr()) + reach * a.element_size()
+    if a.size == 0:
+        return 0, 0
+    reach = a.itemsize + sum((d - 1) * abs(s) for d, s in zip(a.shape, a.strides))
+    return int(a.ctypes.data), int(a.ctypes.data) + reach
+
+
+def _arrays_of(result, found):
+    """the arrays a call returned, in order, through tuples, lists, dicts and Nones"""
+    if isinstance(result, (tuple, list)):
+        for v in result:
+            _arrays_of(v, found)
+    elif isinstance(result, dict):
+        for k in sorted(result):
+            _arrays_of(result[k], found)
+    elif isinstance(result, np.ndarray) or _is_tensor(result):
+        found.append(result)
+    return found
+
+
+def _describe(result):
+    if result is None:
+        return None
+    if isinstance(result, (tuple, list)):
+        return [_describe(v) for v in result]
+    if isinstance(result, dict):
+        return {k: _describe(result[k]) for k in sorted(result)}
+    if _is_tensor(result):
+        return {"kind": "torch", "dtype": str(result.dtype).replace("torch.", ""), "shape": [int(d) for d in result.shape],
+                "contiguous": bool(result.is_contiguous())}
+    if isinstance(result, np.ndarray):
+        return {"kind": "numpy", "dtype": str(result.dtype), "shape": [int(d) for d in result.shape],
+                "contiguous": bool(result.flags["C_CONTIGUOUS"])}
+    if isinstance(result, np.generic):               # an element of an output: under the stand-in its value is uninitialised memory
+        return {"kind": "numpy scalar", "dtype": str(result.dtype)}
+    if isinstance(result, complex):
+        return {"kind": "complex", "value": [result.real, result.imag]}
+    if isinstance(result, (bool, int, float, str)):
+        return {"kind": type(result).__name__, "value": result}
+    raise TypeError("a result the trace does not describe: %r" % (result,))
+
+
+def _normalise(arg, ins, outs):
+    if arg is None:
+        return None
+    if isinstance(arg, _INTS):
+        return int(arg)
+    if isinstance(arg, _FLOATS):
+        return float(arg)
+    if isinstance(arg, ctypes.c_void_p):
+        if not arg.value:
+            return None
+        for tag, arrays in (("in", ins), ("out", outs)):
+            for k, a in enumerate(arrays):
+                lo, hi = _span(a)
+                if lo <= arg.value < hi:
+                    return [tag, k, arg.value - lo]
+        return "tmp"
+    return type(arg).__name__
+
+
+class Arrays:
+    """Makes the arrays of one case in the mode under test (numpy, or torch tensors on the CPU) and keeps them, in order, as the
+    candidates an "in" pointer is resolved against.  Views are taken by the case from what this returns, so they resolve to their base."""
+
+    def __init__(self, mode):
+        self.dev = mode == "dev"
+        self.made = []
+
+    def __call__(self, shape, dtype="float32", host=False):
+        size = int(np.prod(shape))
+        v = (np.arange(size) % 7 - 3.0) / 4.0 + 0.125
+        if np.dtype(dtype).kind == "c":
+            v = v + 1j * ((np.arange(size) % 5 - 2.0) / 4.0)
+        a = np.ascontiguousarray(v.reshape(shape).astype(dtype))
+        if self.dev and not host:
+            a = torch.from_numpy(a)
+        self.made.append(a)
+        return a
+
+
+def run_case(monkeypatch, case, mode):
+    """One call of the table under the stand-in -> what is kept of it (JSON-able)."""
+    name, fn, build = case
+    events = []
+    with monkeypatch.context() as mp:
+        install(mp, events)
+        A = Arrays(mode)
+        args, kwargs = build(A)
+        kept = {}
+        result = None
+        try:
+            result = getattr(engine, fn)(*args, **kwargs)
+            kept["returned"] = _describe(result)
+        except REFUSAL_TYPES as e:
+            kept["refused"] = {"message": str(e), "types": [t.__name__ for t in REFUSAL_TYPES if isinstance(e, t)]}
+        outs = _arrays_of(result, [])
+        kept["events"] = [[ev[0]] + [_normalise(a, A.made, outs) for a in (ev[1] if ev[0].startswith("sp_") else ev[1:])]
+                          for ev in events]
+    return kept
+
+
+def run_table(monkeypatch, only=None):
+    """{case id: what was kept} over the table, both modes; case id = function/name/mode"""
+    out = {}
+    for case in CASES:
+        for mode in MODES:
+            key = "%s/%s/%s" % (case[1], case[0], mode)
+            if only is None or key in only:
+                out[key] = run_case(monkeypatch, case, mode)
+    return out
+
+
+# ------------------------------------------------------------------------------------------ the table
+N, NFFT, HOP, NFR = 512, 64, 32, 15           # a record, and frames of it: (NFR - 1) * HOP + NFFT = N
+WIN = np.hanning(NFFT)                        # float64: the engine's float32 copy of it is a "tmp"
+WIN32 = np.hanning(32)
+TAPS = np.hanning(9) / 4.0
+SOS = np.array([[0.2, 0.1, 0.2, 1.0, -0.5, 0.25], [0.3, 0.0, -0.3, 1.0, 0.1, 0.5]])
+CASES = []
+
+
+def case(fn, name, build):
+    CASES.append((name, fn, build))
+
+
+def K(*args, **kwargs):
+    return args, kwargs
+
+
+F32, C64, F64, C128 = "float32", "complex64", "float64", "complex128"
+
+# -- fft, mean
+case("fft", "c64-rows", lambda A: K(A((4, NFFT), C64)))
+case("fft", "f32-cast", lambda A: K(A((4, NFFT), F32)))
+case("fft", "inverse", lambda A: K(A((NFFT,), C64), inverse=True))
+case("fft", "axis0", lambda A: K(A((NFFT, 3), C64), axis=0))
+case("fft", "n-longer", lambda A: K(A((2, 48), C64), n=64))
+case("fft", "n-shorter", lambda A: K(A((2, 48), C64), n=32))
+for dt in (F32, C64, F64):
+    case("mean", dt, lambda A, dt=dt: K(A((N,), dt)))
+
+# -- Welch PSD and its sharded halves
+for dt in (F32, C64, F64):
+    case("welch_psd", dt, lambda A, dt=dt: K(A((N,), dt), WIN, HOP, NFR))
+case("welch_psd", "strided", lambda A: K(A((2 * N,), C64)[::2], WIN, HOP, NFR))
+case("welch_psd", "mean-value", lambda A: K(A((N,), C64), WIN, HOP, NFR, mean_value=0.25 - 0.5j, scale=0.5))
+case("welch_psd", "no-detrend-one", lambda A: K(A((N,), F32), WIN, HOP, NFR, detrend=False, sided=engine.SIDED_ONE))
+case("welch_psd", "linear-half", lambda A: K(A((N,), F32), WIN, HOP, NFR, detrend="linear", sided=engine.SIDED_HALF))
+case("welch_psd", "segmean", lambda A: K(A((N,), F32), WIN, HOP, NFR, detrend=3))
+case("welch_psd", "seglinear", lambda A: K(A((N,), F32), WIN, HOP, NFR, detrend="seglinear"))
+for fn in ("welch_accum", "welch_export"):
+    case(fn, "c64", lambda A: K(A((N,), C64), WIN, HOP, NFR))
+    case(fn, "f32-nmean", lambda A: K(A((N,), F32), WIN, HOP, NFR - 2, nmean=400))
+    case(fn, "f64", lambda A: K(A((N,), F64), WIN, HOP, NFR))
+case("welch_apply", "f64", lambda A: K(A((5 * NFFT + 8,), F64), WIN, 30))
+case("welch_apply", "f32-one", lambda A: K(A((5 * NFFT + 8,), F32), WIN, 30, sided=engine.SIDED_ONE, scale=2.0))
+case("welch_finish", "own-mean", lambda A: K(NFFT, None, 30, like=A((1,), F32)))
+case("welch_finish", "mean-f64", lambda A: K(NFFT, A((2,), F64), 30, sided=engine.SIDED_ONE, scale=2.0))
+case("welch_finish", "mean-f32", lambda A: K(NFFT, A((2,), F32), 30))
+
+# -- cross spectra
+case("welch_csd", "f32-3ch", lambda A: K(A((N,), F32), A((3, N), F32), WIN, HOP, NFR))
+case("welch_csd", "y-1d", lambda A: K(A((N,), F32), A((N,), F32), WIN, HOP, NFR, detrend=False, sided=engine.SIDED_TWO, scale=0.5))
+case("welch_csd", "c64", lambda A: K(A((N,), C64), A((2, N), C64), WIN, HOP, NFR, detrend="linear"))
+case("welch_csd", "y-rows-longer", lambda A: K(A((N,), F32), A((2, N + 5), F32), WIN, HOP, NFR))
+case("welch_csd", "real-x-complex-y", lambda A: K(A((N,), F32), A((2, N), C64), WIN, HOP, NFR))
+case("welch_csd", "f64", lambda A: K(A((N,), F64), A((2, N), F64), WIN, HOP, NFR))
+case("welch_csd", "y-f64", lambda A: K(A((N,), F32), A((2, N), F64), WIN, HOP, NFR))
+case("welch_csd", "host-y", lambda A: K(A((N,), F32), A((2, N), F32, host=True), WIN, HOP, NFR))
+case("welch_csd", "y-short", lambda A: K(A((N,), F32), A((2, N - 1), F32), WIN, HOP, NFR))
+case("welch_csd", "x-2d", lambda A: K(A((1, N), F32), A((2, N), F32), WIN, HOP, NFR))
+case("csd_matrix", "plain", lambda A: K(A((3, N), F32), WIN, HOP, NFR))
+case("csd_matrix", "no-detrend", lambda A: K(A((3, N), F32), WIN, HOP, NFR, detrend=False, scale=0.5))
+case("csd_matrix", "means", lambda A: K(A((3, N), F32), WIN, HOP, NFR, means=A((3,), F64)))
+case("csd_matrix", "means-list", lambda A: K(A((3, N), F32), WIN, HOP, NFR, means=[0.5, 0.25, 0.0]))
+case("csd_matrix", "means-wrong", lambda A: K(A((3, N), F32), WIN, HOP, NFR, means=A((2,), F64)))
+case("csd_matrix", "f64", lambda A: K(A((3, N), F64), WIN, HOP, NFR))
+case("csd_matrix", "transposed", lambda A: K(A((N, 3), F32).T, WIN, HOP, NFR))
+case("channel_means", "plain", lambda A: K(A((3, N), F32)))
+case("channel_means", "nsamples", lambda A: K(A((3, N), F32), nsamples=400))
+case("channel_means", "f64", lambda A: K(A((3, N), F64)))
+
+# -- STFT and its inverse
+for dt in (F32, C64, F64):
+    case("stft_frames", dt, lambda A, dt=dt: K(A((N,), dt), WIN, HOP, NFR))
+case("stft_frames", "power", lambda A: K(A((N,), F32), WIN, HOP, NFR, power=True, amp_scale=0.5))
+case("stft_frames", "bin-major", lambda A: K(A((N,), C64), WIN, HOP, NFR, bin_major=True, sided=engine.SIDED_TWO))
+case("stft_frames", "pseg", lambda A: K(A((N,), F32), WIN, HOP, NFR, want_pseg=True))
+case("stft_frames", "power-bin-major-pseg", lambda A: K(A((N,), C64), WIN, HOP, NFR, power=True, bin_major=True, want_pseg=True,
+                                                          sided=engine.SIDED_RAW))
+case("stft_frames", "mean-value", lambda A: K(A((N,), C64), WIN, HOP, NFR, mean_value=0.5 + 0.25j))
+case("stft_frames", "segmean", lambda A: K(A((N,), F32), WIN, HOP, NFR, detrend="segmean"))
+case("istft_frames", "half", lambda A: K(A((NFR, NFFT // 2 + 1), C64), WIN, HOP))
+case("istft_frames", "raw-lead", lambda A: K(A((2, NFR, NFFT), C64), WIN, HOP, sided=engine.SIDED_RAW))
+case("istft_frames", "bin-major", lambda A: K(A((NFFT // 2 + 1, NFR), C64), WIN, HOP, bin_major=True))
+case("istft_frames", "skip-nout-scale", lambda A: K(A((NFR, NFFT // 2 + 1), C64), WIN, HOP, scale=2.0, skip=16, nout=300))
+case("istft_frames", "c128", lambda A: K(A((NFR, NFFT // 2 + 1), C128), WIN, HOP))
+case("istft_frames", "transposed", lambda A: K(A((NFFT // 2 + 1, NFR), C64).T, WIN, HOP))
+case("istft_frames", "sided-refused", lambda A: K(A((NFR, NFFT), C64), WIN, HOP, sided=engine.SIDED_TWO))
+case("istft_frames", "1d-refused", lambda A: K(A((NFFT,), C64), WIN, HOP))
+case("istft_frames", "bins-refused", lambda A: K(A((NFR, NFFT), C64), WIN, HOP))
+
+# -- bispectrum, multitaper
+case("bispectrum", "auto", lambda A: K(A((N,), F32), WIN, HOP, NFR))
+case("bispectrum", "y-z", lambda A: K(A((N,), F32), WIN, HOP, NFR, y=A((N,), F32), z=A((N,), F32)))
+case("bispectrum", "y-only-c64", lambda A: K(A((N,), C64), WIN, HOP, NFR, y=A((N,), C64), detrend="linear"))
+case("bispectrum", "z-only-mean-value", lambda A: K(A((N,), F32), WIN, HOP, NFR, z=A((N,), F32), mean_value=0.5))
+case("bispectrum", "y-short", lambda A: K(A((N,), F32), WIN, HOP, NFR, y=A((N - 1,), F32)))
+case("bispectrum", "y-other-dtype", lambda A: K(A((N,), F32), WIN, HOP, NFR, y=A((N,), C64)))
+case("bispectrum", "segmean-refused", lambda A: K(A((N,), F32), WIN, HOP, NFR, detrend="segmean"))
+case("bispectrum", "f64", lambda A: K(A((N,), F64), WIN, HOP, NFR, y=A((N,), F64)))
+TAPERS = np.stack([np.hanning(NFFT), np.hamming(NFFT), np.blackman(NFFT)])
+case("multitaper", "plain", lambda A: K(A((N,), F32), TAPERS, HOP, NFR))
+case("multitaper", "y", lambda A: K(A((N,), F32), TAPERS, HOP, NFR, y=A((N,), F32), scale=0.5))
+case("multitaper", "weights", lambda A: K(A((N,), F32), TAPERS, HOP, NFR, weights=[1.0, 0.5, 0.25]))
+case("multitaper", "y-weights-c64", lambda A: K(A((N,), C64), TAPERS, HOP, NFR, y=A((N,), C64), weights=[1.0, 0.5, 0.25],
+                                                 detrend="linear"))
+case("multitaper", "mean-value", lambda A: K(A((N,), C64), TAPERS, HOP, NFR, mean_value=0.5 - 0.25j))
+case("multitaper", "y-short", lambda A: K(A((N,), F32), TAPERS, HOP, NFR, y=A((N - 1,), F32)))
+case("multitaper", "tapers-1d-refused", lambda A: K(A((N,), F32), TAPERS[0], HOP, NFR))
+case("multitaper", "weights-refused", lambda A: K(A((N,), F32), TAPERS, HOP, NFR, weights=[1.0, 0.5]))
+case("multitaper", "segmean-refused", lambda A: K(A((N,), F32), TAPERS, HOP, NFR, detrend="segmean"))
+case("multitaper", "f64", lambda A: K(A((N,), F64), TAPERS, HOP, NFR, y=A((N,), F64)))
+
+# -- chirp-z, zoom
+RN = 200                                       # a row; the strided views keep RN of RN + 3
+case("czt", "1d", lambda A: K(A((RN,), F32), 50, 0.1, 0.001))
+case("czt", "rows-c64", lambda A: K(A((3, RN), C64), 50, 0.1, 0.001))
+case("czt", "strided-rows", lambda A: K(A((3, RN + 3), C64)[:, :RN], 50, 0.1, 0.001))
+case("czt", "strided-rows-offset", lambda A: K(A((3, RN + 3), F32)[1:, 2:RN + 2], 50, 0.1, 0.001))
+case("czt", "3d", lambda A: K(A((2, 2, RN), F32), 50, 0.1, 0.001))
+case("czt", "3d-strided", lambda A: K(A((2, 2, RN + 3), F32)[..., :RN], 50, 0.1, 0.001))
+case("czt", "transposed", lambda A: K(A((RN, 3), F32).T, 50, 0.1, 0.001))
+case("czt", "f64", lambda A: K(A((RN,), F64), 50, 0.1, 0.001))
+case("czt", "0d", lambda A: K(A((), F32), 50, 0.1, 0.001))
+case("zoom_welch", "plain", lambda A: K(A((N,), F32), WIN, HOP, NFR, 40, 0.1, 0.001))
+case("zoom_welch", "y-c64", lambda A: K(A((N,), C64), WIN, HOP, NFR, 40, 0.1, 0.001, y=A((N,), C64), detrend="linear", scale=0.5))
+case("zoom_welch", "frames", lambda A: K(A((N,), F32), WIN, HOP, NFR, 40, 0.1, 0.001, frames=True))
+case("zoom_welch", "mean-value", lambda A: K(A((N,), C64), WIN, HOP, NFR, 40, 0.1, 0.001, detrend=True, mean_value=0.5 + 1j))
+case("zoom_welch", "frames-y-refused", lambda A: K(A((N,), F32), WIN, HOP, NFR, 40, 0.1, 0.001, y=A((N,), F32), frames=True))
+case("zoom_welch", "segmean-refused", lambda A: K(A((N,), F32), WIN, HOP, NFR, 40, 0.1, 0.001, detrend="segmean"))
+case("zoom_welch", "y-short", lambda A: K(A((N,), F32), WIN, HOP, NFR, 40, 0.1, 0.001, y=A((N - 1,), F32)))
+case("zoom_welch", "f64", lambda A: K(A((N,), F64), WIN, HOP, NFR, 40, 0.1, 0.001))
+
+# -- down-converter, resampler, filter banks
+case("ddc", "1d", lambda A: K(A((RN,), F32), 0.1, 4, TAPS))
+case("ddc", "rows-c64-n0", lambda A: K(A((3, RN), C64), 0.1, 3, TAPS, n0=17))
+case("ddc", "strided-rows", lambda A: K(A((3, RN + 3), C64)[:, :RN], 0.1, 4, TAPS))
+case("ddc", "3d", lambda A: K(A((2, 2, RN), F32), 0.1, 4, TAPS))
+case("ddc", "transposed", lambda A: K(A((RN, 3), F32).T, 0.1, 4, TAPS))
+case("ddc", "f64", lambda A: K(A((RN,), F64), 0.1, 4, TAPS))
+case("ddc", "complex-taps-refused", lambda A: K(A((RN,), F32), 0.1, 4, TAPS + 0j))
+case("ddc", "taps-2d-refused", lambda A: K(A((RN,), F32), 0.1, 4, TAPS[None, :]))
+case("ddc", "q-refused", lambda A: K(A((RN,), F32), 0.1, 65, TAPS))
+case("ddc", "0d", lambda A: K(A((), F32), 0.1, 4, TAPS))
+case("upfirdn", "1d", lambda A: K(A((RN,), F32), TAPS, 3, 2))
+case("upfirdn", "rows-c64-window", lambda A: K(A((3, RN), C64), TAPS, 3, 2, m0=5, nout=100))
+case("upfirdn", "strided-rows", lambda A: K(A((3, RN + 3), F32)[:, :RN], TAPS, 3, 2))
+case("upfirdn", "3d", lambda A: K(A((2, 2, RN), F32), TAPS, 2, 3))
+case("upfirdn", "transposed", lambda A: K(A((RN, 3), F32).T, TAPS, 3, 2))
+case("upfirdn", "f64", lambda A: K(A((RN,), F64), TAPS, 3, 2))
+case("upfirdn", "up-refused", lambda A: K(A((RN,), F32), TAPS, 0, 2))
+case("upfirdn", "taps-empty-refused", lambda A: K(A((RN,), F32), TAPS[:0], 3, 2))
+case("upfirdn", "m0-refused", lambda A: K(A((RN,), F32), TAPS, 3, 2, m0=-1))
+case("upfirdn", "0d", lambda A: K(A((), F32), TAPS, 3, 2))
+PM, PTAPS = 16, np.hanning(64)
+case("pfb", "c64", lambda A: K(A((RN,), C64), PTAPS, PM, 8, 0, 10))
+case("pfb", "f32-major1-phase", lambda A: K(A((3, RN), F32), PTAPS, PM, 8, -3, 10, phase_ref=1, r0=5, out_major=1))
+case("pfb", "power", lambda A: K(A((3, RN), C64), PTAPS, PM, 8, 0, 10, power=True, scale=0.5))
+case("pfb", "strided-rows", lambda A: K(A((3, RN + 3), C64)[:, :RN], PTAPS, PM, 8, 0, 10))
+case("pfb", "3d", lambda A: K(A((2, 2, RN), F32), PTAPS, PM, 8, 0, 10))
+case("pfb", "transposed", lambda A: K(A((RN, 3), F32).T, PTAPS, PM, 8, 0, 10))
+case("pfb", "f64", lambda A: K(A((RN,), F64), PTAPS, PM, 8, 0, 10))
+case("pfb", "M-refused", lambda A: K(A((RN,), F32), PTAPS, 1, 8, 0, 10))
+case("pfb", "complex-taps-refused", lambda A: K(A((RN,), F32), PTAPS + 0j, PM, 8, 0, 10))
+case("pfb", "0d", lambda A: K(A((), F32), PTAPS, PM, 8, 0, 10))
+case("pfb_synth", "onesided", lambda A: K(A((10, PM // 2 + 1), C64), PTAPS, PM, 8, 0, 128))
+case("pfb_synth", "full-lead-phase", lambda A: K(A((2, 10, PM), C64), PTAPS, PM, 8, -3, 128, phase_ref=1, r0=5, onesided=False,
+                                                  scale=0.5))
+case("pfb_synth", "in-major1", lambda A: K(A((PM // 2 + 1, 10), C64), PTAPS, PM, 8, 0, 128, in_major=1))
+case("pfb_synth", "transposed", lambda A: K(A((PM // 2 + 1, 10), C64).T, PTAPS, PM, 8, 0, 128))
+case("pfb_synth", "c128", lambda A: K(A((10, PM // 2 + 1), C128), PTAPS, PM, 8, 0, 128))
+case("pfb_synth", "bins-refused", lambda A: K(A((10, PM), C64), PTAPS, PM, 8, 0, 128))
+case("pfb_synth", "major-refused", lambda A: K(A((10, PM // 2 + 1), C64), PTAPS, PM, 8, 0, 128, in_major=2))
+
+# -- frame reductions
+for dt in (F32, C64, F64):
+    case("stft_cog", dt, lambda A, dt=dt: K(A((N,), dt), WIN, HOP, NFR, 1000.0))
+case("stft_cog", "band-mean-value", lambda A: K(A((N,), C64), WIN, HOP, NFR, 1000.0, fmin=10.0, fmax=400.0, detrend=True,
+                                                 mean_value=0.5j))
+case("stft_cog", "segmean", lambda A: K(A((N,), F32), WIN, HOP, NFR, 1000.0, detrend="segmean"))
+case("hilbert_rows", "f32", lambda A: K(A((3, 50), F32), 64))
+case("hilbert_rows", "f64", lambda A: K(A((3, 50), F64), 64))
+case("hilbert_rows", "transposed", lambda A: K(A((50, 3), F32).T, 64))
+case("frame_sum", "f32", lambda A: K(A((3, N), F32), NFFT, HOP, NFR))
+case("frame_sum", "c64-linear", lambda A: K(A((3, N), C64), NFFT, HOP, NFR, detrend="linear"))
+case("frame_sum", "f64-no-detrend", lambda A: K(A((3, N), F64), NFFT, HOP, NFR, detrend=False))
+case("frame_sum", "c128", lambda A: K(A((3, N), C128), NFFT, HOP, NFR))
+case("frame_sum", "transposed", lambda A: K(A((N, 3), F32).T, NFFT, HOP, NFR))
+case("frame_sum", "segmean-refused", lambda A: K(A((3, N), F32), NFFT, HOP, NFR, detrend="segmean"))
+HTAB = np.exp(-1j * np.arange(NFFT) / 7.0)
+case("spectral_filter_rows", "f32", lambda A: K(A((3, 50), F32), HTAB))
+case("spectral_filter_rows", "f64", lambda A: K(A((3, 50), F64), HTAB))
+case("spectral_filter_rows", "transposed", lambda A: K(A((50, 3), F32).T, HTAB))
+
+# -- correlations, wavenumber spectra
+case("xcorr_normalised", "f32", lambda A: K(A((RN,), F32), A((RN,), F32)))
+case("xcorr_normalised", "f64", lambda A: K(A((RN,), F64), A((RN,), F32)))
+case("xcorr_normalised", "complex-refused", lambda A: K(A((RN,), F32), A((RN,), C64)))
+case("xcorr_normalised", "length-refused", lambda A: K(A((RN,), F32), A((RN - 1,), F32)))
+case("xcorr_normalised", "2d-refused", lambda A: K(A((2, RN), F32), A((2, RN), F32)))
+case("xcorr_normalised", "host-x2", lambda A: K(A((RN,), F32), A((RN,), F32, host=True)))
+XW, XLAG = 32, 8
+case("xcorr_frames", "frames", lambda A: K(A((N,), F32), A((N,), F32), XW, 16, 31, XLAG, frames=True))
+case("xcorr_frames", "avg-c64", lambda A: K(A((N,), C64), A((N,), C64), XW, 16, 31, XLAG, avg=True, segmean=False, coeff=False))
+case("xcorr_frames", "peak-win-beta", lambda A: K(A((N,), F32), A((N,), F32), XW, 16, 31, XLAG, win=WIN32, beta=0.01, peak=True))
+case("xcorr_frames", "all-weight", lambda A: K(A((N,), F32), A((N,), F32), XW, 16, 31, XLAG, frames=True, avg=True, peak=True,
+                                                weight=np.ones(int(engine.lib().sp_xcorr_frames_len(XW, XLAG)))))
+case("xcorr_frames", "f64", lambda A: K(A((N,), F64), A((N,), F64), XW, 16, 31, XLAG, avg=True))
+case("xcorr_frames", "nothing-asked-refused", lambda A: K(A((N,), F32), A((N,), F32), XW, 16, 31, XLAG))
+case("xcorr_frames", "win-refused", lambda A: K(A((N,), F32), A((N,), F32), XW, 16, 31, XLAG, win=WIN, avg=True))
+case("xcorr_frames", "weight-refused", lambda A: K(A((N,), F32), A((N,), F32), XW, 16, 31, XLAG, weight=np.ones(3), avg=True))
+case("xcorr_frames", "y-short", lambda A: K(A((N,), F32), A((N - 1,), F32), XW, 16, 31, XLAG, avg=True))
+case("xcorr_frames", "y-other-dtype", lambda A: K(A((N,), F32), A((N,), C64), XW, 16, 31, XLAG, avg=True))
+case("xcorr_frames", "host-y", lambda A: K(A((N,), F32), A((N,), F32, host=True), XW, 16, 31, XLAG, avg=True))
+case("skf", "plain", lambda A: K(A((N,), F32), A((N,), F32), NFFT, HOP, NFR, 1, 31, 16))
+case("skf", "win-cross-c64", lambda A: K(A((N,), C64), A((N,), C64), NFFT, HOP, NFR, 40, 30, 17, win=WIN, segmean=False, cross=True,
+                                          scale=0.5))
+case("skf", "f64", lambda A: K(A((N,), F64), A((N,), F64), NFFT, HOP, NFR, 1, 31, 16))
+case("skf", "win-refused", lambda A: K(A((N,), F32), A((N,), F32), NFFT, HOP, NFR, 1, 31, 16, win=WIN32))
+case("skf", "y-short", lambda A: K(A((N,), F32), A((N - 1,), F32), NFFT, HOP, NFR, 1, 31, 16))
+case("skf", "host-y", lambda A: K(A((N,), F32), A((N,), F32, host=True), NFFT, HOP, NFR, 1, 31, 16))
+
+# -- time-resolved Welch spectra
+case("welch_blocks", "x-only", lambda A: K(A((N,), F32), WIN, HOP, NFR, 4))
+case("welch_blocks", "y-1d-step-doubled", lambda A: K(A((N,), F32), WIN, HOP, NFR, 4, step=2, y=A((N,), F32), doubled=True, scale=0.5))
+case("welch_blocks", "y-rows-longer-c64", lambda A: K(A((N,), C64), WIN, HOP, NFR, 4, y=A((2, N + 5), C64), detrend=False))
+case("welch_blocks", "boxcar", lambda A: K(A((N,), F32), None, HOP, NFR, 4, nfft=NFFT, detrend="constant"))
+case("welch_blocks", "real-x-complex-y", lambda A: K(A((N,), F32), WIN, HOP, NFR, 4, y=A((N,), C64)))
+case("welch_blocks", "complex-x-real-y", lambda A: K(A((N,), C64), WIN, HOP, NFR, 4, y=A((N,), F32)))
+case("welch_blocks", "f64", lambda A: K(A((N,), F64), WIN, HOP, NFR, 4, y=A((N,), F64)))
+case("welch_blocks", "host-y", lambda A: K(A((N,), F32), WIN, HOP, NFR, 4, y=A((N,), F32, host=True)))
+case("welch_blocks", "nfft-refused", lambda A: K(A((N,), F32), np.hanning(48), HOP, 10, 4))
+case("welch_blocks", "no-nfft-refused", lambda A: K(A((N,), F32), None, HOP, NFR, 4))
+case("welch_blocks", "y-short-refused", lambda A: K(A((N,), F32), WIN, HOP, NFR, 4, y=A((N - 1,), F32)))
+case("welch_blocks", "y-3d-refused", lambda A: K(A((N,), F32), WIN, HOP, NFR, 4, y=A((1, 1, N), F32)))
+case("welch_blocks", "detrend-refused", lambda A: K(A((N,), F32), WIN, HOP, NFR, 4, detrend="linear"))
+case("welch_blocks", "scale-refused", lambda A: K(A((N,), F32), WIN, HOP, NFR, 4, scale=float("inf")))
+
+# -- wavelets
+SCALES, CL, CM = [2.0, 4.0, 8.0], 256, 32
+case("cwt", "W", lambda A: K(A((400,), F32), SCALES, "morlet", 6.0, CL, CM))
+case("cwt", "gws-only-paul", lambda A: K(A((400,), C64), SCALES, "paul", 4.0, CL, CM, W=False, gws=True))
+case("cwt", "recon-only", lambda A: K(A((2, 400), F32), SCALES, "morlet", 6.0, CL, CM, W=False, recon=[1.0, 0.5, 0.25]))
+case("cwt", "bandpow-only", lambda A: K(A((2, 400), F32), SCALES, "morlet", 6.0, CL, CM, W=False, bandpow=[1.0, 0.5, 0.25]))
+case("cwt", "all", lambda A: K(A((2, 2, 400), C64), SCALES, "morlet", 6.0, CL, CM, gws=True, recon=[1.0, 0.5, 0.25],
+                               bandpow=[1.0, 0.5, 0.25]))
+case("cwt", "strided-rows", lambda A: K(A((3, 403), C64)[:, :400], SCALES, "morlet", 6.0, CL, CM))
+case("cwt", "transposed", lambda A: K(A((400, 3), F32).T, SCALES, "morlet", 6.0, CL, CM))
+case("cwt", "f64", lambda A: K(A((400,), F64), SCALES, "morlet", 6.0, CL, CM))
+case("cwt", "L-refused", lambda A: K(A((400,), F32), SCALES, "morlet", 6.0, 100, 10))
+case("cwt", "family-refused", lambda A: K(A((400,), F32), SCALES, "dog", 2.0, CL, CM))
+case("cwt", "no-output-refused", lambda A: K(A((400,), F32), SCALES, "morlet", 6.0, CL, CM, W=False))
+case("cwt", "weights-refused", lambda A: K(A((400,), F32), SCALES, "morlet", 6.0, CL, CM, recon=[1.0, 0.5]))
+case("cwt", "0d", lambda A: K(A((), F32), SCALES, "morlet", 6.0, CL, CM))
+case("icwt_sum", "plain", lambda A: K(A((3, 400), C64), [1.0, 0.5, 0.25]))
+case("icwt_sum", "lead", lambda A: K(A((2, 3, 400), C64), [1.0, 0.5, 0.25]))
+case("icwt_sum", "transposed", lambda A: K(A((400, 3), C64).T, [1.0, 0.5, 0.25]))
+case("icwt_sum", "c128", lambda A: K(A((3, 400), C128), [1.0, 0.5, 0.25]))
+case("icwt_sum", "no-weights-refused", lambda A: K(A((3, 400), C64), None))
+case("icwt_sum", "weights-wrong-refused", lambda A: K(A((3, 400), C64), [1.0, 0.5]))
+case("icwt_sum", "1d-refused", lambda A: K(A((400,), C64), [1.0]))
+
+# -- Hermitian eigensolver (check=False: under the stand-in the sweep counts are uninitialised memory)
+case("eigh", "c128", lambda A: K(A((5, 5), C128), check=False))
+case("eigh", "f64-batch", lambda A: K(A((2, 3, 5, 5), F64), check=False, max_sweeps=20))
+case("eigh", "c64-nvec2", lambda A: K(A((2, 5, 5), C64), nvec=2, check=False))
+case("eigh", "nvec0", lambda A: K(A((5, 5), C128), nvec=0, check=False))
+case("eigh", "transposed", lambda A: K(A((5, 5, 2), C128).permute(2, 1, 0) if A.dev else A((5, 5, 2), C128).transpose(2, 1, 0),
+                                      check=False))
+case("eigh", "order-refused", lambda A: K(A((65, 65), F32), check=False))
+case("eigh", "square-refused", lambda A: K(A((4, 5), F32), check=False))
+case("eigh", "nvec-refused", lambda A: K(A((5, 5), F32), nvec=6, check=False))
+
+# -- filters
+case("fir_filter", "f32", lambda A: K(TAPS, A((N,), F32)))
+case("fir_filter", "f64-nfft", lambda A: K(TAPS, A((N,), F64), nfft=128))
+B3, A3 = [0.2, 0.1, 0.2], [1.0, -0.5, 0.25]
+case("biquad_filter", "f32", lambda A: K(B3, A3, A((N,), F32)))
+case("biquad_filter", "f64-short-b", lambda A: K(B3[:2], A3, A((N,), F64)))
+case("biquad_filter", "complex-refused", lambda A: K(B3, A3, A((N,), C64)))
+case("biquad_filter", "2d-refused", lambda A: K(B3, A3, A((2, N), F32)))
+case("biquad_filter", "unstable-refused", lambda A: K(B3, [1.0, -2.5, 1.0], A((N,), F32)))
+case("sos_filter", "f32", lambda A: K(SOS, A((N,), F32)))
+case("sos_filter", "rows-f64", lambda A: K(SOS, A((3, N), F64)))
+case("sos_filter", "c64", lambda A: K(SOS, A((2, N), C64)))
+case("sos_filter", "c128", lambda A: K(SOS, A((N,), C128)))
+case("sos_filter", "zi", lambda A: K(SOS, A((3, N), F32), zi=A((2, 3, 2), F64)))
+case("sos_filter", "zi-real-complex-x", lambda A: K(SOS, A((N,), C64), zi=A((2, 2), F64)))
+case("sos_filter", "zi-complex", lambda A: K(SOS, A((N,), C64), zi=A((2, 2), C128)))
+case("sos_filter", "zi-complex-real-x", lambda A: K(SOS, A((N,), F32), zi=A((2, 2), C128)))
+case("sos_filter", "zi-host", lambda A: K(SOS, A((N,), F32), zi=A((2, 2), F64, host=True)))
+case("sos_filter", "zi-refused", lambda A: K(SOS, A((N,), F32), zi=A((2, 3), F64)))
+case("sos_filter", "empty-refused", lambda A: K(SOS, A((0,), F32)))
+case("sos_filter", "sos-refused", lambda A: K(SOS[:, :5], A((N,), F32)))
+case("sos_filtfilt", "odd", lambda A: K(SOS, A((N,), F32), padlen=15))
+case("sos_filtfilt", "none-rows-f64", lambda A: K(SOS, A((3, N), F64), padtype=None, padlen=15))
+case("sos_filtfilt", "even-c64", lambda A: K(SOS, A((N,), C64), padtype="even", padlen=9))
+case("sos_filtfilt", "constant-default", lambda A: K(SOS, A((N,), F32), padtype="constant"))
+case("sos_filtfilt", "padlen-refused", lambda A: K(SOS, A((10,), F32), padlen=10))
+case("sos_filtfilt", "padtype-refused", lambda A: K(SOS, A((N,), F32), padtype="wrap"))
+
+# -- the pwelch epilogue
+NB1 = NFFT // 2
+case("csd_epilogue", "onesided", lambda A: K(A((NB1,), F64), A((2, NB1), F64), A((2, NB1), C128), NFFT, True, 1.5))
+case("csd_epilogue", "twosided", lambda A: K(A((NFFT,), F64), A((2, NFFT), F64), A((2, NFFT), C128), NFFT, False, 1.5))
+case("csd_epilogue", "one-channel", lambda A: K(A((NB1,), F64), A((NB1,), F64), A((NB1,), C128), NFFT, True, 1.5))
+case("csd_epilogue", "casts", lambda A: K(A((NB1,), F32), A((2, NB1), F32), A((2, NB1), C64), NFFT, True, 1.5))
+case("csd_epilogue", "complex-powers", lambda A: K(A((NB1,), C128), A((2, NB1), C128), A((2, NB1), C128), NFFT, True, 1.5))
+
+FUNCTIONS = ("fft", "mean", "welch_psd", "welch_accum", "welch_export", "welch_apply", "welch_finish", "welch_csd", "csd_matrix",
+             "channel_means", "stft_frames", "istft_frames", "bispectrum", "multitaper", "czt", "zoom_welch", "ddc", "upfirdn", "pfb",
+             "pfb_synth", "stft_cog", "hilbert_rows", "frame_sum", "spectral_filter_rows", "xcorr_normalised", "xcorr_frames", "skf",
+             "welch_blocks", "cwt", "icwt_sum", "eigh", "fir_filter", "biquad_filter", "sos_filter", "sos_filtfilt", "csd_epilogue")
