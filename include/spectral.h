@@ -56,7 +56,7 @@ int sp_max_wg_fft(void);             /* largest power-of-two FFT done inside one
  * recorded on the launch stream; sp_profile_last_ms() waits for them and returns the kernel's duration. */
 int sp_profile_enable(int on);
 int sp_profile_last_ms(double *ms);
-const char *sp_profile_last_kernel(void); /* name of the kernel the last Welch call dispatched */
+const char *sp_profile_last_kernel(void); /* name of the kernel the last Welch call dispatched (also set by the pipeline paths of sp_stft_cog and sp_csd_matrix) */
 /* device properties used by the host to size grids: out[0]=CU count, out[1]=LDS bytes/CU,
  * out[2]=clock kHz, out[3]=wavefront size */
 int sp_device_info(int64_t out[4]);

@@ -358,20 +358,38 @@ __global__ __launch_bounds__(768) void k_welch_pipe(const void *__restrict__ x_i
             if constexpr (ONEPASS && !LOBE) spartial[gid * hop + tid + T * s] = sacc[s];
     } else if (role == 1) {
         // period p: the gather of frame p-1 is ISSUED first and lands while the butterflies of frame p-2 (gathered one period
-        // earlier into the other register set) run -- no wave starts a period by waiting for the LDS pipe
+        // earlier into the other register set) run -- no wave starts a period by waiting for the LDS pipe.
+        // STEADY: a period that does both (2 <= p <= trips) runs without the guards, two of them per trip of a loop of its own;
+        // the guarded form is left to the fill and drain periods around that loop.  The guards were uniform branches around the
+        // gather and around the transform (gfx950 has no scalar ordered 64-bit compare: each is a v_cmp_*_i64 that the branch
+        // waits for) and cut every period into four blocks; as one block per period the step is about 2 % shorter
+        // (profiles/r12_pipe_sched_ab.txt; counting the loop in 32 bits on top of that changed nothing, and so did not stay)
         f.template load_tw_one<1>(tb.tw, tid);
         cf va[R], vb[R];
-        auto step = [&](cf (&fill)[R], cf (&use)[R], int64_t p, const cf *src, cf *dst) __attribute__((always_inline)) {
-            if (p >= 1 && p <= trips) f.template gather<0>(fill, src, tid);
-            if (p >= 2 && p <= trips + 1) {
+        auto step = [&](auto steady, cf (&fill)[R], cf (&use)[R], int64_t p, const cf *src, cf *dst) __attribute__((always_inline)) {
+            constexpr bool STEADY = decltype(steady)::value;
+            if (STEADY || (p >= 1 && p <= trips)) f.template gather<0>(fill, src, tid);
+            if (STEADY || (p >= 2 && p <= trips + 1)) {
                 if constexpr (UPROT) f.template bfly_scatter_rot<1, true>(use, tau_out, dst, tid);
                 else f.template bfly_scatter<1>(use, dst, tid);
             }
             __syncthreads();
+            // (keeps the two periods of a trip apart: hipcc otherwise starts the second one's butterflies above the barrier, with
+            //  both register sets and their temporaries live at once: 166 VGPRs instead of 142)
+            if constexpr (STEADY) __builtin_amdgcn_sched_barrier(0);
         };
-        for (int64_t p = 0; p < periods; p += 2) {
-            step(va, vb, p, imgA + IMG, imgB);
-            if (p + 1 < periods) step(vb, va, p + 1, imgA, imgB + IMGB);
+        const std::true_type yes;
+        const std::false_type no;
+        step(no, va, vb, 0, imgA + IMG, imgB);                    // (periods >= DRAIN = 4)
+        step(no, vb, va, 1, imgA, imgB + IMGB);
+        int64_t p = 2;
+        for (; p + 1 <= trips; p += 2) {
+            step(yes, va, vb, p, imgA + IMG, imgB);
+            step(yes, vb, va, p + 1, imgA, imgB + IMGB);
+        }
+        for (; p < periods; p += 2) {
+            step(no, va, vb, p, imgA + IMG, imgB);
+            if (p + 1 < periods) step(no, vb, va, p + 1, imgA, imgB + IMGB);
         }
     } else {
         f.template load_tw_one<2>(tb.tw, tid);
@@ -393,11 +411,13 @@ __global__ __launch_bounds__(768) void k_welch_pipe(const void *__restrict__ x_i
             const int64_t gg = g0 + (i - sel) + li;
             if (li <= sel && gg < nframes) reinterpret_cast<cf *>(partial)[(int64_t)(tid >> 6) * nframes + gg] = pend;
         };
-        auto step = [&](cf (&fill)[R], cf (&use)[R], int64_t p, const cf *src) __attribute__((always_inline)) {
-            if (p >= 3 && p <= trips + 2) {
+        // STEADY (4 <= p <= trips + 2: the period gathers and transforms): no guards, as in the middle role
+        auto step = [&](auto steady, cf (&fill)[R], cf (&use)[R], int64_t p, const cf *src) __attribute__((always_inline)) {
+            constexpr bool STEADY = decltype(steady)::value;
+            if (STEADY || (p >= 3 && p <= trips + 2)) {
                 f.template gather<1>(fill, src, tid);
             }
-            if (p >= 4 && p <= trips + 3) {
+            if (STEADY || (p >= 4 && p <= trips + 3)) {
                 if constexpr (UPROT) f.template bfly_prerot<2>(use, tid);
                 else f.template bfly<2>(use, tid);
                 if constexpr (SPEC) {
@@ -453,10 +473,23 @@ __global__ __launch_bounds__(768) void k_welch_pipe(const void *__restrict__ x_i
                 }
             }
             __syncthreads();
+            if constexpr (STEADY) __builtin_amdgcn_sched_barrier(0);      // (as in the middle role)
         };
-        for (int64_t p = 0; p < periods; p += 2) {
-            step(va, vb, p, imgB + IMGB);
-            if (p + 1 < periods) step(vb, va, p + 1, imgB);
+        const std::true_type yes;
+        const std::false_type no;
+        int64_t p = 0;
+#pragma unroll 1
+        for (; p < DRAIN; p += 2) {                               // (periods >= DRAIN)
+            step(no, va, vb, p, imgB + IMGB);
+            step(no, vb, va, p + 1, imgB);
+        }
+        for (; p + 1 <= trips + 2; p += 2) {
+            step(yes, va, vb, p, imgB + IMGB);
+            step(yes, vb, va, p + 1, imgB);
+        }
+        for (; p < periods; p += 2) {
+            step(no, va, vb, p, imgB + IMGB);
+            if (p + 1 < periods) step(no, vb, va, p + 1, imgB);
         }
         if constexpr (!COG && !SPEC) {
 #pragma unroll

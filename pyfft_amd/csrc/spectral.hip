@@ -2133,6 +2133,7 @@ static int csd_matrix_impl(const char *who, const float *x, int nch, int64_t nsi
             LAUNCHCHK(launch_welch_pipe(lc(), xd + (size_t)f0 * (size_t)hop, false, (const float *)win_d, hop, m, tb.f + 4 * nch, xf,
                                         (float *)Xs, rp, spartial, 5, nch, x_ld, nfft / 8));
             LAUNCHCHK(launch_csdm_bf16(lc(), Xs, Xt, nch, pairs, nfft, (double *)g.cmH.p, nfft, split2, h_init));
+            g.last_kernel = cm_onepass ? "k_welch_pipe(spectra,onepass)" : "k_welch_pipe(spectra)";
             continue;
         } else if (use_bf16) {
             const RunPart rp = run_partition_2d(xf.L, (m + 1) / 2, g.ncu, nch);
@@ -2380,6 +2381,7 @@ int sp_stft_cog(const void *x, int x_dtype, int64_t nsig, const float *win, int 
             void *Wf_d;
             if (get_window_spectrum(win, nfft, xf, &Wf_d)) return -1;
             LAUNCHCHK(launch_welch_pipe(lc(), xd, cplx, (const float *)win_d, hop, nframes, tb.f, xf, (float *)acc, rp, spartial, 2));
+            g.last_kernel = "k_welch_pipe(cog,onepass)";
             LAUNCHCHK(launch_cm_blocksums(lc(), spartial, 1, (int)rp.groups, hop, Sl));
             LAUNCHCHK(launch_op_finish_channels(lc(), xd, 0, 1, tb.f, (const float *)win_d, Sl, (const cf *)Wf_d, hop, nframes, nsig, xf,
                                                 st, cplx));
@@ -2393,6 +2395,7 @@ int sp_stft_cog(const void *x, int x_dtype, int64_t nsig, const float *win, int 
         }
         if (pipe) {
             LAUNCHCHK(launch_welch_pipe(lc(), xd, cplx, (const float *)win_d, hop, nframes, tb.f, xf, (float *)acc, rp, nullptr, 2));
+            g.last_kernel = "k_welch_pipe(cog)";
             generic = 0;
         } else if (!segmean && detrend != 2 && !env_flag("SP_COG_GENERIC"))
             generic = launch_cog_carry(lc(), xd, cplx, (const float *)win_d, hop, nframes, tb.f, xf, acc, rp, klo, khi);
