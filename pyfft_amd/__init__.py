@@ -50,3 +50,4 @@ from .running import (running_psd, running_csd, running_coherence, running_spect
                       coherence_level)
 from . import wavelet as _wavelet_mod                          # noqa: F401
 from .wavelet import Morlet, Paul, cwt_scales, cwt, icwt, cwt_power, cwt_filter, cwt_plan   # noqa: F401
+from .wavelet import xwt, wct, wct_plan   # noqa: F401

@@ -93,6 +93,13 @@ SIGNATURES = {
     "sp_mean": (_i, [_vp, _i, _i64, C.POINTER(_d), _i]),
 }
 
+# the second table: must list every symbol include/spectral_ext.h declares, and none of the first
+EXT_SIGNATURES = {
+    "sp_wct_time": (_i, [_vp, _i64, _vp, _i64, _i, _i64, _i64, _vp, _i, _i, _d, _i, _i, _i, _vp, _vp, _i]),
+    "sp_wct_scale": (_i, [_vp, _i64, _i, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
+    "sp_wct_plan": (_i, [_i64, _i, _i64, _i, _i, _i, _i, _vp]),
+}
+
 
 class SpectralError(RuntimeError):
     pass
@@ -107,10 +114,11 @@ def load_library():
         raise SpectralError("libspectral.so not found at %s -- run `make` (or __graft_entry__.build()); "
                             "pyfft_amd has no CPU fallback" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)      # AttributeError if the .so lacks a declared symbol
-        fn.restype = res
-        fn.argtypes = args
+    for table in (SIGNATURES, EXT_SIGNATURES):
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)      # AttributeError if the .so lacks a declared symbol
+            fn.restype = res
+            fn.argtypes = args
     _lib = lib
     return lib
 

@@ -25,6 +25,7 @@ namespace sp {
 //   SP_SKF_FPG, SP_SKF_CELLS (int: the wavenumber-frequency histogram's frames per run; a cap on the cells nk x bins of a tile)
 //   SP_EIGH_GRID (int: the eigensolver's workgroups, so that a small batch walks the batch loop)
 //   SP_CWT_CHUNK (int: the wavelet transform's scales per workgroup, where no output needs the whole scale set in one)
+//   SP_WCT_CHUNK (int: the same for the cross-wavelet and coherence kernel)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
     return v && v[0] && v[0] != '0';
@@ -697,6 +698,37 @@ int launch_cwt(LaunchCtx c, const CwtArgs &a, int L, const cf *tw, const CwtPlan
 int launch_cwt_gws_finish(LaunchCtx c, const float *gpart, int64_t rows_x_scales, int64_t nframes, double *gws);
 // out[row][n] = sum_s w[s] W[row][s][n] (w: device table)
 int launch_icwt(LaunchCtx c, const cf *W, const float *w, int S, int64_t N, int64_t rows, cf *out);
+
+// cross-wavelet spectra and wavelet coherence by overlap-save (k_wct.hip): the frames of k_cwt with the margin M = Mw + Mg, Mw the reach of
+// the wavelets and Mg that of the time-smoothing Gaussians, hop = L - 2 M.  Per frame the spectra of x and y are kept (bins 1 .. L / 2:
+// in registers below 2048 points, in an LDS stash from there on); per scale Wx and Wy, then either Wxy = Wx conj(Wy) [rows][S][nsig]
+// (T null: the cross-wavelet transform, Mg = 0) or the products |Wx|^2 / s', |Wy|^2 / s', Wx conj(Wy) / s' (zero outside the row)
+// filtered by exp(-(s' w)^2 / 2) as two complex records (a + i b, c) and stored as T [rows][S][nsig] float4 = (A_t, B_t, Re C_t, Im C_t).
+// sc[s] = (step_s, c_s, 1 / s', 0) is a device table, step and c as in CwtArgs.
+struct WctArgs {
+    const void *x, *y;
+    int cplx;
+    int64_t nsig, x_ld, y_ld, nframes;
+    const float *sc;
+    float p, a, b, u0;
+    int S, chunk, M, hop;
+    float4 *T;
+    cf *Wxy;
+};
+constexpr bool wct_stash(int L) { return L >= 2048; }
+// the exchange images and, from 2048 points on, two half spectra per transform group
+inline size_t wct_lds_bytes(int L) {
+    const int R = 16, T = L / R;
+    const size_t img = (size_t)(R * (T + 1) > L ? R * (T + 1) : L);
+    return sizeof(cf) * (size_t)fpw_of(L) * (img + (wct_stash(L) ? (size_t)L : 0));
+}
+int launch_wct_time(LaunchCtx c, const WctArgs &a, int L, const cf *tw, const CwtPlan &pl, int64_t rows);
+// every scale row of T summed with its neighbours (taps [ntaps], a device table: row s - ntaps / 2 + j takes taps[ntaps - 1 - j], rows
+// outside the set count as zero, ascending row order; up to 16 taps a thread walks the rows of its sample with the window in registers
+// and reads T once, beyond that the rows are re-read through the caches), then R2 = |C|^2 / (A B) and phase = atan2(Im C, Re C), 0 where A B == 0: float32
+// [rows][S][nsig] each; A, B (float32) and C (complex64) of the same shape on request (all three or none)
+int launch_wct_scale(LaunchCtx c, const float4 *T, const float *taps, int ntaps, int S, int64_t N, int64_t rows, float *R2, float *phase,
+                     float *A, float *B, cf *C);
 
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;

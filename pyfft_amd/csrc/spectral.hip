@@ -1,5 +1,6 @@
 // spectral.hip -- C ABI (include/spectral.h) over the gfx950 kernels (kernels.h via launch.h).
 #include "../../include/spectral.h"
+#include "../../include/spectral_ext.h"
 #include "launch.h"
 #include "table_cache.h"
 
@@ -3617,6 +3618,173 @@ int sp_icwt(const void *W, int64_t nsig, int nscales, int64_t batch, const float
     }
     if (!mem) {
         HIPCHK(hipMemcpyAsync(out, od, obytes, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
+// ---- cross-wavelet spectra and wavelet coherence (k_wct.hip; include/spectral_ext.h) -------------------
+// the shape checks sp_wct_time and its plan share; 0 or the message's tail
+static const char *wct_shape(int64_t nsig, int nscales, int64_t batch, int L, int Mw, int Mg, bool xwt) {
+    if (L < SP_CWT_MIN_L || L > SP_CWT_MAX_L || !is_pow2(L)) return "L must be a power of two from 256 to 8192";
+    if (Mw < 0 || Mg < 0 || 2 * ((int64_t)Mw + Mg) >= L) return "Mw and Mg must not be negative, and Mw + Mg must lie in 0 .. L / 2 - 1";
+    if (L - 2 * (Mw + Mg) < L / 4) return "Mw + Mg leaves hop = L - 2 (Mw + Mg) below L / 4";
+    if (xwt && Mg != 0) return "Mg must be 0 with Wxy";
+    if (nscales < 1 || nscales > 65535) return "nscales must lie in 1 .. 65535";
+    if (nsig < 1) return "nsig must be at least 1";
+    if (batch < 0 || batch > 65535) return "batch must lie in 0 .. 65535";
+    return nullptr;
+}
+
+int sp_wct_plan(int64_t nsig, int nscales, int64_t batch, int L, int Mw, int Mg, int xwt, int64_t out[5]) {
+    if (wct_shape(nsig, nscales, batch, L, Mw, Mg, xwt != 0) || !out) return -1;
+    const CwtPlan p = cwt_plan_of(L, Mw + Mg, nsig, nscales, batch, false, false, g.ncu, env_int("SP_WCT_CHUNK", 0));
+    out[0] = p.hop;
+    out[1] = p.frames;
+    out[2] = p.chunk;
+    out[3] = p.grid;
+    out[4] = (int64_t)wct_lds_bytes(L);
+    return 0;
+}
+
+int sp_wct_time(const void *x, int64_t x_ld, const void *y, int64_t y_ld, int dtype, int64_t nsig, int64_t batch, const double *scales,
+                int nscales, int family, double p0, int L, int Mw, int Mg, void *T, void *Wxy, int mem) {
+    // every refusal comes before the device is touched
+    if ((T != nullptr) == (Wxy != nullptr)) return fail("sp_wct_time: exactly one output is required: T or Wxy");
+    if (const char *why = wct_shape(nsig, nscales, batch, L, Mw, Mg, Wxy != nullptr))
+        return fail("sp_wct_time: %s (L %d, Mw %d, Mg %d, nscales %d, nsig %lld, batch %lld)", why, L, Mw, Mg, nscales, (long long)nsig,
+                    (long long)batch);
+    if (dtype != SP_DTYPE_F32 && dtype != SP_DTYPE_C64) return fail("sp_wct_time: dtype must be float32 or complex64, got %d", dtype);
+    if (x_ld < nsig) return fail("sp_wct_time: x_ld = %lld is below nsig = %lld", (long long)x_ld, (long long)nsig);
+    if (y_ld < nsig) return fail("sp_wct_time: y_ld = %lld is below nsig = %lld", (long long)y_ld, (long long)nsig);
+    if (family != SP_CWT_MORLET && family != SP_CWT_PAUL)
+        return fail("sp_wct_time: family %d is neither SP_CWT_MORLET nor SP_CWT_PAUL", family);
+    if (T && family != SP_CWT_MORLET) return fail("sp_wct_time: family must be SP_CWT_MORLET with T (the smoothing operator is Morlet's)");
+    if (!isfinite(p0) || !(p0 > 0.0) || p0 > 64.0 || (family == SP_CWT_PAUL && p0 < 1.0))
+        return fail("sp_wct_time: parameter p0 = %g must lie in (0, 64] (Morlet's w0) or [1, 64] (Paul's m)", p0);
+    if (!scales) return fail("sp_wct_time: scales is required");
+    for (int s = 0; s < nscales; ++s)
+        if (!isfinite(scales[s]) || !(scales[s] > 0.0) || scales[s] > 1e9)
+            return fail("sp_wct_time: scales[%d] = %g must be positive and finite", s, scales[s]);
+    if (mem && T && ((uintptr_t)T & 15) != 0) return fail("sp_wct_time: T must be 16-byte aligned");
+    if (batch == 0) return 0;
+    if (!x || !y) return fail("sp_wct_time: x and y are required");
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const bool cplx = dtype == SP_DTYPE_C64;
+    const int M = Mw + Mg;
+    const CwtPlan pl = cwt_plan_of(L, M, nsig, nscales, batch, false, false, g.ncu, env_int("SP_WCT_CHUNK", 0));
+    if (pl.blocks_x > INT_MAX) return fail("sp_wct_time: nsig = %lld is too many frames for one launch", (long long)nsig);
+    const size_t esz = cplx ? 8 : 4, S = (size_t)nscales, rows = (size_t)batch;
+    const size_t x_elems = (size_t)((batch - 1) * x_ld + nsig), y_elems = (size_t)((batch - 1) * y_ld + nsig);
+    // the scales' constants: step = 2 pi s' / L, c = ln(norm sqrt(2 pi s') / L), 1 / s'
+    const double lognorm = family == SP_CWT_MORLET ? -0.25 * log(M_PI) : p0 * log(2.0) - 0.5 * (log(p0) + lgamma(2.0 * p0));
+    std::vector<float> sc(4 * S);
+    for (size_t s = 0; s < S; ++s) {
+        sc[4 * s] = (float)(2.0 * M_PI * scales[s] / (double)L);
+        sc[4 * s + 1] = (float)(lognorm + 0.5 * log(2.0 * M_PI * scales[s]) - log((double)L));
+        sc[4 * s + 2] = (float)(1.0 / scales[s]);
+        sc[4 * s + 3] = 0.f;
+    }
+    void *sc_d = nullptr;
+    if (get_table(18, sc.data(), sizeof(float) * sc.size(), &sc_d, nullptr)) return -1;
+    const cf *tw;
+    if (get_twiddles(L, &tw)) return -1;
+    const size_t obytes = (T ? sizeof(float4) : sizeof(cf)) * rows * S * (size_t)nsig;
+    const void *xd = x, *yd = y;
+    void *od = T ? T : Wxy;
+    if (!mem) {
+        if (g.in0.ensure(esz * x_elems) || g.in1.ensure(esz * y_elems) || g.out0.ensure(obytes)) return -1;
+        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * x_elems, hipMemcpyHostToDevice, g.stream));
+        HIPCHK(hipMemcpyAsync(g.in1.p, y, esz * y_elems, hipMemcpyHostToDevice, g.stream));
+        xd = g.in0.p;
+        yd = g.in1.p;
+        od = g.out0.p;
+    }
+    WctArgs a;
+    a.x = xd;
+    a.y = yd;
+    a.cplx = cplx ? 1 : 0;
+    a.nsig = nsig;
+    a.x_ld = x_ld;
+    a.y_ld = y_ld;
+    a.nframes = pl.frames;
+    a.sc = (const float *)sc_d;
+    a.p = family == SP_CWT_PAUL ? (float)p0 : 0.f;
+    a.a = family == SP_CWT_MORLET ? 0.5f : 0.f;
+    a.b = family == SP_CWT_PAUL ? 1.f : 0.f;
+    a.u0 = family == SP_CWT_MORLET ? (float)p0 : 0.f;
+    a.S = nscales;
+    a.chunk = pl.chunk;
+    a.M = M;
+    a.hop = pl.hop;
+    a.T = T ? (float4 *)od : nullptr;
+    a.Wxy = T ? nullptr : (cf *)od;
+    {
+        ProfScope ps;
+        if (launch_wct_time(lc(), a, L, tw, pl, batch) != 0)
+            return fail("sp_wct_time: the launch was refused (L %d, Mw %d, Mg %d, nscales %d, %lld rows)", L, Mw, Mg, nscales,
+                        (long long)batch);
+        HIPCHK(hipGetLastError());
+        g.last_kernel = "k_wct_time";
+    }
+    if (!mem) {
+        HIPCHK(hipMemcpyAsync(T ? T : Wxy, od, obytes, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
+int sp_wct_scale(const void *T, int64_t nsig, int nscales, int64_t batch, const float *taps, int ntaps, float *R2, float *phase, float *A,
+                 float *B, void *C, int mem) {
+    // every refusal comes before the device is touched
+    if (nscales < 1 || nscales > 65535) return fail("sp_wct_scale: nscales must lie in 1 .. 65535");
+    if (nsig < 1) return fail("sp_wct_scale: nsig must be at least 1");
+    if (batch < 0 || batch > 65535) return fail("sp_wct_scale: batch must lie in 0 .. 65535");
+    if (ntaps < 1 || ntaps > 4096) return fail("sp_wct_scale: ntaps must lie in 1 .. 4096");
+    if (!taps) return fail("sp_wct_scale: taps is required");
+    for (int j = 0; j < ntaps; ++j)
+        if (!isfinite(taps[j])) return fail("sp_wct_scale: taps must be finite (tap %d)", j);
+    if ((A != nullptr) != (B != nullptr) || (A != nullptr) != (C != nullptr))
+        return fail("sp_wct_scale: A, B and C are given together or not at all");
+    if (mem && T && ((uintptr_t)T & 15) != 0) return fail("sp_wct_scale: T must be 16-byte aligned");
+    if (batch == 0) return 0;
+    if (!T || !R2 || !phase) return fail("sp_wct_scale: T, R2 and phase are required");
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const size_t cells = (size_t)batch * (size_t)nscales * (size_t)nsig, fb = sizeof(float) * cells, fa = (fb + 255) & ~(size_t)255;
+    const void *Td = T;
+    float *R2_d = R2, *ph_d = phase, *A_d = A, *B_d = B;
+    cf *C_d = (cf *)C;
+    if (!mem) {
+        // outputs staged for host callers: [R2 | phase | A | B | C], each piece 256-byte aligned
+        if (g.in0.ensure(sizeof(float4) * cells) || g.out0.ensure(A ? 6 * fa : 2 * fa)) return -1;
+        HIPCHK(hipMemcpyAsync(g.in0.p, T, sizeof(float4) * cells, hipMemcpyHostToDevice, g.stream));
+        Td = g.in0.p;
+        char *o = (char *)g.out0.p;
+        R2_d = (float *)o;
+        ph_d = (float *)(o + fa);
+        if (A) {
+            A_d = (float *)(o + 2 * fa);
+            B_d = (float *)(o + 3 * fa);
+            C_d = (cf *)(o + 4 * fa);
+        }
+    }
+    void *taps_d = nullptr;
+    if (get_table(19, taps, sizeof(float) * (size_t)ntaps, &taps_d, nullptr)) return -1;
+    {
+        ProfScope ps;
+        LAUNCHCHK(launch_wct_scale(lc(), (const float4 *)Td, (const float *)taps_d, ntaps, nscales, nsig, batch, R2_d, ph_d, A_d, B_d, C_d));
+        g.last_kernel = "k_wct_scale";
+    }
+    if (!mem) {
+        HIPCHK(hipMemcpyAsync(R2, R2_d, fb, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipMemcpyAsync(phase, ph_d, fb, hipMemcpyDeviceToHost, g.stream));
+        if (A) {
+            HIPCHK(hipMemcpyAsync(A, A_d, fb, hipMemcpyDeviceToHost, g.stream));
+            HIPCHK(hipMemcpyAsync(B, B_d, fb, hipMemcpyDeviceToHost, g.stream));
+            HIPCHK(hipMemcpyAsync(C, C_d, 2 * fb, hipMemcpyDeviceToHost, g.stream));
+        }
         HIPCHK(hipStreamSynchronize(g.stream));
     }
     return 0;

@@ -1092,6 +1092,115 @@ def icwt_sum(W, weights):
     return out
 
 
+WCT_MAX_SCALES, WCT_MAX_TAPS = 65535, 4096
+
+
+class WctRefused(ValueError, NotImplementedError):
+    """A shape the cross-wavelet and coherence kernels do not take: outside the limits, and a path that is not built (the refusals of
+    the fused wavelet transform, with the margin Mw + Mg; the smoothing operator of any wavelet but Morlet)."""
+
+
+def wct_check(who, nsig, scales, family, param, L, Mw, Mg, rows=1, xwt=False):
+    """Every refusal of sp_wct_time's shape, before the library is touched -> (scales float64, family code, param)."""
+    L, Mw, Mg = int(L), int(Mw), int(Mg)
+    if Mw < 0 or Mg < 0:
+        raise WctRefused("%s: Mw = %d and Mg = %d must not be negative" % (who, Mw, Mg))
+    if xwt and Mg != 0:
+        raise WctRefused("%s: Mg = %d must be 0 for the cross-wavelet transform (nothing is smoothed)" % (who, Mg))
+    try:
+        sc, code, param = cwt_check(who, nsig, scales, family, param, L, Mw + Mg, rows)
+    except CwtRefused as e:
+        raise WctRefused(str(e).replace("M =", "M = Mw + Mg =")) from None
+    if sc.size > WCT_MAX_SCALES:
+        raise WctRefused("%s: %d scales are outside 1 .. %d" % (who, sc.size, WCT_MAX_SCALES))
+    if not xwt and code != _ffi.CWT_MORLET:
+        raise WctRefused("%s: the coherence is built for Morlet wavelets only (the smoothing operator is Morlet's), not %r" % (who, family))
+    return sc, code, param
+
+
+def _wct_lead(who, x):
+    if x.ndim < 1:
+        raise WctRefused("%s: x must have at least one axis" % who)
+    rows = 1
+    for d in x.shape[:-1]:
+        rows *= int(d)
+    return tuple(x.shape[:-1]), rows
+
+
+def wct_time(x, y, scales, family, param, L, Mw, Mg=0, xwt=False):
+    """The time half of the wavelet coherence along the last axis by overlap-save (sp_wct_time): scales in samples, frames of L samples
+    with the margin Mw + Mg on either side.  -> T float32 [..., S, N, 4] = (A_t, B_t, Re C_t, Im C_t): |Wx|^2 / s', |Wy|^2 / s' and
+    Wx conj(Wy) / s' smoothed along n by the Gaussian of standard deviation s' (family 'morlet' only); or, with xwt=True (Mg = 0;
+    'morlet' or 'paul'), Wxy = Wx conj(Wy) complex64 [..., S, N].  x and y: equal shapes and dtypes.  numpy in -> numpy out; device
+    tensor in -> device tensor on x's stream (rows of a 2-D tensor may be strided)."""
+    md = _mode(x)
+    if _mode(y) is not md:
+        raise TypeError("wct_time: x and y must both be numpy arrays or both be device tensors")
+    x, y = md.checked(x), md.checked(y)
+    if tuple(x.shape) != tuple(y.shape) or x.dtype != y.dtype or (md.dev and x.device != y.device):
+        raise WctRefused("wct_time: x and y must share their shape and dtype%s" % (" and device" if md.dev else ""))
+    lead, rows = _wct_lead("wct_time", x)
+    n = int(x.shape[-1])
+    sc, code, param = wct_check("wct_time", n, scales, family, param, L, Mw, Mg, rows, xwt)
+    md.bind(x)
+    xs, xld = md.rows(x)
+    ys, yld = md.rows(y)
+    if xwt:
+        out = md.empty(lead + (sc.size, n), "complex64", x)
+    else:
+        out = md.empty(lead + (sc.size, n, 4), "float32", x)
+    md.call(lib().sp_wct_time, md.addr(xs), xld, md.addr(ys), yld, md.code(xs), n, rows, ptr(sc), sc.size, code, param, int(L), int(Mw),
+            int(Mg), None if xwt else md.addr(out), md.addr(out) if xwt else None)
+    return out
+
+
+def wct_taps(who, taps):
+    taps = np.ascontiguousarray(np.asarray(taps), dtype=np.float32)
+    if taps.ndim != 1 or not (1 <= taps.size <= WCT_MAX_TAPS) or not np.all(np.isfinite(taps)):
+        raise WctRefused("%s: taps must hold 1 .. %d finite weights" % (who, WCT_MAX_TAPS))
+    return taps
+
+
+def wct_scale(T, taps, spectra=False):
+    """The scale half of the wavelet coherence (sp_wct_scale): T float32 [..., S, N, 4] as wct_time leaves it, summed over neighbouring
+    scale rows with `taps` (scipy.signal.convolve2d(., taps[:, None], 'same'), rows outside the set zero) -> (R2, phase) float32
+    [..., S, N], R2 = |C|^2 / (A B) and phase = atan2(Im C, Re C), both 0 where A B == 0; with spectra=True (R2, phase, A, B, C), the
+    smoothed spectra float32, float32 and complex64.  numpy in -> numpy out; device tensor in -> device tensors on T's stream."""
+    md = _mode(T)
+    if md.dev:
+        if T.dtype != torch.float32:
+            raise TypeError("wct_scale: T must be float32, got %s" % T.dtype)
+    else:
+        T = md.cast(np.asarray(T), "float32")
+    if T.ndim < 3 or T.shape[-1] != 4 or T.shape[-2] < 1 or not (1 <= T.shape[-3] <= WCT_MAX_SCALES):
+        raise WctRefused("wct_scale: T must be [..., S, N, 4] with N >= 1 and S in 1 .. %d" % WCT_MAX_SCALES)
+    taps = wct_taps("wct_scale", taps)
+    S, n = int(T.shape[-3]), int(T.shape[-2])
+    lead = tuple(T.shape[:-3])
+    rows = 1
+    for d in lead:
+        rows *= int(d)
+    if rows < 1 or rows > CWT_MAX_ROWS:
+        raise WctRefused("wct_scale: %d rows are outside 1 .. %d" % (rows, CWT_MAX_ROWS))
+    md.bind(T)
+    Tc = md.cast(T, "float32")
+    shape = lead + (S, n)
+    out = [md.empty(shape, "float32", T), md.empty(shape, "float32", T)]
+    if spectra:
+        out += [md.empty(shape, "float32", T), md.empty(shape, "float32", T), md.empty(shape, "complex64", T)]
+    md.call(lib().sp_wct_scale, md.addr(Tc), n, S, rows, ptr(taps), taps.size, *([md.addr(o) for o in out] + [None] * (5 - len(out))))
+    return tuple(out)
+
+
+def wct_plan(nsig, nscales, L, Mw, Mg=0, rows=1, xwt=False):
+    """sp_wct_plan as a dict (host only): hop, frames (per row), chunk (scales per workgroup), workgroups, lds_bytes."""
+    wct_check("wct_plan", int(nsig), np.ones(max(int(nscales), 0)), "morlet", 6.0, L, Mw, Mg, int(rows), xwt)
+    out = np.zeros(5, dtype=np.int64)
+    if lib().sp_wct_plan(int(nsig), int(nscales), int(rows), int(L), int(Mw), int(Mg), 1 if xwt else 0, ptr(out)) != 0:
+        raise WctRefused("wct_plan: the shape is refused")
+    return dict(zip(("hop", "frames", "chunk", "workgroups", "lds_bytes"), (int(v) for v in out)))
+
+
 EIGH_MAX_N = 64
 
 

@@ -13,7 +13,16 @@ Two paths, chosen per scale and reported by cwt_plan:
             that fall off like 1 / n (Morlet-6 below s = 3.7 dt) -- take engine.fft of the record zero-padded to next_pow2(2 N), a
             broadcast multiply with the filter rows and batched engine.ifft, a chunk of scales at a time.
 
+Two records: xwt (the cross-wavelet transform Wx conj(Wy)) and wct (wavelet coherence and phase after Torrence & Webster 1999), on the
+same frames with the margin of the time-smoothing Gaussian added to the wavelet's (engine.wct_time, engine.wct_scale; k_wct.hip); see
+the section at the end of this module.
+
 numpy in -> numpy out; device tensor in -> device tensors on x's stream.  There is no CPU implementation behind these functions.
+xwt and wct differ from the rest in one respect: where torch has a GPU, numpy records are copied to torch's current device, run the
+device-tensor path on torch's current stream and are copied back (_on_device), so that both calling modes give the same bits -- the
+glue between the library calls of the whole-record path is then the same code -- and T never crosses to the host.  Without torch, or
+without a GPU visible to it, numpy records take the library's host path with numpy glue, as cwt's do; the results then agree with the
+device mode to rounding, not bit for bit.
 """
 import functools
 import math
@@ -388,3 +397,231 @@ def cwt_filter(x, dt=1.0, dj=1.0 / 12, s0=None, J=None, wavelet=None, scales=Non
             add = (Wc * torch.from_numpy(wc).to(x.device)[:, None]).sum(-2) if dev else (Wc * wc[:, None]).sum(-2)
             y = add if y is None else y + add
     return y if cplx else y.real
+
+
+# ---- cross-wavelet spectra and wavelet coherence (Torrence & Webster 1999; pycwt.xwt, pycwt.wct) --------------------------------------
+#   Wxy = Wx conj(Wy);   a, b, c = |Wx|^2 / s', |Wy|^2 / s', Wxy / s' on the record, zero outside;
+#   A, B, C = a, b, c smoothed along time by the unit-gain Gaussian of standard deviation s' samples (a LINEAR convolution: pycwt pads
+#   to a power of two and wraps) and then across scales by the boxcar of 2 dj0 / dj rows with half weights at its ends;
+#   R2 = |C|^2 / (A B), phase = atan2(Im C, Re C), both 0 where A B == 0.
+# Fused scales run in engine.wct_time (k_wct_time): the frames of cwt with the margin Mw + Mg, Mg the Gaussian's reach by the tail rule of
+# `margin`.  The others take the whole-record path; both write rows of one T, and one engine.wct_scale call smooths them together.
+
+def gauss_rows(scales, L):
+    """exp(-(s' w_k)^2 / 2) on a grid of L points, w_k the signed bin frequency, float64 [S, L]; scales in samples."""
+    s = np.asarray(scales, dtype=np.float64).reshape(-1, 1)
+    k = np.arange(L)
+    w = 2.0 * math.pi * np.where(k <= L // 2, k, k - L) / L
+    return np.exp(-0.5 * (s * w[None, :]) ** 2)
+
+
+@functools.lru_cache(maxsize=4096)
+def _smooth_margin_cached(s, tail):
+    G = MARGIN_GRID
+    a = np.abs(np.fft.ifft(gauss_rows([s], G)[0]))
+    c = a[:G // 2 + 1].copy()
+    c[1:G // 2] += a[:G // 2:-1]
+    tails = np.cumsum(c[::-1])[::-1]
+    ok = np.nonzero(tails <= tail * tails[0])[0]
+    return int(ok[0]) if ok.size else G // 2 + 1
+
+
+def smooth_margin(s, tail=1e-6):
+    """The reach of the time-smoothing Gaussian of scale s (in samples) by the rule of `margin`: the smallest M with
+    sum_{|n| >= M} |g[n]| <= tail sum |g|, g = ifft(exp(-(s w)^2 / 2)) on 2^18 points.  About 4.9 s at tail = 1e-6."""
+    s = float(s)
+    if not (s > 0 and math.isfinite(s)):
+        raise E.WctRefused("smooth_margin: the scale must be positive and finite")
+    return _smooth_margin_cached(s, float(tail))
+
+
+def scale_window(dj, dj0=0.6):
+    """The scale-smoothing taps: ones of length round(2 dj0 / dj) + 2 with both ends 0.5, normalised to sum 1."""
+    if not (dj > 0 and dj0 > 0):
+        raise E.WctRefused("scale_window: dj and dj0 must be positive")
+    k = int(round(2.0 * dj0 / dj)) + 2
+    if k > E.WCT_MAX_TAPS:
+        raise E.WctRefused("scale_window: 2 dj0 / dj = %g rows are more than %d taps" % (2.0 * dj0 / dj, E.WCT_MAX_TAPS))
+    win = np.ones(k)
+    win[0] = win[-1] = 0.5
+    return win / win.sum()
+
+
+def _pair(x, y, who):
+    x, cx = _prep(x)
+    y, cy = _prep(y)
+    if _is_torch(x) != _is_torch(y):
+        raise TypeError("%s: x and y must both be arrays or both be device tensors" % who)
+    if tuple(x.shape) != tuple(y.shape):
+        raise E.WctRefused("%s: x and y must have equal shapes, got %r and %r" % (who, tuple(x.shape), tuple(y.shape)))
+    if cx != cy:                            # one real, one complex: both run as complex
+        if _is_torch(x):
+            x, y = x.to(torch.complex64), y.to(torch.complex64)
+        else:
+            x, y = x.astype(np.complex64), y.astype(np.complex64)
+    if x.ndim < 1 or x.shape[-1] < 1:
+        raise E.WctRefused("%s: the records must hold at least one sample" % who)
+    return x, y
+
+
+def wct_plan(n, dt=1.0, dj=1.0 / 12, s0=None, J=None, wavelet=None, scales=None, tail=1e-6, rows=1):
+    """What wct would do for records of n samples: the scales (units of dt), per scale the wavelet's margin, the Gaussian's margin
+    (`margins_w`, `margins_g`, samples) and the path ('fused' or 'composed'); Mw, Mg, M = Mw + Mg, L, hop and frames of the fused call
+    (None without fused scales); n_full (the wavelet transforms) and n_smooth (the time smoothing) of the composed path (None without
+    composed scales); and the bytes of T.  A scale fuses if its own margins sum to at most 3072 samples.  Host only."""
+    wv = Morlet(6.0) if wavelet is None else _wavelet(wavelet)
+    if wv.family != "morlet":
+        raise E.WctRefused("wct: the coherence is built for Morlet wavelets only (the smoothing operator is Torrence & Webster's for "
+                           "Morlet; pycwt has none for the others), not %r" % (wv,))
+    try:
+        base = cwt_plan(n, dt, dj, s0, J, wv, scales, tail, rows)
+    except CwtRefused as e:
+        raise E.WctRefused(str(e).replace("cwt", "wct")) from None
+    n, sc = int(n), base["scales"]
+    sp = sc / dt
+    mw = base["margins"]
+    mg = np.array([smooth_margin(s, tail) for s in sp], dtype=np.int64)
+    fused = mw + mg <= FUSED_MAX_MARGIN
+    # the call's margins are the largest of either kind: a scale whose wavelet reaches far (near Nyquist) beside one whose Gaussian
+    # does may push their sum past the limit; the scale with the longest wavelet then leaves the fused set
+    while fused.any() and mw[fused].max() + mg[fused].max() > FUSED_MAX_MARGIN:
+        cand = np.nonzero(fused)[0]
+        fused[cand[np.argmax(mw[cand])]] = False
+    plan = dict(scales=sc, margins_w=mw, margins_g=mg, fused=fused, path=np.where(fused, "fused", "composed"), Mw=None, Mg=None, M=None,
+                L=None, hop=None, frames=None, n_full=None, n_smooth=None, bytes_T=16 * int(rows) * sc.size * n, wavelet=wv, tail=tail)
+    if fused.any():
+        Mw, Mg = int(mw[fused].max()), int(mg[fused].max())
+        M = Mw + Mg
+        L = E.CWT_MIN_L
+        while L < 4 * M and L < E.CWT_MAX_L:
+            L *= 2
+        plan.update(Mw=Mw, Mg=Mg, M=M, L=L, hop=L - 2 * M, frames=-(-n // (L - 2 * M)))
+    if (~fused).any():
+        n_full = 1 << max(int(2 * n - 1).bit_length(), 1)
+        n_smooth = 1 << max(int(n + int(mg[~fused].max()) - 1).bit_length(), 1)
+        if max(n_full, n_smooth) > COMPOSED_MAX_NFULL:
+            raise E.WctRefused("wct: %d of the scales do not fuse (margins above %d samples) and their whole-record path needs a transform "
+                               "of %d points, above 2^26: decimate the records with resample_poly first"
+                               % (int((~fused).sum()), FUSED_MAX_MARGIN, max(n_full, n_smooth)))
+        plan.update(n_full=n_full, n_smooth=n_smooth)
+    return plan
+
+
+def _gauss_rows_device(sp, n_full, device):
+    """gauss_rows as float32 rows on the device, formed there in float64"""
+    k = torch.arange(n_full, dtype=torch.float64, device=device)
+    w = (2.0 * math.pi / n_full) * torch.where(k <= n_full // 2, k, k - n_full)
+    s = torch.as_tensor(np.asarray(sp, dtype=np.float64), device=device)[:, None]
+    return torch.exp(-0.5 * (s * w[None, :]) ** 2).float()
+
+
+def _smooth_composed(p, sp, n, n_smooth):
+    """p [..., len, N] complex64 filtered along the last axis by every scale's Gaussian on a zero-padded grid of n_smooth points"""
+    dev = _is_torch(p)
+    if dev:
+        pp = torch.zeros(tuple(p.shape[:-1]) + (n_smooth,), dtype=torch.complex64, device=p.device)
+        G = _gauss_rows_device(sp, n_smooth, p.device)
+    else:
+        pp = np.zeros(p.shape[:-1] + (n_smooth,), dtype=np.complex64)
+        G = gauss_rows(sp, n_smooth).astype(np.float32)
+    pp[..., :n] = p
+    return E.ifft(E.fft(pp) * G)[..., :n]
+
+
+def _on_device(x, y):
+    """numpy records as device tensors where torch has a GPU: the public functions then run their device path and copy the results
+    back, so that both calling modes give the same bits (the glue between the library calls of the whole-record path is then the same
+    code) and T never crosses to the host.  -> (x, y, host): host = the results go back to numpy."""
+    if _is_torch(x):
+        return x, y, False
+    if torch is not None and torch.cuda.is_available():
+        return torch.as_tensor(x, device="cuda"), torch.as_tensor(y, device="cuda"), True
+    return x, y, False
+
+
+def _back(v, host):
+    return v.cpu().numpy() if host else v
+
+
+def _composed_pairs(x, y, wv, sp, n_full):
+    """the whole-record transforms of both records, chunk by chunk: (i0, i1, Wx, Wy)"""
+    for (a, b, Wx), (_, _, Wy) in zip(_composed_chunks(x, wv, sp, n_full), _composed_chunks(y, wv, sp, n_full)):
+        yield a, b, Wx, Wy
+
+
+def xwt(x, y, dt=1.0, dj=1.0 / 12, s0=None, J=None, wavelet=None, scales=None, tail=1e-6):
+    """The cross-wavelet transform -> (Wxy, scales, freqs, coi): Wxy = Wx conj(Wy), complex64 [..., S, N], of two records of equal
+    shape; scales, freqs and coi as cwt gives them.  Morlet or Paul.  Unlike pycwt.xwt the records are NOT divided by their standard
+    deviations: normalise them first if that is wanted.  Fused scales form neither Wx nor Wy in memory."""
+    x, y = _pair(x, y, "xwt")
+    n = int(x.shape[-1])
+    rows = max(int(np.prod(x.shape[:-1], dtype=np.int64)), 1)
+    plan = cwt_plan(n, dt, dj, s0, J, wavelet, scales, tail, rows)
+    wv, sc = plan["wavelet"], plan["scales"]
+    x, y, host = _on_device(x, y)
+    idx, spf = _fused_args(plan, dt)
+    Wf = None
+    if idx.size:
+        Wf = E.wct_time(x, y, spf, wv.family, wv.param, plan["L"], plan["M"], 0, xwt=True)
+    if idx.size == sc.size:
+        W = Wf
+    else:
+        shape = tuple(x.shape[:-1]) + (sc.size, n)
+        W = torch.empty(shape, dtype=torch.complex64, device=x.device) if _is_torch(x) else np.empty(shape, dtype=np.complex64)
+        if Wf is not None:
+            W[..., _ix(x, idx), :] = Wf
+        cidx = np.nonzero(~plan["fused"])[0]
+        for a, b, Wx, Wy in _composed_pairs(x, y, wv, sc[cidx] / dt, plan["n_full"]):
+            W[..., _ix(x, cidx[a:b]), :] = Wx * Wy.conj()
+    freqs = 1.0 / (wv.flambda() * sc)
+    edge = dt * (n / 2.0 - np.abs(np.arange(n) - (n - 1) / 2.0))
+    return _back(W, host), sc, freqs, wv.flambda() * edge / wv.coi()
+
+
+def wct(x, y, dt=1.0, dj=1.0 / 12, s0=None, J=None, wavelet=None, scales=None, tail=1e-6, dj0=0.6, return_spectra=False):
+    """Wavelet coherence -> (R2, phase, scales, freqs, coi), with return_spectra=True followed by (A, B, C): R2 and phase float32
+    [..., S, N] of two records of equal shape, the doubly smoothed spectra A, B (float32) and C (complex64).  Morlet only.  The scale
+    smoothing spans round(2 dj0 / dj) + 2 rows of the scale set as given (dj is the caller's statement about an explicit `scales`).
+    Monte-Carlo significance levels are not computed."""
+    x, y = _pair(x, y, "wct")
+    n = int(x.shape[-1])
+    rows = max(int(np.prod(x.shape[:-1], dtype=np.int64)), 1)
+    plan = wct_plan(n, dt, dj, s0, J, wavelet, scales, tail, rows)
+    taps = scale_window(dj, dj0)
+    wv, sc = plan["wavelet"], plan["scales"]
+    x, y, host = _on_device(x, y)
+    sp = sc / dt
+    idx = np.nonzero(plan["fused"])[0]
+    Tf = None
+    if idx.size:
+        Tf = E.wct_time(x, y, sp[idx], wv.family, wv.param, plan["L"], plan["Mw"], plan["Mg"])
+    if idx.size == sc.size:
+        T = Tf
+    else:
+        shape = tuple(x.shape[:-1]) + (sc.size, n, 4)
+        T = torch.empty(shape, dtype=torch.float32, device=x.device) if _is_torch(x) else np.empty(shape, dtype=np.float32)
+        if Tf is not None:
+            T[..., _ix(x, idx), :, :] = Tf
+        cidx = np.nonzero(~plan["fused"])[0]
+        spc = sp[cidx]
+        for a, b, Wx, Wy in _composed_pairs(x, y, wv, spc, plan["n_full"]):
+            if _is_torch(x):
+                inv = torch.as_tensor((1.0 / spc[a:b]).astype(np.float32), device=x.device)[:, None]
+                p1 = torch.complex((Wx.real ** 2 + Wx.imag ** 2) * inv, (Wy.real ** 2 + Wy.imag ** 2) * inv)
+            else:
+                inv = (1.0 / spc[a:b]).astype(np.float32)[:, None]
+                p1 = ((Wx.real ** 2 + Wx.imag ** 2) * inv + 1j * ((Wy.real ** 2 + Wy.imag ** 2) * inv)).astype(np.complex64)
+            p2 = Wx * Wy.conj() * inv
+            rows_i = _ix(x, cidx[a:b])
+            for j, p in ((0, p1), (2, p2)):
+                q = _smooth_composed(p, spc[a:b], n, plan["n_smooth"])
+                # (through views of one component: an integer beside an index array is an advanced index in numpy, and with a
+                # slice between the two the indexed axis would move to the front)
+                re, im = T[..., j], T[..., j + 1]
+                re[..., rows_i, :] = q.real
+                im[..., rows_i, :] = q.imag
+    out = tuple(_back(v, host) for v in E.wct_scale(T, taps, spectra=return_spectra))
+    freqs = 1.0 / (wv.flambda() * sc)
+    edge = dt * (n / 2.0 - np.abs(np.arange(n) - (n - 1) / 2.0))
+    head = (out[0], out[1], sc, freqs, wv.flambda() * edge / wv.coi())
+    return head + tuple(out[2:]) if return_spectra else head
