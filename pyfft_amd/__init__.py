@@ -51,3 +51,6 @@ from .running import (running_psd, running_csd, running_coherence, running_spect
 from . import wavelet as _wavelet_mod                          # noqa: F401
 from .wavelet import Morlet, Paul, cwt_scales, cwt, icwt, cwt_power, cwt_filter, cwt_plan   # noqa: F401
 from .wavelet import xwt, wct, wct_plan   # noqa: F401
+from . import reassign as _reassign_mod                        # noqa: F401
+from .reassign import (reassignment_windows, ssq_stft, issq_stft, squeezed_spectrogram, reassignment_fields,   # noqa: F401
+                       ssq_extract, ssq_plan)

@@ -100,6 +100,14 @@ EXT_SIGNATURES = {
     "sp_wct_plan": (_i, [_i64, _i, _i64, _i, _i, _i, _i, _vp]),
 }
 
+# the third table: must list every symbol include/spectral_tfr.h declares, and none of the other two
+TFR_SIGNATURES = {
+    "sp_ssq": (_i, [_vp, _i64, _i, _i64, _i64, _vp, _vp, _vp, _i, _i, _i64, _i64, _i, _d, _d, _i, _i, _vp, _vp, _vp, _vp, _i]),
+    "sp_ssq_bands": (_i, [_vp, _i64, _i, _i64, _i64, _vp, _vp, _i, _i, _i64, _i64, _i, _d, _d, _i, _vp, _vp, _d, _vp, _i]),
+    "sp_ssq_sum": (_i, [_vp, _i64, _i, _i64, _i, _i, _i, _vp, _vp, _i, _d, _vp, _i]),
+    "sp_ssq_plan": (_i, [_i, _i, _i64, _i64, _i, _i, _vp]),
+}
+
 
 class SpectralError(RuntimeError):
     pass
@@ -114,7 +122,7 @@ def load_library():
         raise SpectralError("libspectral.so not found at %s -- run `make` (or __graft_entry__.build()); "
                             "pyfft_amd has no CPU fallback" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for table in (SIGNATURES, EXT_SIGNATURES):
+    for table in (SIGNATURES, EXT_SIGNATURES, TFR_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)      # AttributeError if the .so lacks a declared symbol
             fn.restype = res

@@ -26,6 +26,7 @@ namespace sp {
 //   SP_EIGH_GRID (int: the eigensolver's workgroups, so that a small batch walks the batch loop)
 //   SP_CWT_CHUNK (int: the wavelet transform's scales per workgroup, where no output needs the whole scale set in one)
 //   SP_WCT_CHUNK (int: the same for the cross-wavelet and coherence kernel)
+//   SP_SSQ_FPG (int: the synchrosqueezed STFT's frames per run)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
     return v && v[0] && v[0] != '0';
@@ -729,6 +730,52 @@ int launch_wct_time(LaunchCtx c, const WctArgs &a, int L, const cf *tw, const Cw
 // [rows][S][nsig] each; A, B (float32) and C (complex64) of the same shape on request (all three or none)
 int launch_wct_scale(LaunchCtx c, const float4 *T, const float *taps, int ntaps, int S, int64_t N, int64_t rows, float *R2, float *phase,
                      float *A, float *B, cf *C);
+
+// synchrosqueezed STFT and reassignment fields (k_ssq.hip): frame g of a row = the L samples from first + g hop on (zero outside the
+// row), L a power of two in 32 .. 8192, under the windows h, dh and (for IF / GD) th, device tables of L floats.  A workgroup owns a
+// run of fpr consecutive frames of one row; grid: runs x rows.  Scatter form (out null): any of T complex64, P, IF, GD float32
+// [rows][nframes][nb], the band of nb bins from b0 on (modulo L for complex rows).  Band form (out set): out[rows][nbands][nframes],
+// edges (lo, hi) per band by value or, per_frame, a device table float32 [nbands][nframes][2].
+// LDS of a workgroup: an image of L + 16 complex per transform and group, and behind them the groups' 64-bit accumulators: 16 bytes a
+// bin for T, 8 for P.
+#define SP_SSQ_LDS_MAX ((size_t)160 * 1024)
+#define SP_SSQ_MAX_L 8192
+#define SP_SSQ_MAX_BANDS 8
+struct SsqEdges {
+    float v[2 * SP_SSQ_MAX_BANDS];      // (lo, hi) per band, constant over the frames: passed by value, no table
+};
+struct SsqArgs {
+    const void *x;
+    int64_t x_ld, nsig, first, nframes, fpr;
+    const float *h, *dh, *th;
+    int hop, segmean;
+    float gamma, rel;
+    int b0, nb;
+    cf *T;
+    float *P, *IF, *GD;
+    int nbands, per_frame;
+    const float *edges;                 // per_frame: [nbands][nframes][2], else edges_c
+    SsqEdges edges_c;
+    float scale;
+    cf *out;
+};
+inline int ssq_transforms(bool cplx, bool fields) { return (cplx ? 2 : 1) + (fields ? 1 : 0); }
+inline size_t ssq_lds_bytes(bool cplx, int L, int nb, bool wantT, bool wantP, bool fields) {
+    return (size_t)fpw_of(L) * ((size_t)ssq_transforms(cplx, fields) * (size_t)(L + 16) * 8 + (size_t)nb * ((wantT ? 16 : 0) + (wantP ? 8 : 0)));
+}
+// frames per run: about four workgroups per CU over runs x rows, whole rounds of the workgroup's groups; forced > 0: that many
+inline int64_t ssq_fpr(int L, int64_t nframes, int64_t rows, int ncu, int forced) {
+    if (forced > 0) return forced;
+    const int fpw = fpw_of(L);
+    int64_t want = (int64_t)ncu * 4 / (rows > 0 ? rows : 1);
+    if (want < 1) want = 1;
+    const int64_t f = ((nframes + want - 1) / want + fpw - 1) / fpw * fpw;
+    return f < fpw ? fpw : f;
+}
+int launch_ssq(LaunchCtx c, const SsqArgs &a, bool cplx, int L, const cf *tw, int64_t runs, int64_t rows, size_t lds_bytes);
+// out[row][b][g] = scale * sum over lo <= m < hi of w_m T[row][g][j], m = (b0 + j) mod n, w = 1/2 at the bins 0 and n / 2 when `half`
+int launch_ssq_sum(LaunchCtx c, const cf *T, int64_t nframes, int nb, int n, int b0, int nbands, int per_frame, const float *edges,
+                   const SsqEdges &ec, int half, float scale, int64_t rows, cf *out);
 
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;

@@ -1,6 +1,7 @@
 // spectral.hip -- C ABI (include/spectral.h) over the gfx950 kernels (kernels.h via launch.h).
 #include "../../include/spectral.h"
 #include "../../include/spectral_ext.h"
+#include "../../include/spectral_tfr.h"
 #include "launch.h"
 #include "table_cache.h"
 
@@ -3785,6 +3786,245 @@ int sp_wct_scale(const void *T, int64_t nsig, int nscales, int64_t batch, const 
             HIPCHK(hipMemcpyAsync(B, B_d, fb, hipMemcpyDeviceToHost, g.stream));
             HIPCHK(hipMemcpyAsync(C, C_d, 2 * fb, hipMemcpyDeviceToHost, g.stream));
         }
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
+// ---- synchrosqueezed STFT and reassignment fields (k_ssq.hip; include/spectral_tfr.h) ------------------
+// the checks the three front ends share; 0 or the message's tail
+static const char *ssq_shape(int n, int hop, int64_t first, int64_t nframes, int64_t batch, int dtype, int64_t nsig, int64_t x_ld,
+                             double gamma, double rel) {
+    if (n < 32 || n > SP_SSQ_MAX_L || !is_pow2(n)) return "n must be a power of two from 32 to 8192";
+    if (hop < 1) return "hop must be at least 1";
+    if (nframes < 0) return "nframes must not be negative";
+    if (nframes > ((int64_t)1 << 40) / hop || first > ((int64_t)1 << 40) || first < -((int64_t)1 << 40)) return "nframes, hop and first: the frames lie beyond 2^40 samples";
+    if (batch < 0 || batch > 65535) return "batch must lie in 0 .. 65535";
+    if (dtype != SP_DTYPE_F32 && dtype != SP_DTYPE_C64) return "dtype must be float32 or complex64";
+    if (nsig < 1) return "nsig must be at least 1";
+    if (x_ld < nsig) return "x_ld is below nsig";
+    if (!isfinite(gamma) || gamma < 0.0) return "gamma must be finite and not negative";
+    if (!isfinite(rel) || rel < 0.0) return "rel must be finite and not negative";
+    return nullptr;
+}
+static bool ssq_band_ok(bool cplx, int n, int b0, int nb) {
+    return nb >= 1 && b0 >= 0 && (cplx ? (b0 < n && nb <= n) : (nb <= n / 2 + 1 && b0 <= n / 2 + 1 - nb));
+}
+
+int sp_ssq_plan(int cplx, int n, int64_t nframes, int64_t batch, int nb, int what, int64_t out[5]) {
+    if (n < 32 || n > SP_SSQ_MAX_L || !is_pow2(n) || nframes < 0 || batch < 0 || batch > 65535 || !out) return -1;
+    const bool bands = what == 8;
+    if (!bands && (what < 1 || what > 7)) return -1;
+    if (!bands && !ssq_band_ok(cplx != 0, n, 0, nb)) return -1;
+    const bool fields = !bands && (what & 4);
+    const int64_t fpr = ssq_fpr(n, nframes, batch, g.ncu, env_int("SP_SSQ_FPG", 0));
+    const size_t lds = ssq_lds_bytes(cplx != 0, n, bands ? 0 : nb, !bands && (what & 1), !bands && (what & 2), fields);
+    out[0] = fpr;
+    out[1] = (nframes + fpr - 1) / fpr * batch;
+    out[2] = (int64_t)lds;
+    out[3] = ssq_transforms(cplx != 0, fields);
+    out[4] = lds <= SP_SSQ_LDS_MAX ? 1 : 0;
+    return 0;
+}
+
+// the frames of one call: stages x for host callers, uploads the windows, fills what the two kernels' arguments share
+static int ssq_front(const char *who, SsqArgs &a, const void *x, int64_t x_ld, bool cplx, int64_t nsig, int64_t batch, const float *h,
+                     const float *dh, const float *th, int n, int hop, int64_t first, int64_t nframes, int segmean, double gamma,
+                     double rel, int mem, const cf **tw) {
+    const size_t esz = cplx ? 8 : 4, x_elems = (size_t)((batch - 1) * x_ld + nsig);
+    const void *xd = x;
+    if (!mem) {
+        if (g.in0.ensure(esz * x_elems)) return -1;
+        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * x_elems, hipMemcpyHostToDevice, g.stream));
+        xd = g.in0.p;
+    }
+    void *h_d = nullptr, *dh_d = nullptr, *th_d = nullptr;
+    if (get_table(1, h, sizeof(float) * (size_t)n, &h_d, nullptr)) return -1;
+    if (get_table(20, dh, sizeof(float) * (size_t)n, &dh_d, nullptr)) return -1;
+    if (th && get_table(21, th, sizeof(float) * (size_t)n, &th_d, nullptr)) return -1;
+    if (get_twiddles(n, tw)) return -1;
+    a = SsqArgs{};
+    a.x = xd;
+    a.x_ld = x_ld;
+    a.nsig = nsig;
+    a.first = first;
+    a.nframes = nframes;
+    a.fpr = ssq_fpr(n, nframes, batch, g.ncu, env_int("SP_SSQ_FPG", 0));
+    a.h = (const float *)h_d;
+    a.dh = (const float *)dh_d;
+    a.th = (const float *)th_d;
+    a.hop = hop;
+    a.segmean = segmean ? 1 : 0;
+    a.gamma = (float)gamma;
+    a.rel = (float)rel;
+    if ((a.nframes + a.fpr - 1) / a.fpr > INT_MAX) return fail("%s: nframes = %lld is too many runs for one launch", who, (long long)nframes);
+    return 0;
+}
+
+int sp_ssq(const void *x, int64_t x_ld, int dtype, int64_t nsig, int64_t batch, const float *h, const float *dh, const float *th, int n,
+           int hop, int64_t first, int64_t nframes, int segmean, double gamma, double rel, int b0, int nb, void *T, float *P, float *IF,
+           float *GD, int mem) {
+    // every refusal comes before the device is touched
+    if (const char *why = ssq_shape(n, hop, first, nframes, batch, dtype, nsig, x_ld, gamma, rel))
+        return fail("sp_ssq: %s (n %d, hop %d, nframes %lld, batch %lld, nsig %lld, x_ld %lld)", why, n, hop, (long long)nframes,
+                    (long long)batch, (long long)nsig, (long long)x_ld);
+    const bool cplx = dtype == SP_DTYPE_C64, fields = IF || GD;
+    if (!T && !P && !IF && !GD) return fail("sp_ssq: an output is required: T, P, IF or GD");
+    if (fields && !th) return fail("sp_ssq: th is required with IF or GD");
+    if (!ssq_band_ok(cplx, n, b0, nb))
+        return fail("sp_ssq: nb = %d bins from b0 = %d lie outside the %d bins of the spectrum", nb, b0, cplx ? n : n / 2 + 1);
+    const size_t lds = ssq_lds_bytes(cplx, n, nb, T != nullptr, P != nullptr, fields);
+    if (lds > SP_SSQ_LDS_MAX)
+        return fail("sp_ssq: the LDS of a workgroup, %zu bytes, does not fit %zu (n %d, nb %d): take a narrower band or fewer outputs", lds,
+                    SP_SSQ_LDS_MAX, n, nb);
+    if (!h || !dh) return fail("sp_ssq: h and dh are required");
+    if (batch == 0 || nframes == 0) return 0;
+    if (!x) return fail("sp_ssq: x is required");
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    SsqArgs a;
+    const cf *tw;
+    if (ssq_front("sp_ssq", a, x, x_ld, cplx, nsig, batch, h, dh, fields ? th : nullptr, n, hop, first, nframes, segmean, gamma, rel, mem, &tw))
+        return -1;
+    const size_t cells = (size_t)batch * (size_t)nframes * (size_t)nb, fb = sizeof(float) * cells, fa = (fb + 255) & ~(size_t)255;
+    a.b0 = b0;
+    a.nb = nb;
+    a.T = (cf *)T;
+    a.P = P;
+    a.IF = IF;
+    a.GD = GD;
+    if (!mem) {
+        // outputs staged for host callers: [T | P | IF | GD], each piece 256-byte aligned
+        if (g.out0.ensure(5 * fa)) return -1;
+        char *o = (char *)g.out0.p;
+        a.T = T ? (cf *)o : nullptr;
+        a.P = P ? (float *)(o + 2 * fa) : nullptr;
+        a.IF = IF ? (float *)(o + 3 * fa) : nullptr;
+        a.GD = GD ? (float *)(o + 4 * fa) : nullptr;
+    }
+    {
+        ProfScope ps;
+        if (launch_ssq(lc(), a, cplx, n, tw, (nframes + a.fpr - 1) / a.fpr, batch, lds) != 0)
+            return fail("sp_ssq: the launch was refused (n %d, nb %d, %lld frames, %lld rows)", n, nb, (long long)nframes, (long long)batch);
+        HIPCHK(hipGetLastError());
+        g.last_kernel = "k_ssq";
+    }
+    if (!mem) {
+        if (T) HIPCHK(hipMemcpyAsync(T, a.T, 2 * fb, hipMemcpyDeviceToHost, g.stream));
+        if (P) HIPCHK(hipMemcpyAsync(P, a.P, fb, hipMemcpyDeviceToHost, g.stream));
+        if (IF) HIPCHK(hipMemcpyAsync(IF, a.IF, fb, hipMemcpyDeviceToHost, g.stream));
+        if (GD) HIPCHK(hipMemcpyAsync(GD, a.GD, fb, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
+// the band edges of sp_ssq_bands / sp_ssq_sum; 0 or the message's tail
+static const char *ssq_edges_why(int nbands, const double *edges, const float *edges_t, double scale) {
+    if (nbands < 1 || nbands > SP_SSQ_MAX_BANDS) return "nbands must lie in 1 .. 8";
+    if ((edges != nullptr) == (edges_t != nullptr)) return "exactly one of edges and edges_t is required";
+    if (edges)
+        for (int j = 0; j < 2 * nbands; ++j)
+            if (!isfinite(edges[j])) return "edges must be finite";
+    if (!isfinite(scale)) return "scale must be finite";
+    return nullptr;
+}
+// the edges as float32: the constant pairs by value, the per-frame ones staged for host callers
+static int ssq_edges(int nbands, const double *edges, const float *edges_t, int64_t nframes, int mem, SsqEdges *ec, const float **out) {
+    *ec = SsqEdges{};
+    *out = nullptr;
+    if (edges) {
+        for (int j = 0; j < 2 * nbands; ++j) ec->v[j] = (float)edges[j];
+        return 0;
+    }
+    *out = edges_t;
+    if (!mem) {
+        const size_t bytes = sizeof(float) * 2 * (size_t)nbands * (size_t)nframes;
+        if (g.in1.ensure(bytes)) return -1;
+        HIPCHK(hipMemcpyAsync(g.in1.p, edges_t, bytes, hipMemcpyHostToDevice, g.stream));
+        *out = (const float *)g.in1.p;
+    }
+    return 0;
+}
+
+int sp_ssq_bands(const void *x, int64_t x_ld, int dtype, int64_t nsig, int64_t batch, const float *h, const float *dh, int n, int hop,
+                 int64_t first, int64_t nframes, int segmean, double gamma, double rel, int nbands, const double *edges,
+                 const float *edges_t, double scale, void *out, int mem) {
+    // every refusal comes before the device is touched
+    if (const char *why = ssq_shape(n, hop, first, nframes, batch, dtype, nsig, x_ld, gamma, rel))
+        return fail("sp_ssq_bands: %s (n %d, hop %d, nframes %lld, batch %lld, nsig %lld, x_ld %lld)", why, n, hop, (long long)nframes,
+                    (long long)batch, (long long)nsig, (long long)x_ld);
+    if (const char *why = ssq_edges_why(nbands, edges, edges_t, scale)) return fail("sp_ssq_bands: %s (nbands %d)", why, nbands);
+    const bool cplx = dtype == SP_DTYPE_C64;
+    const size_t lds = ssq_lds_bytes(cplx, n, 0, false, false, false);
+    if (lds > SP_SSQ_LDS_MAX) return fail("sp_ssq_bands: the LDS of a workgroup, %zu bytes, does not fit %zu", lds, SP_SSQ_LDS_MAX);
+    if (!h || !dh) return fail("sp_ssq_bands: h and dh are required");
+    if (!out) return fail("sp_ssq_bands: out is required");
+    if (batch == 0 || nframes == 0) return 0;
+    if (!x) return fail("sp_ssq_bands: x is required");
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    SsqArgs a;
+    const cf *tw;
+    if (ssq_front("sp_ssq_bands", a, x, x_ld, cplx, nsig, batch, h, dh, nullptr, n, hop, first, nframes, segmean, gamma, rel, mem, &tw)) return -1;
+    if (ssq_edges(nbands, edges, edges_t, nframes, mem, &a.edges_c, &a.edges)) return -1;
+    const size_t obytes = sizeof(cf) * (size_t)batch * (size_t)nbands * (size_t)nframes;
+    a.nbands = nbands;
+    a.per_frame = edges ? 0 : 1;
+    a.scale = (float)scale;
+    a.out = (cf *)out;
+    if (!mem) {
+        if (g.out0.ensure(obytes)) return -1;
+        a.out = (cf *)g.out0.p;
+    }
+    {
+        ProfScope ps;
+        if (launch_ssq(lc(), a, cplx, n, tw, (nframes + a.fpr - 1) / a.fpr, batch, lds) != 0)
+            return fail("sp_ssq_bands: the launch was refused (n %d, %d bands, %lld frames, %lld rows)", n, nbands, (long long)nframes,
+                        (long long)batch);
+        HIPCHK(hipGetLastError());
+        g.last_kernel = "k_ssq";
+    }
+    if (!mem) {
+        HIPCHK(hipMemcpyAsync(out, a.out, obytes, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+    }
+    return 0;
+}
+
+int sp_ssq_sum(const void *T, int64_t nframes, int nb, int64_t batch, int n, int b0, int nbands, const double *edges, const float *edges_t,
+               int half, double scale, void *out, int mem) {
+    // every refusal comes before the device is touched
+    if (n < 32 || n > SP_SSQ_MAX_L || !is_pow2(n)) return fail("sp_ssq_sum: n = %d must be a power of two from 32 to 8192", n);
+    if (nframes < 0) return fail("sp_ssq_sum: nframes must not be negative");
+    if (batch < 0 || batch > 65535) return fail("sp_ssq_sum: batch must lie in 0 .. 65535");
+    if (!ssq_band_ok(true, n, b0, nb)) return fail("sp_ssq_sum: nb = %d bins from b0 = %d lie outside the %d bins of the spectrum", nb, b0, n);
+    if (const char *why = ssq_edges_why(nbands, edges, edges_t, scale)) return fail("sp_ssq_sum: %s (nbands %d)", why, nbands);
+    if (!out) return fail("sp_ssq_sum: out is required");
+    if (batch == 0 || nframes == 0) return 0;
+    if (!T) return fail("sp_ssq_sum: T is required");
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const size_t tbytes = sizeof(cf) * (size_t)batch * (size_t)nframes * (size_t)nb;
+    const size_t obytes = sizeof(cf) * (size_t)batch * (size_t)nbands * (size_t)nframes;
+    const void *Td = T;
+    cf *od = (cf *)out;
+    if (!mem) {
+        if (g.in0.ensure(tbytes) || g.out0.ensure(obytes)) return -1;
+        HIPCHK(hipMemcpyAsync(g.in0.p, T, tbytes, hipMemcpyHostToDevice, g.stream));
+        Td = g.in0.p;
+        od = (cf *)g.out0.p;
+    }
+    const float *ed;
+    SsqEdges ec;
+    if (ssq_edges(nbands, edges, edges_t, nframes, mem, &ec, &ed)) return -1;
+    {
+        ProfScope ps;
+        LAUNCHCHK(launch_ssq_sum(lc(), (const cf *)Td, nframes, nb, n, b0, nbands, edges ? 0 : 1, ed, ec, half ? 1 : 0, (float)scale, batch, od));
+        g.last_kernel = "k_ssq_sum";
+    }
+    if (!mem) {
+        HIPCHK(hipMemcpyAsync(out, od, obytes, hipMemcpyDeviceToHost, g.stream));
         HIPCHK(hipStreamSynchronize(g.stream));
     }
     return 0;

@@ -1201,6 +1201,191 @@ def wct_plan(nsig, nscales, L, Mw, Mg=0, rows=1, xwt=False):
     return dict(zip(("hop", "frames", "chunk", "workgroups", "lds_bytes"), (int(v) for v in out)))
 
 
+SSQ_MIN_N, SSQ_MAX_N, SSQ_MAX_ROWS, SSQ_MAX_BANDS, SSQ_LDS_MAX = 32, 8192, 65535, 8, 160 * 1024
+
+
+class SsqRefused(ValueError, NotImplementedError):
+    """A shape the synchrosqueezing kernel does not take: outside the limits, and what is not built (segments that are no power of two
+    or longer than one workgroup transform, a band and output set whose accumulators do not fit the LDS of a workgroup)."""
+
+
+def ssq_lds_bytes(cplx, n, nb, T=True, P=False, fields=False):
+    """The LDS of a workgroup: an image of n + 16 complex per transform and 16 (T) + 8 (P) bytes per bin of the band, per group."""
+    return max(1, 4096 // n) * (((2 if cplx else 1) + (1 if fields else 0)) * (n + 16) * 8 + nb * ((16 if T else 0) + (8 if P else 0)))
+
+
+def ssq_check(who, cplx, n, hop, nframes, rows, gamma=0.0, rel=0.0, nsig=None, x_ld=None):
+    """The refusals sp_ssq, sp_ssq_bands and sp_ssq_plan share, before the library is touched."""
+    if n < SSQ_MIN_N or n > SSQ_MAX_N or n & (n - 1):
+        raise SsqRefused("%s: n = %d must be a power of two from %d to %d" % (who, n, SSQ_MIN_N, SSQ_MAX_N))
+    if hop < 1:
+        raise SsqRefused("%s: hop = %d must be at least 1" % (who, hop))
+    if nframes < 0:
+        raise SsqRefused("%s: nframes = %d must not be negative" % (who, nframes))
+    if rows < 0 or rows > SSQ_MAX_ROWS:
+        raise SsqRefused("%s: %d rows are outside 0 .. %d" % (who, rows, SSQ_MAX_ROWS))
+    if nsig is not None and nsig < 1:
+        raise SsqRefused("%s: the rows must hold at least one sample" % who)
+    if x_ld is not None and x_ld < nsig:
+        raise SsqRefused("%s: x_ld = %d is below nsig = %d" % (who, x_ld, nsig))
+    for name, v in (("gamma", gamma), ("rel", rel)):
+        if not np.isfinite(v) or v < 0:
+            raise SsqRefused("%s: %s = %r must be finite and not negative" % (who, name, v))
+
+
+def ssq_band_check(who, cplx, n, b0, nb, T, P, fields):
+    nbins = n if cplx else n // 2 + 1
+    if nb < 1 or b0 < 0 or (b0 >= n or nb > n if cplx else b0 + nb > nbins):
+        raise SsqRefused("%s: nb = %d bins from b0 = %d lie outside the %d bins of the spectrum" % (who, nb, b0, nbins))
+    lds = ssq_lds_bytes(cplx, n, nb, T, P, fields)
+    if lds > SSQ_LDS_MAX:
+        raise SsqRefused("%s: the LDS of a workgroup, %d bytes, does not fit %d (n %d, nb %d): take a narrower band or fewer outputs"
+                         % (who, lds, SSQ_LDS_MAX, n, nb))
+
+
+def ssq_windows(who, n, h, dh, th=None):
+    tabs = [None if w is None else _win32(w) for w in (h, dh, th)]
+    for name, w in zip(("h", "dh", "th"), tabs):
+        if w is not None and (w.shape != (n,) or not np.all(np.isfinite(w))):
+            raise SsqRefused("%s: %s must hold n = %d finite values" % (who, name, n))
+    if tabs[0] is None or tabs[1] is None:
+        raise SsqRefused("%s: h and dh are required" % who)
+    return tabs
+
+
+def _ssq_front(who, x, n, hop, nframes, gamma, rel):
+    md = _mode(x)
+    x = md.checked(x)
+    if x.ndim < 1:
+        raise SsqRefused("%s: x must have at least one axis" % who)
+    lead = tuple(int(d) for d in x.shape[:-1])
+    rows = 1
+    for d in lead:
+        rows *= d
+    nsig = int(x.shape[-1])
+    cplx = md.code(x) == _ffi.DTYPE_C64
+    ssq_check(who, cplx, n, hop, nframes, rows, gamma, rel, nsig)
+    md.bind(x)
+    xs, xld = md.rows(x)
+    return md, xs, xld, lead, rows, nsig, cplx
+
+
+def ssq(x, h, dh, hop, first, nframes, th=None, b0=0, nb=None, T=True, P=False, IF=False, GD=False, segmean=False, gamma=0.0, rel=0.0):
+    """The synchrosqueezed STFT and the reassignment fields along the last axis (sp_ssq): frame g = the n = len(h) samples from
+    first + g*hop on (zero outside the row) under the windows h, dh (dh/dj) and th ((j - n/2) h, needed for IF / GD).
+    -> (T, P, IF, GD), None for what was not asked: T complex64 [..., nframes, nb] = the sums of (-1)^k X_h over the used cells whose
+    rint(khat) is the bin, P float32 the same sums of |X_h|^2, IF = khat (bins) and GD = that (samples from the frame's centre) float32
+    at the source bins, NaN where |X_h| <= max(gamma, rel * the frame's largest).  The band: nb bins from b0 on (modulo n for complex
+    rows; real rows have the bins 0 .. n/2).  numpy in -> numpy out; device tensor in -> device tensors on x's stream."""
+    n, hop, first, nframes, b0 = int(np.asarray(h).shape[-1]), int(hop), int(first), int(nframes), int(b0)
+    gamma, rel = float(gamma), float(rel)
+    md, xs, xld, lead, rows, nsig, cplx = _ssq_front("ssq", x, n, hop, nframes, gamma, rel)
+    nb = (n if cplx else n // 2 + 1) - b0 if nb is None else int(nb)
+    fields = bool(IF or GD)
+    if not (T or P or fields):
+        raise SsqRefused("ssq: an output is required: T, P, IF or GD")
+    if fields and th is None:
+        raise SsqRefused("ssq: th is required with IF or GD")
+    ssq_band_check("ssq", cplx, n, b0, nb, bool(T), bool(P), fields)
+    hw, dw, tw = ssq_windows("ssq", n, h, dh, th if fields else None)
+    shape = lead + (nframes, nb)
+    out = [md.empty(shape, dt, xs) if want else None
+           for want, dt in ((T, "complex64"), (P, "float32"), (IF, "float32"), (GD, "float32"))]
+    md.call(lib().sp_ssq, md.addr(xs), xld, md.code(xs), nsig, rows, ptr(hw), ptr(dw), ptr(tw), n, hop, first, nframes,
+            1 if segmean else 0, gamma, rel, b0, nb, *[md.addr(o) for o in out])
+    return tuple(out)
+
+
+def _ssq_edges(who, md, edges, nframes, like):
+    """-> (nbands, host float64 [nbands, 2] or None, per-frame float32 [nbands, nframes, 2] in the call's memory or None)"""
+    if _is_torch(edges):
+        e = edges
+        if e.dim() != 3 or e.shape[0] < 1 or e.shape[0] > SSQ_MAX_BANDS or e.shape[1] != nframes or e.shape[2] != 2:
+            raise SsqRefused("%s: per-frame edges must be [nbands <= %d, nframes = %d, 2]" % (who, SSQ_MAX_BANDS, nframes))
+        if not md.dev:
+            return int(e.shape[0]), None, np.ascontiguousarray(e.detach().cpu().numpy(), dtype=np.float32)
+        return int(e.shape[0]), None, e.to(device=like.device, dtype=torch.float32).contiguous()
+    e = np.asarray(edges, dtype=np.float64)
+    if e.ndim == 1 and e.shape == (2,):
+        e = e[None, :]
+    if e.ndim not in (2, 3) or e.shape[-1] != 2 or e.shape[0] < 1 or e.shape[0] > SSQ_MAX_BANDS or (e.ndim == 3 and e.shape[1] != nframes):
+        raise SsqRefused("%s: edges must be [nbands, 2] or [nbands, nframes = %d, 2] with nbands in 1 .. %d" % (who, nframes, SSQ_MAX_BANDS))
+    if not np.all(np.isfinite(e)):
+        raise SsqRefused("%s: edges must be finite" % who)
+    if e.ndim == 2:
+        return int(e.shape[0]), np.ascontiguousarray(e), None
+    e32 = np.ascontiguousarray(e, dtype=np.float32)
+    if md.dev:
+        return int(e.shape[0]), None, torch.from_numpy(e32).to(like.device)
+    return int(e.shape[0]), None, e32
+
+
+def ssq_bands(x, h, dh, hop, first, nframes, edges, scale=1.0, segmean=False, gamma=0.0, rel=0.0):
+    """Modes without forming T (sp_ssq_bands): out complex64 [..., nbands, nframes], out[b, g] = scale * the sum of (-1)^k X_h over the
+    used cells of frame g with lo[b, g] <= khat < hi[b, g] (the un-rounded khat, edges in bins).  edges: [nbands, 2] or, per frame,
+    [nbands, nframes, 2]; nbands <= 8.  With first = -n/2 and hop = 1 and scale = 1 / (n h[n/2]) this is the band's analytic waveform;
+    with hop > 1 its samples at the frame centres, carrier included."""
+    n, hop, first, nframes = int(np.asarray(h).shape[-1]), int(hop), int(first), int(nframes)
+    gamma, rel, scale = float(gamma), float(rel), float(scale)
+    md, xs, xld, lead, rows, nsig, cplx = _ssq_front("ssq_bands", x, n, hop, nframes, gamma, rel)
+    if not np.isfinite(scale):
+        raise SsqRefused("ssq_bands: scale must be finite")
+    nbands, ec, et = _ssq_edges("ssq_bands", md, edges, nframes, xs)
+    hw, dw, _ = ssq_windows("ssq_bands", n, h, dh)
+    out = md.empty(lead + (nbands, nframes), "complex64", xs)
+    md.call(lib().sp_ssq_bands, md.addr(xs), xld, md.code(xs), nsig, rows, ptr(hw), ptr(dw), n, hop, first, nframes, 1 if segmean else 0,
+            gamma, rel, nbands, ptr(ec), md.addr(et), scale, md.addr(out))
+    return out
+
+
+def ssq_sum(T, n, edges, b0=0, half=False, scale=1.0):
+    """Band sums over an existing T [..., nframes, nb] whose first bin is b0 of an n-point transform (sp_ssq_sum): out complex64
+    [..., nbands, nframes], out[b, g] = scale * sum over lo <= m < hi of w_m T[g, m - b0], w = 1/2 at the bins 0 and n/2 when `half`."""
+    n, b0, scale = int(n), int(b0), float(scale)
+    md = _mode(T)
+    if md.dev:
+        if T.dtype != torch.complex64:
+            raise TypeError("ssq_sum: T must be complex64, got %s" % T.dtype)
+    else:
+        T = np.asarray(T)
+    if T.ndim < 2:
+        raise SsqRefused("ssq_sum: T must be [..., nframes, nb]")
+    nframes, nb = int(T.shape[-2]), int(T.shape[-1])
+    lead = tuple(int(d) for d in T.shape[:-2])
+    rows = 1
+    for d in lead:
+        rows *= d
+    ssq_check("ssq_sum", True, n, 1, nframes, rows)
+    if nb < 1 or b0 < 0 or b0 >= n or nb > n:
+        raise SsqRefused("ssq_sum: nb = %d bins from b0 = %d lie outside the %d bins of the spectrum" % (nb, b0, n))
+    if not np.isfinite(scale):
+        raise SsqRefused("ssq_sum: scale must be finite")
+    md.bind(T)
+    Tc = md.cast(T, "complex64")
+    nbands, ec, et = _ssq_edges("ssq_sum", md, edges, nframes, Tc)
+    out = md.empty(lead + (nbands, nframes), "complex64", Tc)
+    md.call(lib().sp_ssq_sum, md.addr(Tc), nframes, nb, rows, n, b0, nbands, ptr(ec), md.addr(et), 1 if half else 0, scale, md.addr(out))
+    return out
+
+
+def ssq_plan(n, nframes, rows=1, cplx=False, nb=None, T=True, P=False, fields=False, bands=False):
+    """sp_ssq_plan as a dict (host only): fpr (frames per run), workgroups, lds_bytes, transforms (per frame), fits."""
+    n, nframes, rows = int(n), int(nframes), int(rows)
+    ssq_check("ssq_plan", cplx, n, 1, nframes, rows)
+    nb = (n if cplx else n // 2 + 1) if nb is None else int(nb)
+    what = 8 if bands else (1 if T else 0) | (2 if P else 0) | (4 if fields else 0)
+    if what == 0:
+        raise SsqRefused("ssq_plan: an output is required")
+    if not bands and (nb < 1 or nb > (n if cplx else n // 2 + 1)):
+        raise SsqRefused("ssq_plan: nb = %d lies outside the %d bins of the spectrum" % (nb, n if cplx else n // 2 + 1))
+    out = np.zeros(5, dtype=np.int64)
+    if lib().sp_ssq_plan(1 if cplx else 0, n, nframes, rows, nb, what, ptr(out)) != 0:
+        raise SsqRefused("ssq_plan: the shape is refused")
+    d = dict(zip(("fpr", "workgroups", "lds_bytes", "transforms", "fits"), (int(v) for v in out)))
+    d["fits"] = bool(d["fits"])
+    return d
+
+
 EIGH_MAX_N = 64
 
 
