@@ -3,6 +3,7 @@
 #include "../../include/spectral_ext.h"
 #include "../../include/spectral_tfr.h"
 #include "launch.h"
+#include "stage.h"
 #include "table_cache.h"
 
 #include <hip/hip_runtime.h>
@@ -224,6 +225,61 @@ TableCache g_tables;
 struct ApiLock {
     std::lock_guard<std::mutex> lk;
     ApiLock() : lk(g.mu) { g_tables.begin_call(); }
+};
+
+// Staging of one call's host-memory (mem = 0) arguments: the one place that grows the scratch buffers, copies inputs in
+// and results back (layout rules: stage.h).  in / out / inout name a scratch, the caller's pointer and its size and take the
+// address of the pointer the kernels will use: with mem = 1 that is the caller's own pointer at once and nothing else
+// happens.  With mem = 0, commit() sizes every scratch named since the last commit once, sets the pointers and enqueues the
+// copies in on g.stream; finish(), at every successful return, enqueues the copies back in registration order and
+// synchronises.  An error return in between copies nothing back.
+struct Stage {
+    const bool host;
+    int done = 0;       // pieces already committed
+    StagePlan plan;
+    explicit Stage(int mem) : host(!mem) {}
+    template <class H, class D> void in(Scratch &s, const H *h, size_t bytes, const D **dev) {
+        *dev = (const D *)h;
+        if (host) plan.add(&s, h, nullptr, bytes, dev);
+    }
+    template <class H, class D> void out(Scratch &s, H *h, size_t bytes, D **dev) {
+        *dev = (D *)h;
+        if (host) plan.add(&s, nullptr, h, bytes, dev);
+    }
+    // one piece that is copied in from `h_in` and back to `h_out`: the kernels read *din and write *dout, the same staged
+    // address for host arrays (the work is done in place there), the caller's two pointers otherwise
+    template <class H, class D> void inout(Scratch &s, const H *h_in, H *h_out, size_t bytes, const D **din, D **dout) {
+        *din = (const D *)h_in;
+        *dout = (D *)h_out;
+        if (host) plan.add(&s, h_in, h_out, bytes, dout, din);
+    }
+    int commit() {
+        if (!host) return 0;
+        if (plan.err) return fail("staging: %s", plan.err);
+        for (int a = 0; a < plan.nareas; ++a)
+            if (!plan.area[a].sealed) {
+                if (((Scratch *)plan.area[a].key)->ensure(plan.area[a].total)) return -1;
+                plan.seal(a);
+            }
+        for (; done < plan.npieces; ++done) {
+            const StagePlan::Piece &p = plan.piece[done];
+            void *d = (char *)((Scratch *)plan.area[p.area].key)->p + p.off;
+            memcpy(p.slot, &d, sizeof d);
+            if (p.slot2) memcpy(p.slot2, &d, sizeof d);
+            if (p.from && p.bytes) HIPCHK(hipMemcpyAsync(d, p.from, p.bytes, hipMemcpyHostToDevice, g.stream));
+        }
+        return 0;
+    }
+    int finish() {
+        if (!host) return 0;
+        for (int i = plan.next_back(-1); i >= 0; i = plan.next_back(i)) {
+            const StagePlan::Piece &p = plan.piece[i];
+            const void *d = (const char *)((Scratch *)plan.area[p.area].key)->p + p.off;
+            if (p.bytes) HIPCHK(hipMemcpyAsync(p.to, d, p.bytes, hipMemcpyDeviceToHost, g.stream));
+        }
+        HIPCHK(hipStreamSynchronize(g.stream));
+        return 0;
+    }
 };
 
 // content hash of a host table (FNV-1a style, 8 bytes per step: a 4096-point window hashes in ~1 us)
@@ -1386,16 +1442,14 @@ int sp_mean(const void *x, int x_dtype, int64_t n, double out[2], int mem) {
     if (n <= 0) return fail("sp_mean: n must be positive");
     ApiLock lk;
     const size_t esz = x_dtype == SP_DTYPE_C64 ? 8 : 4;
-    const void *xd = x;
-    if (!mem) {
-        if (g.in0.ensure(esz * (size_t)n)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * (size_t)n, hipMemcpyHostToDevice, g.stream));
-        xd = g.in0.p;
-    }
+    Stage st(mem);
+    const void *xd;
+    st.in(g.in0, x, esz * (size_t)n, &xd);
+    if (st.commit()) return -1;
     TrendBuf tb;
     if (get_trendbuf(1, &tb)) return -1;
     if (set_trend(tb, 0, xd, x_dtype == SP_DTYPE_C64, n, 1, 0, 0)) return -1;
-    double h[2];
+    double h[2];   // (the result goes to the host in both modes: no finish())
     HIPCHK(hipMemcpyAsync(h, tb.d, sizeof h, hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
     out[0] = h[0];
@@ -1410,20 +1464,13 @@ int sp_fft_c2c(const void *in, void *out, int64_t n, int64_t batch, int directio
     if (batch == 0) return 0;
     ApiLock lk;
     const size_t bytes = sizeof(cf) * (size_t)n * (size_t)batch;
-    const cf *din = (const cf *)in;
-    cf *dout = (cf *)out;
-    if (!mem) {
-        if (g.in0.ensure(bytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, in, bytes, hipMemcpyHostToDevice, g.stream));
-        din = (const cf *)g.in0.p;
-        dout = (cf *)g.in0.p;
-    }
+    Stage st(mem);
+    const cf *din;
+    cf *dout;
+    st.inout(g.in0, in, out, bytes, &din, &dout);
+    if (st.commit()) return -1;
     if (dev_fft_any(din, dout, n, batch, direction > 0)) return -1;
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int sp_welch_psd(const void *x, int x_dtype, int64_t nsig, const float *win, int nfft, int hop, int64_t nframes,
@@ -1443,18 +1490,13 @@ int sp_welch_psd(const void *x, int x_dtype, int64_t nsig, const float *win, int
     if (!lng && get_xf(nfft, &xf)) return -1;
     const bool cplx = x_dtype == SP_DTYPE_C64;
     const size_t esz = cplx ? 8 : 4;
-    const void *xd = x;
-    if (!mem) {
-        if (g.in0.ensure(esz * (size_t)nsig)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
-        xd = g.in0.p;
-    }
     const int nb = nbins_host(nfft, sided);
-    double *out_d = pxx_out;
-    if (!mem) {
-        if (g.out0.ensure(sizeof(double) * (size_t)nb)) return -1;
-        out_d = (double *)g.out0.p;
-    }
+    Stage st(mem);
+    const void *xd;
+    double *out_d;
+    st.in(g.in0, x, esz * (size_t)nsig, &xd);
+    st.out(g.out0, pxx_out, sizeof(double) * (size_t)nb, &out_d);
+    if (st.commit()) return -1;
     const bool allow_carry = !env_flag("SP_WELCH_GENERIC");
     if (lng) {
         void *win_d;
@@ -1518,11 +1560,7 @@ int sp_welch_psd(const void *x, int x_dtype, int64_t nsig, const float *win, int
         }
         LAUNCHCHK(launch_welch_finish(lc(), partial, rp.groups, xf, sided, scale / (double)nframes, out_d, pair ? 1 : 0));
     }
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(pxx_out, out_d, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int sp_welch_accum(const void *x, int x_dtype, int64_t nsig, const float *win, int nfft, int hop, int64_t nframes,
@@ -1532,21 +1570,15 @@ int sp_welch_accum(const void *x, int x_dtype, int64_t nsig, const float *win, i
     ApiLock lk;
     const bool cplx = x_dtype == SP_DTYPE_C64;
     const size_t esz = cplx ? 8 : 4;
-    const void *xd = x;
-    if (!mem) {
-        if (g.in0.ensure(esz * (size_t)nsig)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
-        xd = g.in0.p;
-    }
+    Stage st(mem);
+    const void *xd;
+    st.in(g.in0, x, esz * (size_t)nsig, &xd);
+    if (st.commit()) return -1;
     if (welch_accum_locked(xd, cplx, nsig, win, nfft, hop, nframes, nmean, true)) return -1;
-    if (sum_out) {
-        if (mem) HIPCHK(hipMemcpyAsync(sum_out, g_pend.sum_d, sizeof(double) * 2, hipMemcpyDeviceToDevice, g.stream));
-        else {
-            HIPCHK(hipMemcpyAsync(sum_out, g_pend.sum_d, sizeof(double) * 2, hipMemcpyDeviceToHost, g.stream));
-            HIPCHK(hipStreamSynchronize(g.stream));
-        }
-    }
-    return 0;
+    if (!sum_out) return 0;
+    // real difference: the sums live in the pending state, not in a staged piece -- a device caller gets them by a copy in stream order
+    HIPCHK(hipMemcpyAsync(sum_out, g_pend.sum_d, sizeof(double) * 2, mem ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, g.stream));
+    return st.finish();
 }
 
 int sp_welch_finish(const double *mean, int64_t frames_total, int sided, double scale, double *pxx_out, int mem) {
@@ -1556,23 +1588,14 @@ int sp_welch_finish(const double *mean, int64_t frames_total, int sided, double 
     ApiLock lk;
     if (!g_pend.valid) return fail("sp_welch_finish: no pending sp_welch_accum");
     const int nb = nbins_host(g_pend.nfft, sided);
-    double *out_d = pxx_out;
-    const double *mean_d = mean;
-    if (!mem) {
-        if (g.out0.ensure(sizeof(double) * (size_t)nb + 64)) return -1;
-        out_d = (double *)g.out0.p;
-        if (mean) {
-            double *md = out_d + nb + 2;
-            HIPCHK(hipMemcpyAsync(md, mean, sizeof(double) * 2, hipMemcpyHostToDevice, g.stream));
-            mean_d = md;
-        }
-    }
+    Stage st(mem);
+    double *out_d;
+    const double *mean_d;
+    st.out(g.out0, pxx_out, sizeof(double) * (size_t)nb, &out_d);
+    st.in(g.out0, mean, sizeof(double) * 2, &mean_d);
+    if (st.commit()) return -1;
     if (welch_finish_locked(mean_d, frames_total, sided, scale, out_d)) return -1;
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(pxx_out, out_d, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int sp_welch_export(const void *x, int x_dtype, int64_t nsig, const float *win, int nfft, int hop, int64_t nframes,
@@ -1582,24 +1605,15 @@ int sp_welch_export(const void *x, int x_dtype, int64_t nsig, const float *win, 
     ApiLock lk;
     const bool cplx = x_dtype == SP_DTYPE_C64;
     const size_t esz = cplx ? 8 : 4;
-    const void *xd = x;
-    if (!mem) {
-        if (g.in0.ensure(esz * (size_t)nsig)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
-        xd = g.in0.p;
-    }
     const size_t nst = 5 * (size_t)nfft + 8;
-    double *st_d = state;
-    if (!mem) {
-        if (g.out0.ensure(sizeof(double) * nst)) return -1;
-        st_d = (double *)g.out0.p;
-    }
+    Stage st(mem);
+    const void *xd;
+    double *st_d;
+    st.in(g.in0, x, esz * (size_t)nsig, &xd);
+    st.out(g.out0, state, sizeof(double) * nst, &st_d);
+    if (st.commit()) return -1;
     if (welch_export_locked(xd, cplx, nsig, win, nfft, hop, nframes, nmean, st_d)) return -1;
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(state, st_d, sizeof(double) * nst, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int sp_welch_apply(const double *state, const float *win, int nfft, int64_t frames_total, int sided, double scale,
@@ -1617,21 +1631,14 @@ int sp_welch_apply(const double *state, const float *win, int nfft, int64_t fram
     if (get_window_spectrum(win, nfft, xf, &Wf_d)) return -1;
     const int nb = nbins_host(nfft, sided);
     const size_t nst = 5 * (size_t)nfft + 8;
-    const double *st_d = state;
-    double *out_d = pxx_out;
-    if (!mem) {
-        if (g.out0.ensure(sizeof(double) * (nst + (size_t)nb) + 64)) return -1;
-        double *sd = (double *)g.out0.p;
-        HIPCHK(hipMemcpyAsync(sd, state, sizeof(double) * nst, hipMemcpyHostToDevice, g.stream));
-        st_d = sd;
-        out_d = sd + nst;
-    }
+    Stage st(mem);
+    const double *st_d;
+    double *out_d;
+    st.in(g.out0, state, sizeof(double) * nst, &st_d);
+    st.out(g.out0, pxx_out, sizeof(double) * (size_t)nb, &out_d);
+    if (st.commit()) return -1;
     LAUNCHCHK(launch_op_apply(lc(), st_d, (const cf *)Wf_d, nfft, sided, scale / (double)frames_total, out_d));
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(pxx_out, out_d, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 /* ---- multi-GPU inside the library: one process per GPU, RCCL over xGMI --------------------------------------------------- */
@@ -1832,15 +1839,11 @@ int sp_welch_csd(const void *x, const void *y, int dtype, int64_t nsig, int nch,
     if (!lng && get_xf(nfft, &xf)) return -1;
     const bool cplx = dtype == SP_DTYPE_C64;
     const size_t esz = cplx ? 8 : 4;
-    const void *xd = x, *yd = y;
-    if (!mem) {
-        if (g.in0.ensure(esz * (size_t)nsig)) return -1;
-        if (g.in1.ensure(esz * (size_t)y_ld * (size_t)nch)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
-        HIPCHK(hipMemcpyAsync(g.in1.p, y, esz * (size_t)y_ld * (size_t)nch, hipMemcpyHostToDevice, g.stream));
-        xd = g.in0.p;
-        yd = g.in1.p;
-    }
+    Stage st(mem);
+    const void *xd, *yd;
+    st.in(g.in0, x, esz * (size_t)nsig, &xd);
+    st.in(g.in1, y, esz * (size_t)y_ld * (size_t)nch, &yd);
+    if (st.commit()) return -1;
     void *win_d;
     if (get_table(1, win, sizeof(float) * (size_t)nfft, &win_d, nullptr)) return -1;
     TrendBuf tb;
@@ -1869,13 +1872,11 @@ int sp_welch_csd(const void *x, const void *y, int dtype, int64_t nsig, int nch,
                 return -1;
     }
     const size_t nb = (size_t)nbins_host(nfft, sided);
-    double *pxx_d = pxx, *pyy_d = pyy, *pxy_d = pxy;
-    if (!mem) {
-        if (g.out0.ensure(sizeof(double) * nb * (1 + 3 * (size_t)nch))) return -1;
-        pxx_d = (double *)g.out0.p;
-        pyy_d = pxx_d + nb;
-        pxy_d = pyy_d + nb * nch;
-    }
+    double *pxx_d, *pyy_d, *pxy_d;
+    st.out(g.out0, pxx, sizeof(double) * nb, &pxx_d);
+    st.out(g.out0, pyy, sizeof(double) * nb * nch, &pyy_d);
+    st.out(g.out0, pxy, sizeof(double) * nb * nch * 2, &pxy_d);
+    if (st.commit()) return -1;
     if (lng) {
         // long segments: spectra of a chunk of frames of x, then of every channel against them (k_long.hip)
         const int64_t mc = long_chunk_frames(nfft, nframes);
@@ -1903,13 +1904,7 @@ int sp_welch_csd(const void *x, const void *y, int dtype, int64_t nsig, int nch,
             LAUNCHCHK(launch_long_finish(lc(), ayy + nf * (size_t)c, nfft, sided, sc, false, pyy_d + nb * (size_t)c));
             LAUNCHCHK(launch_long_finish(lc(), axy + 2 * nf * (size_t)c, nfft, sided, sc, true, pxy_d + 2 * nb * (size_t)c));
         }
-        if (!mem) {
-            HIPCHK(hipMemcpyAsync(pxx, pxx_d, sizeof(double) * nb, hipMemcpyDeviceToHost, g.stream));
-            HIPCHK(hipMemcpyAsync(pyy, pyy_d, sizeof(double) * nb * nch, hipMemcpyDeviceToHost, g.stream));
-            HIPCHK(hipMemcpyAsync(pxy, pxy_d, sizeof(double) * nb * nch * 2, hipMemcpyDeviceToHost, g.stream));
-            HIPCHK(hipStreamSynchronize(g.stream));
-        }
-        return 0;
+        return st.finish();
     }
     const RunPart rp = run_partition_2d(xf.L, nframes, g.ncu, nch);
     if (g.work.ensure(sizeof(float) * (size_t)rp.groups * xf.L * 4 * (size_t)nch)) return -1;
@@ -1971,13 +1966,7 @@ int sp_welch_csd(const void *x, const void *y, int dtype, int64_t nsig, int nch,
         LAUNCHCHK(launch_csd_finish(lc(), partial, rp.groups, xf, nch, sided, scale / (double)nframes, pxx_d, pyy_d,
                                     pxy_d));
     }
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(pxx, pxx_d, sizeof(double) * nb, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipMemcpyAsync(pyy, pyy_d, sizeof(double) * nb * nch, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipMemcpyAsync(pxy, pxy_d, sizeof(double) * nb * nch * 2, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 __global__ void k_set_trends(const double *__restrict__ means, float *__restrict__ trend, int nch) {
@@ -2004,23 +1993,17 @@ static int csd_matrix_impl(const char *who, const float *x, int nch, int64_t nsi
     xf.blue = true;
     if (!lng && get_xf(nfft, &xf)) return -1;
     const int nb = nfft / 2 + 1;
-    const float *xd = x;
-    if (!mem) {
-        const size_t ib = sizeof(float) * (size_t)x_ld * (size_t)nch;
-        if (g.in0.ensure(ib)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, ib, hipMemcpyHostToDevice, g.stream));
-        xd = (const float *)g.in0.p;
-    }
+    const size_t gbytes = sizeof(double) * 2 * (size_t)nb * (size_t)nch * (size_t)nch;
+    Stage st(mem);
+    const float *xd;
+    double *G;
+    st.in(g.in0, x, sizeof(float) * (size_t)x_ld * (size_t)nch, &xd);
+    st.out(g.cmG, g_out, gbytes, &G);
+    if (st.commit()) return -1;
     void *win_d;
     if (get_table(1, win, sizeof(float) * (size_t)nfft, &win_d, nullptr)) return -1;
     TrendBuf tb;
     if (get_trendbuf(2 * nch, &tb)) return -1;           // second half: trends re-based to the current frame chunk
-    const size_t gbytes = sizeof(double) * 2 * (size_t)nb * (size_t)nch * (size_t)nch;
-    double *G = g_out;
-    if (!mem) {
-        if (g.cmG.ensure(gbytes)) return -1;
-        G = (double *)g.cmG.p;
-    }
     // (G is zeroed lazily, by the first chunk that adds into it directly: a call whose chunks all go through the packed spectra
     //  never needs it -- k_csdm_fold then stores, scales and mirrors in its one sweep)
     bool g_zeroed = false;
@@ -2186,11 +2169,7 @@ static int csd_matrix_impl(const char *who, const float *x, int nch, int64_t nsi
         LAUNCHCHK(launch_csdm_fold(lc(), (const double *)g.cmH.p, G, nch, nfft, nullptr, nullptr, nullptr, 0, 0, gscale, fold_init));
     }
     if (!fold_init) LAUNCHCHK(launch_csdm_finish(lc(), G, nch, nb, gscale));
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(g_out, G, gbytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int sp_csd_matrix(const float *x, int nch, int64_t nsig, int64_t x_ld, const float *win, int nfft, int hop,
@@ -2208,23 +2187,20 @@ int sp_channel_means(const float *x, int nch, int64_t nsig, int64_t x_ld, double
     if (ensure_init()) return -1;
     if (nch < 1 || nch > 512 || nsig < 1 || x_ld < nsig) return fail("sp_channel_means: need 1 <= nch <= 512, 1 <= nsig <= x_ld");
     ApiLock lk;
-    const float *xd = x;
-    if (!mem) {
-        const size_t ib = sizeof(float) * (size_t)x_ld * (size_t)nch;
-        if (g.in0.ensure(ib)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, ib, hipMemcpyHostToDevice, g.stream));
-        xd = (const float *)g.in0.p;
-    }
+    Stage st(mem);
+    const float *xd;
+    st.in(g.in0, x, sizeof(float) * (size_t)x_ld * (size_t)nch, &xd);
+    if (st.commit()) return -1;
     TrendBuf tb;
     if (get_trendbuf(nch, &tb)) return -1;
     double *scr = moments_scratch();
     if (!scr) return -1;
     LAUNCHCHK(launch_moments(lc(), xd, false, nsig, 1, scr, tb.d, tb.f, nch, x_ld));
-    // tb.d holds 8 doubles per channel, the mean first
+    // tb.d holds 8 doubles per channel, the mean first.  real difference: the means are gathered by one strided copy straight
+    // into the caller's array, host or device, instead of through a staged piece
     HIPCHK(hipMemcpy2DAsync(means_out, sizeof(double), tb.d, sizeof(double) * 8, sizeof(double), (size_t)nch,
                             mem ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, g.stream));
-    if (!mem) HIPCHK(hipStreamSynchronize(g.stream));
-    return 0;
+    return st.finish();
 }
 
 int sp_stft(const void *x, int x_dtype, int64_t nsig, const float *win, int nfft, int hop, int64_t nframes,
@@ -2248,24 +2224,20 @@ int sp_stft(const void *x, int x_dtype, int64_t nsig, const float *win, int nfft
     const size_t osz = out_kind ? 4 : 8;
     const size_t nb = (size_t)nbins_host(nfft, sided);
     const size_t obytes = osz * nb * (size_t)nframes;
-    const void *xd = x;
-    if (!mem) {
-        if (g.in0.ensure(esz * (size_t)nsig)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
-        xd = g.in0.p;
-    }
+    Stage st(mem);
+    const void *xd;
+    st.in(g.in0, x, esz * (size_t)nsig, &xd);
+    if (st.commit()) return -1;
     void *win_d;
     if (get_table(1, win, sizeof(float) * (size_t)nfft, &win_d, nullptr)) return -1;
     TrendBuf tb;
     if (get_trendbuf(1, &tb)) return -1;
     if (set_trend(tb, 0, xd, cplx, nsig, detrend, mean_re, mean_im)) return -1;
-    void *fin = out;                     // final layout
-    double *pseg_d = pseg_out;
-    if (!mem) {
-        if (g.out0.ensure(obytes + (pseg_out ? sizeof(double) * (size_t)nframes + 16 : 0))) return -1;
-        fin = g.out0.p;
-        if (pseg_out) pseg_d = (double *)((char *)g.out0.p + ((obytes + 15) & ~(size_t)15));
-    }
+    void *fin;                           // final layout
+    double *pseg_d;
+    st.out(g.out0, out, obytes, &fin);
+    st.out(g.out0, pseg_out, sizeof(double) * (size_t)nframes, &pseg_d);
+    if (st.commit()) return -1;
     void *fm = fin;                      // frame-major result; bin-major needs a transpose into `fin`
     if (out_major == 1) {
         if (g.work.ensure(obytes)) return -1;
@@ -2293,13 +2265,7 @@ int sp_stft(const void *x, int x_dtype, int64_t nsig, const float *win, int nfft
                               (float)amp_scale, out_kind, fm, pseg_d, segmean));
     }
     if (out_major == 1) LAUNCHCHK(launch_transpose(lc(), fm, fin, nframes, (int64_t)nb, (int)osz));
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(out, fin, obytes, hipMemcpyDeviceToHost, g.stream));
-        if (pseg_out)
-            HIPCHK(hipMemcpyAsync(pseg_out, pseg_d, sizeof(double) * (size_t)nframes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int sp_stft_cog(const void *x, int x_dtype, int64_t nsig, const float *win, int nfft, int hop, int64_t nframes,
@@ -2319,12 +2285,10 @@ int sp_stft_cog(const void *x, int x_dtype, int64_t nsig, const float *win, int 
     if (!lng && get_xf(nfft, &xf)) return -1;
     const bool cplx = x_dtype == SP_DTYPE_C64;
     const size_t esz = cplx ? 8 : 4;
-    const void *xd = x;
-    if (!mem) {
-        if (g.in0.ensure(esz * (size_t)nsig)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
-        xd = g.in0.p;
-    }
+    Stage st(mem);
+    const void *xd;
+    st.in(g.in0, x, esz * (size_t)nsig, &xd);
+    if (st.commit()) return -1;
     void *win_d;
     if (get_table(1, win, sizeof(float) * (size_t)nfft, &win_d, nullptr)) return -1;
     TrendBuf tb;
@@ -2354,11 +2318,9 @@ int sp_stft_cog(const void *x, int x_dtype, int64_t nsig, const float *win, int 
     const size_t abytes = sizeof(cf) * (size_t)wpf * (size_t)nframes + (cog_op ? sizeof(cf) * 8 * (size_t)nframes : 0);
     if (g.work.ensure(abytes)) return -1;
     cf *acc = (cf *)g.work.p;
-    double *fin = cog_out;
-    if (!mem) {
-        if (g.out0.ensure(sizeof(double) * (size_t)nframes)) return -1;
-        fin = (double *)g.out0.p;
-    }
+    double *fin;
+    st.out(g.out0, cog_out, sizeof(double) * (size_t)nframes, &fin);
+    if (st.commit()) return -1;
     if (lng) {
         const int64_t mc = long_chunk_frames(nfft, nframes);
         if (g.bigA.ensure(sizeof(cf) * (size_t)mc * (size_t)nfft)) return -1;
@@ -2379,21 +2341,17 @@ int sp_stft_cog(const void *x, int x_dtype, int64_t nsig, const float *win, int 
             const size_t b_sp = sizeof(cf) * (size_t)rp.groups * (size_t)hop, b_sl = sizeof(double) * (size_t)(2 * hop > nfft ? 2 * hop : nfft);
             if (g.cmO.ensure(b_sp + b_sl + sizeof(double) * (size_t)(5 * nfft + 8))) return -1;
             cf *spartial = (cf *)g.cmO.p;
-            double *Sl = (double *)((char *)g.cmO.p + b_sp), *st = (double *)((char *)g.cmO.p + b_sp + b_sl);
+            double *Sl = (double *)((char *)g.cmO.p + b_sp), *ops = (double *)((char *)g.cmO.p + b_sp + b_sl);
             void *Wf_d;
             if (get_window_spectrum(win, nfft, xf, &Wf_d)) return -1;
             LAUNCHCHK(launch_welch_pipe(lc(), xd, cplx, (const float *)win_d, hop, nframes, tb.f, xf, (float *)acc, rp, spartial, 2));
             g.last_kernel = "k_welch_pipe(cog,onepass)";
             LAUNCHCHK(launch_cm_blocksums(lc(), spartial, 1, (int)rp.groups, hop, Sl));
             LAUNCHCHK(launch_op_finish_channels(lc(), xd, 0, 1, tb.f, (const float *)win_d, Sl, (const cf *)Wf_d, hop, nframes, nsig, xf,
-                                                st, cplx));
-            LAUNCHCHK(launch_cog_finish_op(lc(), acc, wpf, nframes, df, fin, acc + (size_t)wpf * (size_t)nframes, lobe_w, st, tb.f, nsig,
+                                                ops, cplx));
+            LAUNCHCHK(launch_cog_finish_op(lc(), acc, wpf, nframes, df, fin, acc + (size_t)wpf * (size_t)nframes, lobe_w, ops, tb.f, nsig,
                                            nfft));
-            if (!mem) {
-                HIPCHK(hipMemcpyAsync(cog_out, fin, sizeof(double) * (size_t)nframes, hipMemcpyDeviceToHost, g.stream));
-                HIPCHK(hipStreamSynchronize(g.stream));
-            }
-            return 0;
+            return st.finish();
         }
         if (pipe) {
             LAUNCHCHK(launch_welch_pipe(lc(), xd, cplx, (const float *)win_d, hop, nframes, tb.f, xf, (float *)acc, rp, nullptr, 2));
@@ -2407,11 +2365,7 @@ int sp_stft_cog(const void *x, int x_dtype, int64_t nsig, const float *win, int 
                                   nullptr, segmean, acc, klo, khi));
     }
     LAUNCHCHK(launch_cog_finish(lc(), acc, wpf, nframes, df, fin));
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(cog_out, fin, sizeof(double) * (size_t)nframes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int sp_bispectrum(const void *x, const void *y, const void *z, int x_dtype, int64_t nsig, const float *win, int nfft, int hop,
@@ -2433,14 +2387,10 @@ int sp_bispectrum(const void *x, const void *y, const void *z, int x_dtype, int6
     const int sided = cplx ? SP_SIDED_TWO : SP_SIDED_HALF;
     const size_t esz = cplx ? 8 : 4;
     const void *src[3] = {x, y ? y : x, z ? z : x};
-    const void *xd[3] = {x, src[1], src[2]};
-    if (!mem) {
-        if (g.bsIn.ensure(esz * (size_t)nsig * (size_t)nsp)) return -1;
-        for (int k = 0; k < nsp; ++k) {
-            xd[k] = (char *)g.bsIn.p + esz * (size_t)nsig * (size_t)k;
-            HIPCHK(hipMemcpyAsync((void *)xd[k], src[k], esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
-        }
-    }
+    const void *xd[3];
+    Stage st(mem);
+    for (int k = 0; k < nsp; ++k) st.in(g.bsIn, src[k], esz * (size_t)nsig, &xd[k]);
+    if (st.commit()) return -1;
     if (sym) xd[1] = xd[2] = xd[0];
     // the tiles that meet the valid region (j <= i for the auto case) and the map (ti, tj) -> tile number (-1: none)
     const int T = bispec_tile_dim(), ntd = (nb + T - 1) / T;
@@ -2499,23 +2449,15 @@ int sp_bispectrum(const void *x, const void *y, const void *z, int x_dtype, int6
         LAUNCHCHK(launch_bispec_pzz(lc(), S[2], nb, m, ppart));
         LAUNCHCHK(launch_bispec_reduce(lc(), part, ppart, ntiles, m, nb, f0 == 0, acc, p64));
     }
-    void *Bd = B_out;
-    double *b2d = b2_out, *pzd = pzz_out;
+    void *Bd;
+    double *b2d, *pzd;
     const size_t nn = (size_t)nb * (size_t)nb;
-    if (!mem) {
-        if (g.out0.ensure(sizeof(double) * (3 * nn + (size_t)nb))) return -1;
-        Bd = g.out0.p;
-        b2d = (double *)g.out0.p + 2 * nn;
-        pzd = pzz_out ? b2d + nn : nullptr;
-    }
+    st.out(g.out0, B_out, 2 * sizeof(double) * nn, &Bd);
+    st.out(g.out0, b2_out, sizeof(double) * nn, &b2d);
+    st.out(g.out0, pzz_out, sizeof(double) * (size_t)nb, &pzd);
+    if (st.commit()) return -1;
     LAUNCHCHK(launch_bispec_finish(lc(), acc, p64, tmap_d, ntd, nb, c0, sym ? 1 : 0, nframes, Bd, b2d, pzd));
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(B_out, Bd, 2 * sizeof(double) * nn, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipMemcpyAsync(b2_out, b2d, sizeof(double) * nn, hipMemcpyDeviceToHost, g.stream));
-        if (pzz_out) HIPCHK(hipMemcpyAsync(pzz_out, pzd, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int sp_multitaper(const void *x, const void *y, int dtype, int64_t nsig, const float *tapers, int ntapers, int nfft, int hop,
@@ -2548,33 +2490,25 @@ int sp_multitaper(const void *x, const void *y, int dtype, int64_t nsig, const f
     const size_t esz = cplx ? 8 : 4;
     const int sided = cplx ? SP_SIDED_RAW : SP_SIDED_HALF;
     const size_t nb = (size_t)nbins_host(nfft, sided), K = (size_t)ntapers;
-    const void *xd = x, *yd = y;
-    if (!mem) {
-        if (g.in0.ensure(esz * (size_t)nsig) || (cross && g.in1.ensure(esz * (size_t)nsig))) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
-        xd = g.in0.p;
-        if (cross) {
-            HIPCHK(hipMemcpyAsync(g.in1.p, y, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
-            yd = g.in1.p;
-        }
-    }
+    Stage st(mem);
+    const void *xd, *yd;
+    st.in(g.in0, x, esz * (size_t)nsig, &xd);
+    st.in(g.in1, y, esz * (size_t)nsig, &yd);
+    if (st.commit()) return -1;
     void *tap_d;
     if (get_table(8, tapers, sizeof(float) * K * (size_t)nfft, &tap_d, nullptr)) return -1;
     TrendBuf tb;
     if (get_trendbuf(2, &tb)) return -1;
     if (set_trend(tb, 0, xd, cplx, nsig, detrend, mean_x ? mean_x[0] : 0, mean_x ? mean_x[1] : 0)) return -1;
     if (cross && set_trend(tb, 1, yd, cplx, nsig, detrend, mean_y ? mean_y[0] : 0, mean_y ? mean_y[1] : 0)) return -1;
-    // outputs: [pxx | pyy | pxy | skx | sky] staged for host callers
-    const size_t n_w = cross ? 4 * nb : nb, n_e = eigen ? (cross ? 2 : 1) * K * nb : 0;
-    double *pxx_d = pxx, *pyy_d = pyy, *pxy_d = pxy, *skx_d = skx, *sky_d = sky;
-    if (!mem) {
-        if (g.out0.ensure(sizeof(double) * (n_w + n_e))) return -1;
-        pxx_d = (double *)g.out0.p;
-        pyy_d = pxx_d + nb;
-        pxy_d = pyy_d + nb;
-        skx_d = pxx_d + n_w;
-        sky_d = skx_d + K * nb;
-    }
+    // the outputs the call's form has; the others are not written, whatever the caller passed
+    double *pxx_d, *pyy_d, *pxy_d, *skx_d, *sky_d;
+    st.out(g.out0, pxx, sizeof(double) * nb, &pxx_d);
+    st.out(g.out0, cross ? pyy : nullptr, sizeof(double) * nb, &pyy_d);
+    st.out(g.out0, cross ? pxy : nullptr, sizeof(double) * 2 * nb, &pxy_d);
+    st.out(g.out0, eigen ? skx : nullptr, sizeof(double) * K * nb, &skx_d);
+    st.out(g.out0, eigen && cross ? sky : nullptr, sizeof(double) * K * nb, &sky_d);
+    if (st.commit()) return -1;
     // the PSD of a real record transforms PAIRS of frames; the eigenspectra run one taper per grid row
     const bool pair = !cross && !cplx;
     const int64_t nunits = pair ? (nframes + 1) / 2 : nframes;
@@ -2612,19 +2546,7 @@ int sp_multitaper(const void *x, const void *y, int dtype, int64_t nsig, const f
             LAUNCHCHK(launch_mtaper_combine(lc(), sxy_d, ntapers, (int64_t)(2 * nb), cn, pxy_d));
         }
     }
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(pxx, pxx_d, sizeof(double) * nb, hipMemcpyDeviceToHost, g.stream));
-        if (cross) {
-            HIPCHK(hipMemcpyAsync(pyy, pyy_d, sizeof(double) * nb, hipMemcpyDeviceToHost, g.stream));
-            HIPCHK(hipMemcpyAsync(pxy, pxy_d, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost, g.stream));
-        }
-        if (eigen) {
-            HIPCHK(hipMemcpyAsync(skx, skx_d, sizeof(double) * K * nb, hipMemcpyDeviceToHost, g.stream));
-            if (cross) HIPCHK(hipMemcpyAsync(sky, sky_d, sizeof(double) * K * nb, hipMemcpyDeviceToHost, g.stream));
-        }
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int sp_czt_chirp(int64_t i0, int64_t count, double step, double start, float *cs_out) {
@@ -2647,14 +2569,12 @@ int sp_czt(const void *x, int x_dtype, int64_t n, int64_t x_ld, int64_t batch, i
     ApiLock lk;
     const bool cplx = x_dtype == SP_DTYPE_C64;
     const size_t esz = cplx ? 8 : 4, in_elems = (size_t)((batch - 1) * x_ld + n), obytes = sizeof(cf) * (size_t)batch * (size_t)m;
-    const void *xd = x;
-    cf *od = (cf *)out;
-    if (!mem) {
-        if (g.in0.ensure(esz * in_elems) || g.out0.ensure(obytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * in_elems, hipMemcpyHostToDevice, g.stream));
-        xd = g.in0.p;
-        od = (cf *)g.out0.p;
-    }
+    Stage st(mem);
+    const void *xd;
+    cf *od;
+    st.in(g.in0, x, esz * in_elems, &xd);
+    st.out(g.out0, out, obytes, &od);
+    if (st.commit()) return -1;
     CztTab t;
     if (get_czt(n, m, start, step, &t)) return -1;
     if (t.L <= SP_MAX_WG_FFT) {
@@ -2676,11 +2596,7 @@ int sp_czt(const void *x, int x_dtype, int64_t n, int64_t x_ld, int64_t batch, i
             LAUNCHCHK(launch_czt_post(lc(), A, t.L, rows, t.post, m, 1.f, b0, od));
         }
     }
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(out, od, obytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 // ---- digital down-converter (k_ddc.hip) -----------------------------------------------------------
@@ -2719,14 +2635,12 @@ int sp_ddc(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t batch
     ApiLock lk;
     const bool cplx = x_dtype == SP_DTYPE_C64;
     const size_t esz = cplx ? 8 : 4, in_elems = (size_t)((batch - 1) * x_ld + nsig), obytes = sizeof(cf) * (size_t)batch * (size_t)nout;
-    const void *xd = x;
-    cf *od = (cf *)out;
-    if (!mem) {
-        if (g.in0.ensure(esz * in_elems) || g.out0.ensure(obytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * in_elems, hipMemcpyHostToDevice, g.stream));
-        xd = g.in0.p;
-        od = (cf *)g.out0.p;
-    }
+    Stage st(mem);
+    const void *xd;
+    cf *od;
+    st.in(g.in0, x, esz * in_elems, &xd);
+    st.out(g.out0, out, obytes, &od);
+    if (st.commit()) return -1;
     // the taps, one row per polyphase component, reversed: taps[s][p] = h[(PP - 1 - p) q + s]
     std::vector<float> tp((size_t)q * geom.PP, 0.f);
     for (int s = 0; s < q; ++s)
@@ -2763,11 +2677,7 @@ int sp_ddc(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t batch
         HIPCHK(hipGetLastError());
         g.last_kernel = "k_ddc";
     }
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(out, od, obytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 // ---- rational resampler (k_upfirdn.hip) ------------------------------------------------------------
@@ -2807,14 +2717,12 @@ int sp_upfirdn(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t b
     if (ensure_init()) return -1;
     ApiLock lk;
     const size_t esz = cplx ? 8 : 4, in_elems = (size_t)((batch - 1) * x_ld + nsig), obytes = esz * (size_t)batch * (size_t)nout;
-    const void *xd = x;
-    void *od = out;
-    if (!mem) {
-        if (g.in0.ensure(esz * in_elems) || g.out0.ensure(obytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * in_elems, hipMemcpyHostToDevice, g.stream));
-        xd = g.in0.p;
-        od = g.out0.p;
-    }
+    Stage st(mem);
+    const void *xd;
+    void *od;
+    st.in(g.in0, x, esz * in_elems, &xd);
+    st.out(g.out0, out, obytes, &od);
+    if (st.commit()) return -1;
     // the taps, one row per phase: taps[phi][p] = h[phi + p up]
     std::vector<float> tp((size_t)up * geom.pitch, 0.f);
     for (int j = 0; j < ntaps; ++j) tp[(size_t)(j % up) * geom.pitch + j / up] = h[j];
@@ -2828,11 +2736,7 @@ int sp_upfirdn(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t b
         HIPCHK(hipGetLastError());
         g.last_kernel = "k_upfirdn";
     }
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(out, od, obytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 // ---- polyphase filter-bank channelizer (k_pfb.hip) ------------------------------------------------
@@ -2873,14 +2777,12 @@ int sp_pfb(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t batch
     const int P = ntaps / M, nb = cplx ? M : M / 2 + 1;
     const size_t esz = cplx ? 8 : 4, in_elems = (size_t)((batch - 1) * x_ld + nsig);
     const size_t obytes = (out_kind ? sizeof(double) : sizeof(cf) * (size_t)nframes) * (size_t)nb * (size_t)batch;
-    const void *xd = x;
-    void *od = out;
-    if (!mem) {
-        if (g.in0.ensure(esz * in_elems) || g.out0.ensure(obytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * in_elems, hipMemcpyHostToDevice, g.stream));
-        xd = g.in0.p;
-        od = g.out0.p;
-    }
+    Stage st(mem);
+    const void *xd;
+    void *od;
+    st.in(g.in0, x, esz * in_elems, &xd);
+    st.out(g.out0, out, obytes, &od);
+    if (st.commit()) return -1;
     void *taps_d = nullptr;
     if (get_table(11, h, sizeof(float) * (size_t)ntaps, &taps_d, nullptr)) return -1;
     // the run partition of one row (SP_PFB_FPG: a test hook like those of launch.h, read on every call; any value >= 1 is valid)
@@ -2918,11 +2820,7 @@ int sp_pfb(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t batch
             LAUNCHCHK(launch_transpose(lc(), (const char *)kout + (size_t)b * row, (char *)od + (size_t)b * row, nframes, (int64_t)nb,
                                        (int)sizeof(cf)));
     }
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(out, od, obytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 // ---- polyphase synthesis bank (k_pfb_synth.hip) -----------------------------------------------------
@@ -3019,14 +2917,12 @@ int sp_pfb_synth(const void *X, int sided, int in_major, int64_t batch, int64_t 
     const int P = ntaps / M, nb = cplx ? M : M / 2 + 1;
     const size_t xbytes = sizeof(cf) * (size_t)nb * (size_t)nframes * (size_t)batch;
     const size_t esz = cplx ? sizeof(cf) : sizeof(float), ybytes = esz * (size_t)nout * (size_t)batch;
-    const cf *xd = (const cf *)X;
-    void *yd = y;
-    if (!mem) {
-        if (g.in0.ensure(xbytes) || g.out0.ensure(ybytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, X, xbytes, hipMemcpyHostToDevice, g.stream));
-        xd = (const cf *)g.in0.p;
-        yd = g.out0.p;
-    }
+    Stage st(mem);
+    const cf *xd;
+    void *yd;
+    st.in(g.in0, X, xbytes, &xd);
+    st.out(g.out0, y, ybytes, &yd);
+    if (st.commit()) return -1;
     void *taps_d = nullptr;
     if (get_table(12, tap.data(), sizeof(float) * (size_t)ntaps, &taps_d, nullptr)) return -1;
     if (in_major == 1) {                 // bin-major frames [row][nb][nframes]: transposed per row into scratch, as sp_pfb writes them
@@ -3063,11 +2959,7 @@ int sp_pfb_synth(const void *X, int sided, int in_major, int64_t batch, int64_t 
                                           nout, yd));
         g.last_kernel = "k_pfb_synth(composed)";
     }
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(y, yd, ybytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int sp_zoom_welch(const void *x, const void *y, int dtype, int64_t nsig, const float *win, int nfft, int hop, int64_t nframes,
@@ -3091,16 +2983,11 @@ int sp_zoom_welch(const void *x, const void *y, int dtype, int64_t nsig, const f
     ApiLock lk;
     const bool cplx = dtype == SP_DTYPE_C64, lin = detrend == SP_DETREND_LINEAR;
     const size_t esz = cplx ? 8 : 4, mm = (size_t)m;
-    const void *xd = x, *yd = y;
-    if (!mem) {
-        if (g.in0.ensure(esz * (size_t)nsig) || (cross && g.in1.ensure(esz * (size_t)nsig))) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
-        xd = g.in0.p;
-        if (cross) {
-            HIPCHK(hipMemcpyAsync(g.in1.p, y, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
-            yd = g.in1.p;
-        }
-    }
+    Stage st(mem);
+    const void *xd, *yd;
+    st.in(g.in0, x, esz * (size_t)nsig, &xd);
+    st.in(g.in1, y, esz * (size_t)nsig, &yd);
+    if (st.commit()) return -1;
     void *win_d;
     if (get_table(1, win, sizeof(float) * (size_t)nfft, &win_d, nullptr)) return -1;
     TrendBuf tb;
@@ -3109,18 +2996,14 @@ int sp_zoom_welch(const void *x, const void *y, int dtype, int64_t nsig, const f
     if (cross && set_trend(tb, 1, yd, cplx, nsig, detrend, mean_y ? mean_y[0] : 0, mean_y ? mean_y[1] : 0)) return -1;
     CztTab t;
     if (get_czt(nfft, m, start, step, &t)) return -1;
-    // outputs staged for host callers: [pxx | pyy | pxy], or the frames
-    const size_t obytes = stft ? sizeof(cf) * (size_t)nframes * mm : sizeof(double) * (cross ? 4 : 1) * mm;
-    double *pxx_d = pxx, *pyy_d = pyy, *pxy_d = pxy;
-    cf *fr_d = (cf *)frames;
-    if (!mem) {
-        if (g.out0.ensure(obytes)) return -1;
-        if (stft) fr_d = (cf *)g.out0.p;
-        pxx_d = (double *)g.out0.p;
-        pyy_d = cross ? pxx_d + mm : nullptr;
-        pxy_d = cross ? pyy_d + mm : nullptr;
-    }
-    if (!cross) pyy_d = pxy_d = nullptr;
+    // the outputs the call's form has: the frames, or pxx, or pxx, pyy and pxy
+    double *pxx_d, *pyy_d, *pxy_d;
+    cf *fr_d;
+    st.out(g.out0, frames, sizeof(cf) * (size_t)nframes * mm, &fr_d);
+    st.out(g.out0, stft ? nullptr : pxx, sizeof(double) * mm, &pxx_d);
+    st.out(g.out0, !stft && cross ? pyy : nullptr, sizeof(double) * mm, &pyy_d);
+    st.out(g.out0, !stft && cross ? pxy : nullptr, sizeof(double) * 2 * mm, &pxy_d);
+    if (st.commit()) return -1;
     const double sc = scale / (double)nframes;
     if (t.L <= SP_MAX_WG_FFT) {
         CztTables ct{nullptr, t.pre, t.post, t.bf, nfft, (int)m};
@@ -3167,19 +3050,7 @@ int sp_zoom_welch(const void *x, const void *y, int dtype, int64_t nsig, const f
         }
         if (!stft) LAUNCHCHK(launch_zoom_acc_out(lc(), acc, m, sc, pxx_d, pyy_d, pxy_d));
     }
-    if (!mem) {
-        if (stft) {
-            HIPCHK(hipMemcpyAsync(frames, fr_d, obytes, hipMemcpyDeviceToHost, g.stream));
-        } else {
-            HIPCHK(hipMemcpyAsync(pxx, pxx_d, sizeof(double) * mm, hipMemcpyDeviceToHost, g.stream));
-            if (cross) {
-                HIPCHK(hipMemcpyAsync(pyy, pyy_d, sizeof(double) * mm, hipMemcpyDeviceToHost, g.stream));
-                HIPCHK(hipMemcpyAsync(pxy, pxy_d, sizeof(double) * 2 * mm, hipMemcpyDeviceToHost, g.stream));
-            }
-        }
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 // ---- short-time cross-correlation (k_xcorr_frames.hip) -------------------------------------------
@@ -3221,32 +3092,23 @@ int sp_xcorr_frames(const void *x, const void *y, int dtype, int64_t nsig, const
     ApiLock lk;
     const bool cplx = dtype == SP_DTYPE_C64;
     const size_t esz = cplx ? 8 : 4, lsz = cplx ? sizeof(cf) : sizeof(float), nl = 2 * (size_t)maxlag + 1;
-    const void *xd = x, *yd = y;
-    if (!mem) {
-        if (g.in0.ensure(esz * (size_t)nsig) || g.in1.ensure(esz * (size_t)nsig)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
-        HIPCHK(hipMemcpyAsync(g.in1.p, y, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
-        xd = g.in0.p;
-        yd = g.in1.p;
-    }
+    Stage st(mem);
+    const void *xd, *yd;
+    st.in(g.in0, x, esz * (size_t)nsig, &xd);
+    st.in(g.in1, y, esz * (size_t)nsig, &yd);
+    if (st.commit()) return -1;
     void *win_d = nullptr, *wt_d = nullptr;
     if (win && get_table(1, win, sizeof(float) * (size_t)nw, &win_d, nullptr)) return -1;
     if (weight && get_table(13, weight, sizeof(float) * (size_t)L, &wt_d, nullptr)) return -1;
     const cf *tw;
     if (get_twiddles(L, &tw)) return -1;
-    // outputs staged for host callers: [frames | avg | peak], each piece 256-byte aligned
-    const size_t fbytes = frames ? lsz * (size_t)nframes * nl : 0, abytes = avg ? sizeof(double) * (cplx ? 2 : 1) * nl : 0;
-    const size_t pbytes = peak ? sizeof(float) * 2 * (size_t)nframes : 0;
-    const size_t aoff = (fbytes + 255) & ~(size_t)255, poff = aoff + ((abytes + 255) & ~(size_t)255);
-    void *fr_d = frames;
-    double *avg_d = avg;
-    float *pk_d = peak;
-    if (!mem) {
-        if (g.out0.ensure(poff + pbytes)) return -1;
-        fr_d = frames ? g.out0.p : nullptr;
-        avg_d = avg ? (double *)((char *)g.out0.p + aoff) : nullptr;
-        pk_d = peak ? (float *)((char *)g.out0.p + poff) : nullptr;
-    }
+    void *fr_d;
+    double *avg_d;
+    float *pk_d;
+    st.out(g.out0, frames, lsz * (size_t)nframes * nl, &fr_d);
+    st.out(g.out0, avg, sizeof(double) * (cplx ? 2 : 1) * nl, &avg_d);
+    st.out(g.out0, peak, sizeof(float) * 2 * (size_t)nframes, &pk_d);
+    if (st.commit()) return -1;
     RunPart rp = run_partition(L, nframes, g.ncu);
     if (const int fpg = env_int("SP_XCF_FPG", 0); fpg > 0) {           // test hook: runs of this many frames
         const int fpw = fpw_of(L);
@@ -3267,13 +3129,7 @@ int sp_xcorr_frames(const void *x, const void *y, int dtype, int64_t nsig, const
         g.last_kernel = "k_xcorr_frames";
     }
     if (avg) LAUNCHCHK(launch_xcorr_frames_finish(lc(), partial, cplx, rp.groups, L, maxlag, nframes, avg_d));
-    if (!mem) {
-        if (frames) HIPCHK(hipMemcpyAsync(frames, fr_d, fbytes, hipMemcpyDeviceToHost, g.stream));
-        if (avg) HIPCHK(hipMemcpyAsync(avg, avg_d, abytes, hipMemcpyDeviceToHost, g.stream));
-        if (peak) HIPCHK(hipMemcpyAsync(peak, pk_d, pbytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 // ---- two-point wavenumber-frequency spectrum S(k, f) (k_skf.hip) --------------------------------
@@ -3316,14 +3172,11 @@ int sp_skf(const void *x, const void *y, int dtype, int64_t nsig, const float *w
     if (ensure_init()) return -1;
     ApiLock lk;
     const size_t esz = cplx ? 8 : 4;
-    const void *xd = x, *yd = y;
-    if (!mem) {
-        if (g.in0.ensure(esz * (size_t)nsig) || g.in1.ensure(esz * (size_t)nsig)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
-        HIPCHK(hipMemcpyAsync(g.in1.p, y, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
-        xd = g.in0.p;
-        yd = g.in1.p;
-    }
+    Stage st(mem);
+    const void *xd, *yd;
+    st.in(g.in0, x, esz * (size_t)nsig, &xd);
+    st.in(g.in1, y, esz * (size_t)nsig, &yd);
+    if (st.commit()) return -1;
     void *win_d = nullptr;
     if (win && get_table(1, win, sizeof(float) * (size_t)nfft, &win_d, nullptr)) return -1;
     const cf *tw;
@@ -3339,11 +3192,9 @@ int sp_skf(const void *x, const void *y, int dtype, int64_t nsig, const float *w
     if (const int v = env_int("SP_SKF_FPG", 0); v > 0) fpr = v;            // test hook: runs of this many frames
     const int64_t runs = (nframes + fpr - 1) / fpr;
     if (g.work.ensure(sizeof(float) * (size_t)runs * (size_t)cells)) return -1;
-    double *out_d = s_out;
-    if (!mem) {
-        if (g.out0.ensure(sizeof(double) * (size_t)cells)) return -1;
-        out_d = (double *)g.out0.p;
-    }
+    double *out_d;
+    st.out(g.out0, s_out, sizeof(double) * (size_t)cells, &out_d);
+    if (st.commit()) return -1;
     const SkfArgs a{xd, yd, (const float *)win_d, hop, detrend == SP_DETREND_SEGMEAN ? 1 : 0, power == SP_SKF_CROSS ? 1 : 0, b0, nb, nk,
                     pl.tile_bins, pl.stride, nframes, fpr};
     {
@@ -3352,11 +3203,7 @@ int sp_skf(const void *x, const void *y, int dtype, int64_t nsig, const float *w
         g.last_kernel = "k_skf";
     }
     LAUNCHCHK(launch_skf_finish(lc(), (const float *)g.work.p, runs, nb, nk, scale / (double)nframes, out_d));
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(s_out, out_d, sizeof(double) * (size_t)cells, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 // ---- time-resolved Welch spectra (k_welch_blocks.hip) ---------------------------------------------
@@ -3413,25 +3260,16 @@ int sp_welch_blocks(const void *x, const void *y, int dtype, int64_t nsig, int n
     const WelchBlocksPlan pl = welch_blocks_plan_of(cplx, nfft, nframes, navg, step, y ? nch : 0, g.ncu);
     const size_t esz = cplx ? 8 : 4, cells = (size_t)pl.nblocks * (size_t)pl.nb;
     const size_t xxb = sizeof(float) * cells, yyb = y ? sizeof(float) * cells * (size_t)nch : 0, xyb = 2 * yyb;
-    const size_t yoff = (xxb + 255) & ~(size_t)255, xyoff = yoff + ((yyb + 255) & ~(size_t)255);
-    const void *xd = x, *yd = y;
-    float *pxx_d = pxx, *pyy_d = pyy;
-    cf *pxy_d = (cf *)pxy;
-    if (!mem) {
-        if (g.in0.ensure(esz * (size_t)nsig)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * (size_t)nsig, hipMemcpyHostToDevice, g.stream));
-        xd = g.in0.p;
-        if (y) {
-            const size_t yb = esz * ((size_t)(nch - 1) * (size_t)y_ld + (size_t)nsig);
-            if (g.in1.ensure(yb)) return -1;
-            HIPCHK(hipMemcpyAsync(g.in1.p, y, yb, hipMemcpyHostToDevice, g.stream));
-            yd = g.in1.p;
-        }
-        if (g.out0.ensure(xyoff + xyb)) return -1;       // staged outputs: [pxx | pyy | pxy], each piece 256-byte aligned
-        pxx_d = (float *)g.out0.p;
-        pyy_d = y ? (float *)((char *)g.out0.p + yoff) : nullptr;
-        pxy_d = y ? (cf *)((char *)g.out0.p + xyoff) : nullptr;
-    }
+    Stage st(mem);
+    const void *xd, *yd;
+    float *pxx_d, *pyy_d;
+    cf *pxy_d;
+    st.in(g.in0, x, esz * (size_t)nsig, &xd);
+    st.in(g.in1, y, esz * ((size_t)(pairs - 1) * (size_t)y_ld + (size_t)nsig), &yd);
+    st.out(g.out0, pxx, xxb, &pxx_d);
+    st.out(g.out0, y ? pyy : nullptr, yyb, &pyy_d);
+    st.out(g.out0, y ? pxy : nullptr, xyb, &pxy_d);
+    if (st.commit()) return -1;
     void *win_d = nullptr;
     if (win && get_table(1, win, sizeof(float) * (size_t)nfft, &win_d, nullptr)) return -1;
     const cf *tw;
@@ -3453,15 +3291,7 @@ int sp_welch_blocks(const void *x, const void *y, int dtype, int64_t nsig, int n
     if (!pl.final_form)
         LAUNCHCHK(launch_block_sum(lc(), partial, pl.runs, y ? 4 : 1, pl.nb, pl.nblocks, pl.adv, pl.nsum, dbl, nfft, mult, pairs, pxx_d,
                                    pyy_d, pxy_d));
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(pxx, pxx_d, xxb, hipMemcpyDeviceToHost, g.stream));
-        if (y) {
-            HIPCHK(hipMemcpyAsync(pyy, pyy_d, yyb, hipMemcpyDeviceToHost, g.stream));
-            HIPCHK(hipMemcpyAsync(pxy, pxy_d, xyb, hipMemcpyDeviceToHost, g.stream));
-        }
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 // ---- continuous wavelet transform (k_cwt.hip) ------------------------------------------------------
@@ -3527,24 +3357,17 @@ int sp_cwt(const void *x, int dtype, int64_t nsig, int64_t x_ld, int64_t batch, 
     if (bandpow && get_table(17, wband, sizeof(float) * S, &wb_d, nullptr)) return -1;
     const cf *tw;
     if (get_twiddles(L, &tw)) return -1;
-    // outputs staged for host callers: [W | gws | recon | bandpow], each piece 256-byte aligned
-    const size_t wbytes = W ? sizeof(cf) * rows * S * (size_t)nsig : 0, gbytes = gws ? sizeof(double) * rows * S : 0;
-    const size_t rbytes = recon ? sizeof(cf) * rows * (size_t)nsig : 0, bbytes = bandpow ? sizeof(float) * rows * (size_t)nsig : 0;
-    const size_t goff = (wbytes + 255) & ~(size_t)255, roff = goff + ((gbytes + 255) & ~(size_t)255);
-    const size_t boff = roff + ((rbytes + 255) & ~(size_t)255);
-    const void *xd = x;
-    cf *W_d = (cf *)W, *rec_d = (cf *)recon;
-    double *gws_d = gws;
-    float *bp_d = bandpow;
-    if (!mem) {
-        if (g.in0.ensure(esz * in_elems) || g.out0.ensure(boff + bbytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * in_elems, hipMemcpyHostToDevice, g.stream));
-        xd = g.in0.p;
-        W_d = W ? (cf *)g.out0.p : nullptr;
-        gws_d = gws ? (double *)((char *)g.out0.p + goff) : nullptr;
-        rec_d = recon ? (cf *)((char *)g.out0.p + roff) : nullptr;
-        bp_d = bandpow ? (float *)((char *)g.out0.p + boff) : nullptr;
-    }
+    Stage st(mem);
+    const void *xd;
+    cf *W_d, *rec_d;
+    double *gws_d;
+    float *bp_d;
+    st.in(g.in0, x, esz * in_elems, &xd);
+    st.out(g.out0, W, sizeof(cf) * rows * S * (size_t)nsig, &W_d);
+    st.out(g.out0, gws, sizeof(double) * rows * S, &gws_d);
+    st.out(g.out0, recon, sizeof(cf) * rows * (size_t)nsig, &rec_d);
+    st.out(g.out0, bandpow, sizeof(float) * rows * (size_t)nsig, &bp_d);
+    if (st.commit()) return -1;
     float *gpart = nullptr;
     if (gws) {
         if (g.work.ensure(pl.scratch_bytes)) return -1;
@@ -3579,14 +3402,7 @@ int sp_cwt(const void *x, int dtype, int64_t nsig, int64_t x_ld, int64_t batch, 
         g.last_kernel = "k_cwt";
     }
     if (gws) LAUNCHCHK(launch_cwt_gws_finish(lc(), gpart, (int64_t)(rows * S), pl.frames, gws_d));
-    if (!mem) {
-        if (W) HIPCHK(hipMemcpyAsync(W, W_d, wbytes, hipMemcpyDeviceToHost, g.stream));
-        if (gws) HIPCHK(hipMemcpyAsync(gws, gws_d, gbytes, hipMemcpyDeviceToHost, g.stream));
-        if (recon) HIPCHK(hipMemcpyAsync(recon, rec_d, rbytes, hipMemcpyDeviceToHost, g.stream));
-        if (bandpow) HIPCHK(hipMemcpyAsync(bandpow, bp_d, bbytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int sp_icwt(const void *W, int64_t nsig, int nscales, int64_t batch, const float *w, void *out, int mem) {
@@ -3602,14 +3418,12 @@ int sp_icwt(const void *W, int64_t nsig, int nscales, int64_t batch, const float
     if (ensure_init()) return -1;
     ApiLock lk;
     const size_t ibytes = sizeof(cf) * (size_t)batch * (size_t)nscales * (size_t)nsig, obytes = sizeof(cf) * (size_t)batch * (size_t)nsig;
-    const void *Wd = W;
-    void *od = out;
-    if (!mem) {
-        if (g.in0.ensure(ibytes) || g.out0.ensure(obytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, W, ibytes, hipMemcpyHostToDevice, g.stream));
-        Wd = g.in0.p;
-        od = g.out0.p;
-    }
+    Stage st(mem);
+    const void *Wd;
+    void *od;
+    st.in(g.in0, W, ibytes, &Wd);
+    st.out(g.out0, out, obytes, &od);
+    if (st.commit()) return -1;
     void *w_d = nullptr;
     if (get_table(16, w, sizeof(float) * (size_t)nscales, &w_d, nullptr)) return -1;
     {
@@ -3617,11 +3431,7 @@ int sp_icwt(const void *W, int64_t nsig, int nscales, int64_t batch, const float
         LAUNCHCHK(launch_icwt(lc(), (const cf *)Wd, (const float *)w_d, nscales, nsig, batch, (cf *)od));
         g.last_kernel = "k_icwt";
     }
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(out, od, obytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 // ---- cross-wavelet spectra and wavelet coherence (k_wct.hip; include/spectral_ext.h) -------------------
@@ -3667,6 +3477,7 @@ int sp_wct_time(const void *x, int64_t x_ld, const void *y, int64_t y_ld, int dt
     for (int s = 0; s < nscales; ++s)
         if (!isfinite(scales[s]) || !(scales[s] > 0.0) || scales[s] > 1e9)
             return fail("sp_wct_time: scales[%d] = %g must be positive and finite", s, scales[s]);
+    // real difference: a device caller's own T is stored with 16-byte vectors (a staged T starts a scratch buffer)
     if (mem && T && ((uintptr_t)T & 15) != 0) return fail("sp_wct_time: T must be 16-byte aligned");
     if (batch == 0) return 0;
     if (!x || !y) return fail("sp_wct_time: x and y are required");
@@ -3692,16 +3503,13 @@ int sp_wct_time(const void *x, int64_t x_ld, const void *y, int64_t y_ld, int dt
     const cf *tw;
     if (get_twiddles(L, &tw)) return -1;
     const size_t obytes = (T ? sizeof(float4) : sizeof(cf)) * rows * S * (size_t)nsig;
-    const void *xd = x, *yd = y;
-    void *od = T ? T : Wxy;
-    if (!mem) {
-        if (g.in0.ensure(esz * x_elems) || g.in1.ensure(esz * y_elems) || g.out0.ensure(obytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * x_elems, hipMemcpyHostToDevice, g.stream));
-        HIPCHK(hipMemcpyAsync(g.in1.p, y, esz * y_elems, hipMemcpyHostToDevice, g.stream));
-        xd = g.in0.p;
-        yd = g.in1.p;
-        od = g.out0.p;
-    }
+    Stage st(mem);
+    const void *xd, *yd;
+    void *od;
+    st.in(g.in0, x, esz * x_elems, &xd);
+    st.in(g.in1, y, esz * y_elems, &yd);
+    st.out(g.out0, T ? T : Wxy, obytes, &od);
+    if (st.commit()) return -1;
     WctArgs a;
     a.x = xd;
     a.y = yd;
@@ -3729,11 +3537,7 @@ int sp_wct_time(const void *x, int64_t x_ld, const void *y, int64_t y_ld, int dt
         HIPCHK(hipGetLastError());
         g.last_kernel = "k_wct_time";
     }
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(T ? T : Wxy, od, obytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int sp_wct_scale(const void *T, int64_t nsig, int nscales, int64_t batch, const float *taps, int ntaps, float *R2, float *phase, float *A,
@@ -3748,29 +3552,24 @@ int sp_wct_scale(const void *T, int64_t nsig, int nscales, int64_t batch, const 
         if (!isfinite(taps[j])) return fail("sp_wct_scale: taps must be finite (tap %d)", j);
     if ((A != nullptr) != (B != nullptr) || (A != nullptr) != (C != nullptr))
         return fail("sp_wct_scale: A, B and C are given together or not at all");
+    // real difference: a device caller's own T is read with 16-byte vectors (a staged T starts a scratch buffer)
     if (mem && T && ((uintptr_t)T & 15) != 0) return fail("sp_wct_scale: T must be 16-byte aligned");
     if (batch == 0) return 0;
     if (!T || !R2 || !phase) return fail("sp_wct_scale: T, R2 and phase are required");
     if (ensure_init()) return -1;
     ApiLock lk;
-    const size_t cells = (size_t)batch * (size_t)nscales * (size_t)nsig, fb = sizeof(float) * cells, fa = (fb + 255) & ~(size_t)255;
-    const void *Td = T;
-    float *R2_d = R2, *ph_d = phase, *A_d = A, *B_d = B;
-    cf *C_d = (cf *)C;
-    if (!mem) {
-        // outputs staged for host callers: [R2 | phase | A | B | C], each piece 256-byte aligned
-        if (g.in0.ensure(sizeof(float4) * cells) || g.out0.ensure(A ? 6 * fa : 2 * fa)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, T, sizeof(float4) * cells, hipMemcpyHostToDevice, g.stream));
-        Td = g.in0.p;
-        char *o = (char *)g.out0.p;
-        R2_d = (float *)o;
-        ph_d = (float *)(o + fa);
-        if (A) {
-            A_d = (float *)(o + 2 * fa);
-            B_d = (float *)(o + 3 * fa);
-            C_d = (cf *)(o + 4 * fa);
-        }
-    }
+    const size_t cells = (size_t)batch * (size_t)nscales * (size_t)nsig, fb = sizeof(float) * cells;
+    Stage st(mem);
+    const void *Td;
+    float *R2_d, *ph_d, *A_d, *B_d;
+    cf *C_d;
+    st.in(g.in0, T, sizeof(float4) * cells, &Td);
+    st.out(g.out0, R2, fb, &R2_d);
+    st.out(g.out0, phase, fb, &ph_d);
+    st.out(g.out0, A, fb, &A_d);
+    st.out(g.out0, B, fb, &B_d);
+    st.out(g.out0, C, 2 * fb, &C_d);
+    if (st.commit()) return -1;
     void *taps_d = nullptr;
     if (get_table(19, taps, sizeof(float) * (size_t)ntaps, &taps_d, nullptr)) return -1;
     {
@@ -3778,17 +3577,7 @@ int sp_wct_scale(const void *T, int64_t nsig, int nscales, int64_t batch, const 
         LAUNCHCHK(launch_wct_scale(lc(), (const float4 *)Td, (const float *)taps_d, ntaps, nscales, nsig, batch, R2_d, ph_d, A_d, B_d, C_d));
         g.last_kernel = "k_wct_scale";
     }
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(R2, R2_d, fb, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipMemcpyAsync(phase, ph_d, fb, hipMemcpyDeviceToHost, g.stream));
-        if (A) {
-            HIPCHK(hipMemcpyAsync(A, A_d, fb, hipMemcpyDeviceToHost, g.stream));
-            HIPCHK(hipMemcpyAsync(B, B_d, fb, hipMemcpyDeviceToHost, g.stream));
-            HIPCHK(hipMemcpyAsync(C, C_d, 2 * fb, hipMemcpyDeviceToHost, g.stream));
-        }
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 // ---- synchrosqueezed STFT and reassignment fields (k_ssq.hip; include/spectral_tfr.h) ------------------
@@ -3830,14 +3619,11 @@ int sp_ssq_plan(int cplx, int n, int64_t nframes, int64_t batch, int nb, int wha
 // the frames of one call: stages x for host callers, uploads the windows, fills what the two kernels' arguments share
 static int ssq_front(const char *who, SsqArgs &a, const void *x, int64_t x_ld, bool cplx, int64_t nsig, int64_t batch, const float *h,
                      const float *dh, const float *th, int n, int hop, int64_t first, int64_t nframes, int segmean, double gamma,
-                     double rel, int mem, const cf **tw) {
+                     double rel, Stage &st, const cf **tw) {
     const size_t esz = cplx ? 8 : 4, x_elems = (size_t)((batch - 1) * x_ld + nsig);
-    const void *xd = x;
-    if (!mem) {
-        if (g.in0.ensure(esz * x_elems)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, esz * x_elems, hipMemcpyHostToDevice, g.stream));
-        xd = g.in0.p;
-    }
+    const void *xd;
+    st.in(g.in0, x, esz * x_elems, &xd);
+    if (st.commit()) return -1;
     void *h_d = nullptr, *dh_d = nullptr, *th_d = nullptr;
     if (get_table(1, h, sizeof(float) * (size_t)n, &h_d, nullptr)) return -1;
     if (get_table(20, dh, sizeof(float) * (size_t)n, &dh_d, nullptr)) return -1;
@@ -3884,24 +3670,17 @@ int sp_ssq(const void *x, int64_t x_ld, int dtype, int64_t nsig, int64_t batch, 
     ApiLock lk;
     SsqArgs a;
     const cf *tw;
-    if (ssq_front("sp_ssq", a, x, x_ld, cplx, nsig, batch, h, dh, fields ? th : nullptr, n, hop, first, nframes, segmean, gamma, rel, mem, &tw))
+    Stage st(mem);
+    if (ssq_front("sp_ssq", a, x, x_ld, cplx, nsig, batch, h, dh, fields ? th : nullptr, n, hop, first, nframes, segmean, gamma, rel, st, &tw))
         return -1;
-    const size_t cells = (size_t)batch * (size_t)nframes * (size_t)nb, fb = sizeof(float) * cells, fa = (fb + 255) & ~(size_t)255;
+    const size_t cells = (size_t)batch * (size_t)nframes * (size_t)nb, fb = sizeof(float) * cells;
     a.b0 = b0;
     a.nb = nb;
-    a.T = (cf *)T;
-    a.P = P;
-    a.IF = IF;
-    a.GD = GD;
-    if (!mem) {
-        // outputs staged for host callers: [T | P | IF | GD], each piece 256-byte aligned
-        if (g.out0.ensure(5 * fa)) return -1;
-        char *o = (char *)g.out0.p;
-        a.T = T ? (cf *)o : nullptr;
-        a.P = P ? (float *)(o + 2 * fa) : nullptr;
-        a.IF = IF ? (float *)(o + 3 * fa) : nullptr;
-        a.GD = GD ? (float *)(o + 4 * fa) : nullptr;
-    }
+    st.out(g.out0, T, 2 * fb, &a.T);
+    st.out(g.out0, P, fb, &a.P);
+    st.out(g.out0, IF, fb, &a.IF);
+    st.out(g.out0, GD, fb, &a.GD);
+    if (st.commit()) return -1;
     {
         ProfScope ps;
         if (launch_ssq(lc(), a, cplx, n, tw, (nframes + a.fpr - 1) / a.fpr, batch, lds) != 0)
@@ -3909,14 +3688,7 @@ int sp_ssq(const void *x, int64_t x_ld, int dtype, int64_t nsig, int64_t batch, 
         HIPCHK(hipGetLastError());
         g.last_kernel = "k_ssq";
     }
-    if (!mem) {
-        if (T) HIPCHK(hipMemcpyAsync(T, a.T, 2 * fb, hipMemcpyDeviceToHost, g.stream));
-        if (P) HIPCHK(hipMemcpyAsync(P, a.P, fb, hipMemcpyDeviceToHost, g.stream));
-        if (IF) HIPCHK(hipMemcpyAsync(IF, a.IF, fb, hipMemcpyDeviceToHost, g.stream));
-        if (GD) HIPCHK(hipMemcpyAsync(GD, a.GD, fb, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 // the band edges of sp_ssq_bands / sp_ssq_sum; 0 or the message's tail
@@ -3930,21 +3702,15 @@ static const char *ssq_edges_why(int nbands, const double *edges, const float *e
     return nullptr;
 }
 // the edges as float32: the constant pairs by value, the per-frame ones staged for host callers
-static int ssq_edges(int nbands, const double *edges, const float *edges_t, int64_t nframes, int mem, SsqEdges *ec, const float **out) {
+static int ssq_edges(int nbands, const double *edges, const float *edges_t, int64_t nframes, Stage &st, SsqEdges *ec, const float **out) {
     *ec = SsqEdges{};
     *out = nullptr;
     if (edges) {
         for (int j = 0; j < 2 * nbands; ++j) ec->v[j] = (float)edges[j];
         return 0;
     }
-    *out = edges_t;
-    if (!mem) {
-        const size_t bytes = sizeof(float) * 2 * (size_t)nbands * (size_t)nframes;
-        if (g.in1.ensure(bytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in1.p, edges_t, bytes, hipMemcpyHostToDevice, g.stream));
-        *out = (const float *)g.in1.p;
-    }
-    return 0;
+    st.in(g.in1, edges_t, sizeof(float) * 2 * (size_t)nbands * (size_t)nframes, out);
+    return st.commit();
 }
 
 int sp_ssq_bands(const void *x, int64_t x_ld, int dtype, int64_t nsig, int64_t batch, const float *h, const float *dh, int n, int hop,
@@ -3966,17 +3732,14 @@ int sp_ssq_bands(const void *x, int64_t x_ld, int dtype, int64_t nsig, int64_t b
     ApiLock lk;
     SsqArgs a;
     const cf *tw;
-    if (ssq_front("sp_ssq_bands", a, x, x_ld, cplx, nsig, batch, h, dh, nullptr, n, hop, first, nframes, segmean, gamma, rel, mem, &tw)) return -1;
-    if (ssq_edges(nbands, edges, edges_t, nframes, mem, &a.edges_c, &a.edges)) return -1;
-    const size_t obytes = sizeof(cf) * (size_t)batch * (size_t)nbands * (size_t)nframes;
+    Stage st(mem);
+    if (ssq_front("sp_ssq_bands", a, x, x_ld, cplx, nsig, batch, h, dh, nullptr, n, hop, first, nframes, segmean, gamma, rel, st, &tw)) return -1;
+    if (ssq_edges(nbands, edges, edges_t, nframes, st, &a.edges_c, &a.edges)) return -1;
     a.nbands = nbands;
     a.per_frame = edges ? 0 : 1;
     a.scale = (float)scale;
-    a.out = (cf *)out;
-    if (!mem) {
-        if (g.out0.ensure(obytes)) return -1;
-        a.out = (cf *)g.out0.p;
-    }
+    st.out(g.out0, out, sizeof(cf) * (size_t)batch * (size_t)nbands * (size_t)nframes, &a.out);
+    if (st.commit()) return -1;
     {
         ProfScope ps;
         if (launch_ssq(lc(), a, cplx, n, tw, (nframes + a.fpr - 1) / a.fpr, batch, lds) != 0)
@@ -3985,11 +3748,7 @@ int sp_ssq_bands(const void *x, int64_t x_ld, int dtype, int64_t nsig, int64_t b
         HIPCHK(hipGetLastError());
         g.last_kernel = "k_ssq";
     }
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(out, a.out, obytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int sp_ssq_sum(const void *T, int64_t nframes, int nb, int64_t batch, int n, int b0, int nbands, const double *edges, const float *edges_t,
@@ -4007,27 +3766,21 @@ int sp_ssq_sum(const void *T, int64_t nframes, int nb, int64_t batch, int n, int
     ApiLock lk;
     const size_t tbytes = sizeof(cf) * (size_t)batch * (size_t)nframes * (size_t)nb;
     const size_t obytes = sizeof(cf) * (size_t)batch * (size_t)nbands * (size_t)nframes;
-    const void *Td = T;
-    cf *od = (cf *)out;
-    if (!mem) {
-        if (g.in0.ensure(tbytes) || g.out0.ensure(obytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, T, tbytes, hipMemcpyHostToDevice, g.stream));
-        Td = g.in0.p;
-        od = (cf *)g.out0.p;
-    }
+    Stage st(mem);
+    const void *Td;
+    cf *od;
+    st.in(g.in0, T, tbytes, &Td);
+    st.out(g.out0, out, obytes, &od);
+    if (st.commit()) return -1;
     const float *ed;
     SsqEdges ec;
-    if (ssq_edges(nbands, edges, edges_t, nframes, mem, &ec, &ed)) return -1;
+    if (ssq_edges(nbands, edges, edges_t, nframes, st, &ec, &ed)) return -1;
     {
         ProfScope ps;
         LAUNCHCHK(launch_ssq_sum(lc(), (const cf *)Td, nframes, nb, n, b0, nbands, edges ? 0 : 1, ed, ec, half ? 1 : 0, (float)scale, batch, od));
         g.last_kernel = "k_ssq_sum";
     }
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(out, od, obytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 // ---- batched Hermitian eigensolver (k_eigh.hip) --------------------------------------------------
@@ -4054,30 +3807,22 @@ int sp_eigh(const double *a, int n, int64_t batch, int nvec, int max_sweeps, dou
     ApiLock lk;
     const size_t abytes = sizeof(double) * 2 * (size_t)batch * n * n, wbytes = sizeof(double) * (size_t)batch * n;
     const size_t vbytes = sizeof(double) * 2 * (size_t)batch * n * nvec, sbytes = sizeof(int32_t) * (size_t)batch;
-    const double *ad = a;
-    double *wd = w, *vd = v;
-    int32_t *sd = sweeps;
-    if (!mem) {
-        if (g.in0.ensure(abytes) || g.out0.ensure(vbytes + wbytes + sbytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, a, abytes, hipMemcpyHostToDevice, g.stream));
-        ad = (const double *)g.in0.p;
-        vd = (double *)g.out0.p;
-        wd = (double *)((char *)g.out0.p + vbytes);
-        sd = (int32_t *)((char *)g.out0.p + vbytes + wbytes);
-    }
+    Stage st(mem);
+    const double *ad;
+    double *wd, *vd;
+    int32_t *sd;
+    st.in(g.in0, a, abytes, &ad);
+    st.out(g.out0, nvec > 0 ? v : nullptr, vbytes, &vd);
+    st.out(g.out0, w, wbytes, &wd);
+    st.out(g.out0, sweeps, sbytes, &sd);
+    if (st.commit()) return -1;
     const EighPlan pl = eigh_plan_of(n, nvec > 0, batch, g.ncu, env_int("SP_EIGH_GRID", 0));
     {
         ProfScope ps;
-        LAUNCHCHK(launch_eigh(lc(), ad, n, batch, nvec, max_sweeps, wd, nvec > 0 ? vd : nullptr, sd, pl));
+        LAUNCHCHK(launch_eigh(lc(), ad, n, batch, nvec, max_sweeps, wd, vd, sd, pl));
         g.last_kernel = "k_eigh";
     }
-    if (!mem) {
-        if (nvec > 0) HIPCHK(hipMemcpyAsync(v, vd, vbytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipMemcpyAsync(w, wd, wbytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipMemcpyAsync(sweeps, sd, sbytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 // reciprocal window-square envelope of sp_istft as [period: hop][head: head_len][tail: n - hop] float32 from float64 sums; entries
@@ -4130,14 +3875,12 @@ int sp_istft(const void *Z, int sided, int in_major, int nch, int64_t nframes, c
     // real output from a power-of-two transform: two frames per transform
     const int mode = cplx ? 0 : ((!xf.blue && xf.L >= 32 && M >= 2 && !env_flag("SP_NO_REALPAIR")) ? 2 : 1);
     const size_t zbytes = sizeof(cf) * (size_t)nb * (size_t)M * (size_t)nch, ybytes = (cplx ? 8 : 4) * (size_t)nout * (size_t)nch;
-    const cf *zd = (const cf *)Z;
-    void *yd = y;
-    if (!mem) {
-        if (g.in0.ensure(zbytes) || g.out0.ensure(ybytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, Z, zbytes, hipMemcpyHostToDevice, g.stream));
-        zd = (const cf *)g.in0.p;
-        yd = g.out0.p;
-    }
+    Stage st(mem);
+    const cf *zd;
+    void *yd;
+    st.in(g.in0, Z, zbytes, &zd);
+    st.out(g.out0, y, ybytes, &yd);
+    if (st.commit()) return -1;
     void *win_d;
     if (get_table(1, win, sizeof(float) * (size_t)nfft, &win_d, nullptr)) return -1;
     // the envelope pieces, cached beside the window by (window, hop, and the frame count where the two ends meet)
@@ -4187,27 +3930,21 @@ int sp_istft(const void *Z, int sided, int in_major, int nch, int64_t nframes, c
                                    c1 == M));
         }
     }
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(y, yd, ybytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int sp_hilbert(const float *x, int64_t n_in, int64_t x_ld, int64_t nfft, int64_t batch, void *out, int mem) {
     if (ensure_init()) return -1;
     if (n_in < 1 || nfft < 2 || batch < 1 || x_ld < n_in) return fail("sp_hilbert: bad sizes");
     ApiLock lk;
-    const float *xd = x;
-    cf *od = (cf *)out;
     const size_t ibytes = sizeof(float) * (size_t)x_ld * (size_t)batch;
     const size_t obytes = sizeof(cf) * (size_t)nfft * (size_t)batch;
-    if (!mem) {
-        if (g.in0.ensure(ibytes) || g.out0.ensure(obytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, ibytes, hipMemcpyHostToDevice, g.stream));
-        xd = (const float *)g.in0.p;
-        od = (cf *)g.out0.p;
-    }
+    Stage st(mem);
+    const float *xd;
+    cf *od;
+    st.in(g.in0, x, ibytes, &xd);
+    st.out(g.out0, out, obytes, &od);
+    if (st.commit()) return -1;
     const int64_t nuse = n_in < nfft ? n_in : nfft;
     if (wg_capable(nfft)) {
         Xf xf;
@@ -4300,11 +4037,7 @@ int sp_hilbert(const float *x, int64_t n_in, int64_t x_ld, int64_t nfft, int64_t
             }
         }
     }
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(out, od, obytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int sp_frame_sum(const void *x, int x_dtype, int64_t nsig, int nch, int64_t x_ld, int nfft, int hop, int64_t nframes,
@@ -4316,14 +4049,14 @@ int sp_frame_sum(const void *x, int x_dtype, int64_t nsig, int nch, int64_t x_ld
     ApiLock lk;
     const bool cplx = x_dtype == SP_DTYPE_C64;
     const size_t esz = cplx ? 8 : 4;
-    const void *xd = x;
     const size_t ibytes = esz * ((size_t)x_ld * (size_t)(nch - 1) + (size_t)nsig);
     const size_t obytes = sizeof(double) * 2 * (size_t)nfft * (size_t)nch;
-    if (!mem) {
-        if (g.in1.ensure(ibytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in1.p, x, ibytes, hipMemcpyHostToDevice, g.stream));
-        xd = g.in1.p;
-    }
+    Stage st(mem);
+    const void *xd;
+    double *od;
+    st.in(g.in1, x, ibytes, &xd);
+    st.out(g.out0, out, obytes, &od);
+    if (st.commit()) return -1;
     TrendBuf tb;
     if (get_trendbuf(nch + 1, &tb)) return -1;
     if (detrend != 0 && nch <= 512) {
@@ -4334,19 +4067,10 @@ int sp_frame_sum(const void *x, int x_dtype, int64_t nsig, int nch, int64_t x_ld
         for (int c = 0; c < nch; ++c)
             if (set_trend(tb, c + 1, (const char *)xd + esz * (size_t)x_ld * (size_t)c, cplx, nsig, detrend, 0, 0)) return -1;
     }
-    double *od = out;
-    if (!mem) {
-        if (g.out0.ensure(obytes)) return -1;
-        od = (double *)g.out0.p;
-    }
     const size_t pbytes = obytes * (size_t)frame_sum_slices(g.ncu, nch, nfft, nframes);
     if (g.work.ensure(pbytes)) return -1;
     LAUNCHCHK(launch_frame_sum(lc(), xd, cplx, x_ld, nch, nfft, hop, nframes, tb.f + 4, detrend == 2, od, (double *)g.work.p));
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(out, od, obytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int sp_spectral_filter(const float *x, int64_t n_in, int64_t x_ld, int64_t nfft, int64_t batch, const void *H, void *out,
@@ -4354,17 +4078,15 @@ int sp_spectral_filter(const float *x, int64_t n_in, int64_t x_ld, int64_t nfft,
     if (ensure_init()) return -1;
     if (n_in < 1 || nfft < 2 || batch < 1 || x_ld < n_in || H == nullptr) return fail("sp_spectral_filter: bad sizes");
     ApiLock lk;
-    const float *xd = x;
-    cf *od = (cf *)out;
     const size_t ibytes = sizeof(float) * (size_t)x_ld * (size_t)batch;
     const size_t obytes = sizeof(cf) * (size_t)nfft * (size_t)batch;
     const size_t hbytes = sizeof(cf) * (size_t)nfft;
-    if (!mem) {
-        if (g.in0.ensure(ibytes) || g.out0.ensure(obytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, ibytes, hipMemcpyHostToDevice, g.stream));
-        xd = (const float *)g.in0.p;
-        od = (cf *)g.out0.p;
-    }
+    Stage st(mem);
+    const float *xd;
+    cf *od;
+    st.in(g.in0, x, ibytes, &xd);
+    st.out(g.out0, out, obytes, &od);
+    if (st.commit()) return -1;
     const int64_t nuse = n_in < nfft ? n_in : nfft;
     if (wg_capable(nfft)) {
         Xf xf;
@@ -4384,11 +4106,7 @@ int sp_spectral_filter(const float *x, int64_t n_in, int64_t x_ld, int64_t nfft,
         }
         HIPCHK(hipStreamSynchronize(g.stream));        // H was read from the caller's host array
     }
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(out, od, obytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int sp_xcorr(const float *x1, const float *x2, int64_t n, float *co_out, int mem) {
@@ -4398,17 +4116,14 @@ int sp_xcorr(const float *x1, const float *x2, int64_t n, float *co_out, int mem
     if (L > ((int64_t)1 << SP_MAX_BIG_LOG2))
         return fail("sp_xcorr: n=%lld needs a %lld-point transform; the limit is 2^%d", (long long)n, (long long)L, SP_MAX_BIG_LOG2);
     ApiLock lk;
-    const float *a = x1, *b = x2;
-    float *od = co_out;
     const size_t ibytes = sizeof(float) * (size_t)n, obytes = sizeof(float) * (size_t)(2 * n - 1);
-    if (!mem) {
-        if (g.in0.ensure(ibytes) || g.in1.ensure(ibytes) || g.out0.ensure(obytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x1, ibytes, hipMemcpyHostToDevice, g.stream));
-        HIPCHK(hipMemcpyAsync(g.in1.p, x2, ibytes, hipMemcpyHostToDevice, g.stream));
-        a = (const float *)g.in0.p;
-        b = (const float *)g.in1.p;
-        od = (float *)g.out0.p;
-    }
+    Stage st(mem);
+    const float *a, *b;
+    float *od;
+    st.in(g.in0, x1, ibytes, &a);
+    st.in(g.in1, x2, ibytes, &b);
+    st.out(g.out0, co_out, obytes, &od);
+    if (st.commit()) return -1;
     TrendBuf tb;
     if (get_trendbuf(3, &tb)) return -1;
     double *scr = moments_scratch();
@@ -4457,11 +4172,7 @@ int sp_xcorr(const float *x1, const float *x2, int64_t n, float *co_out, int mem
                     RowsOut ro{od, n, L, tb.d + 16};
                     ro.kind = 3;
                     LAUNCHCHK(launch_fft_cols_lag(lc(), A, C2, Bb, Bb * Cc, Cc, xa, ro));
-                    if (!mem) {
-                        HIPCHK(hipMemcpyAsync(co_out, od, obytes, hipMemcpyDeviceToHost, g.stream));
-                        HIPCHK(hipStreamSynchronize(g.stream));
-                    }
-                    return 0;
+                    return st.finish();
                 }
             }
             if (dev_fft_big_pow2(A, B, L, 0, 0, 1, &f1)) return -1;          // B = FFT(z)
@@ -4489,11 +4200,7 @@ int sp_xcorr(const float *x1, const float *x2, int64_t n, float *co_out, int mem
             LAUNCHCHK(launch_xc_out(lc(), B, n, L, tb.d + 16, od));
         }
     }
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(co_out, od, obytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int sp_csd_epilogue(const double *pxx, const double *pyy, const double *pxy, int nch, int nb, int nfft, int onesided, double enbw,
@@ -4504,21 +4211,15 @@ int sp_csd_epilogue(const double *pxx, const double *pyy, const double *pxy, int
     if (!onesided && nb != nfft) return fail("sp_csd_epilogue: two-sided spectra hold nfft bins");
     ApiLock lk;
     const size_t NB = (size_t)nb, NF = (size_t)nfft, C = (size_t)nch;
-    const size_t n_in = NB * (1 + 3 * C);                                  // pxx | pyy | pxy (complex)
     const size_t n_out = sp_csd_epilogue_doubles(nch, nb, nfft);
-    const double *dxx = pxx, *dyy = pyy, *dxy = pxy;
-    double *od = out;
-    if (!mem) {
-        if (g.out0.ensure(sizeof(double) * (n_in + n_out))) return -1;
-        double *st = (double *)g.out0.p;
-        HIPCHK(hipMemcpyAsync(st, pxx, sizeof(double) * NB, hipMemcpyHostToDevice, g.stream));
-        HIPCHK(hipMemcpyAsync(st + NB, pyy, sizeof(double) * NB * C, hipMemcpyHostToDevice, g.stream));
-        HIPCHK(hipMemcpyAsync(st + NB * (1 + C), pxy, sizeof(double) * 2 * NB * C, hipMemcpyHostToDevice, g.stream));
-        dxx = st;
-        dyy = st + NB;
-        dxy = st + NB * (1 + C);
-        od = st + n_in;
-    }
+    Stage st(mem);
+    const double *dxx, *dyy, *dxy;
+    double *od;
+    st.in(g.out0, pxx, sizeof(double) * NB, &dxx);
+    st.in(g.out0, pyy, sizeof(double) * NB * C, &dyy);
+    st.in(g.out0, pxy, sizeof(double) * 2 * NB * C, &dxy);
+    st.out(g.out0, out, sizeof(double) * n_out, &od);
+    if (st.commit()) return -1;
     // out layout (doubles): cxy[C][NB][2] | cxy2[C][NB] | phi[C][NB] | lxx[NB] | lyy[C][NB] | lxy[C][NB] |
     //                       rxx[NF][2] | ryy[C][NF][2] | rxy[C][NF][2] | icxy[C][NF][2] | corrcoef[C][NF][2] | e[1+C][2]
     double *cxy = od, *cxy2 = cxy + 2 * C * NB, *phi = cxy2 + C * NB, *lxx = phi + C * NB, *lyy = lxx + NB, *lxy = lyy + C * NB;
@@ -4533,11 +4234,7 @@ int sp_csd_epilogue(const double *pxx, const double *pyy, const double *pxy, int
     LAUNCHCHK(launch_epi_spec(lc(), dxx, dyy, dxy, cxy, nch, nb, nfft, onesided, X, rowmax));
     if (dev_fft_any(X, X, nfft, (int64_t)nsig, 1)) return -1;
     LAUNCHCHK(launch_epi_corr(lc(), X, nch, nfft, onesided, rxx, ryy, rxy, icxy, ee, cc, rowmax));
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(out, od, sizeof(double) * n_out, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int64_t sp_csd_epilogue_doubles(int nch, int nb, int nfft) {
@@ -4557,22 +4254,16 @@ int sp_biquad(const double *b, const double *a, const float *x, int64_t n, float
             return fail("sp_biquad: unstable section (pole radius %.9g > 1): the blocked scan of the state maps does not apply", rad);
     }
     ApiLock lk;
-    const float *xd = x;
-    float *yd = y;
     const size_t bytes = sizeof(float) * (size_t)n;
-    if (!mem) {
-        if (g.in0.ensure(bytes) || g.out0.ensure(bytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, bytes, hipMemcpyHostToDevice, g.stream));
-        xd = (const float *)g.in0.p;
-        yd = (float *)g.out0.p;
-    }
+    Stage st(mem);
+    const float *xd;
+    float *yd;
+    st.in(g.in0, x, bytes, &xd);
+    st.out(g.out0, y, bytes, &yd);
+    if (st.commit()) return -1;
     if (g.work.ensure(sizeof(double) * 4 * (size_t)biquad_tiles(n) + 64)) return -1;
     LAUNCHCHK(launch_biquad(lc(), b, a, xd, n, yd, (double *)g.work.p));
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(y, yd, bytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int sp_fftfilt(const float *h, int ntaps, const float *x, int64_t n, int nfft, float *y, int mem) {
@@ -4596,21 +4287,15 @@ int sp_fftfilt(const float *h, int ntaps, const float *x, int64_t n, int nfft, f
     bool fresh = false;
     if (get_table(2, hp.data(), sizeof(cf) * (size_t)nfft, &H_d, &fresh)) return -1;
     if (fresh) LAUNCHCHK(launch_fft_c2c(lc(), (const cf *)H_d, (cf *)H_d, 1, 0, xf));
-    const float *xd = x;
-    float *yd = y;
     const size_t bytes = sizeof(float) * (size_t)n;
-    if (!mem) {
-        if (g.in0.ensure(bytes) || g.out0.ensure(bytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, bytes, hipMemcpyHostToDevice, g.stream));
-        xd = (const float *)g.in0.p;
-        yd = (float *)g.out0.p;
-    }
+    Stage st(mem);
+    const float *xd;
+    float *yd;
+    st.in(g.in0, x, bytes, &xd);
+    st.out(g.out0, y, bytes, &yd);
+    if (st.commit()) return -1;
     LAUNCHCHK(launch_fftfilt(lc(), xd, n, ntaps, (const cf *)H_d, xf, yd));
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(y, yd, bytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 // checks shared by sp_sosfilt / sp_sosfiltfilt: refuses before any launch
@@ -4651,31 +4336,21 @@ int sp_sosfilt(const double *sos, int nsec, const float *x, int64_t nrows, int64
     const int S = 2 * nsec;
     const double *plan_d;
     if (sos_plan_table(sos, nsec, n, &plan_d)) return -1;
-    const float *xd = x;
-    float *yd = y;
-    const double *zid = zi;
-    double *zfd = zf;
     const size_t bytes = sizeof(float) * (size_t)(nrows * n), zbytes = sizeof(double) * (size_t)(nrows * S);
-    if (!mem) {
-        if (g.in0.ensure(bytes) || g.out0.ensure(bytes) || g.sosZ.ensure(2 * zbytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, bytes, hipMemcpyHostToDevice, g.stream));
-        xd = (const float *)g.in0.p;
-        yd = (float *)g.out0.p;
-        if (zi) {
-            HIPCHK(hipMemcpyAsync(g.sosZ.p, zi, zbytes, hipMemcpyHostToDevice, g.stream));
-            zid = (const double *)g.sosZ.p;
-        }
-        if (zf) zfd = (double *)g.sosZ.p + nrows * S;
-    }
+    Stage st(mem);
+    const float *xd;
+    float *yd;
+    const double *zid;
+    double *zfd;
+    st.in(g.in0, x, bytes, &xd);
+    st.out(g.out0, y, bytes, &yd);
+    st.in(g.sosZ, zi, zbytes, &zid);
+    st.out(g.sosZ, zf, zbytes, &zfd);
+    if (st.commit()) return -1;
     if (g.work.ensure(sizeof(double) * (size_t)sos_work_doubles(nsec, n, nrows) + 64)) return -1;
     const SosIO io{xd, n, n, n, 0, 0, 0, yd, n, 0, n};
     LAUNCHCHK(launch_sos_pass(lc(), nsec, plan_d, io, nrows, zid ? 1 : 0, zid, zfd, (double *)g.work.p));
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(y, yd, bytes, hipMemcpyDeviceToHost, g.stream));
-        if (zf) HIPCHK(hipMemcpyAsync(zf, zfd, zbytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int sp_sosfiltfilt(const double *sos, int nsec, const float *x, int64_t nrows, int64_t n, int padtype, int64_t padlen, float *y,
@@ -4696,15 +4371,13 @@ int sp_sosfiltfilt(const double *sos, int nsec, const float *x, int64_t nrows, i
     const int64_t N = n + 2 * padlen;
     const double *plan_d;
     if (sos_plan_table(sos, nsec, N, &plan_d)) return -1;
-    const float *xd = x;
-    float *yd = y;
     const size_t bytes = sizeof(float) * (size_t)(nrows * n);
-    if (!mem) {
-        if (g.in0.ensure(bytes) || g.out0.ensure(bytes)) return -1;
-        HIPCHK(hipMemcpyAsync(g.in0.p, x, bytes, hipMemcpyHostToDevice, g.stream));
-        xd = (const float *)g.in0.p;
-        yd = (float *)g.out0.p;
-    }
+    Stage st(mem);
+    const float *xd;
+    float *yd;
+    st.in(g.in0, x, bytes, &xd);
+    st.out(g.out0, y, bytes, &yd);
+    if (st.commit()) return -1;
     if (g.sosY.ensure(sizeof(float) * (size_t)(nrows * N)) ||
         g.work.ensure(sizeof(double) * (size_t)sos_work_doubles(nsec, N, nrows) + 64))
         return -1;
@@ -4715,11 +4388,7 @@ int sp_sosfiltfilt(const double *sos, int nsec, const float *x, int64_t nrows, i
     const SosIO bwd{mid, N, N, N, 0, 0, 1, yd, n, padlen, n};
     LAUNCHCHK(launch_sos_pass(lc(), nsec, plan_d, fwd, nrows, 2, nullptr, nullptr, (double *)g.work.p));
     LAUNCHCHK(launch_sos_pass(lc(), nsec, plan_d, bwd, nrows, 2, nullptr, nullptr, (double *)g.work.p));
-    if (!mem) {
-        HIPCHK(hipMemcpyAsync(y, yd, bytes, hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 }   // extern "C"

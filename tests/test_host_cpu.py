@@ -174,6 +174,22 @@ def test_table_cache_policy(tmp_path):
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
 
 
+def test_stage_layout(tmp_path):
+    """the layout of a host-memory call's staged pieces (pyfft_amd/csrc/stage.h) is host-only logic: built with g++ under
+    AddressSanitizer + UndefinedBehaviorSanitizer and run here as its own process -- no overlap, offsets 0 or a multiple of 256, totals
+    that cover the last piece, absent pieces, the copy-back list, refusals at the capacities and at size_t, zero-byte pieces"""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "stage_layout_test")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-fno-omit-frame-pointer", "-I" + os.path.join(root, "pyfft_amd", "csrc"),
+                    os.path.join(root, "tests", "stage_layout_test.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0"))
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "stage layout ok" in r.stdout
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
+
+
 def test_uncertainty_and_band_integration_match_reference():
     """varcoh / varphi / mean_angle / integratespectra (fft_analysis.py:835-937, :1218-1376; the harmonic-band integration
     of HeatPulse_Funcs.py:498-530): fixture produced by the reference's own functions (make_golden_integrate.py).
