@@ -54,3 +54,5 @@ from .wavelet import xwt, wct, wct_plan   # noqa: F401
 from . import reassign as _reassign_mod                        # noqa: F401
 from .reassign import (reassignment_windows, ssq_stft, issq_stft, squeezed_spectrogram, reassignment_fields,   # noqa: F401
                        ssq_extract, ssq_plan)
+from . import wigner as _wigner_mod                            # noqa: F401
+from .wigner import spwvd, pwvd, wvd, xwvd, wvd_plan           # noqa: F401

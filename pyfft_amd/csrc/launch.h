@@ -27,6 +27,7 @@ namespace sp {
 //   SP_CWT_CHUNK (int: the wavelet transform's scales per workgroup, where no output needs the whole scale set in one)
 //   SP_WCT_CHUNK (int: the same for the cross-wavelet and coherence kernel)
 //   SP_SSQ_FPG (int: the synchrosqueezed STFT's frames per run)
+//   SP_WVD_CPR (int: the Wigner-Ville kernel's columns per run)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
     return v && v[0] && v[0] != '0';
@@ -776,6 +777,58 @@ int launch_ssq(LaunchCtx c, const SsqArgs &a, bool cplx, int L, const cf *tw, in
 // out[row][b][g] = scale * sum over lo <= m < hi of w_m T[row][g][j], m = (b0 + j) mod n, w = 1/2 at the bins 0 and n / 2 when `half`
 int launch_ssq_sum(LaunchCtx c, const cf *T, int64_t nframes, int nb, int n, int b0, int nbands, int per_frame, const float *edges,
                    const SsqEdges &ec, int half, float scale, int64_t rows, cf *out);
+
+// smoothed pseudo Wigner-Ville distribution (k_wvd.hip): column j of a row sits at n_j = first + j hop;
+//   K[j][tau] = h[tau] sum_mu g[mu] z[n_j + mu + tau] conj(y[n_j + mu - tau]),   W[j][k] = scale FFT_L(K[j][tau mod L])[k]
+// h = device table of 2 Lh + 1 taps, g of 2 Lg + 1, both indexed from -L.  A workgroup owns a run of cpr consecutive columns of one row
+// and stages the samples of z they touch in LDS behind its transform images.  Auto (y null): the columns 2p and 2p + 1 of a ROW share
+// one transform whatever the runs are -- a run that starts or ends inside a pair forms the pair and stores its own column -- so the
+// staged columns are cpr rounded up to even; the partner of an odd last column is that column itself.  Cross: one transform per
+// column, y is read through the caches.  W: float [rows][ntimes][nb] (auto) or cf, the nb bins from b0 on modulo L.
+#define SP_WVD_LDS_MAX ((size_t)160 * 1024)
+#define SP_WVD_MAX_L 8192
+#define SP_WVD_MAX_NG 255
+#define SP_WVD_MAX_SPAN ((int64_t)1 << 40)
+struct WvdArgs {
+    const cf *x, *y;
+    int64_t x_ld, nsig, first, ntimes, cpr, hop;
+    const float *h, *g;
+    int Lh, Lg, b0, nb;
+    float scale;
+    void *W;
+};
+// columns a run stages
+inline int64_t wvd_staged_cols(bool cross, int64_t cpr, int64_t ntimes) {
+    const int64_t nc = cross ? cpr : cpr + (cpr & 1);
+    return nc < ntimes ? nc : (ntimes > 1 ? ntimes : 1);
+}
+inline size_t wvd_image_bytes(int L) { return (size_t)fpw_of(L) * (size_t)(L + 16) * 8; }
+// images + 8 bytes per staged sample: (staged columns - 1) hop + 2 (Lh + Lg) + 1 of them
+inline size_t wvd_lds_bytes(bool cross, int L, int nh, int ng, int64_t hop, int64_t cpr, int64_t ntimes) {
+    const int64_t nc = wvd_staged_cols(cross, cpr, ntimes);
+    if (nc > 1 && hop > SP_WVD_MAX_SPAN / (nc - 1)) return (size_t)-1 / 2;
+    return wvd_image_bytes(L) + 8 * (size_t)((nc - 1) * hop + (nh - 1) + (ng - 1) + 1);
+}
+// columns per run: about four workgroups per CU over runs x rows in whole rounds of the workgroup's groups, cut down to what the LDS
+// holds (auto: kept even); forced > 0: that many.  Never more than the row has.
+inline int64_t wvd_cpr(bool cross, int L, int nh, int ng, int64_t hop, int64_t ntimes, int64_t rows, int ncu, int forced) {
+    if (ntimes < 1) return 1;
+    int64_t c = forced;
+    if (forced <= 0) {
+        const int per = fpw_of(L) * (cross ? 1 : 2);
+        int64_t want = (int64_t)ncu * 4 / (rows > 0 ? rows : 1);
+        if (want < 1) want = 1;
+        c = ((ntimes + want - 1) / want + per - 1) / per * per;
+        const int64_t room = (int64_t)((SP_WVD_LDS_MAX - wvd_image_bytes(L)) / 8) - ((nh - 1) + (ng - 1) + 1);
+        if (room >= 0 && c > room / hop + 1) {
+            c = room / hop + 1;
+            if (!cross && c > 1) c &= ~(int64_t)1;
+        }
+    }
+    return c < ntimes ? c : ntimes;
+}
+inline int64_t wvd_transforms_per_run(bool cross, int64_t cpr) { return cross ? cpr : (cpr + 1) / 2; }
+int launch_wvd(LaunchCtx c, const WvdArgs &a, int L, const cf *tw, int64_t runs, int64_t rows, size_t lds_bytes);
 
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;

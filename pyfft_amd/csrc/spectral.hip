@@ -2,6 +2,7 @@
 #include "../../include/spectral.h"
 #include "../../include/spectral_ext.h"
 #include "../../include/spectral_tfr.h"
+#include "../../include/spectral_quad.h"
 #include "launch.h"
 #include "stage.h"
 #include "table_cache.h"
@@ -3779,6 +3780,97 @@ int sp_ssq_sum(const void *T, int64_t nframes, int nb, int64_t batch, int n, int
         ProfScope ps;
         LAUNCHCHK(launch_ssq_sum(lc(), (const cf *)Td, nframes, nb, n, b0, nbands, edges ? 0 : 1, ed, ec, half ? 1 : 0, (float)scale, batch, od));
         g.last_kernel = "k_ssq_sum";
+    }
+    return st.finish();
+}
+
+// ---- smoothed pseudo Wigner-Ville distribution (k_wvd.hip; include/spectral_quad.h) --------------------
+// the checks sp_wvd and sp_wvd_plan share; 0 or the message's tail
+static const char *wvd_shape(int nfft, int nh, int ng, int64_t hop, int64_t first, int64_t ntimes, int64_t batch, int nb) {
+    if (nfft < 32 || nfft > SP_WVD_MAX_L || !is_pow2(nfft)) return "nfft must be a power of two from 32 to 8192";
+    if (nh < 1 || !(nh & 1) || nh > nfft - 1) return "nh must be odd and lie in 1 .. nfft - 1";
+    if (ng < 1 || !(ng & 1) || ng > SP_WVD_MAX_NG) return "ng must be odd and lie in 1 .. 255";
+    if (hop < 1) return "hop must be at least 1";
+    if (ntimes < 0) return "ntimes must not be negative";
+    if (batch < 0 || batch > 65535) return "batch must lie in 0 .. 65535";
+    if (nb < 1 || nb > nfft) return "nb must lie in 1 .. nfft";
+    if (hop > SP_WVD_MAX_SPAN || ntimes > SP_WVD_MAX_SPAN / hop || first > SP_WVD_MAX_SPAN || first < -SP_WVD_MAX_SPAN)
+        return "ntimes, hop and first: the columns lie beyond 2^40 samples";
+    return nullptr;
+}
+
+int sp_wvd_plan(int cross, int nfft, int nh, int ng, int64_t hop, int64_t ntimes, int64_t batch, int nb, int64_t out[5]) {
+    if (!out || wvd_shape(nfft, nh, ng, hop, 0, ntimes, batch, nb)) return -1;
+    const int64_t cpr = wvd_cpr(cross != 0, nfft, nh, ng, hop, ntimes, batch, g.ncu, env_int("SP_WVD_CPR", 0));
+    const size_t lds = wvd_lds_bytes(cross != 0, nfft, nh, ng, hop, cpr, ntimes);
+    out[0] = cpr;
+    out[1] = (ntimes + cpr - 1) / cpr * batch;
+    out[2] = (int64_t)lds;
+    out[3] = wvd_transforms_per_run(cross != 0, cpr);
+    out[4] = lds <= SP_WVD_LDS_MAX ? 1 : 0;
+    return 0;
+}
+
+int sp_wvd(const void *x, const void *y, int64_t x_ld, int64_t nsig, int64_t batch, const float *h, int nh, const float *gw, int ng,
+           int nfft, int64_t hop, int64_t first, int64_t ntimes, int b0, int nb, double scale, void *W, int mem) {
+    // every refusal comes before the device is touched
+    if (const char *why = wvd_shape(nfft, nh, ng, hop, first, ntimes, batch, nb))
+        return fail("sp_wvd: %s (nfft %d, nh %d, ng %d, hop %lld, ntimes %lld, batch %lld, nb %d)", why, nfft, nh, ng, (long long)hop,
+                    (long long)ntimes, (long long)batch, nb);
+    if (nsig < 1) return fail("sp_wvd: nsig = %lld must be at least 1", (long long)nsig);
+    if (x_ld < nsig) return fail("sp_wvd: x_ld = %lld is below nsig = %lld", (long long)x_ld, (long long)nsig);
+    if (b0 < 0 || b0 >= nfft) return fail("sp_wvd: b0 = %d lies outside 0 .. nfft - 1 = %d", b0, nfft - 1);
+    if (!isfinite(scale)) return fail("sp_wvd: scale must be finite");
+    if (!x) return fail("sp_wvd: x is required");
+    if (!h) return fail("sp_wvd: h is required");
+    if (!gw) return fail("sp_wvd: g is required");
+    if (!W) return fail("sp_wvd: W is required");
+    const bool cross = y != nullptr;
+    const int64_t cpr = wvd_cpr(cross, nfft, nh, ng, hop, ntimes, batch, g.ncu, env_int("SP_WVD_CPR", 0));
+    const size_t lds = wvd_lds_bytes(cross, nfft, nh, ng, hop, cpr, ntimes);
+    if (lds > SP_WVD_LDS_MAX)
+        return fail("sp_wvd: the LDS of a workgroup, %zu bytes, does not fit %zu (nfft %d, nh %d, ng %d, hop %lld, %lld columns per run)",
+                    lds, SP_WVD_LDS_MAX, nfft, nh, ng, (long long)hop, (long long)cpr);
+    if (batch == 0 || ntimes == 0) return 0;
+    const int64_t runs = (ntimes + cpr - 1) / cpr;
+    if (runs > INT_MAX) return fail("sp_wvd: ntimes = %lld is too many runs for one launch", (long long)ntimes);
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    WvdArgs a{};
+    Stage st(mem);
+    const size_t x_elems = (size_t)((batch - 1) * x_ld + nsig);
+    st.in(g.in0, x, sizeof(cf) * x_elems, &a.x);
+    st.in(g.in1, y, sizeof(cf) * x_elems, &a.y);
+    st.out(g.out0, W, (cross ? sizeof(cf) : sizeof(float)) * (size_t)batch * (size_t)ntimes * (size_t)nb, &a.W);
+    if (st.commit()) return -1;
+    // auto: W is the real part, the distribution under the even part of h (h itself when it is symmetric: (v + v) / 2 is exact)
+    std::vector<float> hs(h, h + nh);
+    if (!cross)
+        for (int j = 0; j < nh; ++j) hs[(size_t)j] = 0.5f * (h[j] + h[nh - 1 - j]);
+    void *h_d = nullptr, *g_d = nullptr;
+    const cf *tw;
+    if (get_table(22, hs.data(), sizeof(float) * (size_t)nh, &h_d, nullptr)) return -1;
+    if (get_table(23, gw, sizeof(float) * (size_t)ng, &g_d, nullptr)) return -1;
+    if (get_twiddles(nfft, &tw)) return -1;
+    a.x_ld = x_ld;
+    a.nsig = nsig;
+    a.first = first;
+    a.ntimes = ntimes;
+    a.cpr = cpr;
+    a.hop = hop;
+    a.h = (const float *)h_d;
+    a.g = (const float *)g_d;
+    a.Lh = nh / 2;
+    a.Lg = ng / 2;
+    a.b0 = b0;
+    a.nb = nb;
+    a.scale = (float)scale;
+    {
+        ProfScope ps;
+        if (launch_wvd(lc(), a, nfft, tw, runs, batch, lds) != 0)
+            return fail("sp_wvd: the launch was refused (nfft %d, nb %d, %lld columns, %lld rows)", nfft, nb, (long long)ntimes, (long long)batch);
+        HIPCHK(hipGetLastError());
+        g.last_kernel = "k_wvd";
     }
     return st.finish();
 }

@@ -1386,6 +1386,121 @@ def ssq_plan(n, nframes, rows=1, cplx=False, nb=None, T=True, P=False, fields=Fa
     return d
 
 
+WVD_MIN_N, WVD_MAX_N, WVD_MAX_NG, WVD_MAX_ROWS, WVD_LDS_MAX = 32, 8192, 255, 65535, 160 * 1024
+
+
+class WvdRefused(ValueError, NotImplementedError):
+    """A shape the Wigner-Ville kernel does not take: outside the limits, and what is not built (transforms that are no power of two
+    or longer than one workgroup's, time windows beyond 255 taps, real rows, a run whose staged samples do not fit the LDS)."""
+
+
+def wvd_lds_bytes(cross, nfft, nh, ng, hop, cpr, ntimes):
+    """The LDS of a workgroup: max(1, 4096 / nfft) images of nfft + 16 complex, and 8 bytes per staged sample: (c - 1) hop + nh + ng - 1
+    of them, c = the columns per run (auto: rounded up to even), at most ntimes."""
+    c = cpr if cross else cpr + (cpr & 1)
+    c = min(c, max(ntimes, 1))
+    return max(1, 4096 // nfft) * (nfft + 16) * 8 + 8 * ((c - 1) * hop + nh + ng - 1)
+
+
+def wvd_check(who, nfft, nh, ng, hop, ntimes, rows, nb, b0=0, scale=1.0, nsig=None, x_ld=None):
+    """The refusals of sp_wvd and sp_wvd_plan, before the library is touched."""
+    if nfft < WVD_MIN_N or nfft > WVD_MAX_N or nfft & (nfft - 1):
+        raise WvdRefused("%s: nfft = %d must be a power of two from %d to %d" % (who, nfft, WVD_MIN_N, WVD_MAX_N))
+    if nh < 1 or not nh & 1 or nh > nfft - 1:
+        raise WvdRefused("%s: nh = %d must be odd and lie in 1 .. nfft - 1 = %d" % (who, nh, nfft - 1))
+    if ng < 1 or not ng & 1 or ng > WVD_MAX_NG:
+        raise WvdRefused("%s: ng = %d must be odd and lie in 1 .. %d" % (who, ng, WVD_MAX_NG))
+    if hop < 1:
+        raise WvdRefused("%s: hop = %d must be at least 1" % (who, hop))
+    if ntimes < 0:
+        raise WvdRefused("%s: ntimes = %d must not be negative" % (who, ntimes))
+    if rows < 0 or rows > WVD_MAX_ROWS:
+        raise WvdRefused("%s: %d rows are outside 0 .. %d" % (who, rows, WVD_MAX_ROWS))
+    if nsig is not None and nsig < 1:
+        raise WvdRefused("%s: the rows must hold at least one sample" % who)
+    if x_ld is not None and x_ld < nsig:
+        raise WvdRefused("%s: x_ld = %d is below nsig = %d" % (who, x_ld, nsig))
+    if nb < 1 or nb > nfft:
+        raise WvdRefused("%s: nb = %d must lie in 1 .. nfft = %d" % (who, nb, nfft))
+    if b0 < 0 or b0 >= nfft:
+        raise WvdRefused("%s: b0 = %d lies outside 0 .. nfft - 1 = %d" % (who, b0, nfft - 1))
+    if not np.isfinite(scale):
+        raise WvdRefused("%s: scale must be finite" % who)
+
+
+def _wvd_window(who, name, w):
+    if w is None:
+        raise WvdRefused("%s: %s is required" % (who, name))
+    w = _win32(w)
+    if w.ndim != 1 or not np.all(np.isfinite(w)):
+        raise WvdRefused("%s: %s must be one axis of finite values" % (who, name))
+    return w
+
+
+def _wvd_plan_raw(who, cross, nfft, nh, ng, hop, ntimes, rows, nb):
+    out = np.zeros(5, dtype=np.int64)
+    if lib().sp_wvd_plan(1 if cross else 0, nfft, nh, ng, hop, ntimes, rows, nb, ptr(out)) != 0:
+        raise WvdRefused("%s: the shape is refused" % who)
+    d = dict(zip(("cpr", "workgroups", "lds_bytes", "transforms", "fits"), (int(v) for v in out)))
+    d["fits"] = bool(d["fits"])
+    return d
+
+
+def wvd(x, h, g, hop, first, ntimes, nfft, y=None, b0=0, nb=None, scale=1.0):
+    """The smoothed pseudo Wigner-Ville distribution along the last axis (sp_wvd): column j sits at n = first + j*hop,
+    K[j, tau] = h[tau] * sum_mu g[mu] x[n + mu + tau] conj(y[n + mu - tau]) with the rows zero outside themselves, h and g odd, centred
+    tables, and W[j] = scale * FFT_nfft(K[j]) at the nb bins from b0 on (modulo nfft); bin k stands for k fs / (2 nfft).
+    y None: float32 [..., ntimes, nb] (the distribution of x with itself is real); else the cross distribution, complex64.
+    x (and y) must be complex; a real record is made analytic first (pyfft_amd.wigner does).  numpy in -> numpy out; device tensor
+    in -> a device tensor on x's stream."""
+    nfft, hop, first, ntimes, b0, scale = int(nfft), int(hop), int(first), int(ntimes), int(b0), float(scale)
+    md = _mode(x)
+    x = md.checked(x)
+    if x.ndim < 1:
+        raise WvdRefused("wvd: x must have at least one axis")
+    if md.code(x) != _ffi.DTYPE_C64:
+        raise WvdRefused("wvd: float32 rows are not taken directly: make the record analytic first (pyfft_amd.wigner.spwvd does)")
+    lead = tuple(int(d) for d in x.shape[:-1])
+    rows = 1
+    for d in lead:
+        rows *= d
+    nsig = int(x.shape[-1])
+    hw, gw = _wvd_window("wvd", "h", h), _wvd_window("wvd", "g", g)
+    nb = nfft if nb is None else int(nb)
+    wvd_check("wvd", nfft, int(hw.size), int(gw.size), hop, ntimes, rows, nb, b0, scale, nsig)
+    cross = y is not None
+    if cross:
+        if _mode(y) is not md:
+            raise TypeError("wvd: x and y must both be numpy arrays or both device tensors")
+        y = md.checked(y)
+        if tuple(y.shape) != tuple(x.shape) or not md.alike(x, y):
+            raise WvdRefused("wvd: y must share x's shape, %s" % md.ALIKE)
+    md.bind(x)
+    xs, xld = md.rows(x)
+    ys = None
+    if cross:
+        ys, yld = md.rows(y)
+        if yld != xld:
+            xs, ys = md.samples(xs), md.samples(ys)
+            xld = nsig
+    plan = _wvd_plan_raw("wvd", cross, nfft, int(hw.size), int(gw.size), hop, ntimes, rows, nb)
+    if not plan["fits"]:
+        raise WvdRefused("wvd: the LDS of a workgroup, %d bytes, does not fit %d (nfft %d, nh %d, ng %d, hop %d, %d columns per run)"
+                         % (plan["lds_bytes"], WVD_LDS_MAX, nfft, hw.size, gw.size, hop, plan["cpr"]))
+    out = md.empty(lead + (ntimes, nb), "complex64" if cross else "float32", xs)
+    md.call(lib().sp_wvd, md.addr(xs), md.addr(ys), xld, nsig, rows, ptr(hw), int(hw.size), ptr(gw), int(gw.size), nfft, hop, first,
+            ntimes, b0, nb, scale, md.addr(out))
+    return out
+
+
+def wvd_plan(nfft, nh, ng, hop, ntimes, rows=1, cross=False, nb=None):
+    """sp_wvd_plan as a dict (host only): cpr (columns per run), workgroups, lds_bytes, transforms (per run), fits."""
+    nfft, nh, ng, hop, ntimes, rows = int(nfft), int(nh), int(ng), int(hop), int(ntimes), int(rows)
+    nb = nfft if nb is None else int(nb)
+    wvd_check("wvd_plan", nfft, nh, ng, hop, ntimes, rows, nb)
+    return _wvd_plan_raw("wvd_plan", cross, nfft, nh, ng, hop, ntimes, rows, nb)
+
+
 EIGH_MAX_N = 64
 
 
