@@ -49,6 +49,17 @@ int sp_wct_scale(const void *T, int64_t nsig, int nscales, int64_t batch, const 
                  float *B, void *C, int mem);
 int sp_wct_plan(int64_t nsig, int nscales, int64_t batch, int L, int Mw, int Mg, int xwt, int64_t out[5]);
 
+/* ---- Loop passes of the last call (for the tests of the host loops; never touches the device).  The library cuts long work into
+ *      chunks of frames (segments beyond one workgroup transform: sp_welch_psd, sp_welch_csd, sp_stft, sp_stft_cog, sp_zoom_welch;
+ *      sp_csd_matrix and sp_bispectrum at every length) and batches of long transforms into slices of rows (sp_fft_c2c, sp_czt and
+ *      every transform inside a frame chunk).  which = 0: the passes the outermost frame-chunk loop of the last API call made;
+ *      which = 1: the most slice passes one batch of long transforms made inside it.  0 where the call had no such loop, or for
+ *      another `which`.  Both are reset where a call that touches the device begins.  The budgets behind the loops can be capped
+ *      through the environment, read on every call (unset or <= 0: no cap): SP_LONG_CHUNK_FRAMES (frames of a long chunk),
+ *      SP_LONG_SLICE_ROWS (rows of a slice), SP_CSDM_CHUNK_FRAMES (frames of a chunk of sp_csd_matrix, before its chunks are
+ *      equalised and rounded to 32). */
+int sp_last_passes(int which);
+
 #ifdef __cplusplus
 }
 #endif

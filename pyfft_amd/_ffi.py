@@ -98,6 +98,7 @@ EXT_SIGNATURES = {
     "sp_wct_time": (_i, [_vp, _i64, _vp, _i64, _i, _i64, _i64, _vp, _i, _i, _d, _i, _i, _i, _vp, _vp, _i]),
     "sp_wct_scale": (_i, [_vp, _i64, _i, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
     "sp_wct_plan": (_i, [_i64, _i, _i64, _i, _i, _i, _i, _vp]),
+    "sp_last_passes": (_i, [_i]),
 }
 
 # the third table: must list every symbol include/spectral_tfr.h declares, and none of the other two

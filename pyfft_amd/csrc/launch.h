@@ -28,6 +28,10 @@ namespace sp {
 //   SP_WCT_CHUNK (int: the same for the cross-wavelet and coherence kernel)
 //   SP_SSQ_FPG (int: the synchrosqueezed STFT's frames per run)
 //   SP_WVD_CPR (int: the Wigner-Ville kernel's columns per run)
+//   SP_LONG_CHUNK_FRAMES (int: a cap on the frames per chunk of the long-segment paths, long_chunk_frames)
+//   SP_LONG_SLICE_ROWS (int: a cap on the rows per slice of a batch of long transforms, dev_fft_any and sp_czt)
+//   SP_CSDM_CHUNK_FRAMES (int: a cap on the frames per chunk of sp_csd_matrix, before the chunks are equalised)
+//   (the last three: unset or <= 0 leaves the budget alone; sp_last_passes reports the passes a call made)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
     return v && v[0] && v[0] != '0';

@@ -221,11 +221,27 @@ int get_xf(int64_t n, Xf *xf) {
 // before the entry is freed, because asynchronous (mem=1) work of an earlier call may still read it.
 TableCache g_tables;
 
+// sp_last_passes: [0] the passes of the current call's outermost frame-chunk loop, [1] the most slice passes one
+// dev_fft_any / sp_czt loop made inside it.  Both are zeroed where a call begins (ApiLock), so that a test can assert
+// that the shape it chose really walks a loop past its first pass.
+int g_passes[2] = {0, 0};
+inline void note_slices(int64_t n) {
+    if (n > g_passes[1]) g_passes[1] = (int)n;
+}
+// a test hook that caps a loop's budget: unset or <= 0 leaves `v` as it is
+inline int64_t hook_cap(const char *name, int64_t v) {
+    const int64_t h = env_int(name, 0);
+    return h > 0 && h < v ? h : v;
+}
+
 // every C-ABI entry point that touches device state holds this for its whole body: the library lock, and the start of
 // a new "current call" for the table cache
 struct ApiLock {
     std::lock_guard<std::mutex> lk;
-    ApiLock() : lk(g.mu) { g_tables.begin_call(); }
+    ApiLock() : lk(g.mu) {
+        g_tables.begin_call();
+        g_passes[0] = g_passes[1] = 0;
+    }
 };
 
 // Staging of one call's host-memory (mem = 0) arguments: the one place that grows the scratch buffers, copies inputs in
@@ -618,6 +634,8 @@ int dev_fft_any(const cf *in, cf *out, int64_t n, int64_t batch, int inverse) {
     int64_t slice = (int64_t)(SP_LONG_SLICE_BYTES / (sizeof(cf) * (size_t)L));
     if (slice < 1) slice = 1;
     if (slice > 32768) slice = 32768;
+    slice = hook_cap("SP_LONG_SLICE_ROWS", slice);
+    note_slices((batch + slice - 1) / slice);
     if (is_pow2(n)) {
         for (int64_t b0 = 0; b0 < batch; b0 += slice) {
             const int64_t m = batch - b0 < slice ? batch - b0 : slice;
@@ -773,7 +791,7 @@ int64_t long_chunk_frames(int nfft, int64_t nframes) {
     if (m > 32768) m = 32768;
     if (m > nframes) m = nframes;
     if (m < 1) m = 1;
-    return m;
+    return hook_cap("SP_LONG_CHUNK_FRAMES", m);
 }
 // spectra of frames [f0, f0+m) of one signal -> buf[m][nfft] (natural bin order, unscaled); segmean: 1 / 2 = every
 // frame's own mean / least-squares line is removed first; pseg_d (optional, zeroed): per-frame time-domain power
@@ -1304,6 +1322,10 @@ extern "C" {
 int sp_version(void) { return SP_VERSION; }
 int sp_max_wg_fft(void) { return SP_MAX_WG_FFT; }
 const char *sp_last_error(void) { return g_err.c_str(); }
+int sp_last_passes(int which) {
+    std::lock_guard<std::mutex> lk(g.mu);
+    return which == 0 || which == 1 ? g_passes[which] : 0;
+}
 
 int sp_init(int device_id) {
     std::lock_guard<std::mutex> lk(g.mu);
@@ -1510,7 +1532,7 @@ int sp_welch_psd(const void *x, int x_dtype, int64_t nsig, const float *win, int
         cf *S = (cf *)g.bigA.p;
         double *acc = (double *)g.work.p;
         HIPCHK(hipMemsetAsync(acc, 0, sizeof(double) * (size_t)nfft, g.stream));
-        for (int64_t f0 = 0; f0 < nframes; f0 += mc) {
+        for (int64_t f0 = 0; f0 < nframes; f0 += mc, ++g_passes[0]) {
             const int64_t m = nframes - f0 < mc ? nframes - f0 : mc;
             if (long_spectra(xd, cplx, (const float *)win_d, nfft, hop, f0, m, tb.f, detrend == 2, segmean, S, nullptr)) return -1;
             LAUNCHCHK(launch_long_acc_psd(lc(), S, m, nfft, acc));
@@ -1824,6 +1846,8 @@ int sp_welch_psd_dist(const void *x, int x_dtype, int64_t nsig, const float *win
 int sp_welch_csd(const void *x, const void *y, int dtype, int64_t nsig, int nch, int64_t y_ld, const float *win,
                  int nfft, int hop, int64_t nframes, int detrend, const double *mean_x, const double *mean_y,
                  int sided, double scale, double *pxx, double *pyy, double *pxy, int mem) {
+    // (the frame kernels and their finish take the channel as grid.y; long segments walk the channels one by one)
+    if (nch > 65535 && wg_capable(nfft)) return fail("sp_welch_csd: nch = %d is beyond the limit of 65535 channels per call", nch);
     if (ensure_init()) return -1;
     if (check_frames("sp_welch_csd", nsig, nfft, hop, nframes)) return -1;
     if (nch < 1 || y_ld < nsig) return fail("sp_welch_csd: bad nch / y_ld");
@@ -1888,7 +1912,7 @@ int sp_welch_csd(const void *x, const void *y, int dtype, int64_t nsig, int nch,
         cf *Sx = (cf *)g.bigA.p, *Sy = (cf *)g.bigB.p;
         double *axx = (double *)g.work.p, *ayy = axx + nf, *axy = ayy + nf * (size_t)nch;
         HIPCHK(hipMemsetAsync(axx, 0, sizeof(double) * nf * (1 + 3 * (size_t)nch), g.stream));
-        for (int64_t f0 = 0; f0 < nframes; f0 += mc) {
+        for (int64_t f0 = 0; f0 < nframes; f0 += mc, ++g_passes[0]) {
             const int64_t m = nframes - f0 < mc ? nframes - f0 : mc;
             if (long_spectra(xd, cplx, (const float *)win_d, nfft, hop, f0, m, tb.f, detrend == 2, segmean, Sx, nullptr)) return -1;
             LAUNCHCHK(launch_long_acc_psd(lc(), Sx, m, nfft, axx));
@@ -1983,6 +2007,8 @@ __global__ void k_set_trends(const double *__restrict__ means, float *__restrict
 static int csd_matrix_impl(const char *who, const float *x, int nch, int64_t nsig, int64_t x_ld, const float *win, int nfft,
                            int hop, int64_t nframes, int detrend, const double *means_host, double scale, double *g_out,
                            int mem) {
+    // (the transposed contraction takes the pairs of 64-channel superblocks, nsb (nsb - 1) / 2 with nsb = ceil(nch / 64), as grid.y)
+    if (nch > 23168) return fail("%s: nch = %d is beyond the limit of 23168 channels", who, nch);
     if (ensure_init()) return -1;
     if (check_frames(who, nsig, nfft, hop, nframes)) return -1;
     if (nch < 1 || x_ld < nsig) return fail("%s: bad nch / x_ld", who);
@@ -2011,6 +2037,7 @@ static int csd_matrix_impl(const char *who, const float *x, int nch, int64_t nsi
     // frames are processed in chunks so the two spectra buffers stay <= 8 GiB each (and float sums stay short)
     int64_t mc = ((int64_t)1 << 31) / ((int64_t)nch * nb);     // <= 16 GiB per spectra buffer
     if (mc > 16384) mc = 16384;
+    mc = hook_cap("SP_CSDM_CHUNK_FRAMES", mc);
     if (mc < 32) mc = 32;
     mc &= ~(int64_t)31;
     {
@@ -2076,7 +2103,7 @@ static int csd_matrix_impl(const char *who, const float *x, int nch, int64_t nsi
     size_t op_sp = 0, op_sl = 0;
     int op_runs = 0;
     bool fold_pending = false;                            // packed-spectra path used: H (g.cmH) is folded into G at the end
-    for (int64_t f0 = 0; f0 < nframes; f0 += mc) {
+    for (int64_t f0 = 0; f0 < nframes; f0 += mc, ++g_passes[0]) {
         const int64_t m = nframes - f0 < mc ? nframes - f0 : mc;
         hipLaunchKernelGGL(k_trend_shift, dim3((nch + 63) / 64), dim3(64), 0, g.stream, tb.f, tb.f + 4 * nch, nch,
                            (double)f0 * (double)hop);
@@ -2207,6 +2234,9 @@ int sp_channel_means(const float *x, int nch, int64_t nsig, int64_t x_ld, double
 int sp_stft(const void *x, int x_dtype, int64_t nsig, const float *win, int nfft, int hop, int64_t nframes,
             int detrend, double mean_re, double mean_im, int sided, double amp_scale, int out_kind, int out_major,
             void *out, double *pseg_out, int mem) {
+    if (out_major == 1 && nframes > (int64_t)65535 * 32)
+        return fail("sp_stft: nframes = %lld is beyond the %lld frames the bin-major layout takes per call", (long long)nframes,
+                    (long long)65535 * 32);
     if (ensure_init()) return -1;
     if (check_frames("sp_stft", nsig, nfft, hop, nframes)) return -1;
     if (sided < 1 || sided > 4) return fail("sp_stft: bad sided");
@@ -2250,7 +2280,7 @@ int sp_stft(const void *x, int x_dtype, int64_t nsig, const float *win, int nfft
         const int64_t mc = long_chunk_frames(nfft, nframes);
         if (g.bigA.ensure(sizeof(cf) * (size_t)mc * (size_t)nfft)) return -1;
         cf *S = (cf *)g.bigA.p;
-        for (int64_t f0 = 0; f0 < nframes; f0 += mc) {
+        for (int64_t f0 = 0; f0 < nframes; f0 += mc, ++g_passes[0]) {
             const int64_t m = nframes - f0 < mc ? nframes - f0 : mc;
             if (long_spectra(xd, cplx, (const float *)win_d, nfft, hop, f0, m, tb.f, detrend == 2, segmean, S, pseg_d)) return -1;
             LAUNCHCHK(launch_long_stft_out(lc(), S, m, nfft, sided, (float)amp_scale, out_kind, fm, f0, (int)nb));
@@ -2326,7 +2356,7 @@ int sp_stft_cog(const void *x, int x_dtype, int64_t nsig, const float *win, int 
         const int64_t mc = long_chunk_frames(nfft, nframes);
         if (g.bigA.ensure(sizeof(cf) * (size_t)mc * (size_t)nfft)) return -1;
         cf *S = (cf *)g.bigA.p;
-        for (int64_t f0 = 0; f0 < nframes; f0 += mc) {
+        for (int64_t f0 = 0; f0 < nframes; f0 += mc, ++g_passes[0]) {
             const int64_t m = nframes - f0 < mc ? nframes - f0 : mc;
             if (long_spectra(xd, cplx, (const float *)win_d, nfft, hop, f0, m, tb.f, detrend == 2, segmean, S, nullptr)) return -1;
             LAUNCHCHK(launch_long_cog(lc(), S, m, nfft, klo, khi, acc, f0));
@@ -2436,7 +2466,7 @@ int sp_bispectrum(const void *x, const void *y, const void *z, int x_dtype, int6
     if (get_trendbuf(6, &tb)) return -1;                  // records 0 .. 2: the signals' trends; 3 .. 5: shifted to a chunk
     for (int k = 0; k < nsp; ++k)
         if (set_trend(tb, k, xd[k], cplx, nsig, detrend, mean_re, mean_im)) return -1;
-    for (int64_t f0 = 0; f0 < nframes; f0 += mc) {
+    for (int64_t f0 = 0; f0 < nframes; f0 += mc, ++g_passes[0]) {
         const int64_t m = std::min(mc, nframes - f0);
         LAUNCHCHK(launch_bispec_trend_shift(lc(), tb.f, tb.f + 12, nsp, f0 * (int64_t)hop));
         const RunPart rp = run_partition(xf.L, m, g.ncu);
@@ -2588,7 +2618,9 @@ int sp_czt(const void *x, int x_dtype, int64_t n, int64_t x_ld, int64_t batch, i
         int64_t slice = (int64_t)(SP_LONG_SLICE_BYTES / (sizeof(cf) * (size_t)t.L));
         if (slice < 1) slice = 1;
         if (slice > 32768) slice = 32768;
+        slice = hook_cap("SP_LONG_SLICE_ROWS", slice);
         if (slice > batch) slice = batch;
+        note_slices((batch + slice - 1) / slice);
         if (g.blueA.ensure(sizeof(cf) * (size_t)t.L * (size_t)slice)) return -1;
         cf *A = (cf *)g.blueA.p;
         for (int64_t b0 = 0; b0 < batch; b0 += slice) {
@@ -3042,7 +3074,7 @@ int sp_zoom_welch(const void *x, const void *y, int dtype, int64_t nsig, const f
             acc = (double *)g_cztAcc.p;
             HIPCHK(hipMemsetAsync(acc, 0, sizeof(double) * 4 * mm, g.stream));
         }
-        for (int64_t f0 = 0; f0 < nframes; f0 += mc) {
+        for (int64_t f0 = 0; f0 < nframes; f0 += mc, ++g_passes[0]) {
             const int64_t rows = nframes - f0 < mc ? nframes - f0 : mc;
             if (czt_long_rows(xd, cplx, hop, f0, rows, (const float *)win_d, tb.f, lin, t, nfft, Sx)) return -1;
             if (cross && czt_long_rows(yd, cplx, hop, f0, rows, (const float *)win_d, tb.f + 4, lin, t, nfft, Sy)) return -1;
@@ -3950,6 +3982,7 @@ int sp_istft(const void *Z, int sided, int in_major, int nch, int64_t nframes, c
     if (in_major != 0 && in_major != 1) return fail("sp_istft: in_major must be 0 or 1");
     if (nfft < 2 || hop < 1 || hop > nfft) return fail("sp_istft: need nfft >= 2 and 1 <= hop <= nfft (nfft %d, hop %d)", nfft, hop);
     if (nframes < 1 || nch < 1) return fail("sp_istft: nframes and nch must be at least 1");
+    if (nch > 65535) return fail("sp_istft: nch = %d is beyond the limit of 65535 channels per call", nch);
     if (!wg_capable(nfft))
         return fail("sp_istft: nfft %d not supported (powers of two up to %d, other lengths up to %d)", nfft, SP_MAX_WG_FFT,
                     SP_MAX_WG_FFT / 2);

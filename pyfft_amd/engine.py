@@ -183,6 +183,12 @@ def max_wg_fft():
     return int(lib().sp_max_wg_fft())
 
 
+def last_passes(which=0):
+    """Passes the last call's loops made: which=0 its outermost frame-chunk loop, which=1 the most slice passes of one batch of
+    long transforms inside it; 0 where the call had no such loop (sp_last_passes)."""
+    return int(lib().sp_last_passes(int(which)))
+
+
 # ------------------------------------------------------------------------------------------ A7
 def fft(x, n=None, axis=-1, inverse=False):
     """np.fft.fft / ifft semantics (forward unnormalised, inverse 1/n) on the GPU, complex64 math."""

@@ -481,7 +481,8 @@ def test_csd_matrix_per_bin_parity_dynamic_range(E, nch, line_db):
                                                 (2, 8192, 4096, 40960)])
 def test_csd_matrix(E, nch, nfft, hop, nsig):
     """cfg5 shape (reduced): common component with per-channel gain/delay + independent noise; full nch x nch matrix,
-    including more than one 64-channel block, a ragged last frame chunk and a non power-of-two segment"""
+    including more than one 64-channel block, frame counts that are no multiple of 32 (the zero-filled padding of the contraction)
+    and a non power-of-two segment.  Every shape is ONE frame chunk; tests/test_gpu_loop_seams.py runs the second and ragged chunks"""
     rng = np.random.default_rng(nch * nfft)
     k = np.arange(nsig)
     common = np.sin(0.13 * k) + 0.5 * rng.standard_normal(nsig)

@@ -264,10 +264,11 @@ def test_long_cog(P):
 
 
 def test_long_many_midsize_frames(P):
-    """many frames of a mid-size long length go through each launch of the multi-pass transform as one batch, in slices"""
+    """many frames of a mid-size long length go through each launch of the multi-pass transform as one batch: both shapes stay
+    within ONE frame chunk (tests/test_gpu_loop_seams.py crosses the chunk and slice seams); the second makes two Bluestein slices"""
     E = P.engine
     rng = np.random.default_rng(21)
-    nfft, hop, M = 16384, 2048, 700           # 700 x 16384 x 8 B = 92 MB of spectra: 2 chunks of the 192 MiB budget? no: 1; see below
+    nfft, hop, M = 16384, 2048, 700           # 700 x 16384 x 8 B = 92 MB of spectra: one chunk of the 192 MiB budget (1536 frames), one slice
     n = (M - 1) * hop + nfft
     x = rng.standard_normal(n).astype(np.float32)
     win = O.windows("Hanning", nwins=nfft)
@@ -278,7 +279,7 @@ def test_long_many_midsize_frames(P):
         ref += np.abs(np.fft.fft(win * xd[g * hop:g * hop + nfft])) ** 2
     ref /= M
     np.testing.assert_allclose(got, ref, rtol=2e-4, atol=1e-6 * ref.max())
-    # 4 000 frames of 5 000 points (chirp-z on 16 384): several chunks and several FFT slices
+    # 4 000 frames of 5 000 points (chirp-z on 16 384): one chunk (5 033 frames fit), two slices of the Bluestein transform (2 048 + 1 952 rows)
     nfft, hop, M = 5000, 1000, 4000
     n = (M - 1) * hop + nfft
     x = rng.standard_normal(n).astype(np.float32)

@@ -310,10 +310,10 @@ def test_exported_declared_and_bound():
     hdr = open(os.path.join(ROOT, "include", "spectral_ext.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     declared = set(re.findall(r"\b(sp_[a-z0-9_]+)\s*\(", hdr))
-    assert declared == set(_ffi.EXT_SIGNATURES) == {"sp_wct_time", "sp_wct_scale", "sp_wct_plan"}
+    assert declared == set(_ffi.EXT_SIGNATURES) == {"sp_wct_time", "sp_wct_scale", "sp_wct_plan", "sp_last_passes"}
     assert not set(_ffi.SIGNATURES) & set(_ffi.EXT_SIGNATURES)
     lib = ctypes.CDLL(_ffi.LIB_PATH)
-    for name, want in (("sp_wct_time", 17), ("sp_wct_scale", 12), ("sp_wct_plan", 8)):
+    for name, want in (("sp_wct_time", 17), ("sp_wct_scale", 12), ("sp_wct_plan", 8), ("sp_last_passes", 1)):
         mt = re.search(r"int %s\(([^;]*)\);" % name, hdr)
         assert mt and len([a for a in mt.group(1).split(",") if a.strip()]) == len(_ffi.EXT_SIGNATURES[name][1]) == want
         assert hasattr(lib, name)
