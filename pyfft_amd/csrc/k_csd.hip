@@ -639,11 +639,7 @@ int launch_csdm_fused(LaunchCtx c, const cf *Xs, cf *Xt_tail, int nch, int64_t m
         fs = (fs + SP_CMF_F - 1) / SP_CMF_F * SP_CMF_F;
         slices = (int)((m + fs - 1) / fs);
         const size_t lds = 2 * sizeof(cf) * SP_CMF_TILE;                          // 68 KiB
-        static bool attr_done = false;
-        if (!attr_done) {
-            (void)hipFuncSetAttribute((const void *)k_csdm_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr_done = true;
-        }
+        if (lds_raise<k_csdm_fused>(lds)) return -1;
         hipLaunchKernelGGL(k_csdm_fused, dim3(ngroups * slices), dim3(1024), lds, c.stream, Xs, nch, m, ld, G, fs, slices,
                            slices > 1);
     }

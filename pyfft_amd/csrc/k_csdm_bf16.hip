@@ -413,13 +413,7 @@ int launch_csdm_bf16(LaunchCtx c, const cf *Xs, cf *Xt_tail, int nch, int64_t m,
         ps = (ps + CB_FP - 1) / CB_FP * CB_FP;
         slices = (int)((npairs + ps - 1) / ps);
         const size_t lds = 2 * sizeof(cf) * CB_TILE;                              // 68 KiB
-        static bool attr_done = false;
-        if (!attr_done) {
-            if (hipFuncSetAttribute((const void *)k_csdm_bf16<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-                hipFuncSetAttribute((const void *)k_csdm_bf16<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return -1;
-            attr_done = true;
-        }
+        if (!two_pieces ? lds_raise<k_csdm_bf16<0>>(lds) : lds_raise<k_csdm_bf16<4>>(lds)) return -1;
         int mode = slices > 1 ? 1 : 0;
         if (init) {
             if (slices == 1 && nb == CB_BINS * ngroups) mode = 2;

@@ -164,13 +164,6 @@ static __global__ __launch_bounds__(256) void k_icwt(const cf *__restrict__ W, c
     }
 }
 
-#define SP_DISPATCH_CWT(Lval, MACRO)                                                                  \
-    switch (Lval) {                                                                                   \
-        SP_CASE_P(256, MACRO) SP_CASE_P(512, MACRO) SP_CASE_P(1024, MACRO) SP_CASE_P(2048, MACRO)     \
-        SP_CASE_P(4096, MACRO) SP_CASE_P(8192, MACRO)                                                 \
-        default: return -1;                                                                           \
-    }
-
 int launch_cwt(LaunchCtx c, const CwtArgs &a, int L, const cf *tw, const CwtPlan &pl, int64_t rows) {
     const bool acc = a.recon != nullptr || a.bandpow != nullptr;
     if (a.nframes < 1 || a.S < 1 || a.chunk < 1 || a.M < 0 || a.hop != L - 2 * a.M || a.hop < 1 || rows < 1 || rows > 65535 ||
@@ -178,23 +171,18 @@ int launch_cwt(LaunchCtx c, const CwtArgs &a, int L, const cf *tw, const CwtPlan
         return -1;
     const XfTables tb{tw, nullptr, nullptr, L};
     const dim3 grid((unsigned)pl.blocks_x, (unsigned)pl.nchunks, (unsigned)rows);
-#define L_(XT, AC)                                                                                    \
+#define L_(AC)                                                                                        \
     {                                                                                                 \
-        const size_t lds = cwt_lds_bytes<XT::C>(XT::L);                                               \
-        static bool raised = false;                                                                   \
-        if (lds > 64 * 1024 && !raised) {                                                             \
-            if (hipFuncSetAttribute((const void *)k_cwt<XT, AC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-                return -1;                                                                            \
-            raised = true;                                                                            \
-        }                                                                                             \
+        if (lds_raise<k_cwt<XT, AC>>(lds)) return -1;                                                 \
         hipLaunchKernelGGL((k_cwt<XT, AC>), grid, dim3(XT::C::WG), lds, c.stream, a, tb);             \
     }
-#define M_(XT)                                                                                        \
-    if (acc) L_(XT, true) else L_(XT, false)
-    SP_DISPATCH_CWT(L, M_)
-#undef M_
+    return for_pow2<SP_CWT_MIN_L, SP_CWT_MAX_L>(L, [&](auto x) {
+        using XT = typename decltype(x)::type;
+        const size_t lds = cwt_lds_bytes<typename XT::C>(XT::L);
+        if (acc) L_(true) else L_(false)
+        return 0;
+    });
 #undef L_
-    return 0;
 }
 
 int launch_cwt_gws_finish(LaunchCtx c, const float *gpart, int64_t rows_x_scales, int64_t nframes, double *gws) {

@@ -162,26 +162,16 @@ int launch_ddc(LaunchCtx c, const void *x, bool cplx, int64_t x_ld, int64_t nsig
                uint64_t dnu, const cf *tab, const float *taps, bool vec, cf *out) {
     const int64_t nout = (nsig + g.q - 1) / g.q, tiles = (nout + g.K - 1) / g.K;
     if (batch < 1 || nsig < 1 || x_ld < nsig || tiles * batch > 0x7fffffff) return -1;
-    static bool attr_done = false;
-    if (!attr_done) {                             // the largest shapes stage more than 64 KiB
-        const int cap = 96 * 1024;
-        if (hipFuncSetAttribute((const void *)k_ddc<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
-            hipFuncSetAttribute((const void *)k_ddc<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
-            hipFuncSetAttribute((const void *)k_ddc<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
-            hipFuncSetAttribute((const void *)k_ddc<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess)
-            return -1;
-        attr_done = true;
-    }
-    if (g.lds > 96 * 1024) return -1;
     const dim3 grid((unsigned)(tiles * batch));
 #define L_(CP, MX)                                                                                    \
-    hipLaunchKernelGGL((k_ddc<CP, MX>), grid, dim3(256), g.lds, c.stream, x, x_ld, nsig, nout, tiles, g, ph0, dnu, tab, taps, vec ? 1 : 0, out)
-    if (cplx) {
-        if (tab != nullptr) L_(true, true);
-        else L_(true, false);
+    {                                                                                                 \
+        if (lds_raise<k_ddc<CP, MX>>(g.lds)) return -1;       /* the largest shapes stage more than 64 KiB */ \
+        hipLaunchKernelGGL((k_ddc<CP, MX>), grid, dim3(256), g.lds, c.stream, x, x_ld, nsig, nout, tiles, g, ph0, dnu, tab, taps, vec ? 1 : 0, out); \
+    }
+    if (!cplx) {
+        if (tab == nullptr) L_(false, false) else L_(false, true)
     } else {
-        if (tab != nullptr) L_(false, true);
-        else L_(false, false);
+        if (tab == nullptr) L_(true, false) else L_(true, true)
     }
 #undef L_
     return 0;

@@ -279,7 +279,7 @@ size_t eigh_lds_bytes(int NP, bool vec) {
     default: return 0;
     }
 }
-static_assert(sizeof(EighLds<64, true>) <= SP_EIGH_LDS_MAX, "A and V of order 64 fit the LDS of one CU");
+static_assert(sizeof(EighLds<64, true>) <= SP_LDS_MAX, "A and V of order 64 fit the LDS of one CU");
 static_assert(EighCfg<8>::WG == 64 && EighCfg<16>::WG == 64 && EighCfg<32>::WG == 256 && EighCfg<64>::WG == 1024, "eigh_wg_of");
 
 int launch_eigh(LaunchCtx c, const double *a, int n, int64_t batch, int nvec, int max_sweeps, double *w, double *v, int32_t *sweeps,
@@ -287,17 +287,11 @@ int launch_eigh(LaunchCtx c, const double *a, int n, int64_t batch, int nvec, in
     if (n < 1 || n > SP_EIGH_MAX_N || nvec < 0 || nvec > n || batch < 1 || max_sweeps < 1 || !a || !w || !sweeps || (nvec > 0 && !v))
         return -1;
     if (pl.NP != eigh_np_of(n) || pl.grid < 1 || pl.grid > batch || pl.grid > 0x7fffffff ||
-        pl.lds_bytes != eigh_lds_bytes(pl.NP, nvec > 0) || pl.lds_bytes > SP_EIGH_LDS_MAX)
+        pl.lds_bytes != eigh_lds_bytes(pl.NP, nvec > 0) || pl.lds_bytes > SP_LDS_MAX)
         return -1;
 #define L_(NPv, VE)                                                                                   \
     {                                                                                                 \
-        static bool raised = false;                                                                   \
-        if (pl.lds_bytes > 64 * 1024 && !raised) {                                                    \
-            if (hipFuncSetAttribute((const void *)k_eigh<NPv, VE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SP_EIGH_LDS_MAX) != \
-                hipSuccess)                                                                           \
-                return -1;                                                                            \
-            raised = true;                                                                            \
-        }                                                                                             \
+        if (lds_raise<k_eigh<NPv, VE>>(pl.lds_bytes)) return -1;                                      \
         hipLaunchKernelGGL((k_eigh<NPv, VE>), dim3((unsigned)pl.grid), dim3(EighCfg<NPv>::WG), pl.lds_bytes, c.stream,               \
                            (const double2 *)a, n, batch, nvec, max_sweeps, w, (double2 *)v, sweeps);  \
     }

@@ -197,8 +197,8 @@ int pfb_synth_groups(int M, int ntaps, bool cplx, size_t *lds_out) {
         default: return 0;
     }
 #undef R_
-    if (img + ring > SP_PFBS_LDS_MAX) return 0;
-    const size_t fit = (SP_PFBS_LDS_MAX - img) / ring, fpw = (size_t)fpw_of(M);
+    if (img + ring > SP_LDS_MAX) return 0;
+    const size_t fit = (SP_LDS_MAX - img) / ring, fpw = (size_t)fpw_of(M);
     const int ag = (int)(fit < fpw ? fit : fpw);
     if (lds_out) *lds_out = img + (size_t)ag * ring;
     return ag;
@@ -214,17 +214,10 @@ int launch_pfb_synth(LaunchCtx c, const cf *X, bool cplx, int64_t batch, int64_t
     const int64_t groups = (nframes + fpg - 1) / fpg, blocks = (groups + ag - 1) / ag;
     if (blocks * batch > 0x7fffffff) return -1;
     const dim3 grid((unsigned)(blocks * batch));
-    // a ring beyond 64 KiB: the instantiation's dynamic-LDS limit is raised once (as k_ddc does)
 #define L_(XT, CP, FU)                                                                                \
     {                                                                                                 \
         const size_t lds = FU ? lds_f : XT::C::lds_bytes(1);                                          \
-        static bool raised = false;                                                                   \
-        if (FU && lds > 64 * 1024 && !raised) {                                                       \
-            if (hipFuncSetAttribute((const void *)k_pfb_synth<XT, CP, FU>, hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                                    (int)SP_PFBS_LDS_MAX) != hipSuccess)                              \
-                return -1;                                                                            \
-            raised = true;                                                                            \
-        }                                                                                             \
+        if (lds_raise<k_pfb_synth<XT, CP, FU>>(lds)) return -1;                                       \
         hipLaunchKernelGGL((k_pfb_synth<XT, CP, FU>), grid, dim3(XT::C::WG), lds, c.stream, X, nframes, taps, P, hop, first, fpg,   \
                            halo, (int)blocks, ag, phase_ref, r0, xf.tb, nout, y, v);                     \
     }

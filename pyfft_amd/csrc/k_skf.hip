@@ -20,27 +20,6 @@
 #include "launch.h"
 namespace sp {
 
-// sum of one value per thread over the T threads of a transform group (k_xcorr_frames' xc_group_sum: through the group's exchange
-// image, never across the wave); every thread of the workgroup must call it (barriers)
-template <class C> __device__ __forceinline__ cf skf_group_sum(cf s, cf *lds, int tid) {
-    static_assert(C::T >= 2, "a group of at least two threads");
-    __syncthreads();                      // the image may still be read by the previous round's binning
-    lds[tid] = s;
-    __syncthreads();
-    constexpr int W = C::T < 16 ? C::T : 16;
-    cf p = mk(0.f, 0.f);
-    if (tid < W) {
-        for (int j = tid; j < C::T; j += W) p = p + lds[j];
-    }
-    __syncthreads();
-    if (tid < W) lds[tid] = p;
-    __syncthreads();
-    cf tot = mk(0.f, 0.f);
-#pragma unroll 4
-    for (int j = 0; j < W; ++j) tot = tot + lds[j];
-    return tot;
-}
-
 // phase -> histogram row: nk equal bins over [-pi, pi), pi wraps to row 0; always inside 0 .. nk - 1 (a NaN phase lands in row 0)
 __device__ __forceinline__ int skf_row(float re, float im, int nk) {
     const float th = atan2f(im, re);
@@ -78,7 +57,7 @@ __global__ __launch_bounds__(X::C::WG) void k_skf(SkfArgs a, XfTables tb, float 
             cf sm = mk(0.f, 0.f);
 #pragma unroll
             for (int t = 0; t < C::R; ++t) sm = sm + r[t];
-            return (1.f / (float)L) * skf_group_sum<C>(sm, lds, tq);
+            return (1.f / (float)L) * group_image_sum<C>(sm, lds, tq);
         };
         cf v[C::R];
         if constexpr (!CPLX) {
@@ -177,40 +156,25 @@ static __global__ __launch_bounds__(SKF_FIN_E * SKF_FIN_S) void k_skf_finish(con
     }
 }
 
-#define SP_DISPATCH_SKF(Lval, MACRO)                                                                  \
-    switch (Lval) {                                                                                   \
-        SP_CASE_P(32, MACRO) SP_CASE_P(64, MACRO) SP_CASE_P(128, MACRO) SP_CASE_P(256, MACRO)         \
-        SP_CASE_P(512, MACRO) SP_CASE_P(1024, MACRO) SP_CASE_P(2048, MACRO) SP_CASE_P(4096, MACRO)    \
-        default: return -1;                                                                           \
-    }
-
 int launch_skf(LaunchCtx c, const SkfArgs &a, bool cplx, int L, const cf *tw, int64_t runs, const SkfPlan &pl, float *partial) {
-    if (a.nframes < 1 || a.fpr < 1 || runs < 1 || runs > 0x7fffffff || (runs - 1) * a.fpr >= a.nframes || runs * a.fpr < a.nframes)
-        return -1;
-    if (a.nk < 2 || a.nk > SP_SKF_MAX_NK || a.nb < 1 || a.b0 < 0 || a.b0 >= L || a.nb > L || (!cplx && a.b0 + a.nb > L / 2 + 1)) return -1;
+    if (a.nframes < 1 || a.fpr < 1 || !runs_cover(a.nframes, a.fpr, runs)) return -1;
+    if (a.nk < 2 || a.nk > SP_SKF_MAX_NK || !band_in_transform(cplx, L, a.b0, a.nb)) return -1;
     if (pl.tiles < 1 || pl.tiles > 65535 || a.tile_bins != pl.tile_bins || a.stride != pl.stride || pl.tile_bins < 1 ||
         pl.stride < pl.tile_bins || (int64_t)pl.tiles * pl.tile_bins < a.nb || (int64_t)(pl.tiles - 1) * pl.tile_bins >= a.nb ||
-        pl.lds_bytes > SP_SKF_LDS_MAX || pl.lds_bytes != skf_image_bytes(cplx, L) + sizeof(float) * (size_t)a.nk * (size_t)pl.stride)
+        pl.lds_bytes > SP_LDS_MAX || pl.lds_bytes != skf_image_bytes(cplx, L) + sizeof(float) * (size_t)a.nk * (size_t)pl.stride)
         return -1;
     const XfTables tb{tw, nullptr, nullptr, L};
-#define L_(XT, CP)                                                                                    \
+#define L_(CP)                                                                                        \
     {                                                                                                 \
-        static_assert(XT::C::lds_bytes(CP ? 2 : 1) == (size_t)XT::C::FPW * (XT::L + 16) * 8 * (CP ? 2 : 1), "skf_image_bytes");             \
-        if (XT::C::FPW != fpw_of(L)) return -1;                                                       \
-        static size_t raised = 64 * 1024;                                                             \
-        if (pl.lds_bytes > raised) {                                                                  \
-            if (hipFuncSetAttribute((const void *)k_skf<XT, CP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SP_SKF_LDS_MAX) != hipSuccess) \
-                return -1;                                                                            \
-            raised = SP_SKF_LDS_MAX;                                                                  \
-        }                                                                                             \
+        if (lds_raise<k_skf<XT, CP>>(pl.lds_bytes)) return -1;                                        \
         hipLaunchKernelGGL((k_skf<XT, CP>), dim3((unsigned)runs, (unsigned)pl.tiles), dim3(XT::C::WG), pl.lds_bytes, c.stream, a, tb, partial); \
     }
-#define M_(XT)                                                                                        \
-    if (cplx) L_(XT, true) else L_(XT, false)
-    SP_DISPATCH_SKF(L, M_)
-#undef M_
+    return for_pow2<32, SP_SKF_MAX_L>(L, [&](auto x) {
+        using XT = typename decltype(x)::type;
+        if (cplx) L_(true) else L_(false)
+        return 0;
+    });
 #undef L_
-    return 0;
 }
 
 int launch_skf_finish(LaunchCtx c, const float *partial, int64_t runs, int nb, int nk, double mult, double *s_out) {

@@ -277,50 +277,35 @@ static __global__ __launch_bounds__(64 * SSQ_SUM_FRAMES) void k_ssq_sum(const cf
     }
 }
 
-#define SP_DISPATCH_SSQ(Lval, MACRO)                                                                  \
-    switch (Lval) {                                                                                   \
-        SP_CASE_P(32, MACRO) SP_CASE_P(64, MACRO) SP_CASE_P(128, MACRO) SP_CASE_P(256, MACRO)         \
-        SP_CASE_P(512, MACRO) SP_CASE_P(1024, MACRO) SP_CASE_P(2048, MACRO) SP_CASE_P(4096, MACRO)    \
-        SP_CASE_P(8192, MACRO)                                                                        \
-        default: return -1;                                                                           \
-    }
-
 int launch_ssq(LaunchCtx c, const SsqArgs &a, bool cplx, int L, const cf *tw, int64_t runs, int64_t rows, size_t lds_bytes) {
     const bool bands = a.out != nullptr;
-    if (a.nframes < 1 || a.fpr < 1 || runs < 1 || runs > 0x7fffffff || (runs - 1) * a.fpr >= a.nframes || runs * a.fpr < a.nframes) return -1;
+    if (a.nframes < 1 || a.fpr < 1 || !runs_cover(a.nframes, a.fpr, runs)) return -1;
     if (rows < 1 || rows > 65535 || a.hop < 1 || a.nsig < 1 || a.x_ld < a.nsig || !a.x || !a.h || !a.dh) return -1;
     if (bands) {
         if (a.nbands < 1 || a.nbands > SP_SSQ_MAX_BANDS || (a.per_frame && !a.edges) || a.T || a.P || a.IF || a.GD || a.th) return -1;
     } else {
         if (!a.T && !a.P && !a.IF && !a.GD) return -1;
         if ((a.IF || a.GD) && !a.th) return -1;
-        if (a.nb < 1 || a.b0 < 0 || a.b0 >= L || a.nb > L || (!cplx && a.b0 + a.nb > L / 2 + 1)) return -1;
+        if (!band_in_transform(cplx, L, a.b0, a.nb)) return -1;
     }
     const bool fields = !bands && a.th != nullptr;
-    if (lds_bytes > SP_SSQ_LDS_MAX || lds_bytes != ssq_lds_bytes(cplx, L, bands ? 0 : a.nb, a.T != nullptr, a.P != nullptr, fields)) return -1;
+    if (lds_bytes > SP_LDS_MAX || lds_bytes != ssq_lds_bytes(cplx, L, bands ? 0 : a.nb, a.T != nullptr, a.P != nullptr, fields)) return -1;
     const XfTables tb{tw, nullptr, nullptr, L};
-#define L_(XT, CP, MD)                                                                                \
+#define L_(CP, MD)                                                                                    \
     {                                                                                                 \
-        static_assert(XT::C::lds_bytes(1) == (size_t)XT::C::FPW * (XT::L + 16) * 8, "ssq_lds_bytes"); \
-        if (XT::C::FPW != fpw_of(L)) return -1;                                                       \
-        static size_t raised = 64 * 1024;                                                             \
-        if (lds_bytes > raised) {                                                                     \
-            if (hipFuncSetAttribute((const void *)k_ssq<XT, CP, MD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SP_SSQ_LDS_MAX) != hipSuccess) \
-                return -1;                                                                            \
-            raised = SP_SSQ_LDS_MAX;                                                                  \
-        }                                                                                             \
+        if (lds_raise<k_ssq<XT, CP, MD>>(lds_bytes)) return -1;                                       \
         hipLaunchKernelGGL((k_ssq<XT, CP, MD>), dim3((unsigned)runs, (unsigned)rows), dim3(XT::C::WG), lds_bytes, c.stream, a, tb); \
     }
-#define M_(XT)                                                                                        \
-    if (cplx) {                                                                                       \
-        if (bands) L_(XT, true, 1) else L_(XT, true, 0)                                               \
-    } else {                                                                                          \
-        if (bands) L_(XT, false, 1) else L_(XT, false, 0)                                             \
-    }
-    SP_DISPATCH_SSQ(L, M_)
-#undef M_
+    return for_pow2<32, SP_SSQ_MAX_L>(L, [&](auto x) {
+        using XT = typename decltype(x)::type;
+        if (cplx) {
+            if (bands) L_(true, 1) else L_(true, 0)
+        } else {
+            if (bands) L_(false, 1) else L_(false, 0)
+        }
+        return 0;
+    });
 #undef L_
-    return 0;
 }
 
 int launch_ssq_sum(LaunchCtx c, const cf *T, int64_t nframes, int nb, int n, int b0, int nbands, int per_frame, const float *edges,

@@ -125,17 +125,11 @@ int launch_upfirdn(LaunchCtx c, const void *x, bool cplx, int64_t x_ld, int64_t 
                    const float *taps, bool vec, int64_t m0, int64_t nout, void *out) {
     const int64_t tiles = (nout + g.K - 1) / g.K;
     if (batch < 1 || nsig < 1 || nout < 1 || m0 < 0 || x_ld < nsig || tiles > 0x7fffffff / batch) return -1;
-    if (g.lds > SP_UPF_LDS_MAX) return -1;
+    if (g.lds > SP_LDS_MAX) return -1;
     const dim3 grid((unsigned)(tiles * batch));
 #define L_(CP)                                                                                        \
     {                                                                                                 \
-        static bool raised = false;                   /* long filters and heavy decimation stage more than 64 KiB */ \
-        if (g.lds > 64 * 1024 && !raised) {                                                           \
-            if (hipFuncSetAttribute((const void *)k_upfirdn<CP>, hipFuncAttributeMaxDynamicSharedMemorySize,         \
-                                    (int)SP_UPF_LDS_MAX) != hipSuccess)                               \
-                return -1;                                                                            \
-            raised = true;                                                                            \
-        }                                                                                             \
+        if (lds_raise<k_upfirdn<CP>>(g.lds)) return -1;   /* long filters and heavy decimation stage more than 64 KiB */ \
         hipLaunchKernelGGL((k_upfirdn<CP>), grid, dim3(256), g.lds, c.stream, x, x_ld, nsig, m0, nout, tiles, g, taps, vec ? 1 : 0, \
                            out);                                                                      \
     }

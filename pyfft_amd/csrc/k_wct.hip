@@ -235,13 +235,6 @@ static __global__ __launch_bounds__(256) void k_wct_scale_any(const float4 *__re
     }
 }
 
-#define SP_DISPATCH_WCT(Lval, MACRO)                                                                  \
-    switch (Lval) {                                                                                   \
-        SP_CASE_P(256, MACRO) SP_CASE_P(512, MACRO) SP_CASE_P(1024, MACRO) SP_CASE_P(2048, MACRO)     \
-        SP_CASE_P(4096, MACRO) SP_CASE_P(8192, MACRO)                                                 \
-        default: return -1;                                                                           \
-    }
-
 int launch_wct_time(LaunchCtx c, const WctArgs &a, int L, const cf *tw, const CwtPlan &pl, int64_t rows) {
     if (a.nframes < 1 || a.S < 1 || a.chunk < 1 || a.M < 0 || a.hop != L - 2 * a.M || a.hop < 1 || rows < 1 || rows > 65535 ||
         pl.nchunks < 1 || pl.nchunks > 65535 || pl.blocks_x < 1 || pl.blocks_x > INT_MAX || (a.T == nullptr) == (a.Wxy == nullptr))
@@ -249,23 +242,18 @@ int launch_wct_time(LaunchCtx c, const WctArgs &a, int L, const cf *tw, const Cw
     const XfTables tb{tw, nullptr, nullptr, L};
     const dim3 grid((unsigned)pl.blocks_x, (unsigned)pl.nchunks, (unsigned)rows);
     const size_t lds = wct_lds_bytes(L);
-#define L_(XT, XW)                                                                                    \
+#define L_(XW)                                                                                        \
     {                                                                                                 \
-        if (lds !=sizeof(cf) * (size_t)XT::C::FPW * ((size_t)XT::C::LDS_PER + (wct_stash(XT::L) ? (size_t)XT::L : 0))) return -1; \
-        static bool raised = false;                                                                   \
-        if (lds > 64 * 1024 && !raised) {                                                             \
-            if (hipFuncSetAttribute((const void *)k_wct_time<XT, XW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-                return -1;                                                                            \
-            raised = true;                                                                            \
-        }                                                                                             \
+        if (lds_raise<k_wct_time<XT, XW>>(lds)) return -1;                                            \
         hipLaunchKernelGGL((k_wct_time<XT, XW>), grid, dim3(XT::C::WG), lds, c.stream, a, tb);        \
     }
-#define M_(XT)                                                                                        \
-    if (a.T == nullptr) L_(XT, true) else L_(XT, false)
-    SP_DISPATCH_WCT(L, M_)
-#undef M_
+    return for_pow2<SP_CWT_MIN_L, SP_CWT_MAX_L>(L, [&](auto x) {
+        using XT = typename decltype(x)::type;
+        if (lds != sizeof(cf) * (size_t)XT::C::FPW * ((size_t)XT::C::LDS_PER + (wct_stash(XT::L) ? (size_t)XT::L : 0))) return -1;
+        if (a.T == nullptr) L_(true) else L_(false)
+        return 0;
+    });
 #undef L_
-    return 0;
 }
 
 int launch_wct_scale(LaunchCtx c, const float4 *T, const float *taps, int ntaps, int S, int64_t N, int64_t rows, float *R2, float *phase,

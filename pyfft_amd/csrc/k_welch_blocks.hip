@@ -209,14 +209,6 @@ static __global__ __launch_bounds__(WB_SUM_WG) void k_block_sum(const float *__r
     }
 }
 
-#define SP_DISPATCH_WB(Lval, MACRO)                                                                   \
-    switch (Lval) {                                                                                   \
-        SP_CASE_P(32, MACRO) SP_CASE_P(64, MACRO) SP_CASE_P(128, MACRO) SP_CASE_P(256, MACRO)         \
-        SP_CASE_P(512, MACRO) SP_CASE_P(1024, MACRO) SP_CASE_P(2048, MACRO) SP_CASE_P(4096, MACRO)    \
-        SP_CASE_P(8192, MACRO)                                                                        \
-        default: return -1;                                                                           \
-    }
-
 int launch_welch_blocks(LaunchCtx c, const WelchBlocksArgs &a, bool cplx, int L, const cf *tw, int pairs, int64_t wgs) {
     const bool have_y = a.y != nullptr;
     if (a.q < 1 || a.rpt < 1 || a.runs < 1 || a.rstride < 1 || a.hop < 1 || a.nframes < 1 || pairs < 1 || pairs > 65535) return -1;
@@ -229,24 +221,21 @@ int launch_welch_blocks(LaunchCtx c, const WelchBlocksArgs &a, bool cplx, int L,
     if (!have_y && pairs != 1) return -1;
     const size_t lds = welch_blocks_lds_bytes(have_y, L);
     const XfTables tb{tw, nullptr, nullptr, L};
-#define L_(XT, CP, PR)                                                                                  \
+#define L_(CP, PR)                                                                                    \
     {                                                                                                 \
-        static_assert(XT::C::lds_bytes(PR ? 2 : 1) == (size_t)XT::C::FPW * (XT::L + 16) * 8 * (PR ? 2 : 1), "welch_blocks_lds_bytes"); \
-        if (XT::C::FPW != fpw_of(L)) return -1;                                                       \
-        static bool raised = false;                                                                   \
-        if (lds > 64 * 1024 && !raised) {                                                             \
-            if (hipFuncSetAttribute((const void *)k_welch_blocks<XT, CP, PR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-                return -1;                                                                            \
-            raised = true;                                                                            \
-        }                                                                                             \
+        if (lds_raise<k_welch_blocks<XT, CP, PR>>(lds)) return -1;                                    \
         hipLaunchKernelGGL((k_welch_blocks<XT, CP, PR>), dim3((unsigned)wgs, (unsigned)pairs, (unsigned)welch_blocks_bin_split(CP, PR, XT::L)), dim3(XT::C::WG), lds, c.stream, a, tb); \
     }
-#define M_(XT)                                                                                        \
-    if (cplx) { if (have_y) L_(XT, true, true) else L_(XT, true, false) } else { if (have_y) L_(XT, false, true) else L_(XT, false, false) }
-    SP_DISPATCH_WB(L, M_)
-#undef M_
+    return for_pow2<32, 8192>(L, [&](auto x) {
+        using XT = typename decltype(x)::type;
+        if (cplx) {
+            if (have_y) L_(true, true) else L_(true, false)
+        } else {
+            if (have_y) L_(false, true) else L_(false, false)
+        }
+        return 0;
+    });
 #undef L_
-    return 0;
 }
 
 int launch_block_sum(LaunchCtx c, const float *partial, int64_t runs, int planes, int nb, int64_t nblocks, int adv, int nsum, bool dbl,

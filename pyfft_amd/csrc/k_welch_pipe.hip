@@ -516,12 +516,7 @@ int launch_welch_pipe(LaunchCtx c, const void *x, bool cplx, const float *win, i
     const size_t lds = sizeof(cf) * 4 * (size_t)FftPlan<4096>::LDS_ELEMS;
 #define PIPE_(CP, S, OP)                                                                                  \
     {                                                                                                 \
-        static bool once = false;                                                                     \
-        if (!once) {                                                                                  \
-            if (hipFuncSetAttribute((const void *)k_welch_pipe<CP, S, OP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-                return -1;                                                                            \
-            once = true;                                                                              \
-        }                                                                                             \
+        if (lds_raise<k_welch_pipe<CP, S, OP>>(lds)) return -1;                                       \
         if (c.stop)                                                                                   \
             hipExtLaunchKernelGGL((k_welch_pipe<CP, S, OP>), dim3(rp.blocks, gy), dim3(768), lds, c.stream, nullptr, c.stop, 0, x, win, \
                                   nframes, rp.fpg, trend, xf.tb, partial, spartial, x_cs, gpr);       \

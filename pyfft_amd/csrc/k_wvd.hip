@@ -138,43 +138,26 @@ __global__ __launch_bounds__(X::C::WG) void k_wvd(WvdArgs a, XfTables tb) {
     }
 }
 
-#define SP_DISPATCH_WVD(Lval, MACRO)                                                                  \
-    switch (Lval) {                                                                                   \
-        SP_CASE_P(32, MACRO) SP_CASE_P(64, MACRO) SP_CASE_P(128, MACRO) SP_CASE_P(256, MACRO)         \
-        SP_CASE_P(512, MACRO) SP_CASE_P(1024, MACRO) SP_CASE_P(2048, MACRO) SP_CASE_P(4096, MACRO)    \
-        SP_CASE_P(8192, MACRO)                                                                        \
-        default: return -1;                                                                           \
-    }
-
 int launch_wvd(LaunchCtx c, const WvdArgs &a, int L, const cf *tw, int64_t runs, int64_t rows, size_t lds_bytes) {
     const bool cross = a.y != nullptr;
     const int nh = 2 * a.Lh + 1, ng = 2 * a.Lg + 1;
-    if (a.ntimes < 1 || a.cpr < 1 || a.cpr > a.ntimes || runs < 1 || runs > 0x7fffffff || (runs - 1) * a.cpr >= a.ntimes ||
-        runs * a.cpr < a.ntimes)
-        return -1;
+    if (a.ntimes < 1 || a.cpr < 1 || a.cpr > a.ntimes || !runs_cover(a.ntimes, a.cpr, runs)) return -1;
     if (rows < 1 || rows > 65535 || a.hop < 1 || a.nsig < 1 || a.x_ld < a.nsig || !a.x || !a.h || !a.g || !a.W) return -1;
     if (a.Lh < 0 || nh > L - 1 || a.Lg < 0 || ng > SP_WVD_MAX_NG || a.nb < 1 || a.nb > L || a.b0 < 0 || a.b0 >= L) return -1;
     if (a.hop > SP_WVD_MAX_SPAN / a.ntimes || a.first > SP_WVD_MAX_SPAN || a.first < -SP_WVD_MAX_SPAN) return -1;
-    if (lds_bytes > SP_WVD_LDS_MAX || lds_bytes != wvd_lds_bytes(cross, L, nh, ng, a.hop, a.cpr, a.ntimes)) return -1;
+    if (lds_bytes > SP_LDS_MAX || lds_bytes != wvd_lds_bytes(cross, L, nh, ng, a.hop, a.cpr, a.ntimes)) return -1;
     const XfTables tb{tw, nullptr, nullptr, L};
-#define L_(XT, CR)                                                                                    \
+#define L_(CR)                                                                                        \
     {                                                                                                 \
-        static_assert(XT::C::lds_bytes(1) == (size_t)XT::C::FPW * (XT::L + 16) * 8, "wvd_image_bytes"); \
-        if (XT::C::FPW != fpw_of(L)) return -1;                                                       \
-        static size_t raised = 64 * 1024;                                                             \
-        if (lds_bytes > raised) {                                                                     \
-            if (hipFuncSetAttribute((const void *)k_wvd<XT, CR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SP_WVD_LDS_MAX) != hipSuccess) \
-                return -1;                                                                            \
-            raised = SP_WVD_LDS_MAX;                                                                  \
-        }                                                                                             \
+        if (lds_raise<k_wvd<XT, CR>>(lds_bytes)) return -1;                                           \
         hipLaunchKernelGGL((k_wvd<XT, CR>), dim3((unsigned)runs, (unsigned)rows), dim3(XT::C::WG), lds_bytes, c.stream, a, tb); \
     }
-#define M_(XT)                                                                                        \
-    if (cross) L_(XT, true) else L_(XT, false)
-    SP_DISPATCH_WVD(L, M_)
-#undef M_
+    return for_pow2<32, SP_WVD_MAX_L>(L, [&](auto x) {
+        using XT = typename decltype(x)::type;
+        if (cross) L_(true) else L_(false)
+        return 0;
+    });
 #undef L_
-    return 0;
 }
 
 }   // namespace sp

@@ -19,27 +19,6 @@
 #include <type_traits>
 namespace sp {
 
-// sum of one value per thread over the T threads of a transform group, through the group's exchange image; every thread of the
-// workgroup must call it (barriers)
-template <class C> __device__ __forceinline__ cf xc_group_sum(cf s, cf *lds, int tid) {
-    static_assert(C::T >= 2, "a group of at least two threads");
-    __syncthreads();                      // the image may still be read by the previous transform
-    lds[tid] = s;
-    __syncthreads();
-    constexpr int W = C::T < 16 ? C::T : 16;
-    cf p = mk(0.f, 0.f);
-    if (tid < W) {
-        for (int j = tid; j < C::T; j += W) p = p + lds[j];
-    }
-    __syncthreads();
-    if (tid < W) lds[tid] = p;
-    __syncthreads();
-    cf tot = mk(0.f, 0.f);
-#pragma unroll 4                          // (all 16 reads in flight at once are 32 registers on top of a frame and the accumulators)
-    for (int j = 0; j < W; ++j) tot = tot + lds[j];
-    return tot;
-}
-
 // LDS plan.  Complex records from 2048 points: the first spectrum is parked in a second image (the stash) while the second is made -- 32
 // registers that cost a wave per SIMD at 2048 and spill at 8192.  At L = 8192 a workgroup is 512 threads, so a wave has 256 registers
 // and no AGPRs, and a complex frame, 16 complex accumulators and the transform's constants still do not fit: the first XCF_NLA
@@ -110,7 +89,7 @@ __global__ __launch_bounds__(X::C::WG) void k_xcorr_frames(XcfArgs a, int64_t fp
             cf sm = mk(0.f, 0.f);
 #pragma unroll
             for (int t = 0; t < C::R; ++t) sm = sm + (tq + C::T * t < nw ? 1.f : 0.f) * r[t];
-            return (1.f / (float)nw) * xc_group_sum<C>(sm, lds, tq);
+            return (1.f / (float)nw) * group_image_sum<C>(sm, lds, tq);
         };
         cf v[C::R];                       // real records: (a, b) packed; complex: a, then the cross spectrum
         float E;
@@ -132,7 +111,7 @@ __global__ __launch_bounds__(X::C::WG) void k_xcorr_frames(XcfArgs a, int64_t fp
                 v[t] = taper(tq + C::T * t) * v[t];
                 e = e + mk(v[t].x * v[t].x, v[t].y * v[t].y);
             }
-            e = xc_group_sum<C>(e, lds, tq);
+            e = group_image_sum<C>(e, lds, tq);
             E = sqrtf(e.x) * sqrtf(e.y);
             fwd_row(xf, v, lds, tid, n);
             __syncthreads();
@@ -175,7 +154,7 @@ __global__ __launch_bounds__(X::C::WG) void k_xcorr_frames(XcfArgs a, int64_t fp
             }
             cf u[C::R];
             const float ey = prep(yc, u);
-            const cf e = xc_group_sum<C>(mk(ex, ey), lds, tq);
+            const cf e = group_image_sum<C>(mk(ex, ey), lds, tq);
             E = sqrtf(e.x) * sqrtf(e.y);
             fwd_row(xf, u, lds, tid, n);
 #pragma unroll
@@ -282,35 +261,22 @@ static __global__ __launch_bounds__(XCF_FIN_E * XCF_FIN_S) void k_xcorr_frames_f
     }
 }
 
-#define SP_DISPATCH_XCF(Lval, MACRO)                                                                  \
-    switch (Lval) {                                                                                   \
-        SP_CASE_P(32, MACRO) SP_CASE_P(64, MACRO) SP_CASE_P(128, MACRO) SP_CASE_P(256, MACRO)         \
-        SP_CASE_P(512, MACRO) SP_CASE_P(1024, MACRO) SP_CASE_P(2048, MACRO) SP_CASE_P(4096, MACRO)    \
-        SP_CASE_P(8192, MACRO)                                                                        \
-        default: return -1;                                                                           \
-    }
-
 int launch_xcorr_frames(LaunchCtx c, const XcfArgs &a, bool cplx, int L, const cf *tw, const RunPart &rp, void *frames, void *partial,
                         float *peak) {
     if (a.nframes < 1 || a.nw < 2 || a.maxlag < 0 || a.maxlag > a.nw - 1 || (int64_t)a.nw + a.maxlag > L) return -1;
     const XfTables tb{tw, nullptr, nullptr, L};
-#define L_(XT, CP)                                                                                    \
+#define L_(CP)                                                                                        \
     {                                                                                                 \
-        const size_t lds = xcf_lds_bytes<XT::C>(CP, XT::L);                                           \
-        static bool raised = false;                                                                   \
-        if (lds > 64 * 1024 && !raised) {                                                             \
-            if (hipFuncSetAttribute((const void *)k_xcorr_frames<XT, CP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-                return -1;                                                                            \
-            raised = true;                                                                            \
-        }                                                                                             \
+        const size_t lds = xcf_lds_bytes<typename XT::C>(CP, XT::L);                                  \
+        if (lds_raise<k_xcorr_frames<XT, CP>>(lds)) return -1;                                        \
         hipLaunchKernelGGL((k_xcorr_frames<XT, CP>), dim3(rp.blocks), dim3(XT::C::WG), lds, c.stream, a, rp.fpg, tb, frames, partial, peak); \
     }
-#define M_(XT)                                                                                        \
-    if (cplx) L_(XT, true) else L_(XT, false)
-    SP_DISPATCH_XCF(L, M_)
-#undef M_
+    return for_pow2<32, 8192>(L, [&](auto x) {
+        using XT = typename decltype(x)::type;
+        if (cplx) L_(true) else L_(false)
+        return 0;
+    });
 #undef L_
-    return 0;
 }
 
 int launch_xcorr_frames_finish(LaunchCtx c, const void *partial, bool cplx, int64_t G, int L, int maxlag, int64_t nframes, double *avg) {

@@ -175,6 +175,27 @@ template <int W> __device__ __forceinline__ float group_lane_sum(float v) {
     }
 }
 
+// sum of one value per thread over the T threads of a transform group, through the group's exchange image (never across the wave);
+// every thread of the workgroup must call it (barriers)
+template <class C> __device__ __forceinline__ cf group_image_sum(cf s, cf *lds, int tid) {
+    static_assert(C::T >= 2, "a group of at least two threads");
+    __syncthreads();                      // the image may still be read by what came before (a transform, a round of binning)
+    lds[tid] = s;
+    __syncthreads();
+    constexpr int W = C::T < 16 ? C::T : 16;
+    cf p = mk(0.f, 0.f);
+    if (tid < W) {
+        for (int j = tid; j < C::T; j += W) p = p + lds[j];
+    }
+    __syncthreads();
+    if (tid < W) lds[tid] = p;
+    __syncthreads();
+    cf tot = mk(0.f, 0.f);
+#pragma unroll 4                          // (all 16 reads in flight at once are 32 registers on top of a frame and the accumulators)
+    for (int j = 0; j < W; ++j) tot = tot + lds[j];
+    return tot;
+}
+
 // detrend parameters of one signal: value removed at global sample index i is  m + s*i
 struct Trend {
     cf m, s;

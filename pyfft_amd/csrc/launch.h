@@ -57,9 +57,52 @@ struct Xf {
     bool blue;
 };
 
-inline int fpw_of(int L) {
+constexpr int fpw_of(int L) {
     const int R = L < 16 ? L : 16, T = L / R, WG = T >= 256 ? T : 256;
     return WG / T;
+}
+// LDS of `nbuf` transform images for each of a workgroup's groups: L + 16 complex per image
+constexpr size_t xf_image_bytes(int L, int nbuf = 1) { return (size_t)fpw_of(L) * (size_t)(L + 16) * 8 * nbuf; }
+template <int L> constexpr bool xf_image_agrees() {
+    if constexpr (L < 8192) {
+        if (!xf_image_agrees<2 * L>()) return false;
+    }
+    return WgCfg<L>::FPW == fpw_of(L) && WgCfg<L>::lds_bytes(1) == xf_image_bytes(L) && WgCfg<L>::lds_bytes(2) == xf_image_bytes(L, 2);
+}
+static_assert(xf_image_agrees<32>(), "fpw_of and xf_image_bytes are the kernels' FPW and lds_bytes at every L of 32 .. 8192");
+
+// The dynamic LDS a workgroup may take on gfx950, and the one place that lifts a kernel's limit to it: 0, or -1 where lds_bytes is
+// beyond SP_LDS_MAX or the runtime refuses.  Below 64 KiB nothing is asked.  The limit is only a cap: a launch occupies the lds_bytes
+// it passes.  The raise is remembered per instantiation for the life of the process, which assumes that the process is bound to one
+// device, as sp_init enforces; it outlives sp_shutdown, so an sp_init on another device afterwards finds the raise already recorded.
+#define SP_LDS_MAX ((size_t)160 * 1024)
+template <auto K> int lds_raise(size_t lds_bytes) {
+    static size_t raised = 64 * 1024;
+    if (lds_bytes <= raised) return 0;
+    if (lds_bytes > SP_LDS_MAX ||
+        hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SP_LDS_MAX) != hipSuccess)
+        return -1;
+    raised = SP_LDS_MAX;
+    return 0;
+}
+
+// f(XfTag<XfPow2<L>>{}) for a power of two L in LO .. HI, -1 outside: only the lengths of the range are instantiated
+template <class X> struct XfTag {
+    using type = X;
+};
+template <int LO, int HI, class F> int for_pow2(int L, F f) {
+    if (L == LO) return f(XfTag<XfPow2<LO>>{});
+    if constexpr (LO < HI) return for_pow2<2 * LO, HI>(L, f);
+    else return -1;
+}
+
+// `runs` runs of `per` consecutive items cover the n items, the last run not empty
+inline bool runs_cover(int64_t n, int64_t per, int64_t runs) {
+    return runs >= 1 && runs <= 0x7fffffff && (runs - 1) * per < n && runs * per >= n;
+}
+// the nb bins from b0 on lie inside an L-point spectrum: anywhere modulo L for complex records, within 0 .. L / 2 for real ones
+inline bool band_in_transform(bool cplx, int L, int b0, int nb) {
+    return nb >= 1 && b0 >= 0 && b0 < L && nb <= L && (cplx || b0 + nb <= L / 2 + 1);
 }
 
 // frames are dealt to transform groups in contiguous runs
@@ -370,7 +413,7 @@ int launch_zoom_acc_out(LaunchCtx c, const double *acc, int64_t m, double scale,
 // of the q; SG = the largest power of two <= min(q, 32), so that K q, the samples a tile consumes, stays between 2048 and 4096.
 #define SP_DDC_R 8
 #define SP_DDC_MAXQ 64
-#define SP_DDC_MAXTAPS 4095
+#define SP_DDC_MAXTAPS 4095        // with q <= SP_DDC_MAXQ: at most 90720 bytes of LDS (q = 63)
 struct DdcGeom {
     int q, ntaps;
     int sg, og_log2;   // phase groups; log2 of the 256 / sg output groups
@@ -412,14 +455,13 @@ int launch_ddc(LaunchCtx c, const void *x, bool cplx, int64_t x_ld, int64_t nsig
 // tile.  The items are dealt to a thread grid of OT x SG: an item thread owns the R outputs of its item over the taps p = s, s + SG, ..
 // of its slice s.  Few items (heavy decimation: up = 1, K small) leave room for many slices, many items run in several rounds.
 // K is chosen so that a tile consumes about max(4096, 2 P) samples, P = ceil(ntaps / up), at most SP_UPF_MAXK outputs, and so that the
-// LDS image stays within SP_UPF_LDS_MAX.
+// LDS image stays within SP_LDS_MAX.
 #ifndef SP_UPF_R           // -DSP_UPF_R=8 is the variant of profiles/resample_dropped_variants.txt
 #define SP_UPF_R 4
 #endif
 #define SP_UPF_MAXF 256
 #define SP_UPF_MAXTAPS 8191
 #define SP_UPF_MAXK 4096
-#define SP_UPF_LDS_MAX ((size_t)160 * 1024)
 struct UpfGeom {
     int up, down, ntaps;
     int P;             // taps per phase, ceil(ntaps / up)
@@ -459,7 +501,7 @@ inline UpfGeom upf_geom(int up, int down, int ntaps, bool cplx) {
         g.NI = g.P + (int)(((int64_t)(g.K - 1) * down) / up) + 2;
         g.xlen = (g.NI + 1) & ~1;                                                // even: what follows stays 8-byte aligned
         g.lds = es * (size_t)g.xlen + es * (size_t)g.sg * g.K + sizeof(float) * (size_t)up * g.pitch;
-        if (g.lds <= SP_UPF_LDS_MAX || ng == 1) break;
+        if (g.lds <= SP_LDS_MAX || ng == 1) break;
     }
     return g;
 }
@@ -487,10 +529,9 @@ int launch_pfb_finish(LaunchCtx c, const float *partial, int64_t G, int M, int n
 // scaled synthesis prototype [P M] on the device; y = [batch][nout] cf (cplx) or float.  fused: runs of fpg frames, each preceded by
 // `halo` frames that are only accumulated, overlap-added in an LDS ring of P M accumulators per group (v unused).  Not fused: fpg frames
 // per group, the inverse transforms go to v[batch][nframes][M] (cf, or float when !cplx; halo and y unused), and
-// launch_pfb_synth_gather sums every output sample from them.  SP_PFBS_LDS_MAX: the LDS one workgroup may take on gfx950 (160 KiB);
+// launch_pfb_synth_gather sums every output sample from them.
 // pfb_synth_groups: the groups of a workgroup that get a ring in the fused form (<= FPW; 0: not even one ring fits) and the LDS bytes
 // that takes (host only).
-#define SP_PFBS_LDS_MAX ((size_t)160 * 1024)
 int pfb_synth_groups(int M, int ntaps, bool cplx, size_t *lds_out);
 int launch_pfb_synth(LaunchCtx c, const cf *X, bool cplx, int64_t batch, int64_t nframes, const float *taps, int P, int hop,
                      int64_t first, int phase_ref, int r0, const Xf &xf, int64_t fpg, int halo, bool fused, int64_t nout, void *y,
@@ -520,7 +561,6 @@ int launch_xcorr_frames_finish(LaunchCtx c, const void *partial, bool cplx, int6
 // histogram lives in LDS behind the transform images, row j (one phase bin) `stride` floats long.  Grid: runs x tiles.
 // partial: float [runs][nk][nb] (phase-major like the tile, so that the tile leaves LDS and enters memory at unit stride), summed by
 // launch_skf_finish in float64 in ascending run order into s_out[nb][nk] * scale / nframes.
-#define SP_SKF_LDS_MAX ((size_t)160 * 1024)
 #define SP_SKF_MAX_L 4096
 #define SP_SKF_MAX_NK 1024
 struct SkfPlan {
@@ -528,11 +568,11 @@ struct SkfPlan {
     size_t lds_bytes;                   // transform images + histogram tile
 };
 // LDS of the transform images of one workgroup: max(1, 4096 / L) groups of L + 16 complex each, twice for complex records
-inline size_t skf_image_bytes(bool cplx, int L) { return (size_t)fpw_of(L) * (size_t)(L + 16) * 8 * (cplx ? 2 : 1); }
+inline size_t skf_image_bytes(bool cplx, int L) { return xf_image_bytes(L, cplx ? 2 : 1); }
 // cells_cap > 0: at most that many cells (nk x bins) per tile.  Rows are padded to a multiple of 32 floats (the bank of an LDS add is
 // its dword address mod 32, so the bank is the lane's bin whatever the phase bin); where not even 32 bins fit, 16, 8 .. 1.
 inline SkfPlan skf_plan_of(bool cplx, int L, int nb, int nk, int cells_cap) {
-    const int64_t room = (int64_t)(SP_SKF_LDS_MAX - skf_image_bytes(cplx, L)) / 4 / nk;      // floats per row
+    const int64_t room = (int64_t)(SP_LDS_MAX - skf_image_bytes(cplx, L)) / 4 / nk;      // floats per row
     int gran = 32;
     while (gran > 1 && room < gran) gran /= 2;
     int tb = (int)(room / gran) * gran;
@@ -577,7 +617,7 @@ inline int welch_blocks_teams(int L) { return L < 256 ? 256 / L : 1; }
 // a complex pair at 8192 points: the bins are split over two workgroups, each transforms the frames (registers; k_welch_blocks.hip)
 constexpr int welch_blocks_bin_split(bool cplx, bool pair, int L) { return cplx && pair && L >= 8192 ? 2 : 1; }
 // the transform images of a workgroup: two per group with y (X is parked while Y is made)
-inline size_t welch_blocks_lds_bytes(bool pair, int L) { return (size_t)fpw_of(L) * (size_t)(L + 16) * 8 * (pair ? 2 : 1); }
+inline size_t welch_blocks_lds_bytes(bool pair, int L) { return xf_image_bytes(L, pair ? 2 : 1); }
 // pairs = max(nch, 1); have_y = nch >= 1.  rpt: a team should run about four rounds of its groups, as long as that leaves the grid
 // about four workgroups per CU
 inline WelchBlocksPlan welch_blocks_plan_of(bool cplx, int L, int64_t nframes, int navg, int step, int nch, int ncu) {
@@ -622,7 +662,6 @@ int launch_block_sum(LaunchCtx c, const float *partial, int64_t runs, int planes
 // vectors v[batch][n][nvec] and the sweeps used; parallel cyclic Jacobi, one matrix per workgroup, A (and V, if nvec > 0) in LDS at the
 // padded order NP.  The grid walks the batch: at most workgroups-per-CU x CUs workgroups.
 #define SP_EIGH_MAX_N 64
-#define SP_EIGH_LDS_MAX ((size_t)160 * 1024)
 struct EighPlan {
     int NP, wg, wg_per_cu;
     size_t lds_bytes;
@@ -640,7 +679,7 @@ inline EighPlan eigh_plan_of(int n, bool vec, int64_t batch, int ncu, int grid_c
     p.NP = eigh_np_of(n);
     p.wg = eigh_wg_of(p.NP);
     p.lds_bytes = eigh_lds_bytes(p.NP, vec);
-    int per = (int)(SP_EIGH_LDS_MAX / p.lds_bytes);
+    int per = (int)(SP_LDS_MAX / p.lds_bytes);
     if (per > 2048 / p.wg) per = 2048 / p.wg;
     if (per > SP_EIGH_WAVES_PER_CU * 64 / p.wg) per = SP_EIGH_WAVES_PER_CU * 64 / p.wg;
     if (per > 16) per = 16;
@@ -743,7 +782,6 @@ int launch_wct_scale(LaunchCtx c, const float4 *T, const float *taps, int ntaps,
 // edges (lo, hi) per band by value or, per_frame, a device table float32 [nbands][nframes][2].
 // LDS of a workgroup: an image of L + 16 complex per transform and group, and behind them the groups' 64-bit accumulators: 16 bytes a
 // bin for T, 8 for P.
-#define SP_SSQ_LDS_MAX ((size_t)160 * 1024)
 #define SP_SSQ_MAX_L 8192
 #define SP_SSQ_MAX_BANDS 8
 struct SsqEdges {
@@ -766,7 +804,7 @@ struct SsqArgs {
 };
 inline int ssq_transforms(bool cplx, bool fields) { return (cplx ? 2 : 1) + (fields ? 1 : 0); }
 inline size_t ssq_lds_bytes(bool cplx, int L, int nb, bool wantT, bool wantP, bool fields) {
-    return (size_t)fpw_of(L) * ((size_t)ssq_transforms(cplx, fields) * (size_t)(L + 16) * 8 + (size_t)nb * ((wantT ? 16 : 0) + (wantP ? 8 : 0)));
+    return xf_image_bytes(L, ssq_transforms(cplx, fields)) + (size_t)fpw_of(L) * (size_t)nb * ((wantT ? 16 : 0) + (wantP ? 8 : 0));
 }
 // frames per run: about four workgroups per CU over runs x rows, whole rounds of the workgroup's groups; forced > 0: that many
 inline int64_t ssq_fpr(int L, int64_t nframes, int64_t rows, int ncu, int forced) {
@@ -789,7 +827,6 @@ int launch_ssq_sum(LaunchCtx c, const cf *T, int64_t nframes, int nb, int n, int
 // one transform whatever the runs are -- a run that starts or ends inside a pair forms the pair and stores its own column -- so the
 // staged columns are cpr rounded up to even; the partner of an odd last column is that column itself.  Cross: one transform per
 // column, y is read through the caches.  W: float [rows][ntimes][nb] (auto) or cf, the nb bins from b0 on modulo L.
-#define SP_WVD_LDS_MAX ((size_t)160 * 1024)
 #define SP_WVD_MAX_L 8192
 #define SP_WVD_MAX_NG 255
 #define SP_WVD_MAX_SPAN ((int64_t)1 << 40)
@@ -806,7 +843,7 @@ inline int64_t wvd_staged_cols(bool cross, int64_t cpr, int64_t ntimes) {
     const int64_t nc = cross ? cpr : cpr + (cpr & 1);
     return nc < ntimes ? nc : (ntimes > 1 ? ntimes : 1);
 }
-inline size_t wvd_image_bytes(int L) { return (size_t)fpw_of(L) * (size_t)(L + 16) * 8; }
+inline size_t wvd_image_bytes(int L) { return xf_image_bytes(L); }
 // images + 8 bytes per staged sample: (staged columns - 1) hop + 2 (Lh + Lg) + 1 of them
 inline size_t wvd_lds_bytes(bool cross, int L, int nh, int ng, int64_t hop, int64_t cpr, int64_t ntimes) {
     const int64_t nc = wvd_staged_cols(cross, cpr, ntimes);
@@ -823,7 +860,7 @@ inline int64_t wvd_cpr(bool cross, int L, int nh, int ng, int64_t hop, int64_t n
         int64_t want = (int64_t)ncu * 4 / (rows > 0 ? rows : 1);
         if (want < 1) want = 1;
         c = ((ntimes + want - 1) / want + per - 1) / per * per;
-        const int64_t room = (int64_t)((SP_WVD_LDS_MAX - wvd_image_bytes(L)) / 8) - ((nh - 1) + (ng - 1) + 1);
+        const int64_t room = (int64_t)((SP_LDS_MAX - wvd_image_bytes(L)) / 8) - ((nh - 1) + (ng - 1) + 1);
         if (room >= 0 && c > room / hop + 1) {
             c = room / hop + 1;
             if (!cross && c > 1) c &= ~(int64_t)1;

@@ -2721,7 +2721,7 @@ static bool upf_admits(int up, int down, int ntaps) {
 int sp_upfirdn_tile(int up, int down, int ntaps, int cplx) {
     if (!upf_admits(up, down, ntaps)) return 0;
     const UpfGeom geom = upf_geom(up, down, ntaps, cplx != 0);
-    return geom.lds <= SP_UPF_LDS_MAX ? geom.K : 0;
+    return geom.lds <= SP_LDS_MAX ? geom.K : 0;
 }
 
 int sp_upfirdn(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t batch, const float *h, int ntaps, int up, int down,
@@ -2739,7 +2739,7 @@ int sp_upfirdn(const void *x, int x_dtype, int64_t nsig, int64_t x_ld, int64_t b
                     (long long)nout, down);
     const bool cplx = x_dtype == SP_DTYPE_C64;
     const UpfGeom geom = upf_geom(up, down, ntaps, cplx);
-    if (geom.lds > SP_UPF_LDS_MAX)
+    if (geom.lds > SP_LDS_MAX)
         return fail("sp_upfirdn: up = %d, down = %d, ntaps = %d need %zu bytes of LDS", up, down, ntaps, geom.lds);
     if (batch > 0 && (nout + geom.K - 1) / geom.K > INT_MAX / batch)
         return fail("sp_upfirdn: %lld rows of %lld outputs are too many tiles for one launch", (long long)batch, (long long)nout);
@@ -2930,7 +2930,7 @@ int sp_pfb_synth(const void *X, int sided, int in_major, int64_t batch, int64_t 
         if (!strcmp(pv, "fused")) {
             if (ag < 1)
                 return fail("sp_pfb_synth: SP_PFBS_PATH=fused, but one ring of %d %s accumulators behind the %d-point exchange image "
-                            "is beyond the %zu bytes of LDS a workgroup may take", ntaps, cplx ? "complex" : "real", M, SP_PFBS_LDS_MAX);
+                            "is beyond the %zu bytes of LDS a workgroup may take", ntaps, cplx ? "complex" : "real", M, SP_LDS_MAX);
             fused = true;
         } else if (!strcmp(pv, "composed")) {
             fused = false;
@@ -3172,7 +3172,7 @@ static bool skf_shape_ok(int nfft, int nk) {
 
 int sp_skf_plan(int cplx, int nfft, int nb, int nk, int64_t *out) {
     if (!skf_shape_ok(nfft, nk) || !out) return -1;
-    if (nb < 1 || nb > (cplx ? nfft : nfft / 2 + 1)) return -1;
+    if (!band_in_transform(cplx != 0, nfft, 0, nb)) return -1;
     const SkfPlan p = skf_plan_of(cplx != 0, nfft, nb, nk, env_int("SP_SKF_CELLS", 0));
     out[0] = p.tiles;
     out[1] = p.tile_bins;
@@ -3190,7 +3190,7 @@ int sp_skf(const void *x, const void *y, int dtype, int64_t nsig, const float *w
     if (dtype != SP_DTYPE_F32 && dtype != SP_DTYPE_C64) return fail("sp_skf: dtype must be float32 or complex64, got %d", dtype);
     const bool cplx = dtype == SP_DTYPE_C64;
     if (nb < 1) return fail("sp_skf: the band needs at least one bin, got nb = %d", nb);
-    if (cplx ? (b0 < 0 || b0 >= nfft || nb > nfft) : (b0 < 0 || nb > nfft / 2 + 1 || b0 > nfft / 2 + 1 - nb))
+    if (!band_in_transform(cplx, nfft, b0, nb))
         return fail("sp_skf: the band of %d bins from %d lies outside the %d bins of the spectrum", nb, b0, cplx ? nfft : nfft / 2 + 1);
     if (hop < 1) return fail("sp_skf: hop must be at least 1");
     if (nframes < 1) return fail("sp_skf: nframes must be at least 1");
@@ -3629,15 +3629,12 @@ static const char *ssq_shape(int n, int hop, int64_t first, int64_t nframes, int
     if (!isfinite(rel) || rel < 0.0) return "rel must be finite and not negative";
     return nullptr;
 }
-static bool ssq_band_ok(bool cplx, int n, int b0, int nb) {
-    return nb >= 1 && b0 >= 0 && (cplx ? (b0 < n && nb <= n) : (nb <= n / 2 + 1 && b0 <= n / 2 + 1 - nb));
-}
 
 int sp_ssq_plan(int cplx, int n, int64_t nframes, int64_t batch, int nb, int what, int64_t out[5]) {
     if (n < 32 || n > SP_SSQ_MAX_L || !is_pow2(n) || nframes < 0 || batch < 0 || batch > 65535 || !out) return -1;
     const bool bands = what == 8;
     if (!bands && (what < 1 || what > 7)) return -1;
-    if (!bands && !ssq_band_ok(cplx != 0, n, 0, nb)) return -1;
+    if (!bands && !band_in_transform(cplx != 0, n, 0, nb)) return -1;
     const bool fields = !bands && (what & 4);
     const int64_t fpr = ssq_fpr(n, nframes, batch, g.ncu, env_int("SP_SSQ_FPG", 0));
     const size_t lds = ssq_lds_bytes(cplx != 0, n, bands ? 0 : nb, !bands && (what & 1), !bands && (what & 2), fields);
@@ -3645,7 +3642,7 @@ int sp_ssq_plan(int cplx, int n, int64_t nframes, int64_t batch, int nb, int wha
     out[1] = (nframes + fpr - 1) / fpr * batch;
     out[2] = (int64_t)lds;
     out[3] = ssq_transforms(cplx != 0, fields);
-    out[4] = lds <= SP_SSQ_LDS_MAX ? 1 : 0;
+    out[4] = lds <= SP_LDS_MAX ? 1 : 0;
     return 0;
 }
 
@@ -3690,12 +3687,12 @@ int sp_ssq(const void *x, int64_t x_ld, int dtype, int64_t nsig, int64_t batch, 
     const bool cplx = dtype == SP_DTYPE_C64, fields = IF || GD;
     if (!T && !P && !IF && !GD) return fail("sp_ssq: an output is required: T, P, IF or GD");
     if (fields && !th) return fail("sp_ssq: th is required with IF or GD");
-    if (!ssq_band_ok(cplx, n, b0, nb))
+    if (!band_in_transform(cplx, n, b0, nb))
         return fail("sp_ssq: nb = %d bins from b0 = %d lie outside the %d bins of the spectrum", nb, b0, cplx ? n : n / 2 + 1);
     const size_t lds = ssq_lds_bytes(cplx, n, nb, T != nullptr, P != nullptr, fields);
-    if (lds > SP_SSQ_LDS_MAX)
+    if (lds > SP_LDS_MAX)
         return fail("sp_ssq: the LDS of a workgroup, %zu bytes, does not fit %zu (n %d, nb %d): take a narrower band or fewer outputs", lds,
-                    SP_SSQ_LDS_MAX, n, nb);
+                    SP_LDS_MAX, n, nb);
     if (!h || !dh) return fail("sp_ssq: h and dh are required");
     if (batch == 0 || nframes == 0) return 0;
     if (!x) return fail("sp_ssq: x is required");
@@ -3756,7 +3753,7 @@ int sp_ssq_bands(const void *x, int64_t x_ld, int dtype, int64_t nsig, int64_t b
     if (const char *why = ssq_edges_why(nbands, edges, edges_t, scale)) return fail("sp_ssq_bands: %s (nbands %d)", why, nbands);
     const bool cplx = dtype == SP_DTYPE_C64;
     const size_t lds = ssq_lds_bytes(cplx, n, 0, false, false, false);
-    if (lds > SP_SSQ_LDS_MAX) return fail("sp_ssq_bands: the LDS of a workgroup, %zu bytes, does not fit %zu", lds, SP_SSQ_LDS_MAX);
+    if (lds > SP_LDS_MAX) return fail("sp_ssq_bands: the LDS of a workgroup, %zu bytes, does not fit %zu", lds, SP_LDS_MAX);
     if (!h || !dh) return fail("sp_ssq_bands: h and dh are required");
     if (!out) return fail("sp_ssq_bands: out is required");
     if (batch == 0 || nframes == 0) return 0;
@@ -3790,7 +3787,7 @@ int sp_ssq_sum(const void *T, int64_t nframes, int nb, int64_t batch, int n, int
     if (n < 32 || n > SP_SSQ_MAX_L || !is_pow2(n)) return fail("sp_ssq_sum: n = %d must be a power of two from 32 to 8192", n);
     if (nframes < 0) return fail("sp_ssq_sum: nframes must not be negative");
     if (batch < 0 || batch > 65535) return fail("sp_ssq_sum: batch must lie in 0 .. 65535");
-    if (!ssq_band_ok(true, n, b0, nb)) return fail("sp_ssq_sum: nb = %d bins from b0 = %d lie outside the %d bins of the spectrum", nb, b0, n);
+    if (!band_in_transform(true, n, b0, nb)) return fail("sp_ssq_sum: nb = %d bins from b0 = %d lie outside the %d bins of the spectrum", nb, b0, n);
     if (const char *why = ssq_edges_why(nbands, edges, edges_t, scale)) return fail("sp_ssq_sum: %s (nbands %d)", why, nbands);
     if (!out) return fail("sp_ssq_sum: out is required");
     if (batch == 0 || nframes == 0) return 0;
@@ -3839,7 +3836,7 @@ int sp_wvd_plan(int cross, int nfft, int nh, int ng, int64_t hop, int64_t ntimes
     out[1] = (ntimes + cpr - 1) / cpr * batch;
     out[2] = (int64_t)lds;
     out[3] = wvd_transforms_per_run(cross != 0, cpr);
-    out[4] = lds <= SP_WVD_LDS_MAX ? 1 : 0;
+    out[4] = lds <= SP_LDS_MAX ? 1 : 0;
     return 0;
 }
 
@@ -3860,9 +3857,9 @@ int sp_wvd(const void *x, const void *y, int64_t x_ld, int64_t nsig, int64_t bat
     const bool cross = y != nullptr;
     const int64_t cpr = wvd_cpr(cross, nfft, nh, ng, hop, ntimes, batch, g.ncu, env_int("SP_WVD_CPR", 0));
     const size_t lds = wvd_lds_bytes(cross, nfft, nh, ng, hop, cpr, ntimes);
-    if (lds > SP_WVD_LDS_MAX)
+    if (lds > SP_LDS_MAX)
         return fail("sp_wvd: the LDS of a workgroup, %zu bytes, does not fit %zu (nfft %d, nh %d, ng %d, hop %lld, %lld columns per run)",
-                    lds, SP_WVD_LDS_MAX, nfft, nh, ng, (long long)hop, (long long)cpr);
+                    lds, SP_LDS_MAX, nfft, nh, ng, (long long)hop, (long long)cpr);
     if (batch == 0 || ntimes == 0) return 0;
     const int64_t runs = (ntimes + cpr - 1) / cpr;
     if (runs > INT_MAX) return fail("sp_wvd: ntimes = %lld is too many runs for one launch", (long long)ntimes);
