@@ -56,3 +56,6 @@ from .reassign import (reassignment_windows, ssq_stft, issq_stft, squeezed_spect
                        ssq_extract, ssq_plan)
 from . import wigner as _wigner_mod                            # noqa: F401
 from .wigner import spwvd, pwvd, wvd, xwvd, wvd_plan           # noqa: F401
+from . import cyclic as _cyclic_mod                            # noqa: F401
+from .cyclic import (scd, cyclic_coherence, cyclic_spectra, cyclic_profile, alpha_grid, cyclic_level,   # noqa: F401
+                     cyclic_plan)

@@ -115,6 +115,12 @@ QUAD_SIGNATURES = {
     "sp_wvd_plan": (_i, [_i, _i, _i, _i, _i64, _i64, _i64, _i, _vp]),
 }
 
+# the fifth table: must list every symbol include/spectral_cyclo.h declares, and none of the other four
+CYCLO_SIGNATURES = {
+    "sp_cyclic": (_i, [_vp, _vp, _i, _i, _i64, _i64, _i64, _vp, _i, _i64, _i64, _i64, _vp, _i, _i, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _i]),
+    "sp_cyclic_plan": (_i, [_i, _i, _i, _i, _i64, _i64, _i, _i64, _vp]),
+}
+
 
 class SpectralError(RuntimeError):
     pass
@@ -129,7 +135,7 @@ def load_library():
         raise SpectralError("libspectral.so not found at %s -- run `make` (or __graft_entry__.build()); "
                             "pyfft_amd has no CPU fallback" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for table in (SIGNATURES, EXT_SIGNATURES, TFR_SIGNATURES, QUAD_SIGNATURES):
+    for table in (SIGNATURES, EXT_SIGNATURES, TFR_SIGNATURES, QUAD_SIGNATURES, CYCLO_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)      # AttributeError if the .so lacks a declared symbol
             fn.restype = res

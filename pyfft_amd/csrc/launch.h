@@ -31,7 +31,9 @@ namespace sp {
 //   SP_LONG_CHUNK_FRAMES (int: a cap on the frames per chunk of the long-segment paths, long_chunk_frames)
 //   SP_LONG_SLICE_ROWS (int: a cap on the rows per slice of a batch of long transforms, dev_fft_any and sp_czt)
 //   SP_CSDM_CHUNK_FRAMES (int: a cap on the frames per chunk of sp_csd_matrix, before the chunks are equalised)
-//   (the last three: unset or <= 0 leaves the budget alone; sp_last_passes reports the passes a call made)
+//   SP_CYCLIC_CHUNK (int: a cap on the cycle frequencies per pass of sp_cyclic, before its partials fill their budget)
+//   SP_CYCLIC_FPG (int: sp_cyclic's frames per group, so that a small shape walks the kernel's frame loop and its clamped tail)
+//   (the last four: unset or <= 0 leaves the budget alone; sp_last_passes reports the passes a call made)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
     return v && v[0] && v[0] != '0';
@@ -870,6 +872,71 @@ inline int64_t wvd_cpr(bool cross, int L, int nh, int ng, int64_t hop, int64_t n
 }
 inline int64_t wvd_transforms_per_run(bool cross, int64_t cpr) { return cross ? cpr : (cpr + 1) / 2; }
 int launch_wvd(LaunchCtx c, const WvdArgs &a, int L, const cf *tw, int64_t runs, int64_t rows, size_t lds_bytes);
+
+// spectral correlation by the averaged cyclic periodogram (k_cyclic.hip): for every nu_h of nuh[A] (nu / 2 in units of 2^-64 turn) the
+// frames g < nframes of every row (n = L samples from g hop on, absolute index first + g hop + j) under win[j] e(-+nu_h j), transformed
+// and summed over the frames of a group: partial[rows][A][groups][planes][L], planes 3 (mirror: |U|^2, Re, Im of sum p2 U[k] U[n - k])
+// or 4 (|U+|^2, |U-|^2, Re, Im of sum p2 U+ conj(U-)).  mirror: y = x and x' = conj(x) (or x real): one transform per (frame, alpha);
+// else two.  means: device float [rows][4] = mean of x (re, im), mean of y.  Grid: blocks x A workgroups x rows.
+#define SP_CYC_MAX_L 8192
+#define SP_CYC_MAX_A 65535
+#define SP_CYC_PARTIAL_BYTES ((size_t)256 << 20)
+// where a group keeps its rotated window: 0 registers; 1 (one transform, from 2048 points on) an LDS image; 2 (two transforms, from 512
+// points on) a slot of L complex per (row, alpha, group) in memory, gtab.  Images of L + 16 complex per transform group: the
+// exchange image, the window's (place 1), and in the two-transform form the parked Z-.
+constexpr int cyc_tab_place(int L, bool mirror) { return mirror ? (L < 2048 ? 0 : 1) : (L < 512 ? 0 : 2); }
+constexpr size_t cyc_lds_bytes(int L, bool mirror) {
+    return xf_image_bytes(L, 1 + (cyc_tab_place(L, mirror) == 1 ? 1 : 0) + (mirror ? 0 : 1));
+}
+struct CycArgs {
+    const void *x, *y;
+    int64_t x_ld, first, hop, nframes, fpg, groups, blocks;
+    const float *win;
+    const uint64_t *nuh;
+    const float *means;
+    int A, conj;
+    float *partial;
+    cf *gtab;           // place 2: [rows][A][groups][L]
+};
+struct CycPlan {
+    int64_t fpg, groups, used, blocks, apass, passes;
+    int planes, xforms;
+    size_t lds_bytes, cell_floats;      // cell_floats: scratch floats per (row, alpha, group): the partial planes and gtab's slot
+};
+// groups: (alpha, group) workgroups number about four per CU -- a scan of many alpha fills the device by itself and gets one block;
+// alpha per pass: what keeps the partials of a pass within SP_CYC_PARTIAL_BYTES, at least one (one alpha of every row is never cut);
+// chunk_force > 0 caps it, fpg_force > 0 sets the frames per group (test hooks)
+inline CycPlan cyc_plan_of(int L, int64_t nframes, int A, int64_t rows, bool mirror, int ncu, int chunk_force, int fpg_force = 0) {
+    CycPlan p;
+    const int fpw = fpw_of(L);
+    const int64_t cells = (int64_t)A * (rows > 0 ? rows : 1);
+    int64_t want = ((int64_t)4 * ncu + cells - 1) / cells;
+    if (want < 1) want = 1;
+    int64_t f = (nframes + want * fpw - 1) / (want * fpw);
+    if (f < 1) f = 1;
+    if (fpg_force > 0) f = fpg_force;
+    p.fpg = f;
+    p.used = nframes > 0 ? (nframes + f - 1) / f : 1;
+    p.blocks = (p.used + fpw - 1) / fpw;
+    p.groups = p.blocks * fpw;
+    p.planes = mirror ? 3 : 4;
+    p.xforms = mirror ? 1 : 2;
+    p.lds_bytes = cyc_lds_bytes(L, mirror);
+    p.cell_floats = (size_t)(p.planes + (cyc_tab_place(L, mirror) == 2 ? 2 : 0)) * (size_t)L;
+    const size_t per = sizeof(float) * (size_t)(rows > 0 ? rows : 1) * (size_t)p.groups * p.cell_floats;
+    int64_t ap = (int64_t)(SP_CYC_PARTIAL_BYTES / per);
+    if (ap < 1) ap = 1;
+    if (ap > A) ap = A;
+    if (chunk_force > 0 && chunk_force < ap) ap = chunk_force;
+    p.apass = ap;
+    p.passes = (A + ap - 1) / ap;
+    return p;
+}
+int launch_cyclic(LaunchCtx c, const CycArgs &a, bool mirror, bool cplx, int L, const cf *tw, int64_t rows);
+// out[(row a_total + a_off + ai) nb + jb] = scale * the float64 sum over the `used` groups, bin (b0 + jb) mod L; Pm of the mirrored
+// form is Pp at the mirrored bin.  Any of S, Pp, Pm may be null.
+int launch_cyclic_finish(LaunchCtx c, const float *partial, int64_t groups, int64_t used, int L, bool mirror, int A, int a_off,
+                         int a_total, int b0, int nb, double scale, int64_t rows, cf *S, float *Pp, float *Pm);
 
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;

@@ -3,6 +3,7 @@
 #include "../../include/spectral_ext.h"
 #include "../../include/spectral_tfr.h"
 #include "../../include/spectral_quad.h"
+#include "../../include/spectral_cyclo.h"
 #include "launch.h"
 #include "stage.h"
 #include "table_cache.h"
@@ -222,9 +223,9 @@ int get_xf(int64_t n, Xf *xf) {
 TableCache g_tables;
 
 // sp_last_passes: [0] the passes of the current call's outermost frame-chunk loop, [1] the most slice passes one
-// dev_fft_any / sp_czt loop made inside it.  Both are zeroed where a call begins (ApiLock), so that a test can assert
-// that the shape it chose really walks a loop past its first pass.
-int g_passes[2] = {0, 0};
+// dev_fft_any / sp_czt loop made inside it, [2] the passes over the cycle-frequency list of sp_cyclic.  All are zeroed where a
+// call begins (ApiLock), so that a test can assert that the shape it chose really walks a loop past its first pass.
+int g_passes[3] = {0, 0, 0};
 inline void note_slices(int64_t n) {
     if (n > g_passes[1]) g_passes[1] = (int)n;
 }
@@ -240,7 +241,7 @@ struct ApiLock {
     std::lock_guard<std::mutex> lk;
     ApiLock() : lk(g.mu) {
         g_tables.begin_call();
-        g_passes[0] = g_passes[1] = 0;
+        g_passes[0] = g_passes[1] = g_passes[2] = 0;
     }
 };
 
@@ -1324,7 +1325,7 @@ int sp_max_wg_fft(void) { return SP_MAX_WG_FFT; }
 const char *sp_last_error(void) { return g_err.c_str(); }
 int sp_last_passes(int which) {
     std::lock_guard<std::mutex> lk(g.mu);
-    return which == 0 || which == 1 ? g_passes[which] : 0;
+    return which >= 0 && which <= 2 ? g_passes[which] : 0;
 }
 
 int sp_init(int device_id) {
@@ -3900,6 +3901,125 @@ int sp_wvd(const void *x, const void *y, int64_t x_ld, int64_t nsig, int64_t bat
             return fail("sp_wvd: the launch was refused (nfft %d, nb %d, %lld columns, %lld rows)", nfft, nb, (long long)ntimes, (long long)batch);
         HIPCHK(hipGetLastError());
         g.last_kernel = "k_wvd";
+    }
+    return st.finish();
+}
+
+// ---- spectral correlation by the averaged cyclic periodogram (k_cyclic.hip; include/spectral_cyclo.h) ----------
+// the checks sp_cyclic and sp_cyclic_plan share; 0 or the message's tail
+static const char *cyclic_shape(int dtype, int n, int64_t hop, int64_t nframes, int A, int64_t batch) {
+    if (dtype != SP_DTYPE_F32 && dtype != SP_DTYPE_C64) return "x_dtype must be float32 or complex64";
+    if (n < 32 || n > SP_CYC_MAX_L || !is_pow2(n)) return "n must be a power of two from 32 to 8192";
+    if (hop < 1) return "hop must be at least 1";
+    if (nframes < 0) return "nframes must not be negative";
+    if (A < 1 || A > SP_CYC_MAX_A) return "A must lie in 1 .. 65535";
+    if (batch < 0 || batch > 65535) return "batch must lie in 0 .. 65535";
+    return nullptr;
+}
+static bool cyclic_mirror(int dtype, bool cross, int conj) { return !cross && (dtype == SP_DTYPE_F32 || conj != 0); }
+// nu / 2 to the nearest multiple of 2^-64 turn (ties to even), modulo one turn; |nu| <= 1
+static uint64_t cyclic_nuh(double nu) {
+    const double v = nearbyint(ldexp(nu * 0.5, 64));        // |v| <= 2^63, an integer
+    if (v >= 9223372036854775808.0 || v <= -9223372036854775808.0) return (uint64_t)1 << 63;      // +-1/2 turn
+    return (uint64_t)(int64_t)v;
+}
+
+int sp_cyclic_plan(int dtype, int cross, int conj, int n, int64_t hop, int64_t nframes, int A, int64_t batch, int64_t out[5]) {
+    if (!out || cyclic_shape(dtype, n, hop, nframes, A, batch)) return -1;
+    const CycPlan p = cyc_plan_of(n, nframes, A, batch, cyclic_mirror(dtype, cross != 0, conj), g.ncu, env_int("SP_CYCLIC_CHUNK", 0),
+                                   env_int("SP_CYCLIC_FPG", 0));
+    out[0] = p.fpg;
+    out[1] = p.blocks * A * batch;
+    out[2] = p.apass;
+    out[3] = p.passes;
+    out[4] = p.xforms;
+    return 0;
+}
+
+int sp_cyclic(const void *x, const void *y, int x_dtype, int y_dtype, int64_t x_ld, int64_t nsig, int64_t batch, const float *w, int n,
+              int64_t hop, int64_t nframes, int64_t first, const double *nu, int A, int conj, const double *mean_x, const double *mean_y,
+              int b0, int nb, double scale, void *S, void *Pp, void *Pm, int mem) {
+    // every refusal comes before the device is touched
+    if (const char *why = cyclic_shape(x_dtype, n, hop, nframes, A, batch))
+        return fail("sp_cyclic: %s (x_dtype %d, n %d, hop %lld, nframes %lld, A %d, batch %lld)", why, x_dtype, n, (long long)hop,
+                    (long long)nframes, A, (long long)batch);
+    if (y && y_dtype != x_dtype) return fail("sp_cyclic: y_dtype = %d differs from x_dtype = %d", y_dtype, x_dtype);
+    if (nsig < 1) return fail("sp_cyclic: nsig = %lld must be at least 1", (long long)nsig);
+    if (x_ld < nsig) return fail("sp_cyclic: x_ld = %lld is below nsig = %lld", (long long)x_ld, (long long)nsig);
+    if (nframes > 0 && (n > nsig || (nframes - 1) > (nsig - n) / hop))
+        return fail("sp_cyclic: nframes = %lld frames of n = %d at hop %lld reach outside the nsig = %lld samples of a row", (long long)nframes,
+                    n, (long long)hop, (long long)nsig);
+    if (first > ((int64_t)1 << 62) || first < -((int64_t)1 << 62)) return fail("sp_cyclic: first = %lld lies beyond +-2^62", (long long)first);
+    if (!band_in_transform(true, n, b0, nb)) return fail("sp_cyclic: the band of nb = %d bins from b0 = %d lies outside the n = %d bins", nb, b0, n);
+    if (!isfinite(scale)) return fail("sp_cyclic: scale must be finite");
+    if (!x) return fail("sp_cyclic: x is required");
+    if (!w) return fail("sp_cyclic: w is required");
+    if (!nu) return fail("sp_cyclic: nu is required");
+    if (!S && !Pp && !Pm) return fail("sp_cyclic: no output: one of S, Pp and Pm is required");
+    for (int a = 0; a < A; ++a)
+        if (!isfinite(nu[a]) || fabs(nu[a]) > 1.0) return fail("sp_cyclic: nu[%d] = %g must be finite and lie in -1 .. 1", a, nu[a]);
+    const bool cross = y != nullptr, cplx = x_dtype == SP_DTYPE_C64, mirror = cyclic_mirror(x_dtype, cross, conj);
+    for (int64_t b = 0; b < batch; ++b)
+        for (int c = 0; c < 2; ++c)
+            if ((mean_x && !isfinite(mean_x[2 * b + c])) || (cross && mean_y && !isfinite(mean_y[2 * b + c])))
+                return fail("sp_cyclic: mean_x and mean_y must be finite (row %lld)", (long long)b);
+    if (batch == 0 || nframes == 0) return 0;
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const CycPlan p = cyc_plan_of(n, nframes, A, batch, mirror, g.ncu, env_int("SP_CYCLIC_CHUNK", 0), env_int("SP_CYCLIC_FPG", 0));
+    CycArgs a{};
+    Stage st(mem);
+    const size_t es = cplx ? sizeof(cf) : sizeof(float);
+    const size_t x_elems = (size_t)((batch - 1) * x_ld + nsig), o_elems = (size_t)batch * (size_t)A * (size_t)nb;
+    cf *S_d;
+    float *Pp_d, *Pm_d;
+    st.in(g.in0, x, es * x_elems, &a.x);
+    st.in(g.in1, y, es * x_elems, &a.y);
+    st.out(g.out0, S, sizeof(cf) * o_elems, &S_d);
+    st.out(g.out0, Pp, sizeof(float) * o_elems, &Pp_d);
+    st.out(g.out0, Pm, sizeof(float) * o_elems, &Pm_d);
+    if (st.commit()) return -1;
+    if (!cross) a.y = a.x;
+    // small tables: the window, the phases nu / 2 in 2^-64 turns, the means as float32 (x, then y; auto: y = x)
+    std::vector<uint64_t> nuh((size_t)A);
+    for (int i = 0; i < A; ++i) nuh[(size_t)i] = cyclic_nuh(nu[i]);
+    std::vector<float> mh((size_t)batch * 4, 0.f);
+    for (int64_t b = 0; b < batch; ++b)
+        for (int c = 0; c < 2; ++c) {
+            const float mx = mean_x ? (float)mean_x[2 * b + c] : 0.f;
+            mh[(size_t)(4 * b + c)] = mx;
+            mh[(size_t)(4 * b + 2 + c)] = cross ? (mean_y ? (float)mean_y[2 * b + c] : 0.f) : mx;
+        }
+    void *w_d = nullptr, *nu_d = nullptr, *m_d = nullptr;
+    const cf *tw;
+    if (get_table(1, w, sizeof(float) * (size_t)n, &w_d, nullptr)) return -1;
+    if (get_table(24, nuh.data(), sizeof(uint64_t) * (size_t)A, &nu_d, nullptr)) return -1;
+    if (get_table(25, mh.data(), sizeof(float) * mh.size(), &m_d, nullptr)) return -1;
+    if (get_twiddles(n, &tw)) return -1;
+    const size_t cells = (size_t)batch * (size_t)p.apass * (size_t)p.groups;
+    if (g.work.ensure(sizeof(float) * cells * p.cell_floats)) return -1;
+    a.x_ld = x_ld;
+    a.first = first;
+    a.hop = hop;
+    a.nframes = nframes;
+    a.fpg = p.fpg;
+    a.groups = p.groups;
+    a.blocks = p.blocks;
+    a.win = (const float *)w_d;
+    a.means = (const float *)m_d;
+    a.conj = conj ? 1 : 0;
+    a.partial = (float *)g.work.p;
+    a.gtab = (cf *)(a.partial + cells * (size_t)p.planes * (size_t)n);
+    for (int a0 = 0; a0 < A; a0 += (int)p.apass, ++g_passes[2]) {
+        a.A = (int)std::min<int64_t>(p.apass, A - a0);
+        a.nuh = (const uint64_t *)nu_d + a0;
+        ProfScope ps;
+        if (launch_cyclic(lc(), a, mirror, cplx, n, tw, batch) != 0)
+            return fail("sp_cyclic: the launch was refused (n %d, %d cycle frequencies, %lld frames, %lld rows)", n, a.A, (long long)nframes,
+                        (long long)batch);
+        HIPCHK(hipGetLastError());
+        LAUNCHCHK(launch_cyclic_finish(lc(), a.partial, p.groups, p.used, n, mirror, a.A, a0, A, b0, nb, scale, batch, S_d, Pp_d, Pm_d));
+        g.last_kernel = "k_cyclic";
     }
     return st.finish();
 }

@@ -185,7 +185,8 @@ def max_wg_fft():
 
 def last_passes(which=0):
     """Passes the last call's loops made: which=0 its outermost frame-chunk loop, which=1 the most slice passes of one batch of
-    long transforms inside it; 0 where the call had no such loop (sp_last_passes)."""
+    long transforms inside it, which=2 (CYC_PASSES) the passes of `cyclic` over its list of cycle frequencies; 0 where the call had no
+    such loop (sp_last_passes)."""
     return int(lib().sp_last_passes(int(which)))
 
 
@@ -1505,6 +1506,127 @@ def wvd_plan(nfft, nh, ng, hop, ntimes, rows=1, cross=False, nb=None):
     nb = nfft if nb is None else int(nb)
     wvd_check("wvd_plan", nfft, nh, ng, hop, ntimes, rows, nb)
     return _wvd_plan_raw("wvd_plan", cross, nfft, nh, ng, hop, ntimes, rows, nb)
+
+
+CYC_MIN_N, CYC_MAX_N, CYC_MAX_A, CYC_MAX_ROWS, CYC_PASSES = 32, 8192, 65535, 65535, 2
+
+
+class CyclicRefused(ValueError, NotImplementedError):
+    """A shape the cyclic-periodogram kernel does not take: outside the limits, and what is not built (segments that are no power of
+    two or longer than one workgroup's transform)."""
+
+
+def cyclic_check(who, n, hop, nframes, A, rows, nsig=None, x_ld=None, nu=None, b0=0, nb=None, scale=1.0, first=0):
+    """The refusals of sp_cyclic and sp_cyclic_plan, before the library is touched."""
+    if n < CYC_MIN_N or n > CYC_MAX_N or n & (n - 1):
+        raise CyclicRefused("%s: n = %d must be a power of two from %d to %d" % (who, n, CYC_MIN_N, CYC_MAX_N))
+    if hop < 1:
+        raise CyclicRefused("%s: hop = %d must be at least 1" % (who, hop))
+    if nframes < 0:
+        raise CyclicRefused("%s: nframes = %d must not be negative" % (who, nframes))
+    if A < 1 or A > CYC_MAX_A:
+        raise CyclicRefused("%s: %d cycle frequencies are outside 1 .. %d" % (who, A, CYC_MAX_A))
+    if rows < 0 or rows > CYC_MAX_ROWS:
+        raise CyclicRefused("%s: %d rows are outside 0 .. %d" % (who, rows, CYC_MAX_ROWS))
+    if nsig is not None:
+        if nsig < 1:
+            raise CyclicRefused("%s: the rows must hold at least one sample" % who)
+        if nframes > 0 and (nframes - 1) * hop + n > nsig:
+            raise CyclicRefused("%s: %d frames of %d at hop %d reach outside the %d samples of a row" % (who, nframes, n, hop, nsig))
+    if x_ld is not None and x_ld < nsig:
+        raise CyclicRefused("%s: x_ld = %d is below nsig = %d" % (who, x_ld, nsig))
+    if nu is not None and not (np.all(np.isfinite(nu)) and np.all(np.abs(nu) <= 1.0)):
+        raise CyclicRefused("%s: every nu must be finite and lie in -1 .. 1 cycles per sample" % who)
+    nb = n if nb is None else nb
+    if nb < 1 or nb > n or b0 < 0 or b0 >= n:
+        raise CyclicRefused("%s: the band of nb = %d bins from b0 = %d lies outside the n = %d bins" % (who, nb, b0, n))
+    if not np.isfinite(scale):
+        raise CyclicRefused("%s: scale must be finite" % who)
+    if abs(first) > 1 << 62:
+        raise CyclicRefused("%s: first = %d lies beyond +-2^62" % (who, first))
+
+
+def _cyclic_plan_raw(who, cplx, cross, conj, n, hop, nframes, A, rows):
+    out = np.zeros(5, dtype=np.int64)
+    if lib().sp_cyclic_plan(_ffi.DTYPE_C64 if cplx else _ffi.DTYPE_F32, 1 if cross else 0, 1 if conj else 0, n, hop, nframes, A, rows,
+                            ptr(out)) != 0:
+        raise CyclicRefused("%s: the shape is refused" % who)
+    return dict(zip(("fpg", "workgroups", "alpha_per_pass", "passes", "transforms"), (int(v) for v in out)))
+
+
+def cyclic(x, win, hop, nframes, nu, y=None, conj=False, first=0, detrend=True, mean_value=None, b0=0, nb=None, scale=1.0, S=True,
+           Pp=True, Pm=True):
+    """Spectral correlation along the last axis by the averaged cyclic periodogram (sp_cyclic): for every nu (cycles per sample) the
+    frames g < nframes of win.size samples at g*hop, Z+ = DFT(win (y - m_y) e(-nu/2 t)), Z- = DFT(win (x' - m_x') e(+nu/2 t)) with
+    t = first + the sample's index and x' = conj(x) when conj, and S = scale sum_g Z+ conj(Z-), Pp = scale sum_g |Z+|^2,
+    Pm = scale sum_g |Z-|^2 at the nb bins from b0 on (modulo n, two-sided fft order).  y None: y = x.  Returns (S, Pp, Pm):
+    complex64, float32, float32 [..., A, nb], None for the ones not asked for.  detrend: True removes each row's mean (computed on the
+    device), mean_value a given constant, False nothing.  numpy in -> numpy out; device tensors in -> device tensors on x's stream."""
+    hop, nframes, first, b0, scale = int(hop), int(nframes), int(first), int(b0), float(scale)
+    w = _win32(win)
+    n = int(w.size)
+    nuv = np.atleast_1d(np.ascontiguousarray(np.asarray(nu), dtype=np.float64))
+    md = _mode(x)
+    x = md.checked(x)
+    if x.ndim < 1 or w.ndim != 1 or nuv.ndim != 1:
+        raise CyclicRefused("cyclic: x needs at least one axis, win and nu exactly one")
+    if not np.all(np.isfinite(w)):
+        raise CyclicRefused("cyclic: the window must be finite")
+    lead = tuple(int(d) for d in x.shape[:-1])
+    rows = 1
+    for d in lead:
+        rows *= d
+    nsig, A = int(x.shape[-1]), int(nuv.size)
+    nb = n if nb is None else int(nb)
+    cyclic_check("cyclic", n, hop, nframes, A, rows, nsig, None, nuv, b0, nb, scale, first)
+    if not (S or Pp or Pm):
+        raise CyclicRefused("cyclic: no output is asked for")
+    cross = y is not None
+    if cross:
+        if _mode(y) is not md:
+            raise TypeError("cyclic: x and y must both be numpy arrays or both device tensors")
+        y = md.checked(y)
+        if tuple(y.shape) != tuple(x.shape) or not md.alike(x, y):
+            raise CyclicRefused("cyclic: y must share x's shape, %s" % md.ALIKE)
+    md.bind(x)
+    xs, xld = md.rows(x.reshape(rows, nsig) if md.dev and x.ndim != 2 else x)
+    ys = None
+    if cross:
+        ys, yld = md.rows(y.reshape(rows, nsig) if md.dev and y.ndim != 2 else y)
+        if yld != xld:
+            xs, ys = md.samples(xs), md.samples(ys)
+            xld = nsig
+    cplx = md.code(xs) == _ffi.DTYPE_C64
+    outs = [md.empty(lead + (A, nb), dt, xs) if want else None for want, dt in ((S, "complex64"), (Pp, "float32"), (Pm, "float32"))]
+    if nframes == 0:                        # a sum over no frames: the library launches nothing and leaves the outputs as they are
+        for o in outs:
+            if o is not None:
+                o[...] = 0
+        return tuple(outs)
+    means = []
+    for v in (xs, ys):
+        m = np.zeros((max(rows, 1), 2), dtype=np.float64)
+        if v is not None and detrend not in (None, False, 0, "none"):
+            if mean_value is not None:
+                m[:] = (complex(mean_value).real, complex(mean_value).imag)
+            else:
+                v2 = v if md.dev else v.reshape(rows, nsig)        # the existing mean pass (sp_mean), row by row
+                for r in range(rows):
+                    mv = complex(mean(v2[r, :nsig]))
+                    m[r] = (mv.real, mv.imag)
+        means.append(m)
+    md.call(lib().sp_cyclic, md.addr(xs), md.addr(ys), md.code(xs), md.code(ys) if cross else md.code(xs), xld, nsig, rows, ptr(w), n, hop,
+            nframes, first, ptr(nuv), A, 1 if conj else 0, ptr(means[0]), ptr(means[1]) if cross else None, b0, nb, scale,
+            md.addr(outs[0]), md.addr(outs[1]), md.addr(outs[2]))
+    return tuple(outs)
+
+
+def cyclic_plan(n, hop, nframes, A, rows=1, cplx=False, cross=False, conj=False):
+    """sp_cyclic_plan as a dict (host only): fpg (frames per group), workgroups (over all passes), alpha_per_pass, passes,
+    transforms (per frame and cycle frequency: 1 in the mirrored form, else 2)."""
+    n, hop, nframes, A, rows = int(n), int(hop), int(nframes), int(A), int(rows)
+    cyclic_check("cyclic_plan", n, hop, nframes, A, rows)
+    return _cyclic_plan_raw("cyclic_plan", cplx, cross, conj, n, hop, nframes, A, rows)
 
 
 EIGH_MAX_N = 64
