@@ -54,7 +54,9 @@ int sp_wct_plan(int64_t nsig, int nscales, int64_t batch, int L, int Mw, int Mg,
  *      sp_csd_matrix and sp_bispectrum at every length) and batches of long transforms into slices of rows (sp_fft_c2c, sp_czt and
  *      every transform inside a frame chunk).  which = 0: the passes the outermost frame-chunk loop of the last API call made;
  *      which = 1: the most slice passes one batch of long transforms made inside it; which = 2: the passes sp_cyclic
- *      (spectral_cyclo.h) made over its list of cycle frequencies.  0 where the call had no such loop, or for another `which`.
+ *      (spectral_cyclo.h) made over its list of cycle frequencies; which = 3: the passes sp_lomb and sp_lomb_sums
+ *      (spectral_uneven.h) made over their list of frequencies; which = 4: the most launches the row groups of one such pass
+ *      were dealt to.  0 where the call had no such loop, or for another `which`.
  *      All are reset where a call that touches the device begins.  The budgets behind the loops can be capped
  *      through the environment, read on every call (unset or <= 0: no cap): SP_LONG_CHUNK_FRAMES (frames of a long chunk),
  *      SP_LONG_SLICE_ROWS (rows of a slice), SP_CSDM_CHUNK_FRAMES (frames of a chunk of sp_csd_matrix, before its chunks are

@@ -59,3 +59,5 @@ from .wigner import spwvd, pwvd, wvd, xwvd, wvd_plan           # noqa: F401
 from . import cyclic as _cyclic_mod                            # noqa: F401
 from .cyclic import (scd, cyclic_coherence, cyclic_spectra, cyclic_profile, alpha_grid, cyclic_level,   # noqa: F401
                      cyclic_plan)
+from . import lomb as _lomb_mod                                # noqa: F401
+from .lomb import lombscargle, ls_periodogram, ls_window, ls_grid, ls_level, ls_plan     # noqa: F401

@@ -121,6 +121,14 @@ CYCLO_SIGNATURES = {
     "sp_cyclic_plan": (_i, [_i, _i, _i, _i, _i64, _i64, _i, _i64, _vp]),
 }
 
+# the sixth table: must list every symbol include/spectral_uneven.h declares, and none of the other five
+UNEVEN_SIGNATURES = {
+    "sp_lomb": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _d, _vp, _i64, _vp, _i, _i, _vp, _i]),
+    "sp_lomb_sums": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _d, _d, _vp, _i64, _vp, _vp, _vp, _vp, _i]),
+    "sp_lomb_finish": (_i, [_vp, _vp, _vp, _i64, _i64, _d, _vp, _i64, _vp, _i, _i, _vp, _i]),
+    "sp_lomb_plan": (_i, [_i64, _i64, _i64, _vp]),
+}
+
 
 class SpectralError(RuntimeError):
     pass
@@ -135,7 +143,7 @@ def load_library():
         raise SpectralError("libspectral.so not found at %s -- run `make` (or __graft_entry__.build()); "
                             "pyfft_amd has no CPU fallback" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for table in (SIGNATURES, EXT_SIGNATURES, TFR_SIGNATURES, QUAD_SIGNATURES, CYCLO_SIGNATURES):
+    for table in (SIGNATURES, EXT_SIGNATURES, TFR_SIGNATURES, QUAD_SIGNATURES, CYCLO_SIGNATURES, UNEVEN_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)      # AttributeError if the .so lacks a declared symbol
             fn.restype = res

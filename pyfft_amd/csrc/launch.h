@@ -33,7 +33,9 @@ namespace sp {
 //   SP_CSDM_CHUNK_FRAMES (int: a cap on the frames per chunk of sp_csd_matrix, before the chunks are equalised)
 //   SP_CYCLIC_CHUNK (int: a cap on the cycle frequencies per pass of sp_cyclic, before its partials fill their budget)
 //   SP_CYCLIC_FPG (int: sp_cyclic's frames per group, so that a small shape walks the kernel's frame loop and its clamped tail)
-//   (the last four: unset or <= 0 leaves the budget alone; sp_last_passes reports the passes a call made)
+//   SP_LOMB_FREQS (int: a cap on the frequencies per pass of sp_lomb / sp_lomb_sums, before the partials fill their budget)
+//   SP_LOMB_SPLIT (int: the sample runs sp_lomb deals a record into, so that a small record walks the sum over the runs)
+//   (the last six: unset or <= 0 leaves the budget alone; sp_last_passes reports the passes a call made)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
     return v && v[0] && v[0] != '0';
@@ -937,6 +939,105 @@ int launch_cyclic(LaunchCtx c, const CycArgs &a, bool mirror, bool cplx, int L, 
 // form is Pp at the mirrored bin.  Any of S, Pp, Pm may be null.
 int launch_cyclic_finish(LaunchCtx c, const float *partial, int64_t groups, int64_t used, int L, bool mirror, int A, int a_off,
                          int a_total, int b0, int nb, double scale, int64_t rows, cf *S, float *Pp, float *Pm);
+
+// Lomb-Scargle sums of an unevenly sampled record (k_lomb.hip).  With e(p) = exp(2 pi i p), phi = f (t - t_ref), the normalised
+// weights wn = w / wnorm and d_r = y_r - m_r, per frequency
+//   A1 = sum w32 e(phi),  A2 = sum w32 e(2 phi),  B_r = sum wy32_r e(phi);    w32 = float32(wn), wy32_r = float32(wn d_r)
+// and per row the totals W = sum w32, Y'_r = sum wy32_r, YY'_r = sum wy32_r d_r (float64 sums of the float32 values).
+// The prepared record: head[npad] = (t - t_ref as float64, w32, 0) and wy[groups][npad][RP] floats, RP = the rows of a group padded
+// to 4 or 8; samples from N on and rows from batch on are zeros, npad = N rounded up to 4, plus LOMB_SUB, so that no piece of a run
+// is loaded from outside the arrays.
+#define LOMB_SUB 256                      // samples of a sub-run: float32 sums inside it, float64 across; also the staged piece
+#define LOMB_WG 256                       // frequencies of a workgroup: one per lane
+#define LOMB_MAX_M (1 << 24)
+#define LOMB_PARTIAL_BYTES ((size_t)256 << 20)
+#define LOMB_PREP_BLOCKS 64               // at most so many blocks along the samples in the two prep stages
+#define LOMB_PREP_COLS 32768              // at most so many columns of the prepared record in one launch of k_lomb_prep
+struct LombHead {
+    double t;
+    float w, pad;
+};
+constexpr int lomb_rp(int R) { return R == 0 ? 0 : (R <= 4 ? 4 : 8); }
+constexpr int lomb_nv(int R) { return 4 + 2 * R; }
+inline int64_t lomb_npad(int64_t N) { return (N + 3) / 4 * 4 + LOMB_SUB; }
+struct LombPlan {
+    int R, RP, nv;                        // rows of a group (0: no rows, the window sums alone), their padded count, sums per frequency
+    int64_t groups, gpl;                  // row groups; groups per launch
+    int64_t fpass, passes;                // frequencies per pass, passes over the list
+    int64_t split, run_len;               // sample runs and the samples of one (a multiple of 4)
+    int64_t workgroups;                   // over all passes and launches
+    int64_t prep_blocks, prep_len;        // the prep stages' blocks along the samples and the samples of one
+};
+// split: (tile, group) workgroups number about four per CU, a run is no shorter than four sub-runs; frequencies per pass: what keeps
+// the partials [groups of a launch][split][nv][fpass] of float64 within LOMB_PARTIAL_BYTES, whole tiles, at least one; where even
+// one tile of all groups does not fit, the groups are dealt to several launches.  freqs_force > 0 caps the frequencies per pass
+// at any figure, split_force > 0 sets the runs (test hooks).
+inline LombPlan lomb_plan_of(int64_t N, int64_t M, int64_t batch, int ncu, int freqs_force, int split_force) {
+    LombPlan p;
+    p.R = batch <= 0 ? 0 : (batch == 1 ? 1 : (batch <= 4 ? 4 : 8));
+    p.RP = lomb_rp(p.R);
+    p.nv = lomb_nv(p.R);
+    p.groups = p.R ? (batch + p.R - 1) / p.R : 1;
+    const int64_t tiles_all = (M + LOMB_WG - 1) / LOMB_WG;
+    int64_t split = ((int64_t)4 * ncu + tiles_all * p.groups - 1) / (tiles_all * p.groups);
+    const int64_t most = (N + 4 * LOMB_SUB - 1) / (4 * LOMB_SUB);
+    if (split > most) split = most;
+    if (split_force > 0) split = split_force;
+    if (split < 1) split = 1;
+    if (split > N) split = N;
+    p.run_len = ((N + split - 1) / split + 3) / 4 * 4;
+    p.split = (N + p.run_len - 1) / p.run_len;
+    const size_t tile_bytes = sizeof(double) * (size_t)p.split * (size_t)p.nv * LOMB_WG;       // one tile of one group
+    int64_t tiles_fit = (int64_t)(LOMB_PARTIAL_BYTES / tile_bytes);
+    if (tiles_fit < 1) tiles_fit = 1;
+    p.gpl = tiles_fit < p.groups ? tiles_fit : p.groups;
+    int64_t tp = tiles_fit / p.gpl;
+    if (tp < 1) tp = 1;
+    if (tp > tiles_all) tp = tiles_all;
+    p.fpass = tp * LOMB_WG < M ? tp * LOMB_WG : M;
+    if (freqs_force > 0 && freqs_force < p.fpass) p.fpass = freqs_force;
+    p.passes = (M + p.fpass - 1) / p.fpass;
+    int64_t tiles = 0;
+    for (int64_t m0 = 0; m0 < M; m0 += p.fpass) tiles += ((M - m0 < p.fpass ? M - m0 : p.fpass) + LOMB_WG - 1) / LOMB_WG;
+    p.workgroups = tiles * p.split * p.groups;
+    p.prep_blocks = (N + 4095) / 4096;
+    if (p.prep_blocks > LOMB_PREP_BLOCKS) p.prep_blocks = LOMB_PREP_BLOCKS;
+    p.prep_len = (lomb_npad(N) + p.prep_blocks - 1) / p.prep_blocks;
+    return p;
+}
+struct LombPrepArgs {
+    const double *t, *w;                  // w null: equal weights
+    const float *y;
+    int64_t y_ld, N, npad, batch, rows_padded;      // rows_padded = groups * RP
+    int R, RP;                            // rows of a group and their padded count
+    double t_ref, wnorm;                  // wnorm <= 0: the weights' own sum
+    const double *mean;                   // [batch] or null
+    int64_t blocks, len;                  // blocks along the samples, samples of one
+    double *wpart;                        // [blocks]: the blocks' sums of w
+    LombHead *head;
+    float *wy;
+    double *tpart;                        // [1 + 2 batch][blocks]: the blocks' sums of w32; wy32_r; wy32_r d_r
+    double *totals;                       // [1 + 2 batch]: W, then (Y'_r, YY'_r) row by row
+    int *status;                          // [4]: a non-finite t; a weight that is negative or not finite; a weight sum that is not
+};                                        //      positive and finite; a non-finite y
+struct LombSumArgs {
+    const LombHead *head;
+    const float *wy;                      // of the launch's first group
+    const double *f;                      // the pass's frequencies
+    int64_t npad, N4, run_len, split;     // N4: N rounded up to 4
+    int fcount;                           // frequencies of the pass
+    double *partial;                      // [groups of the launch][split][nv][fcount]
+};
+int launch_lomb_prep(LaunchCtx c, const LombPrepArgs &a);
+int launch_lomb_sums(LaunchCtx c, const LombSumArgs &a, int R, int64_t groups);
+// the runs added in ascending order: common[j][4] (from the launch's first group, when common is given) and
+// rows[(g0 R + r) rows_ld + j][2] for the rows below batch
+int launch_lomb_reduce(LaunchCtx c, const double *partial, int R, int64_t groups, int64_t split, int fcount, int64_t g0, int64_t batch,
+                       double *common, double *rows, int64_t rows_ld);
+// P[r][j] of fcount frequencies from their sums (scipy.signal.lombscargle's body in float64): float32, or complex64 for normalize 2
+int launch_lomb_finish(LaunchCtx c, const double *common, const double *rows, int64_t rows_ld, const double *totals, const double *mean,
+                       const double *f, int fcount, int64_t batch, int64_t N, double t_ref, int floating_mean, int normalize, void *P,
+                       int64_t p_ld);
 
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;

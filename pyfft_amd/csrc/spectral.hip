@@ -4,6 +4,7 @@
 #include "../../include/spectral_tfr.h"
 #include "../../include/spectral_quad.h"
 #include "../../include/spectral_cyclo.h"
+#include "../../include/spectral_uneven.h"
 #include "launch.h"
 #include "stage.h"
 #include "table_cache.h"
@@ -223,9 +224,10 @@ int get_xf(int64_t n, Xf *xf) {
 TableCache g_tables;
 
 // sp_last_passes: [0] the passes of the current call's outermost frame-chunk loop, [1] the most slice passes one
-// dev_fft_any / sp_czt loop made inside it, [2] the passes over the cycle-frequency list of sp_cyclic.  All are zeroed where a
-// call begins (ApiLock), so that a test can assert that the shape it chose really walks a loop past its first pass.
-int g_passes[3] = {0, 0, 0};
+// dev_fft_any / sp_czt loop made inside it, [2] the passes over the cycle-frequency list of sp_cyclic, [3] the passes over the
+// frequency list of sp_lomb / sp_lomb_sums, [4] the most launches the row groups of one such pass were dealt to.  All are zeroed
+// where a call begins (ApiLock), so that a test can assert that the shape it chose really walks a loop past its first pass.
+int g_passes[5] = {0, 0, 0, 0, 0};
 inline void note_slices(int64_t n) {
     if (n > g_passes[1]) g_passes[1] = (int)n;
 }
@@ -241,7 +243,7 @@ struct ApiLock {
     std::lock_guard<std::mutex> lk;
     ApiLock() : lk(g.mu) {
         g_tables.begin_call();
-        g_passes[0] = g_passes[1] = g_passes[2] = 0;
+        g_passes[0] = g_passes[1] = g_passes[2] = g_passes[3] = g_passes[4] = 0;
     }
 };
 
@@ -1325,7 +1327,7 @@ int sp_max_wg_fft(void) { return SP_MAX_WG_FFT; }
 const char *sp_last_error(void) { return g_err.c_str(); }
 int sp_last_passes(int which) {
     std::lock_guard<std::mutex> lk(g.mu);
-    return which >= 0 && which <= 2 ? g_passes[which] : 0;
+    return which >= 0 && which <= 4 ? g_passes[which] : 0;
 }
 
 int sp_init(int device_id) {
@@ -4021,6 +4023,224 @@ int sp_cyclic(const void *x, const void *y, int x_dtype, int y_dtype, int64_t x_
         LAUNCHCHK(launch_cyclic_finish(lc(), a.partial, p.groups, p.used, n, mirror, a.A, a0, A, b0, nb, scale, batch, S_d, Pp_d, Pm_d));
         g.last_kernel = "k_cyclic";
     }
+    return st.finish();
+}
+
+// ---- Lomb-Scargle spectra of unevenly sampled records (k_lomb.hip; include/spectral_uneven.h) ------------------
+Scratch g_lombRec, g_lombSums;      // the prepared record with the call's small tables; the reduced sums of one pass of sp_lomb
+
+// the checks every entry shares; 0 or the message's tail
+static const char *lomb_shape(int64_t N, int64_t M, int64_t batch) {
+    if (N < 1 || N >= ((int64_t)1 << 31)) return "N must lie in 1 .. 2^31 - 1";
+    if (M < 1 || M > LOMB_MAX_M) return "M must lie in 1 .. 2^24";
+    if (batch < 0 || batch > 65535) return "batch must lie in 0 .. 65535";
+    return nullptr;
+}
+static const char *lomb_tables(const double *f, int64_t M, double t_ref, const double *mean, int64_t batch, int64_t *where) {
+    *where = -1;
+    if (!isfinite(t_ref)) return "t_ref must be finite";
+    for (int64_t i = 0; i < M; ++i)
+        if (!isfinite(f[i])) return *where = i, "every f must be finite";
+    for (int64_t b = 0; mean && b < batch; ++b)
+        if (!isfinite(mean[b])) return *where = b, "every mean must be finite";
+    return nullptr;
+}
+static LombPlan lomb_plan_now(int64_t N, int64_t M, int64_t batch) {
+    return lomb_plan_of(N, M, batch, g.ncu, env_int("SP_LOMB_FREQS", 0), std::min(env_int("SP_LOMB_SPLIT", 0), 65535));
+}
+static size_t lomb_up(size_t v) { return (v + 255) & ~(size_t)255; }
+
+int sp_lomb_plan(int64_t N, int64_t M, int64_t batch, int64_t out[5]) {
+    if (!out || lomb_shape(N, M, batch)) return -1;
+    const LombPlan p = lomb_plan_now(N, M, batch);
+    out[0] = p.R;
+    out[1] = p.fpass;
+    out[2] = p.passes;
+    out[3] = p.split;
+    out[4] = p.workgroups;
+    return 0;
+}
+
+// f[M] and mean[batch] behind one another at `at` in g_lombRec (sized by the caller), on the stream
+static int lomb_upload(size_t at, const double *f, int64_t M, const double *mean, int64_t batch, const double **f_d, const double **mean_d) {
+    char *base = (char *)g_lombRec.p + at;
+    HIPCHK(hipMemcpyAsync(base, f, sizeof(double) * (size_t)M, hipMemcpyHostToDevice, g.stream));
+    *f_d = (const double *)base;
+    *mean_d = nullptr;
+    if (mean && batch > 0) {
+        char *mp = base + lomb_up(sizeof(double) * (size_t)M);
+        HIPCHK(hipMemcpyAsync(mp, mean, sizeof(double) * (size_t)batch, hipMemcpyHostToDevice, g.stream));
+        *mean_d = (const double *)mp;
+    }
+    return 0;
+}
+
+// sp_lomb (P given) and sp_lomb_sums (common, rows, totals given): the record prepared, then for every pass of frequencies the
+// sums kernel over the row groups, their runs added, and for sp_lomb the finish step
+static int lomb_run(const char *who, const double *t, const double *w, const float *y, int64_t y_ld, int64_t N, int64_t batch, double t_ref,
+                    double wnorm, const double *f, int64_t M, const double *mean, int floating_mean, int normalize, void *P, double *common,
+                    double *rows, double *totals, int mem) {
+    const bool sums_only = P == nullptr;
+    // every refusal comes before the device is touched
+    if (const char *why = lomb_shape(N, M, batch))
+        return fail("%s: %s (N %lld, M %lld, batch %lld)", who, why, (long long)N, (long long)M, (long long)batch);
+    if (batch > 0 && y_ld < N) return fail("%s: y_ld = %lld is below N = %lld", who, (long long)y_ld, (long long)N);
+    if (normalize < 0 || normalize > 2) return fail("%s: normalize = %d must be 0 (power), 1 (normalize) or 2 (amplitude)", who, normalize);
+    if (!t) return fail("%s: t is required", who);
+    if (batch > 0 && !y) return fail("%s: y is required", who);
+    if (!f) return fail("%s: f is required", who);
+    if (!isfinite(wnorm)) return fail("%s: wnorm must be finite", who);
+    int64_t where;
+    if (const char *why = lomb_tables(f, M, t_ref, mean, batch, &where)) return fail("%s: %s (index %lld)", who, why, (long long)where);
+    if (!sums_only && batch == 0) return 0;
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const LombPlan p = lomb_plan_now(N, M, batch);
+    if (batch == 0) y = nullptr;
+    const size_t esz = normalize == 2 ? sizeof(cf) : sizeof(float);
+    const int64_t npad = lomb_npad(N), nt = 1 + 2 * batch;
+    Stage st(mem);
+    const double *t_d, *w_d;
+    const float *y_d;
+    double *common_d = nullptr, *rows_d = nullptr, *totals_d = nullptr;
+    char *P_d = nullptr;
+    st.in(g.in0, t, sizeof(double) * (size_t)N, &t_d);
+    st.in(g.in0, w, sizeof(double) * (size_t)N, &w_d);
+    st.in(g.in0, y, sizeof(float) * (size_t)((batch - 1) * y_ld + N), &y_d);
+    if (sums_only) {
+        st.out(g.out0, common, sizeof(double) * 4 * (size_t)M, &common_d);
+        st.out(g.out0, batch > 0 ? rows : nullptr, sizeof(double) * 2 * (size_t)batch * (size_t)M, &rows_d);
+        st.out(g.out0, totals, sizeof(double) * (size_t)nt, &totals_d);
+    } else {
+        st.out(g.out0, (char *)P, esz * (size_t)batch * (size_t)M, &P_d);
+    }
+    if (st.commit()) return -1;
+    // the prepared record and the call's small tables, each at a multiple of 256 bytes
+    const size_t o_head = 0, o_wy = o_head + lomb_up(sizeof(LombHead) * (size_t)npad);
+    const size_t o_wpart = o_wy + lomb_up(sizeof(float) * (size_t)p.groups * (size_t)npad * (size_t)p.RP);
+    const size_t o_tpart = o_wpart + lomb_up(sizeof(double) * LOMB_PREP_BLOCKS);
+    const size_t o_tot = o_tpart + lomb_up(sizeof(double) * (size_t)nt * LOMB_PREP_BLOCKS);
+    const size_t o_status = o_tot + lomb_up(sizeof(double) * (size_t)nt);
+    const size_t o_f = o_status + 256;
+    const size_t total = o_f + lomb_up(sizeof(double) * (size_t)M) + lomb_up(sizeof(double) * (size_t)(batch + 1));
+    if (g_lombRec.ensure(total)) return -1;
+    char *rec = (char *)g_lombRec.p;
+    const double *f_d, *mean_d;
+    if (lomb_upload(o_f, f, M, mean, batch, &f_d, &mean_d)) return -1;
+    LombPrepArgs pa{};
+    pa.t = t_d, pa.w = w_d, pa.y = y_d;
+    pa.y_ld = y_ld, pa.N = N, pa.npad = npad, pa.batch = batch, pa.rows_padded = p.R ? p.groups * p.RP : 0;
+    pa.R = p.R, pa.RP = p.RP;
+    pa.t_ref = t_ref, pa.wnorm = wnorm;
+    pa.mean = mean_d;
+    pa.blocks = p.prep_blocks, pa.len = p.prep_len;
+    pa.wpart = (double *)(rec + o_wpart);
+    pa.head = (LombHead *)(rec + o_head);
+    pa.wy = p.RP ? (float *)(rec + o_wy) : nullptr;
+    pa.tpart = (double *)(rec + o_tpart);
+    pa.totals = (double *)(rec + o_tot);
+    pa.status = (int *)(rec + o_status);
+    HIPCHK(hipMemsetAsync(pa.status, 0, 4 * sizeof(int), g.stream));
+    if (launch_lomb_prep(lc(), pa) != 0) return fail("%s: the record could not be prepared (N %lld, batch %lld)", who, (long long)N, (long long)batch);
+    HIPCHK(hipGetLastError());
+    int flags[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(flags, pa.status, sizeof flags, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    if (flags[0]) return fail("%s: t holds a value that is not finite", who), SP_LOMB_BAD_RECORD;
+    if (flags[1]) return fail("%s: w holds a weight that is negative or not finite", who), SP_LOMB_BAD_RECORD;
+    if (flags[2]) return fail("%s: the weights (w, or wnorm) do not sum to a positive finite value", who), SP_LOMB_BAD_RECORD;
+    if (flags[3]) return fail("%s: y holds a value that is not finite", who), SP_LOMB_BAD_RECORD;
+    if (sums_only) HIPCHK(hipMemcpyAsync(totals_d, pa.totals, sizeof(double) * (size_t)nt, hipMemcpyDeviceToDevice, g.stream));
+    if (g.work.ensure(sizeof(double) * (size_t)p.gpl * (size_t)p.split * (size_t)p.nv * (size_t)p.fpass)) return -1;
+    double *sc_common = nullptr, *sc_rows = nullptr;
+    if (!sums_only) {
+        if (g_lombSums.ensure(sizeof(double) * (size_t)p.fpass * (size_t)(4 + 2 * batch))) return -1;
+        sc_common = (double *)g_lombSums.p;
+        sc_rows = sc_common + 4 * p.fpass;
+    }
+    for (int64_t m0 = 0; m0 < M; m0 += p.fpass, ++g_passes[3]) {
+        const int fc = (int)std::min<int64_t>(p.fpass, M - m0);
+        double *cm = sums_only ? common_d + 4 * m0 : sc_common;
+        double *rw = sums_only ? (rows_d ? rows_d + 2 * m0 : nullptr) : sc_rows;
+        const int64_t rld = sums_only ? M : p.fpass;
+        int launches = 0;
+        for (int64_t g0 = 0; g0 < p.groups; g0 += p.gpl, g_passes[4] = std::max(g_passes[4], ++launches)) {
+            const int64_t ng = std::min<int64_t>(p.gpl, p.groups - g0);
+            LombSumArgs a{};
+            a.head = pa.head;
+            a.wy = p.RP ? pa.wy + g0 * npad * p.RP : nullptr;
+            a.f = f_d + m0;
+            a.npad = npad, a.N4 = (N + 3) / 4 * 4, a.run_len = p.run_len, a.split = p.split;
+            a.fcount = fc;
+            a.partial = (double *)g.work.p;
+            {
+                ProfScope ps;
+                if (launch_lomb_sums(lc(), a, p.R, ng) != 0)
+                    return fail("%s: the launch was refused (%d frequencies, %lld runs of %lld samples, %lld row groups)", who, fc,
+                                (long long)p.split, (long long)p.run_len, (long long)ng);
+            }
+            HIPCHK(hipGetLastError());
+            g.last_kernel = "k_lomb_sums";
+            if (launch_lomb_reduce(lc(), a.partial, p.R, ng, p.split, fc, g0, batch, g0 == 0 ? cm : nullptr, rw, rld) != 0)
+                return fail("%s: the sum over the runs was refused", who);
+            HIPCHK(hipGetLastError());
+        }
+        if (!sums_only) {
+            if (launch_lomb_finish(lc(), cm, rw, rld, pa.totals, mean_d, f_d + m0, fc, batch, N, t_ref, floating_mean, normalize,
+                                   P_d + esz * (size_t)m0, M) != 0)
+                return fail("%s: the finish step was refused", who);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    return st.finish();
+}
+
+int sp_lomb(const double *t, const double *w, const float *y, int64_t y_ld, int64_t N, int64_t batch, double t_ref, const double *f,
+            int64_t M, const double *mean, int floating_mean, int normalize, void *P, int mem) {
+    if (!P) return fail("sp_lomb: P is required");
+    return lomb_run("sp_lomb", t, w, y, y_ld, N, batch, t_ref, 0.0, f, M, mean, floating_mean, normalize, P, nullptr, nullptr, nullptr, mem);
+}
+
+int sp_lomb_sums(const double *t, const double *w, const float *y, int64_t y_ld, int64_t N, int64_t batch, double t_ref, double wnorm,
+                 const double *f, int64_t M, const double *mean, double *common, double *rows, double *totals, int mem) {
+    if (!common) return fail("sp_lomb_sums: common is required");
+    if (!totals) return fail("sp_lomb_sums: totals is required");
+    if (batch > 0 && !rows) return fail("sp_lomb_sums: rows is required");
+    return lomb_run("sp_lomb_sums", t, w, y, y_ld, N, batch, t_ref, wnorm, f, M, mean, 0, 0, nullptr, common, rows, totals, mem);
+}
+
+int sp_lomb_finish(const double *common, const double *rows, const double *totals, int64_t N, int64_t batch, double t_ref,
+                   const double *f, int64_t M, const double *mean, int floating_mean, int normalize, void *P, int mem) {
+    const char *who = "sp_lomb_finish";
+    if (const char *why = lomb_shape(N, M, batch))
+        return fail("%s: %s (N %lld, M %lld, batch %lld)", who, why, (long long)N, (long long)M, (long long)batch);
+    if (normalize < 0 || normalize > 2) return fail("%s: normalize = %d must be 0 (power), 1 (normalize) or 2 (amplitude)", who, normalize);
+    if (!common) return fail("%s: common is required", who);
+    if (!rows) return fail("%s: rows is required", who);
+    if (!totals) return fail("%s: totals is required", who);
+    if (!f) return fail("%s: f is required", who);
+    if (!P) return fail("%s: P is required", who);
+    int64_t where;
+    if (const char *why = lomb_tables(f, M, t_ref, mean, batch, &where)) return fail("%s: %s (index %lld)", who, why, (long long)where);
+    if (batch == 0) return 0;
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const size_t esz = normalize == 2 ? sizeof(cf) : sizeof(float);
+    Stage st(mem);
+    const double *common_d, *rows_d, *totals_d;
+    char *P_d;
+    st.in(g.in0, common, sizeof(double) * 4 * (size_t)M, &common_d);
+    st.in(g.in0, rows, sizeof(double) * 2 * (size_t)batch * (size_t)M, &rows_d);
+    st.in(g.in0, totals, sizeof(double) * (size_t)(1 + 2 * batch), &totals_d);
+    st.out(g.out0, (char *)P, esz * (size_t)batch * (size_t)M, &P_d);
+    if (st.commit()) return -1;
+    if (g_lombRec.ensure(lomb_up(sizeof(double) * (size_t)M) + lomb_up(sizeof(double) * (size_t)(batch + 1)))) return -1;
+    const double *f_d, *mean_d;
+    if (lomb_upload(0, f, M, mean, batch, &f_d, &mean_d)) return -1;
+    if (launch_lomb_finish(lc(), common_d, rows_d, M, totals_d, mean_d, f_d, (int)M, batch, N, t_ref, floating_mean, normalize, P_d, M) != 0)
+        return fail("%s: the finish step was refused", who);
+    HIPCHK(hipGetLastError());
+    if (!st.host) HIPCHK(hipStreamSynchronize(g.stream));       // f and mean are the caller's again
     return st.finish();
 }
 

@@ -10,6 +10,7 @@ The mode object holds what the two differ in (casting the samples, allocating re
 trailing `mem`), so every entry point below assembles the argument list of its sp_* entry once; where the modes differ in substance
 the function says so with an `if md.dev:`.  There is no CPU implementation behind these functions.
 """
+import collections
 import operator
 
 import numpy as np
@@ -185,8 +186,9 @@ def max_wg_fft():
 
 def last_passes(which=0):
     """Passes the last call's loops made: which=0 its outermost frame-chunk loop, which=1 the most slice passes of one batch of
-    long transforms inside it, which=2 (CYC_PASSES) the passes of `cyclic` over its list of cycle frequencies; 0 where the call had no
-    such loop (sp_last_passes)."""
+    long transforms inside it, which=2 (CYC_PASSES) the passes of `cyclic` over its list of cycle frequencies, which=3 (LOMB_PASSES)
+    the passes of `lomb` and `lomb_sums` over their frequencies, which=4 (LOMB_LAUNCHES) the most launches the row groups of one such
+    pass were dealt to; 0 where the call had no such loop (sp_last_passes)."""
     return int(lib().sp_last_passes(int(which)))
 
 
@@ -1627,6 +1629,186 @@ def cyclic_plan(n, hop, nframes, A, rows=1, cplx=False, cross=False, conj=False)
     n, hop, nframes, A, rows = int(n), int(hop), int(nframes), int(A), int(rows)
     cyclic_check("cyclic_plan", n, hop, nframes, A, rows)
     return _cyclic_plan_raw("cyclic_plan", cplx, cross, conj, n, hop, nframes, A, rows)
+
+
+LOMB_SUB, LOMB_MAX_M, LOMB_MAX_ROWS, LOMB_PASSES, LOMB_LAUNCHES, LOMB_BAD_RECORD = 256, 1 << 24, 65535, 3, 4, -2
+LOMB_NORMALIZE = {"power": 0, "normalize": 1, "amplitude": 2}
+
+
+class LombRefused(ValueError, NotImplementedError):
+    """A record or a frequency list the Lomb-Scargle kernels do not take: outside the limits, values a record must not hold, and what
+    is not built (float64 or complex values on the device, rows with times of their own)."""
+
+
+class LombSums(collections.namedtuple("LombSums", "common rows totals mean t_ref N")):
+    """The float64 sums of `lomb_sums`: common [M, 4] = C, S, C2, S2; rows [..., M, 2] = YC', YS' (None without rows); totals
+    [1 + 2 rows] = W, then (Y', YY') row by row; and what they were taken with.  The sums of the parts of one record, all taken with
+    the same mean, t_ref and wnorm, add up to the whole's: a + b."""
+    __slots__ = ()
+
+    def __add__(self, other):
+        if not isinstance(other, LombSums):
+            return NotImplemented
+        if self.t_ref != other.t_ref or not np.array_equal(self.mean, other.mean):
+            raise LombRefused("LombSums: the parts were taken with different t_ref or mean")
+        rows = None if self.rows is None else self.rows + other.rows
+        return LombSums(self.common + other.common, rows, self.totals + other.totals, self.mean, self.t_ref, self.N + other.N)
+
+
+def _lomb_normalize(who, normalize):
+    if isinstance(normalize, (bool, np.bool_)):
+        return 1 if normalize else 0
+    if isinstance(normalize, str) and normalize in LOMB_NORMALIZE:
+        return LOMB_NORMALIZE[normalize]
+    if isinstance(normalize, (int, np.integer)) and 0 <= int(normalize) <= 2:
+        return int(normalize)
+    raise LombRefused("%s: normalize must be 'power' (0, False), 'normalize' (1, True) or 'amplitude' (2), not %r" % (who, normalize))
+
+
+def lomb_check(who, N, M, rows, y_ld=None, f=None, t_ref=0.0, mean=None):
+    """The refusals of sp_lomb, sp_lomb_sums, sp_lomb_finish and sp_lomb_plan, before the library is touched."""
+    if N < 1 or N >= 1 << 31:
+        raise LombRefused("%s: N = %d samples are outside 1 .. 2^31 - 1" % (who, N))
+    if M < 1 or M > LOMB_MAX_M:
+        raise LombRefused("%s: M = %d frequencies are outside 1 .. 2^24" % (who, M))
+    if rows < 0 or rows > LOMB_MAX_ROWS:
+        raise LombRefused("%s: %d rows are outside 0 .. %d" % (who, rows, LOMB_MAX_ROWS))
+    if y_ld is not None and rows > 0 and y_ld < N:
+        raise LombRefused("%s: y_ld = %d is below N = %d" % (who, y_ld, N))
+    if f is not None and not np.all(np.isfinite(f)):
+        raise LombRefused("%s: every frequency must be finite" % who)
+    if not np.isfinite(t_ref):
+        raise LombRefused("%s: t_ref must be finite" % who)
+    if mean is not None and not np.all(np.isfinite(mean)):
+        raise LombRefused("%s: every mean must be finite" % who)
+
+
+def _lomb_record(who, t, y, f, weights, t_ref, mean_value):
+    """The arguments lomb and lomb_sums share, checked: (md, t, w, y rows or None, pitch, lead, N, rows, f, t_ref, mean [rows])."""
+    md = _mode(t)
+    if y is not None and _mode(y) is not md or weights is not None and _mode(weights) is not md:
+        raise TypeError("%s: t, y and weights must all be numpy arrays or all device tensors" % who)
+    if _is_torch(f):
+        f = f.detach().cpu().numpy()
+    fv = np.ascontiguousarray(np.asarray(f), dtype=np.float64)
+    if md.dev:
+        if t.dtype != torch.float64 or (weights is not None and weights.dtype != torch.float64):
+            raise LombRefused("%s: times and weights on the device are float64 tensors" % who)
+        if y is not None and y.dtype != torch.float32:
+            raise LombRefused("%s: values on the device are float32 tensors, not %s" % (who, y.dtype))
+        tv, wv = t.contiguous(), None if weights is None else weights.contiguous()
+        tdim, N = tv.dim(), int(tv.shape[-1]) if tv.dim() else 0
+    else:
+        tv = np.ascontiguousarray(np.asarray(t), dtype=np.float64)
+        wv = None if weights is None else np.ascontiguousarray(np.asarray(weights), dtype=np.float64)
+        y = None if y is None else np.ascontiguousarray(np.asarray(y), dtype=np.float32)
+        tdim, N = tv.ndim, int(tv.shape[-1]) if tv.ndim else 0
+    if tdim != 1 or fv.ndim != 1 or (wv is not None and tuple(wv.shape) != tuple(tv.shape)):
+        raise LombRefused("%s: t and f need exactly one axis, and weights the shape of t" % who)
+    if y is not None and (len(y.shape) < 1 or int(y.shape[-1]) != N):
+        raise LombRefused("%s: the last axis of y must have the %d samples of t" % (who, N))
+    lead = () if y is None else tuple(int(d) for d in y.shape[:-1])
+    rows = 0 if y is None else int(np.prod(lead, dtype=np.int64))
+    if mean_value is not None and (np.size(mean_value) not in (1, rows) or not np.all(np.isfinite(mean_value))):
+        raise LombRefused("%s: mean_value must be one finite value, or one per row" % who)
+    if N >= 1 and t_ref is None:
+        t_ref = float(tv[0])
+    lomb_check(who, N, int(fv.size), rows, None, fv, 0.0 if t_ref is None else float(t_ref))
+    t_ref = float(t_ref)
+    if not md.dev:                          # a record on the device is checked by the kernel that prepares it
+        if not np.all(np.isfinite(tv)) or (y is not None and not np.all(np.isfinite(y))):
+            raise LombRefused("%s: t and y must be finite" % who)
+        if wv is not None and not (np.all(np.isfinite(wv)) and np.all(wv >= 0) and np.sum(wv) > 0):
+            raise LombRefused("%s: the weights must be finite, not negative and sum to a positive value" % who)
+    md.bind(tv)
+    ys, ld = None, N
+    if rows:
+        ys, ld = md.rows(y.reshape(rows, N) if len(y.shape) != 2 else y)
+    mv = np.zeros(rows, dtype=np.float64)
+    if mean_value is not None:
+        mv[:] = np.asarray(mean_value, dtype=np.float64).reshape(-1) if np.ndim(mean_value) else float(mean_value)
+    else:
+        for r in range(rows):               # the existing mean pass (sp_mean), row by row
+            mv[r] = mean(ys[r, :N])
+    lomb_check(who, N, int(fv.size), rows, ld, None, t_ref, mv)
+    return md, tv, wv, ys, ld, lead, N, rows, fv, t_ref, mv
+
+
+def _lomb_call(md, entry, *args):
+    """md.call, with the return code of a record the device refused (SP_LOMB_BAD_RECORD) raised as LombRefused"""
+    md.init()
+    rc = entry(*args, md.mem)
+    if rc == LOMB_BAD_RECORD:
+        raise LombRefused((lib().sp_last_error() or b"the record was refused").decode())
+    check(rc)
+
+
+def lomb(t, y, f, weights=None, floating_mean=True, normalize="normalize", t_ref=None, mean_value=None):
+    """The generalised Lomb-Scargle periodogram of rows y[..., N] sampled at the times t[N] (float64, any order, shared by the rows),
+    at the frequencies f[M] in cycles per unit of t (sp_lomb): scipy.signal.lombscargle's definition.  weights: float64 [N], not
+    negative.  normalize: 'power', 'normalize' or 'amplitude' (complex).  t_ref: the origin the phases are taken from inside the
+    kernel (default t[0]); the result does not depend on it beyond rounding.  mean_value: the offset taken off each row before its
+    float32 products are formed and put back in float64 (default: each row's mean, computed on the device).  Returns P [..., M],
+    float32 or complex64.  numpy in -> numpy out; device tensors in (t, weights float64, y float32) -> a device tensor on t's stream."""
+    nz = _lomb_normalize("lomb", normalize)
+    if y is None:
+        raise LombRefused("lomb: y is required (lomb_sums takes the window's sums without rows)")
+    md, tv, wv, ys, ld, lead, N, rows, fv, t_ref, mv = _lomb_record("lomb", t, y, f, weights, t_ref, mean_value)
+    M = int(fv.size)
+    P = md.empty(lead + (M,), "complex64" if nz == 2 else "float32", tv)
+    if rows:
+        _lomb_call(md, lib().sp_lomb, md.addr(tv), md.addr(wv), md.addr(ys), ld, N, rows, t_ref, ptr(fv), M, ptr(mv), 1 if floating_mean else 0,
+                   nz, md.addr(P))
+    return P
+
+
+def lomb_sums(t, y, f, weights=None, t_ref=None, mean_value=None, wnorm=None):
+    """The float64 sums behind `lomb`, un-finished (sp_lomb_sums), as a LombSums; y None: the sums of the spectral window alone.
+    wnorm: what the weights are divided by in place of their own sum -- give every part of a record the whole's weight sum (the
+    whole's N for equal weights), the same t_ref and the same mean_value, and the parts' sums add up to the whole's."""
+    wn = 0.0 if wnorm is None else float(wnorm)
+    if not np.isfinite(wn) or (wnorm is not None and wn <= 0):
+        raise LombRefused("lomb_sums: wnorm must be positive and finite")
+    md, tv, wv, ys, ld, lead, N, rows, fv, t_ref, mv = _lomb_record("lomb_sums", t, y, f, weights, t_ref, mean_value)
+    M = int(fv.size)
+    common = md.empty((M, 4), "float64", tv)
+    sums = md.empty(lead + (M, 2), "float64", tv) if rows else None
+    totals = md.empty((1 + 2 * rows,), "float64", tv)
+    _lomb_call(md, lib().sp_lomb_sums, md.addr(tv), md.addr(wv), md.addr(ys), ld, N, rows, t_ref, wn, ptr(fv), M, ptr(mv), md.addr(common),
+               md.addr(sums), md.addr(totals))
+    return LombSums(common, sums, totals, mv, t_ref, N)
+
+
+def lomb_finish(sums, f, floating_mean=True, normalize="normalize"):
+    """P from a LombSums (sp_lomb_finish): lomb_finish(lomb_sums(t, y, f), f, ...) is bitwise lomb(t, y, f, ...)."""
+    nz = _lomb_normalize("lomb_finish", normalize)
+    if not isinstance(sums, LombSums) or sums.rows is None:
+        raise LombRefused("lomb_finish: the sums of lomb_sums with rows are required")
+    md = _mode(sums.rows)
+    fv = np.ascontiguousarray(np.asarray(f), dtype=np.float64)
+    lead = tuple(int(d) for d in sums.rows.shape[:-2])
+    rows, M = int(np.prod(lead, dtype=np.int64)), int(fv.size)
+    if fv.ndim != 1 or tuple(sums.common.shape) != (M, 4) or int(sums.rows.shape[-2]) != M or md.count(sums.totals) != 1 + 2 * rows:
+        raise LombRefused("lomb_finish: the sums do not belong to these %d frequencies" % M)
+    mv = np.ascontiguousarray(sums.mean, dtype=np.float64)
+    lomb_check("lomb_finish", int(sums.N), M, rows, None, fv, float(sums.t_ref), mv)
+    md.bind(sums.rows)
+    cm, rw, tt = (md.cast(a, "float64") for a in (sums.common, sums.rows, sums.totals))
+    P = md.empty(lead + (M,), "complex64" if nz == 2 else "float32", rw)
+    if rows:
+        md.call(lib().sp_lomb_finish, md.addr(cm), md.addr(rw), md.addr(tt), int(sums.N), rows, float(sums.t_ref), ptr(fv), M, ptr(mv),
+                1 if floating_mean else 0, nz, md.addr(P))
+    return P
+
+
+def lomb_plan(N, M, rows=1):
+    """sp_lomb_plan as a dict (host only): rows_per_group, freqs_per_pass, passes, split (sample runs), workgroups."""
+    N, M, rows = int(N), int(M), int(rows)
+    lomb_check("lomb_plan", N, M, rows)
+    out = np.zeros(5, dtype=np.int64)
+    if lib().sp_lomb_plan(N, M, rows, ptr(out)) != 0:
+        raise LombRefused("lomb_plan: the shape is refused")
+    return dict(zip(("rows_per_group", "freqs_per_pass", "passes", "split", "workgroups"), (int(v) for v in out)))
 
 
 EIGH_MAX_N = 64
