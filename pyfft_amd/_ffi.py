@@ -129,6 +129,9 @@ UNEVEN_SIGNATURES = {
     "sp_lomb_plan": (_i, [_i64, _i64, _i64, _vp]),
 }
 
+# the six tables, in the order of their headers
+TABLES = (SIGNATURES, EXT_SIGNATURES, TFR_SIGNATURES, QUAD_SIGNATURES, CYCLO_SIGNATURES, UNEVEN_SIGNATURES)
+
 
 class SpectralError(RuntimeError):
     pass
@@ -143,7 +146,7 @@ def load_library():
         raise SpectralError("libspectral.so not found at %s -- run `make` (or __graft_entry__.build()); "
                             "pyfft_amd has no CPU fallback" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for table in (SIGNATURES, EXT_SIGNATURES, TFR_SIGNATURES, QUAD_SIGNATURES, CYCLO_SIGNATURES, UNEVEN_SIGNATURES):
+    for table in TABLES:
         for name, (res, args) in table.items():
             fn = getattr(lib, name)      # AttributeError if the .so lacks a declared symbol
             fn.restype = res

@@ -11,6 +11,7 @@ trailing `mem`), so every entry point below assembles the argument list of its s
 the function says so with an `if md.dev:`.  There is no CPU implementation behind these functions.
 """
 import collections
+import math
 import operator
 
 import numpy as np
@@ -178,6 +179,76 @@ def _enter(x):
         _bind_stream(x)
         return _DEV
     return _HOST
+
+
+# ---- what the row-batched entries share ------------------------------------------------------------------------------
+def _lead_rows(shape, trailing=1):
+    """the leading axes of a shape (all but its last `trailing`) as ints, and the number of rows they hold"""
+    lead = tuple(map(int, shape[:-trailing]))
+    rows = 1
+    for d in lead:
+        rows *= d
+    return lead, rows
+
+
+def _plan(entry, names, Refused, who, *args):
+    """the answer of a sp_*_plan entry (host arithmetic) as a dict of ints under `names`, `fits` as a bool"""
+    out = np.zeros(len(names), dtype=np.int64)
+    if entry(*args, ptr(out)) != 0:
+        raise Refused("%s: the shape is refused" % who)
+    d = dict(zip(names, (int(v) for v in out)))
+    if "fits" in d:
+        d["fits"] = bool(d["fits"])
+    return d
+
+
+def _second_record(who, Refused, md, x, y):
+    """a second record beside the checked x: None, or y checked to be of x's kind, shape, dtype (and device)"""
+    if y is None:
+        return None
+    if _mode(y) is not md:
+        raise TypeError("%s: x and y must both be numpy arrays or both device tensors" % who)
+    y = md.checked(y)
+    if tuple(y.shape) != tuple(x.shape) or not md.alike(x, y):
+        raise Refused("%s: y must share x's shape, %s" % (who, md.ALIKE))
+    return y
+
+
+def _paired_rows(md, x, y, nsig):
+    """-> (the rows of x, the rows of y or None, the pitch of both): where the two pitches differ both are packed"""
+    xs, xld = md.rows(x)
+    if y is None:
+        return xs, None, xld
+    ys, yld = md.rows(y)
+    if yld != xld:
+        return md.samples(xs), md.samples(ys), nsig
+    return xs, ys, xld
+
+
+def _row_means(v, rows, nsig, out):
+    """out[r] = the mean of row r of v, by the existing mean pass (sp_mean) row by row"""
+    v = v.reshape(rows, nsig)
+    for r in range(rows):
+        out[r] = mean(v[r])
+
+
+def _range_check(Refused, who, length=None, hop=None, count=None, rows=None, nsig=None, x_ld=None, scale=None):
+    """The range refusals the row-batched entries share, in this order; what is left None is not judged.  length = (its name, n, the
+    least, the most), count = (its name, a number of frames or columns), rows = (rows, the most)."""
+    if length is not None and (length[1] < length[2] or length[1] > length[3] or length[1] & (length[1] - 1)):
+        raise Refused("%s: %s = %d must be a power of two from %d to %d" % ((who,) + length))
+    if hop is not None and hop < 1:
+        raise Refused("%s: hop = %d must be at least 1" % (who, hop))
+    if count is not None and count[1] < 0:
+        raise Refused("%s: %s = %d must not be negative" % ((who,) + count))
+    if rows is not None and (rows[0] < 0 or rows[0] > rows[1]):
+        raise Refused("%s: %d rows are outside 0 .. %d" % ((who,) + rows))
+    if nsig is not None and nsig < 1:
+        raise Refused("%s: the rows must hold at least one sample" % who)
+    if x_ld is not None and x_ld < nsig:
+        raise Refused("%s: x_ld = %d is below nsig = %d" % (who, x_ld, nsig))
+    if scale is not None and not math.isfinite(scale):
+        raise Refused("%s: scale must be finite" % who)
 
 
 def max_wg_fft():
@@ -477,8 +548,7 @@ def istft_frames(Z, win, hop, sided=SIDED_HALF, scale=None, bin_major=False, ski
     total = (M - 1) * hop + nfft
     nout = total - skip if nout is None else int(nout)
     sc = float(np.sum(np.asarray(win, dtype=np.float64))) if scale is None else float(scale)
-    lead = tuple(int(d) for d in Z.shape[:-2])
-    nch = int(np.prod(lead)) if lead else 1
+    lead, nch = _lead_rows(Z.shape, 2)
     md = _enter(Z)
     if md.dev and Z.dtype != torch.complex64:            # (host spectra are cast)
         raise TypeError("device path takes complex64 spectra, got %s" % Z.dtype)
@@ -727,8 +797,7 @@ def pfb_synth(X, g, M, hop, first, nout, phase_ref=0, r0=0, onesided=True, in_ma
     if nframes < 1:
         raise ValueError("pfb_synth: there are no frames")
     sided = SIDED_HALF if onesided else SIDED_RAW
-    lead = tuple(int(d) for d in X.shape[:-2])
-    batch = int(np.prod(lead)) if lead else 1
+    lead, batch = _lead_rows(X.shape, 2)
     md = _enter(X)
     if md.dev and X.dtype != torch.complex64:           # (host frames are cast)
         raise TypeError("device path takes complex64 frames, got %s" % X.dtype)
@@ -892,9 +961,7 @@ class WelchBlocksRefused(ValueError, NotImplementedError):
 
 def welch_blocks_check(who, nsig, nfft, hop, nframes, navg, step, detrend, nch=None, y_ld=None):
     """Every refusal of sp_welch_blocks, before the library is touched -> the detrend code."""
-    if nfft < WELCH_BLOCKS_MIN_NFFT or nfft > WELCH_BLOCKS_MAX_NFFT or nfft & (nfft - 1):
-        raise WelchBlocksRefused("%s: nfft = %d must be a power of two from %d to %d"
-                                 % (who, nfft, WELCH_BLOCKS_MIN_NFFT, WELCH_BLOCKS_MAX_NFFT))
+    _range_check(WelchBlocksRefused, who, length=("nfft", nfft, WELCH_BLOCKS_MIN_NFFT, WELCH_BLOCKS_MAX_NFFT))
     if hop < 1 or hop > nfft:
         raise WelchBlocksRefused("%s: hop = %d must lie in 1 .. nfft = %d" % (who, hop, nfft))
     if navg < 1:
@@ -959,8 +1026,7 @@ def welch_blocks(x, win, hop, nframes, navg, step=None, y=None, detrend=True, sc
     nch, ld = (None, None) if ys is None else (int(ys.shape[0]), int(ys.shape[1]))
     code = welch_blocks_check("welch_blocks", nsig, nfft, hop, nframes, navg, step, detrend, nch, ld)
     scale = float(scale)
-    if not np.isfinite(scale):
-        raise ValueError("welch_blocks: scale must be finite")
+    _range_check(ValueError, "welch_blocks", scale=scale)
     nblocks, nb = (nframes - navg) // step + 1, nfft if cplx else nfft // 2 + 1
     md.bind(xs)
     pxx = md.empty((nblocks, nb), "float32", xs)
@@ -979,10 +1045,8 @@ def welch_blocks_plan(nfft, hop, nframes, navg, step=None, nch=1, cplx=False):
     nfft, hop, nframes, navg, nch = int(nfft), int(hop), int(nframes), int(navg), int(nch)
     step = navg if step is None else int(step)
     welch_blocks_check("welch_blocks_plan", (nframes - 1) * hop + nfft, nfft, hop, nframes, navg, step, False, nch if nch else None)
-    out = np.zeros(8, dtype=np.int64)
-    if lib().sp_welch_blocks_plan(1 if cplx else 0, nfft, hop, nframes, navg, step, nch, ptr(out)) != 0:
-        raise WelchBlocksRefused("welch_blocks_plan: the shape is refused")
-    return dict(zip(("nblocks", "nb", "q", "runs", "transforms", "scratch", "workgroups", "lds_bytes"), (int(v) for v in out)))
+    return _plan(lib().sp_welch_blocks_plan, ("nblocks", "nb", "q", "runs", "transforms", "scratch", "workgroups", "lds_bytes"),
+                 WelchBlocksRefused, "welch_blocks_plan", 1 if cplx else 0, nfft, hop, nframes, navg, step, nch)
 
 
 CWT_MIN_L, CWT_MAX_L, CWT_MAX_ROWS = 256, 8192, 65535
@@ -997,8 +1061,7 @@ class CwtRefused(ValueError, NotImplementedError):
 def cwt_check(who, nsig, scales, family, param, L, M, rows=1):
     """Every refusal of sp_cwt's shape, before the library is touched -> (scales float64, family code, param)."""
     L, M = int(L), int(M)
-    if L < CWT_MIN_L or L > CWT_MAX_L or L & (L - 1):
-        raise CwtRefused("%s: L = %d must be a power of two from %d to %d" % (who, L, CWT_MIN_L, CWT_MAX_L))
+    _range_check(CwtRefused, who, length=("L", L, CWT_MIN_L, CWT_MAX_L))
     if M < 0 or 2 * M >= L:
         raise CwtRefused("%s: M = %d must lie in 0 .. L / 2 - 1 = %d" % (who, M, L // 2 - 1))
     if L - 2 * M < L // 4:
@@ -1041,15 +1104,12 @@ def cwt(x, scales, family, param, L, M, W=True, gws=False, recon=None, bandpow=N
     if x.ndim < 1:
         raise CwtRefused("cwt: x must have at least one axis")
     n = int(x.shape[-1])
-    rows = 1
-    for d in x.shape[:-1]:
-        rows *= int(d)
+    lead, rows = _lead_rows(x.shape)
     sc, code, param = cwt_check("cwt", n, scales, family, param, L, M, rows)
     S = sc.size
     wr, wb = _cwt_weights("cwt", recon, S, "recon"), _cwt_weights("cwt", bandpow, S, "bandpow")
     if not W and not gws and wr is None and wb is None:
         raise CwtRefused("cwt: an output is required: W, gws, recon or bandpow")
-    lead = tuple(x.shape[:-1])
     shapes = {"W": (lead + (S, n), "complex64"), "gws": (lead + (S,), "float64"), "recon": (lead + (n,), "complex64"),
               "bandpow": (lead + (n,), "float32")}
     want = {"W": bool(W), "gws": bool(gws), "recon": wr is not None, "bandpow": wb is not None}
@@ -1067,10 +1127,8 @@ def cwt_plan(nsig, nscales, L, M, rows=1, W=True, gws=False, recon=False, bandpo
     bits = (1 if W else 0) | (2 if gws else 0) | (4 if recon else 0) | (8 if bandpow else 0)
     if not bits:
         raise CwtRefused("cwt_plan: an output is required: W, gws, recon or bandpow")
-    out = np.zeros(5, dtype=np.int64)
-    if lib().sp_cwt_plan(int(nsig), int(nscales), int(rows), int(L), int(M), bits, ptr(out)) != 0:
-        raise CwtRefused("cwt_plan: the shape is refused")
-    return dict(zip(("hop", "frames", "chunk", "workgroups", "scratch"), (int(v) for v in out)))
+    return _plan(lib().sp_cwt_plan, ("hop", "frames", "chunk", "workgroups", "scratch"), CwtRefused, "cwt_plan", int(nsig), int(nscales),
+                 int(rows), int(L), int(M), bits)
 
 
 def icwt_sum(W, weights):
@@ -1088,10 +1146,7 @@ def icwt_sum(W, weights):
     w = _cwt_weights("icwt_sum", weights, S, "weights")
     if w is None:
         raise CwtRefused("icwt_sum: weights are required")
-    lead = tuple(W.shape[:-2])
-    rows = 1
-    for d in lead:
-        rows *= int(d)
+    lead, rows = _lead_rows(W.shape, 2)
     if rows < 1 or rows > CWT_MAX_ROWS:
         raise CwtRefused("icwt_sum: %d rows are outside 1 .. %d" % (rows, CWT_MAX_ROWS))
     md.bind(W)
@@ -1127,15 +1182,6 @@ def wct_check(who, nsig, scales, family, param, L, Mw, Mg, rows=1, xwt=False):
     return sc, code, param
 
 
-def _wct_lead(who, x):
-    if x.ndim < 1:
-        raise WctRefused("%s: x must have at least one axis" % who)
-    rows = 1
-    for d in x.shape[:-1]:
-        rows *= int(d)
-    return tuple(x.shape[:-1]), rows
-
-
 def wct_time(x, y, scales, family, param, L, Mw, Mg=0, xwt=False):
     """The time half of the wavelet coherence along the last axis by overlap-save (sp_wct_time): scales in samples, frames of L samples
     with the margin Mw + Mg on either side.  -> T float32 [..., S, N, 4] = (A_t, B_t, Re C_t, Im C_t): |Wx|^2 / s', |Wy|^2 / s' and
@@ -1148,7 +1194,9 @@ def wct_time(x, y, scales, family, param, L, Mw, Mg=0, xwt=False):
     x, y = md.checked(x), md.checked(y)
     if tuple(x.shape) != tuple(y.shape) or x.dtype != y.dtype or (md.dev and x.device != y.device):
         raise WctRefused("wct_time: x and y must share their shape and dtype%s" % (" and device" if md.dev else ""))
-    lead, rows = _wct_lead("wct_time", x)
+    if x.ndim < 1:
+        raise WctRefused("wct_time: x must have at least one axis")
+    lead, rows = _lead_rows(x.shape)
     n = int(x.shape[-1])
     sc, code, param = wct_check("wct_time", n, scales, family, param, L, Mw, Mg, rows, xwt)
     md.bind(x)
@@ -1185,10 +1233,7 @@ def wct_scale(T, taps, spectra=False):
         raise WctRefused("wct_scale: T must be [..., S, N, 4] with N >= 1 and S in 1 .. %d" % WCT_MAX_SCALES)
     taps = wct_taps("wct_scale", taps)
     S, n = int(T.shape[-3]), int(T.shape[-2])
-    lead = tuple(T.shape[:-3])
-    rows = 1
-    for d in lead:
-        rows *= int(d)
+    lead, rows = _lead_rows(T.shape, 3)
     if rows < 1 or rows > CWT_MAX_ROWS:
         raise WctRefused("wct_scale: %d rows are outside 1 .. %d" % (rows, CWT_MAX_ROWS))
     md.bind(T)
@@ -1204,10 +1249,8 @@ def wct_scale(T, taps, spectra=False):
 def wct_plan(nsig, nscales, L, Mw, Mg=0, rows=1, xwt=False):
     """sp_wct_plan as a dict (host only): hop, frames (per row), chunk (scales per workgroup), workgroups, lds_bytes."""
     wct_check("wct_plan", int(nsig), np.ones(max(int(nscales), 0)), "morlet", 6.0, L, Mw, Mg, int(rows), xwt)
-    out = np.zeros(5, dtype=np.int64)
-    if lib().sp_wct_plan(int(nsig), int(nscales), int(rows), int(L), int(Mw), int(Mg), 1 if xwt else 0, ptr(out)) != 0:
-        raise WctRefused("wct_plan: the shape is refused")
-    return dict(zip(("hop", "frames", "chunk", "workgroups", "lds_bytes"), (int(v) for v in out)))
+    return _plan(lib().sp_wct_plan, ("hop", "frames", "chunk", "workgroups", "lds_bytes"), WctRefused, "wct_plan", int(nsig), int(nscales),
+                 int(rows), int(L), int(Mw), int(Mg), 1 if xwt else 0)
 
 
 SSQ_MIN_N, SSQ_MAX_N, SSQ_MAX_ROWS, SSQ_MAX_BANDS, SSQ_LDS_MAX = 32, 8192, 65535, 8, 160 * 1024
@@ -1225,20 +1268,9 @@ def ssq_lds_bytes(cplx, n, nb, T=True, P=False, fields=False):
 
 def ssq_check(who, cplx, n, hop, nframes, rows, gamma=0.0, rel=0.0, nsig=None, x_ld=None):
     """The refusals sp_ssq, sp_ssq_bands and sp_ssq_plan share, before the library is touched."""
-    if n < SSQ_MIN_N or n > SSQ_MAX_N or n & (n - 1):
-        raise SsqRefused("%s: n = %d must be a power of two from %d to %d" % (who, n, SSQ_MIN_N, SSQ_MAX_N))
-    if hop < 1:
-        raise SsqRefused("%s: hop = %d must be at least 1" % (who, hop))
-    if nframes < 0:
-        raise SsqRefused("%s: nframes = %d must not be negative" % (who, nframes))
-    if rows < 0 or rows > SSQ_MAX_ROWS:
-        raise SsqRefused("%s: %d rows are outside 0 .. %d" % (who, rows, SSQ_MAX_ROWS))
-    if nsig is not None and nsig < 1:
-        raise SsqRefused("%s: the rows must hold at least one sample" % who)
-    if x_ld is not None and x_ld < nsig:
-        raise SsqRefused("%s: x_ld = %d is below nsig = %d" % (who, x_ld, nsig))
+    _range_check(SsqRefused, who, ("n", n, SSQ_MIN_N, SSQ_MAX_N), hop, ("nframes", nframes), (rows, SSQ_MAX_ROWS), nsig, x_ld)
     for name, v in (("gamma", gamma), ("rel", rel)):
-        if not np.isfinite(v) or v < 0:
+        if not math.isfinite(v) or v < 0:
             raise SsqRefused("%s: %s = %r must be finite and not negative" % (who, name, v))
 
 
@@ -1267,10 +1299,7 @@ def _ssq_front(who, x, n, hop, nframes, gamma, rel):
     x = md.checked(x)
     if x.ndim < 1:
         raise SsqRefused("%s: x must have at least one axis" % who)
-    lead = tuple(int(d) for d in x.shape[:-1])
-    rows = 1
-    for d in lead:
-        rows *= d
+    lead, rows = _lead_rows(x.shape)
     nsig = int(x.shape[-1])
     cplx = md.code(x) == _ffi.DTYPE_C64
     ssq_check(who, cplx, n, hop, nframes, rows, gamma, rel, nsig)
@@ -1337,8 +1366,7 @@ def ssq_bands(x, h, dh, hop, first, nframes, edges, scale=1.0, segmean=False, ga
     n, hop, first, nframes = int(np.asarray(h).shape[-1]), int(hop), int(first), int(nframes)
     gamma, rel, scale = float(gamma), float(rel), float(scale)
     md, xs, xld, lead, rows, nsig, cplx = _ssq_front("ssq_bands", x, n, hop, nframes, gamma, rel)
-    if not np.isfinite(scale):
-        raise SsqRefused("ssq_bands: scale must be finite")
+    _range_check(SsqRefused, "ssq_bands", scale=scale)
     nbands, ec, et = _ssq_edges("ssq_bands", md, edges, nframes, xs)
     hw, dw, _ = ssq_windows("ssq_bands", n, h, dh)
     out = md.empty(lead + (nbands, nframes), "complex64", xs)
@@ -1360,15 +1388,11 @@ def ssq_sum(T, n, edges, b0=0, half=False, scale=1.0):
     if T.ndim < 2:
         raise SsqRefused("ssq_sum: T must be [..., nframes, nb]")
     nframes, nb = int(T.shape[-2]), int(T.shape[-1])
-    lead = tuple(int(d) for d in T.shape[:-2])
-    rows = 1
-    for d in lead:
-        rows *= d
+    lead, rows = _lead_rows(T.shape, 2)
     ssq_check("ssq_sum", True, n, 1, nframes, rows)
     if nb < 1 or b0 < 0 or b0 >= n or nb > n:
         raise SsqRefused("ssq_sum: nb = %d bins from b0 = %d lie outside the %d bins of the spectrum" % (nb, b0, n))
-    if not np.isfinite(scale):
-        raise SsqRefused("ssq_sum: scale must be finite")
+    _range_check(SsqRefused, "ssq_sum", scale=scale)
     md.bind(T)
     Tc = md.cast(T, "complex64")
     nbands, ec, et = _ssq_edges("ssq_sum", md, edges, nframes, Tc)
@@ -1387,12 +1411,8 @@ def ssq_plan(n, nframes, rows=1, cplx=False, nb=None, T=True, P=False, fields=Fa
         raise SsqRefused("ssq_plan: an output is required")
     if not bands and (nb < 1 or nb > (n if cplx else n // 2 + 1)):
         raise SsqRefused("ssq_plan: nb = %d lies outside the %d bins of the spectrum" % (nb, n if cplx else n // 2 + 1))
-    out = np.zeros(5, dtype=np.int64)
-    if lib().sp_ssq_plan(1 if cplx else 0, n, nframes, rows, nb, what, ptr(out)) != 0:
-        raise SsqRefused("ssq_plan: the shape is refused")
-    d = dict(zip(("fpr", "workgroups", "lds_bytes", "transforms", "fits"), (int(v) for v in out)))
-    d["fits"] = bool(d["fits"])
-    return d
+    return _plan(lib().sp_ssq_plan, ("fpr", "workgroups", "lds_bytes", "transforms", "fits"), SsqRefused, "ssq_plan", 1 if cplx else 0, n,
+                 nframes, rows, nb, what)
 
 
 WVD_MIN_N, WVD_MAX_N, WVD_MAX_NG, WVD_MAX_ROWS, WVD_LDS_MAX = 32, 8192, 255, 65535, 160 * 1024
@@ -1413,28 +1433,17 @@ def wvd_lds_bytes(cross, nfft, nh, ng, hop, cpr, ntimes):
 
 def wvd_check(who, nfft, nh, ng, hop, ntimes, rows, nb, b0=0, scale=1.0, nsig=None, x_ld=None):
     """The refusals of sp_wvd and sp_wvd_plan, before the library is touched."""
-    if nfft < WVD_MIN_N or nfft > WVD_MAX_N or nfft & (nfft - 1):
-        raise WvdRefused("%s: nfft = %d must be a power of two from %d to %d" % (who, nfft, WVD_MIN_N, WVD_MAX_N))
+    _range_check(WvdRefused, who, ("nfft", nfft, WVD_MIN_N, WVD_MAX_N))
     if nh < 1 or not nh & 1 or nh > nfft - 1:
         raise WvdRefused("%s: nh = %d must be odd and lie in 1 .. nfft - 1 = %d" % (who, nh, nfft - 1))
     if ng < 1 or not ng & 1 or ng > WVD_MAX_NG:
         raise WvdRefused("%s: ng = %d must be odd and lie in 1 .. %d" % (who, ng, WVD_MAX_NG))
-    if hop < 1:
-        raise WvdRefused("%s: hop = %d must be at least 1" % (who, hop))
-    if ntimes < 0:
-        raise WvdRefused("%s: ntimes = %d must not be negative" % (who, ntimes))
-    if rows < 0 or rows > WVD_MAX_ROWS:
-        raise WvdRefused("%s: %d rows are outside 0 .. %d" % (who, rows, WVD_MAX_ROWS))
-    if nsig is not None and nsig < 1:
-        raise WvdRefused("%s: the rows must hold at least one sample" % who)
-    if x_ld is not None and x_ld < nsig:
-        raise WvdRefused("%s: x_ld = %d is below nsig = %d" % (who, x_ld, nsig))
+    _range_check(WvdRefused, who, None, hop, ("ntimes", ntimes), (rows, WVD_MAX_ROWS), nsig, x_ld)
     if nb < 1 or nb > nfft:
         raise WvdRefused("%s: nb = %d must lie in 1 .. nfft = %d" % (who, nb, nfft))
     if b0 < 0 or b0 >= nfft:
         raise WvdRefused("%s: b0 = %d lies outside 0 .. nfft - 1 = %d" % (who, b0, nfft - 1))
-    if not np.isfinite(scale):
-        raise WvdRefused("%s: scale must be finite" % who)
+    _range_check(WvdRefused, who, scale=scale)
 
 
 def _wvd_window(who, name, w):
@@ -1447,12 +1456,8 @@ def _wvd_window(who, name, w):
 
 
 def _wvd_plan_raw(who, cross, nfft, nh, ng, hop, ntimes, rows, nb):
-    out = np.zeros(5, dtype=np.int64)
-    if lib().sp_wvd_plan(1 if cross else 0, nfft, nh, ng, hop, ntimes, rows, nb, ptr(out)) != 0:
-        raise WvdRefused("%s: the shape is refused" % who)
-    d = dict(zip(("cpr", "workgroups", "lds_bytes", "transforms", "fits"), (int(v) for v in out)))
-    d["fits"] = bool(d["fits"])
-    return d
+    return _plan(lib().sp_wvd_plan, ("cpr", "workgroups", "lds_bytes", "transforms", "fits"), WvdRefused, who, 1 if cross else 0, nfft, nh,
+                 ng, hop, ntimes, rows, nb)
 
 
 def wvd(x, h, g, hop, first, ntimes, nfft, y=None, b0=0, nb=None, scale=1.0):
@@ -1469,29 +1474,15 @@ def wvd(x, h, g, hop, first, ntimes, nfft, y=None, b0=0, nb=None, scale=1.0):
         raise WvdRefused("wvd: x must have at least one axis")
     if md.code(x) != _ffi.DTYPE_C64:
         raise WvdRefused("wvd: float32 rows are not taken directly: make the record analytic first (pyfft_amd.wigner.spwvd does)")
-    lead = tuple(int(d) for d in x.shape[:-1])
-    rows = 1
-    for d in lead:
-        rows *= d
+    lead, rows = _lead_rows(x.shape)
     nsig = int(x.shape[-1])
     hw, gw = _wvd_window("wvd", "h", h), _wvd_window("wvd", "g", g)
     nb = nfft if nb is None else int(nb)
     wvd_check("wvd", nfft, int(hw.size), int(gw.size), hop, ntimes, rows, nb, b0, scale, nsig)
+    y = _second_record("wvd", WvdRefused, md, x, y)
     cross = y is not None
-    if cross:
-        if _mode(y) is not md:
-            raise TypeError("wvd: x and y must both be numpy arrays or both device tensors")
-        y = md.checked(y)
-        if tuple(y.shape) != tuple(x.shape) or not md.alike(x, y):
-            raise WvdRefused("wvd: y must share x's shape, %s" % md.ALIKE)
     md.bind(x)
-    xs, xld = md.rows(x)
-    ys = None
-    if cross:
-        ys, yld = md.rows(y)
-        if yld != xld:
-            xs, ys = md.samples(xs), md.samples(ys)
-            xld = nsig
+    xs, ys, xld = _paired_rows(md, x, y, nsig)
     plan = _wvd_plan_raw("wvd", cross, nfft, int(hw.size), int(gw.size), hop, ntimes, rows, nb)
     if not plan["fits"]:
         raise WvdRefused("wvd: the LDS of a workgroup, %d bytes, does not fit %d (nfft %d, nh %d, ng %d, hop %d, %d columns per run)"
@@ -1520,40 +1511,22 @@ class CyclicRefused(ValueError, NotImplementedError):
 
 def cyclic_check(who, n, hop, nframes, A, rows, nsig=None, x_ld=None, nu=None, b0=0, nb=None, scale=1.0, first=0):
     """The refusals of sp_cyclic and sp_cyclic_plan, before the library is touched."""
-    if n < CYC_MIN_N or n > CYC_MAX_N or n & (n - 1):
-        raise CyclicRefused("%s: n = %d must be a power of two from %d to %d" % (who, n, CYC_MIN_N, CYC_MAX_N))
-    if hop < 1:
-        raise CyclicRefused("%s: hop = %d must be at least 1" % (who, hop))
-    if nframes < 0:
-        raise CyclicRefused("%s: nframes = %d must not be negative" % (who, nframes))
+    _range_check(CyclicRefused, who, ("n", n, CYC_MIN_N, CYC_MAX_N), hop, ("nframes", nframes))
     if A < 1 or A > CYC_MAX_A:
         raise CyclicRefused("%s: %d cycle frequencies are outside 1 .. %d" % (who, A, CYC_MAX_A))
-    if rows < 0 or rows > CYC_MAX_ROWS:
-        raise CyclicRefused("%s: %d rows are outside 0 .. %d" % (who, rows, CYC_MAX_ROWS))
-    if nsig is not None:
-        if nsig < 1:
-            raise CyclicRefused("%s: the rows must hold at least one sample" % who)
-        if nframes > 0 and (nframes - 1) * hop + n > nsig:
-            raise CyclicRefused("%s: %d frames of %d at hop %d reach outside the %d samples of a row" % (who, nframes, n, hop, nsig))
-    if x_ld is not None and x_ld < nsig:
-        raise CyclicRefused("%s: x_ld = %d is below nsig = %d" % (who, x_ld, nsig))
+    _range_check(CyclicRefused, who, rows=(rows, CYC_MAX_ROWS), nsig=nsig)
+    if nsig is not None and nframes > 0 and (nframes - 1) * hop + n > nsig:
+        raise CyclicRefused("%s: %d frames of %d at hop %d reach outside the %d samples of a row" % (who, nframes, n, hop, nsig))
+    if x_ld is not None:
+        _range_check(CyclicRefused, who, nsig=nsig, x_ld=x_ld)
     if nu is not None and not (np.all(np.isfinite(nu)) and np.all(np.abs(nu) <= 1.0)):
         raise CyclicRefused("%s: every nu must be finite and lie in -1 .. 1 cycles per sample" % who)
     nb = n if nb is None else nb
     if nb < 1 or nb > n or b0 < 0 or b0 >= n:
         raise CyclicRefused("%s: the band of nb = %d bins from b0 = %d lies outside the n = %d bins" % (who, nb, b0, n))
-    if not np.isfinite(scale):
-        raise CyclicRefused("%s: scale must be finite" % who)
+    _range_check(CyclicRefused, who, scale=scale)
     if abs(first) > 1 << 62:
         raise CyclicRefused("%s: first = %d lies beyond +-2^62" % (who, first))
-
-
-def _cyclic_plan_raw(who, cplx, cross, conj, n, hop, nframes, A, rows):
-    out = np.zeros(5, dtype=np.int64)
-    if lib().sp_cyclic_plan(_ffi.DTYPE_C64 if cplx else _ffi.DTYPE_F32, 1 if cross else 0, 1 if conj else 0, n, hop, nframes, A, rows,
-                            ptr(out)) != 0:
-        raise CyclicRefused("%s: the shape is refused" % who)
-    return dict(zip(("fpg", "workgroups", "alpha_per_pass", "passes", "transforms"), (int(v) for v in out)))
 
 
 def cyclic(x, win, hop, nframes, nu, y=None, conj=False, first=0, detrend=True, mean_value=None, b0=0, nb=None, scale=1.0, S=True,
@@ -1574,31 +1547,18 @@ def cyclic(x, win, hop, nframes, nu, y=None, conj=False, first=0, detrend=True, 
         raise CyclicRefused("cyclic: x needs at least one axis, win and nu exactly one")
     if not np.all(np.isfinite(w)):
         raise CyclicRefused("cyclic: the window must be finite")
-    lead = tuple(int(d) for d in x.shape[:-1])
-    rows = 1
-    for d in lead:
-        rows *= d
+    lead, rows = _lead_rows(x.shape)
     nsig, A = int(x.shape[-1]), int(nuv.size)
     nb = n if nb is None else int(nb)
     cyclic_check("cyclic", n, hop, nframes, A, rows, nsig, None, nuv, b0, nb, scale, first)
     if not (S or Pp or Pm):
         raise CyclicRefused("cyclic: no output is asked for")
+    y = _second_record("cyclic", CyclicRefused, md, x, y)
     cross = y is not None
-    if cross:
-        if _mode(y) is not md:
-            raise TypeError("cyclic: x and y must both be numpy arrays or both device tensors")
-        y = md.checked(y)
-        if tuple(y.shape) != tuple(x.shape) or not md.alike(x, y):
-            raise CyclicRefused("cyclic: y must share x's shape, %s" % md.ALIKE)
     md.bind(x)
-    xs, xld = md.rows(x.reshape(rows, nsig) if md.dev and x.ndim != 2 else x)
-    ys = None
-    if cross:
-        ys, yld = md.rows(y.reshape(rows, nsig) if md.dev and y.ndim != 2 else y)
-        if yld != xld:
-            xs, ys = md.samples(xs), md.samples(ys)
-            xld = nsig
-    cplx = md.code(xs) == _ffi.DTYPE_C64
+    if md.dev and x.ndim != 2:              # the leading axes of a tensor as one: its rows keep their pitch where they have one
+        x, y = x.reshape(rows, nsig), y.reshape(rows, nsig) if cross else None
+    xs, ys, xld = _paired_rows(md, x, y, nsig)
     outs = [md.empty(lead + (A, nb), dt, xs) if want else None for want, dt in ((S, "complex64"), (Pp, "float32"), (Pm, "float32"))]
     if nframes == 0:                        # a sum over no frames: the library launches nothing and leaves the outputs as they are
         for o in outs:
@@ -1606,16 +1566,13 @@ def cyclic(x, win, hop, nframes, nu, y=None, conj=False, first=0, detrend=True, 
                 o[...] = 0
         return tuple(outs)
     means = []
-    for v in (xs, ys):
-        m = np.zeros((max(rows, 1), 2), dtype=np.float64)
-        if v is not None and detrend not in (None, False, 0, "none"):
+    for v in (xs, ys) if cross else (xs,):
+        m = np.zeros(max(rows, 1), dtype=np.complex128)             # (re, im) pairs of float64
+        if detrend not in (None, False, 0, "none"):
             if mean_value is not None:
-                m[:] = (complex(mean_value).real, complex(mean_value).imag)
+                m[:] = complex(mean_value)
             else:
-                v2 = v if md.dev else v.reshape(rows, nsig)        # the existing mean pass (sp_mean), row by row
-                for r in range(rows):
-                    mv = complex(mean(v2[r, :nsig]))
-                    m[r] = (mv.real, mv.imag)
+                _row_means(v, rows, nsig, m)
         means.append(m)
     md.call(lib().sp_cyclic, md.addr(xs), md.addr(ys), md.code(xs), md.code(ys) if cross else md.code(xs), xld, nsig, rows, ptr(w), n, hop,
             nframes, first, ptr(nuv), A, 1 if conj else 0, ptr(means[0]), ptr(means[1]) if cross else None, b0, nb, scale,
@@ -1628,7 +1585,8 @@ def cyclic_plan(n, hop, nframes, A, rows=1, cplx=False, cross=False, conj=False)
     transforms (per frame and cycle frequency: 1 in the mirrored form, else 2)."""
     n, hop, nframes, A, rows = int(n), int(hop), int(nframes), int(A), int(rows)
     cyclic_check("cyclic_plan", n, hop, nframes, A, rows)
-    return _cyclic_plan_raw("cyclic_plan", cplx, cross, conj, n, hop, nframes, A, rows)
+    return _plan(lib().sp_cyclic_plan, ("fpg", "workgroups", "alpha_per_pass", "passes", "transforms"), CyclicRefused, "cyclic_plan",
+                 _ffi.DTYPE_C64 if cplx else _ffi.DTYPE_F32, 1 if cross else 0, 1 if conj else 0, n, hop, nframes, A, rows)
 
 
 LOMB_SUB, LOMB_MAX_M, LOMB_MAX_ROWS, LOMB_PASSES, LOMB_LAUNCHES, LOMB_BAD_RECORD = 256, 1 << 24, 65535, 3, 4, -2
@@ -1671,8 +1629,7 @@ def lomb_check(who, N, M, rows, y_ld=None, f=None, t_ref=0.0, mean=None):
         raise LombRefused("%s: N = %d samples are outside 1 .. 2^31 - 1" % (who, N))
     if M < 1 or M > LOMB_MAX_M:
         raise LombRefused("%s: M = %d frequencies are outside 1 .. 2^24" % (who, M))
-    if rows < 0 or rows > LOMB_MAX_ROWS:
-        raise LombRefused("%s: %d rows are outside 0 .. %d" % (who, rows, LOMB_MAX_ROWS))
+    _range_check(LombRefused, who, rows=(rows, LOMB_MAX_ROWS))
     if y_ld is not None and rows > 0 and y_ld < N:
         raise LombRefused("%s: y_ld = %d is below N = %d" % (who, y_ld, N))
     if f is not None and not np.all(np.isfinite(f)):
@@ -1707,8 +1664,7 @@ def _lomb_record(who, t, y, f, weights, t_ref, mean_value):
         raise LombRefused("%s: t and f need exactly one axis, and weights the shape of t" % who)
     if y is not None and (len(y.shape) < 1 or int(y.shape[-1]) != N):
         raise LombRefused("%s: the last axis of y must have the %d samples of t" % (who, N))
-    lead = () if y is None else tuple(int(d) for d in y.shape[:-1])
-    rows = 0 if y is None else int(np.prod(lead, dtype=np.int64))
+    lead, rows = ((), 0) if y is None else _lead_rows(y.shape)
     if mean_value is not None and (np.size(mean_value) not in (1, rows) or not np.all(np.isfinite(mean_value))):
         raise LombRefused("%s: mean_value must be one finite value, or one per row" % who)
     if N >= 1 and t_ref is None:
@@ -1727,9 +1683,8 @@ def _lomb_record(who, t, y, f, weights, t_ref, mean_value):
     mv = np.zeros(rows, dtype=np.float64)
     if mean_value is not None:
         mv[:] = np.asarray(mean_value, dtype=np.float64).reshape(-1) if np.ndim(mean_value) else float(mean_value)
-    else:
-        for r in range(rows):               # the existing mean pass (sp_mean), row by row
-            mv[r] = mean(ys[r, :N])
+    elif rows:
+        _row_means(ys, rows, N, mv)
     lomb_check(who, N, int(fv.size), rows, ld, None, t_ref, mv)
     return md, tv, wv, ys, ld, lead, N, rows, fv, t_ref, mv
 
@@ -1786,8 +1741,8 @@ def lomb_finish(sums, f, floating_mean=True, normalize="normalize"):
         raise LombRefused("lomb_finish: the sums of lomb_sums with rows are required")
     md = _mode(sums.rows)
     fv = np.ascontiguousarray(np.asarray(f), dtype=np.float64)
-    lead = tuple(int(d) for d in sums.rows.shape[:-2])
-    rows, M = int(np.prod(lead, dtype=np.int64)), int(fv.size)
+    lead, rows = _lead_rows(sums.rows.shape, 2)
+    M = int(fv.size)
     if fv.ndim != 1 or tuple(sums.common.shape) != (M, 4) or int(sums.rows.shape[-2]) != M or md.count(sums.totals) != 1 + 2 * rows:
         raise LombRefused("lomb_finish: the sums do not belong to these %d frequencies" % M)
     mv = np.ascontiguousarray(sums.mean, dtype=np.float64)
@@ -1805,10 +1760,8 @@ def lomb_plan(N, M, rows=1):
     """sp_lomb_plan as a dict (host only): rows_per_group, freqs_per_pass, passes, split (sample runs), workgroups."""
     N, M, rows = int(N), int(M), int(rows)
     lomb_check("lomb_plan", N, M, rows)
-    out = np.zeros(5, dtype=np.int64)
-    if lib().sp_lomb_plan(N, M, rows, ptr(out)) != 0:
-        raise LombRefused("lomb_plan: the shape is refused")
-    return dict(zip(("rows_per_group", "freqs_per_pass", "passes", "split", "workgroups"), (int(v) for v in out)))
+    return _plan(lib().sp_lomb_plan, ("rows_per_group", "freqs_per_pass", "passes", "split", "workgroups"), LombRefused, "lomb_plan", N, M,
+                 rows)
 
 
 EIGH_MAX_N = 64
@@ -1845,10 +1798,7 @@ def eigh(A, nvec=None, max_sweeps=30, check=True):
     max_sweeps = int(max_sweeps)
     if max_sweeps < 1:
         raise ValueError("eigh: max_sweeps must be at least 1")
-    lead = shape[:-2]
-    batch = 1
-    for d in lead:
-        batch *= int(d)
+    lead, batch = _lead_rows(shape, 2)
     md = _enter(A)
     a = md.cast(A, "complex128")
     w = md.empty(lead + (n,), "float64", a)

@@ -19,11 +19,13 @@ except Exception:                       # pragma: no cover
 
 # entries whose result the engine reads: answered by the built library, which needs no GPU for them; not recorded
 HOST_ARITHMETIC = ("sp_xcorr_frames_len", "sp_csd_epilogue_doubles", "sp_ddc_tile", "sp_upfirdn_tile", "sp_pfb_synth_plan", "sp_skf_plan",
-                   "sp_welch_blocks_plan", "sp_cwt_plan", "sp_eigh_plan", "sp_version", "sp_max_wg_fft")
+                   "sp_welch_blocks_plan", "sp_cwt_plan", "sp_eigh_plan", "sp_version", "sp_max_wg_fft", "sp_wct_plan", "sp_ssq_plan",
+                   "sp_wvd_plan", "sp_cyclic_plan", "sp_lomb_plan", "sp_last_passes")
 REFUSAL_TYPES = (ValueError, TypeError, NotImplementedError)
 MODES = ("host", "dev")
 
 _INTS, _FLOATS = (int, np.integer), (float, np.floating)
+DECLARED = {name: sig for table in _ffi.TABLES for name, sig in table.items()}      # every entry of the six signature tables
 
 
 class StandIn:
@@ -38,15 +40,15 @@ class StandIn:
         if self._real is None:
             self._real = ctypes.CDLL(_ffi.LIB_PATH)
         fn = getattr(self._real, name)
-        fn.restype, fn.argtypes = _ffi.SIGNATURES[name]
+        fn.restype, fn.argtypes = DECLARED[name]
         return fn
 
     def __getattr__(self, name):
-        if name not in _ffi.SIGNATURES:
+        if name not in DECLARED:
             raise AttributeError(name)
         if name in HOST_ARITHMETIC:
             return self._delegate(name)
-        argtypes = _ffi.SIGNATURES[name][1]
+        argtypes = DECLARED[name][1]
 
         def record(*args):
             if len(args) != len(argtypes):
@@ -502,7 +504,221 @@ case("csd_epilogue", "one-channel", lambda A: K(A((NB1,), F64), A((NB1,), F64), 
 case("csd_epilogue", "casts", lambda A: K(A((NB1,), F32), A((2, NB1), F32), A((2, NB1), C64), NFFT, True, 1.5))
 case("csd_epilogue", "complex-powers", lambda A: K(A((NB1,), C128), A((2, NB1), C128), A((2, NB1), C128), NFFT, True, 1.5))
 
-FUNCTIONS = ("fft", "mean", "welch_psd", "welch_accum", "welch_export", "welch_apply", "welch_finish", "welch_csd", "csd_matrix",
+
+def squared(a):
+    """a * a in a's own memory, so that a pointer to it still resolves: weights, which must not be negative"""
+    a *= a
+    return a
+
+
+def as_tensor(A, a):
+    """an array of the case as a tensor in both modes (host mode: on the same memory)"""
+    return a if A.dev else torch.from_numpy(a)
+
+
+# -- cross-wavelet spectra and wavelet coherence
+WN = 400                                       # the wavelet record; the strided views keep WN of WN + 3 and WN + 5
+case("wct_time", "coherence", lambda A: K(A((2, WN), F32), A((2, WN), F32), SCALES, "morlet", 6.0, CL, CM, 16))
+case("wct_time", "xwt-paul-c64", lambda A: K(A((WN,), C64), A((WN,), C64), SCALES, "paul", 4.0, CL, CM, xwt=True))
+case("wct_time", "strided-rows-two-pitches", lambda A: K(A((3, WN + 3), C64)[:, :WN], A((3, WN + 5), C64)[:, :WN], SCALES, "morlet", 6.0,
+                                                           CL, CM, 16))
+case("wct_time", "3d", lambda A: K(A((2, 2, WN), F32), A((2, 2, WN), F32), SCALES, "morlet", 6.0, CL, CM, 16))
+case("wct_time", "f64", lambda A: K(A((WN,), F64), A((WN,), F64), SCALES, "morlet", 6.0, CL, CM, 16))
+case("wct_time", "host-y", lambda A: K(A((WN,), F32), A((WN,), F32, host=True), SCALES, "morlet", 6.0, CL, CM, 16))
+case("wct_time", "shape-refused", lambda A: K(A((WN,), F32), A((WN - 1,), F32), SCALES, "morlet", 6.0, CL, CM, 16))
+case("wct_time", "dtype-refused", lambda A: K(A((WN,), F32), A((WN,), C64), SCALES, "morlet", 6.0, CL, CM, 16))
+case("wct_time", "Mg-xwt-refused", lambda A: K(A((WN,), F32), A((WN,), F32), SCALES, "morlet", 6.0, CL, CM, 16, xwt=True))
+case("wct_time", "paul-coherence-refused", lambda A: K(A((WN,), F32), A((WN,), F32), SCALES, "paul", 4.0, CL, CM, 16))
+case("wct_time", "margin-refused", lambda A: K(A((WN,), F32), A((WN,), F32), SCALES, "morlet", 6.0, CL, 100, 16))
+WTAPS = [0.25, 0.5, 0.25]
+case("wct_scale", "r2-phase", lambda A: K(A((3, WN, 4), F32), WTAPS))
+case("wct_scale", "spectra", lambda A: K(A((3, WN + 1, 4), F32), WTAPS, spectra=True))
+case("wct_scale", "lead", lambda A: K(A((2, 2, 3, WN, 4), F32), WTAPS))
+case("wct_scale", "strided", lambda A: K(A((3, WN, 8), F32)[..., :4], WTAPS))
+case("wct_scale", "f64", lambda A: K(A((3, WN, 4), F64), WTAPS))
+case("wct_scale", "last-axis-refused", lambda A: K(A((3, WN, 3), F32), WTAPS))
+case("wct_scale", "2d-refused", lambda A: K(A((WN, 4), F32), WTAPS))
+case("wct_scale", "taps-empty-refused", lambda A: K(A((3, WN, 4), F32), []))
+case("wct_scale", "rows-0-refused", lambda A: K(A((0, 3, WN, 4), F32), WTAPS))
+
+# -- synchrosqueezing and the reassignment fields
+SSQ_H = np.hanning(NFFT)
+SSQ_DH, SSQ_TH = np.gradient(SSQ_H), (np.arange(NFFT) - NFFT // 2) * SSQ_H
+case("ssq", "f32-T", lambda A: K(A((2, N), F32), SSQ_H, SSQ_DH, HOP, -NFFT // 2, NFR))
+case("ssq", "c64-band", lambda A: K(A((N,), C64), SSQ_H, SSQ_DH, HOP, 0, NFR, th=SSQ_TH, b0=60, nb=9, P=True, IF=True))
+case("ssq", "GD-only-segmean-gamma-rel", lambda A: K(A((N,), F32), SSQ_H, SSQ_DH, HOP, 0, NFR, th=SSQ_TH, T=False, GD=True, segmean=True,
+                                                      gamma=0.5, rel=1e-3))
+case("ssq", "strided-rows", lambda A: K(A((3, N + 3), F32)[:, :N], SSQ_H, SSQ_DH, HOP, 0, NFR))
+case("ssq", "3d", lambda A: K(A((2, 2, N), F32), SSQ_H, SSQ_DH, HOP, 0, NFR))
+case("ssq", "f64", lambda A: K(A((N,), F64), SSQ_H, SSQ_DH, HOP, 0, NFR))
+case("ssq", "th-missing-refused", lambda A: K(A((N,), F32), SSQ_H, SSQ_DH, HOP, 0, NFR, IF=True))
+case("ssq", "no-output-refused", lambda A: K(A((N,), F32), SSQ_H, SSQ_DH, HOP, 0, NFR, T=False))
+case("ssq", "lds-refused", lambda A: K(A((N,), C64), SSQ_H, SSQ_DH, HOP, 0, NFR, th=SSQ_TH, P=True, IF=True))
+case("ssq", "band-refused", lambda A: K(A((N,), F32), SSQ_H, SSQ_DH, HOP, 0, NFR, b0=30, nb=9))
+case("ssq", "n-refused", lambda A: K(A((N,), F32), np.hanning(48), np.hanning(48), 0, 0, NFR))         # n before hop
+case("ssq", "hop-refused", lambda A: K(A((65536, 1), F32), SSQ_H, SSQ_DH, 0, 0, -1))                    # hop before nframes and rows
+case("ssq", "nframes-refused", lambda A: K(A((65536, 1), F32), SSQ_H, SSQ_DH, HOP, 0, -1))              # nframes before rows
+case("ssq", "rows-refused", lambda A: K(A((65536, 0), F32), SSQ_H, SSQ_DH, HOP, 0, NFR))                # rows before the empty rows
+case("ssq", "empty-rows-refused", lambda A: K(A((2, 0), F32), SSQ_H, SSQ_DH, HOP, 0, NFR, gamma=-1.0))  # the empty rows before gamma
+case("ssq", "gamma-refused", lambda A: K(A((N,), F32), SSQ_H, SSQ_DH, HOP, 0, NFR, gamma=-1.0, rel=float("nan")))
+case("ssq", "rel-refused", lambda A: K(A((N,), F32), SSQ_H, SSQ_DH, HOP, 0, NFR, rel=float("nan")))
+case("ssq", "dh-refused", lambda A: K(A((N,), F32), SSQ_H, SSQ_DH[:-1], HOP, 0, NFR))
+case("ssq", "0d", lambda A: K(A((), F32), SSQ_H, SSQ_DH, HOP, 0, NFR))
+EDGES = [[2.0, 9.5], [9.5, 30.0]]
+FRAME_EDGES = np.tile(np.array(EDGES)[:, None, :], (1, NFR, 1))
+for fn, front in (("ssq_bands", lambda A, x: (x, SSQ_H, SSQ_DH, HOP, -NFFT // 2, NFR)), ("ssq_sum", lambda A, x: (x, NFFT))):
+    rec = (lambda A: A((2, N), F32)) if fn == "ssq_bands" else (lambda A: A((2, NFR, NFFT // 2 + 1), C64))
+    case(fn, "fixed-edges", lambda A, front=front, rec=rec: K(*front(A, rec(A)), EDGES, scale=0.5))
+    case(fn, "frame-edges", lambda A, front=front, rec=rec: K(*front(A, rec(A)), FRAME_EDGES))
+    case(fn, "frame-edges-tensor", lambda A, front=front, rec=rec: K(*front(A, rec(A)), as_tensor(A, A((2, NFR, 2), F32))))
+    case(fn, "frame-edges-tensor-f64", lambda A, front=front, rec=rec: K(*front(A, rec(A)), as_tensor(A, A((2, NFR, 2), F64))))
+    case(fn, "frame-edges-host-tensor", lambda A, front=front, rec=rec: K(*front(A, rec(A)), torch.from_numpy(A((2, NFR, 2), F32, host=True))))
+    case(fn, "one-band", lambda A, front=front, rec=rec: K(*front(A, rec(A)), (2.0, 9.5)))
+    case(fn, "nine-bands-refused", lambda A, front=front, rec=rec: K(*front(A, rec(A)), [[k, k + 1.0] for k in range(9)]))
+    case(fn, "frame-count-refused", lambda A, front=front, rec=rec: K(*front(A, rec(A)), FRAME_EDGES[:, :-1]))
+    case(fn, "tensor-frame-count-refused", lambda A, front=front, rec=rec: K(*front(A, rec(A)), as_tensor(A, A((2, NFR - 1, 2), F32))))
+    case(fn, "edges-nonfinite-refused", lambda A, front=front, rec=rec: K(*front(A, rec(A)), [[2.0, float("inf")]]))
+    case(fn, "scale-refused", lambda A, front=front, rec=rec: K(*front(A, rec(A)), EDGES, scale=float("nan")))
+case("ssq_bands", "c64-strided-segmean", lambda A: K(A((3, N + 3), C64)[:, :N], SSQ_H, SSQ_DH, HOP, 0, NFR, EDGES, segmean=True, gamma=0.5,
+                                                      rel=1e-3))
+case("ssq_bands", "f64", lambda A: K(A((N,), F64), SSQ_H, SSQ_DH, HOP, 0, NFR, EDGES))
+case("ssq_bands", "hop-refused", lambda A: K(A((N,), F32), SSQ_H, SSQ_DH, 0, 0, NFR, EDGES))
+case("ssq_sum", "half", lambda A: K(A((2, 2, NFR, NFFT // 2 + 1), C64), NFFT, EDGES, half=True))
+case("ssq_sum", "b0", lambda A: K(A((NFR, 20), C64), NFFT, FRAME_EDGES, b0=3, scale=2.0))
+case("ssq_sum", "strided", lambda A: K(A((NFR, 40), C64)[:, :20], NFFT, EDGES, b0=3))
+case("ssq_sum", "f64", lambda A: K(A((NFR, 20), F64), NFFT, EDGES))
+case("ssq_sum", "1d-refused", lambda A: K(A((20,), C64), NFFT, EDGES))
+case("ssq_sum", "n-refused", lambda A: K(A((NFR, 20), C64), 48, EDGES))
+case("ssq_sum", "band-refused", lambda A: K(A((NFR, 20), C64), NFFT, EDGES, b0=NFFT))
+
+# -- the smoothed pseudo Wigner-Ville distribution
+WVD_H, WVD_G, NT = np.hanning(31), np.hanning(9), 16
+case("wvd", "auto", lambda A: K(A((2, N), C64), WVD_H, WVD_G, HOP, 0, NT, NFFT))
+case("wvd", "cross", lambda A: K(A((2, N), C64), WVD_H, WVD_G, HOP, 0, NT, NFFT, y=A((2, N), C64)))
+case("wvd", "cross-y-other-pitch", lambda A: K(A((2, N + 3), C64)[:, :N], WVD_H, WVD_G, HOP, 0, NT, NFFT, y=A((2, N + 5), C64)[:, :N]))
+case("wvd", "cross-same-pitch", lambda A: K(A((2, N + 3), C64)[:, :N], WVD_H, WVD_G, HOP, 0, NT, NFFT, y=A((2, N + 3), C64)[:, :N]))
+case("wvd", "band-first-scale", lambda A: K(A((N,), C64), WVD_H, WVD_G, HOP, -7, NT, NFFT, b0=60, nb=9, scale=0.5))
+case("wvd", "strided-rows", lambda A: K(A((3, N + 3), C64)[:, :N], WVD_H, WVD_G, HOP, 0, NT, NFFT))
+case("wvd", "3d-cross", lambda A: K(A((2, 2, N), C64), WVD_H, WVD_G, HOP, 0, NT, NFFT, y=A((2, 2, N), C64)))
+case("wvd", "c128", lambda A: K(A((N,), C128), WVD_H, WVD_G, HOP, 0, NT, NFFT))
+case("wvd", "f32-refused", lambda A: K(A((N,), F32), WVD_H, WVD_G, HOP, 0, NT, NFFT))
+case("wvd", "nh-even-refused", lambda A: K(A((N,), C64), np.hanning(32), WVD_G, HOP, 0, NT, NFFT))
+case("wvd", "ng-257-refused", lambda A: K(A((N,), C64), WVD_H, np.hanning(257), HOP, 0, NT, NFFT))
+case("wvd", "lds-refused", lambda A: K(A((N,), C64), WVD_H, WVD_G, 100000, 0, 2, NFFT))
+case("wvd", "y-shape-refused", lambda A: K(A((2, N), C64), WVD_H, WVD_G, HOP, 0, NT, NFFT, y=A((2, N - 1), C64)))
+case("wvd", "y-dtype-refused", lambda A: K(A((2, N), C64), WVD_H, WVD_G, HOP, 0, NT, NFFT, y=A((2, N), F32)))
+case("wvd", "host-y", lambda A: K(A((2, N), C64), WVD_H, WVD_G, HOP, 0, NT, NFFT, y=A((2, N), C64, host=True)))
+case("wvd", "g-missing-refused", lambda A: K(A((N,), C64), WVD_H, None, HOP, 0, NT, NFFT))
+case("wvd", "nfft-refused", lambda A: K(A((N,), C64), WVD_H, WVD_G, 0, 0, NT, 48))                       # nfft before hop
+case("wvd", "hop-refused", lambda A: K(A((65536, 1), C64), WVD_H, WVD_G, 0, 0, -1, NFFT))                 # hop before ntimes and rows
+case("wvd", "ntimes-refused", lambda A: K(A((65536, 1), C64), WVD_H, WVD_G, HOP, 0, -1, NFFT))            # ntimes before rows
+case("wvd", "rows-refused", lambda A: K(A((65536, 0), C64), WVD_H, WVD_G, HOP, 0, NT, NFFT))              # rows before the empty rows
+case("wvd", "empty-rows-refused", lambda A: K(A((2, 0), C64), WVD_H, WVD_G, HOP, 0, NT, NFFT, nb=0))      # the empty rows before nb
+case("wvd", "nb-refused", lambda A: K(A((N,), C64), WVD_H, WVD_G, HOP, 0, NT, NFFT, nb=NFFT + 1, b0=NFFT))
+case("wvd", "b0-refused", lambda A: K(A((N,), C64), WVD_H, WVD_G, HOP, 0, NT, NFFT, b0=NFFT, scale=float("inf")))
+case("wvd", "scale-refused", lambda A: K(A((N,), C64), WVD_H, WVD_G, HOP, 0, NT, NFFT, scale=float("inf")))
+
+# -- spectral correlation (the row means it computes itself are read from a zeroed buffer under the stand-in: they replay alike)
+NU = [0.0, 0.1, -0.25, 0.5]
+case("cyclic", "f32-own-means", lambda A: K(A((2, N), F32), WIN, HOP, NFR, NU))
+case("cyclic", "c64-conj", lambda A: K(A((N,), C64), WIN, HOP, NFR, NU, conj=True, mean_value=0.25 - 0.5j))
+case("cyclic", "y-own-means", lambda A: K(A((2, N), F32), WIN, HOP, NFR, NU, y=A((2, N), F32)))
+case("cyclic", "y-other-pitch", lambda A: K(A((2, N + 3), C64)[:, :N], WIN, HOP, NFR, NU, y=A((2, N + 5), C64)[:, :N], mean_value=0.5))
+case("cyclic", "strided-rows-own-means", lambda A: K(A((3, N + 3), F32)[:, :N], WIN, HOP, NFR, NU))
+case("cyclic", "no-detrend", lambda A: K(A((2, N), F32), WIN, HOP, NFR, NU, detrend=False))
+case("cyclic", "mean-value-band-first-scale", lambda A: K(A((N,), F32), WIN, HOP, NFR - 1, NU, mean_value=0.5, first=7, b0=60, nb=9,
+                                                           scale=0.5))
+case("cyclic", "nu-scalar", lambda A: K(A((N,), F32), WIN, HOP, NFR, 0.1, mean_value=0.5))
+case("cyclic", "nframes-0", lambda A: K(A((2, N), F32), WIN, HOP, 0, NU))
+case("cyclic", "S-Pm", lambda A: K(A((N,), F32), WIN, HOP, NFR, NU, mean_value=0.5, Pp=False))
+case("cyclic", "Pp-only", lambda A: K(A((N,), F32), WIN, HOP, NFR, NU, mean_value=0.5, S=False, Pm=False))
+case("cyclic", "3d-own-means", lambda A: K(A((2, 2, N), F32), WIN, HOP, NFR, NU))
+case("cyclic", "3d-y", lambda A: K(A((2, 2, N), C64), WIN, HOP, NFR, NU, y=A((2, 2, N), C64), mean_value=0.5j))
+case("cyclic", "f64", lambda A: K(A((N,), F64), WIN, HOP, NFR, NU, mean_value=0.5))
+case("cyclic", "no-output-refused", lambda A: K(A((N,), F32), WIN, HOP, NFR, NU, S=False, Pp=False, Pm=False))
+case("cyclic", "nu-refused", lambda A: K(A((N,), F32), WIN, HOP, NFR, [0.0, 1.5]))
+case("cyclic", "nu-2d-refused", lambda A: K(A((N,), F32), WIN, HOP, NFR, [NU]))
+case("cyclic", "reach-refused", lambda A: K(A((N,), F32), WIN, HOP, NFR + 1, NU))
+case("cyclic", "y-shape-refused", lambda A: K(A((2, N), F32), WIN, HOP, NFR, NU, y=A((N,), F32)))
+case("cyclic", "y-dtype-refused", lambda A: K(A((2, N), F32), WIN, HOP, NFR, NU, y=A((2, N), C64)))
+case("cyclic", "host-y", lambda A: K(A((2, N), F32), WIN, HOP, NFR, NU, y=A((2, N), F32, host=True)))
+case("cyclic", "n-refused", lambda A: K(A((N,), F32), np.hanning(48), 0, NFR, NU))                       # n before hop
+case("cyclic", "hop-refused", lambda A: K(A((65536, 1), F32), WIN, 0, -1, NU))                            # hop before nframes and rows
+case("cyclic", "nframes-refused", lambda A: K(A((65536, 1), F32), WIN, HOP, -1, []))                      # nframes before A
+case("cyclic", "A-refused", lambda A: K(A((65536, 1), F32), WIN, HOP, NFR, []))                           # A before rows
+case("cyclic", "rows-refused", lambda A: K(A((65536, 0), F32), WIN, HOP, NFR, NU))                        # rows before the empty rows
+case("cyclic", "empty-rows-refused", lambda A: K(A((2, 0), F32), WIN, HOP, NFR, [1.5]))                   # the empty rows before nu
+case("cyclic", "band-refused", lambda A: K(A((N,), F32), WIN, HOP, NFR, NU, b0=NFFT, scale=float("inf")))
+case("cyclic", "scale-refused", lambda A: K(A((N,), F32), WIN, HOP, NFR, NU, scale=float("inf"), first=1 << 63))
+case("cyclic", "first-refused", lambda A: K(A((N,), F32), WIN, HOP, NFR, NU, first=1 << 63))
+
+# -- Lomb-Scargle spectra (every case gives mean_value: the default is read back from the library and judged in Python)
+FREQ = np.linspace(0.01, 0.5, 40)
+NF = FREQ.size
+case("lomb", "plain", lambda A: K(A((N,), F64), A((2, N), F32), FREQ, mean_value=0.25))
+case("lomb", "weights-power-row-means", lambda A: K(A((N,), F64), A((2, N), F32), FREQ, weights=squared(A((N,), F64)), normalize="power",
+                                                     mean_value=[0.25, -0.5]))
+case("lomb", "amplitude-fixed-mean-t-ref", lambda A: K(A((N,), F64), A((N,), F32), FREQ, floating_mean=False, normalize="amplitude", t_ref=0.5,
+                                                        mean_value=0.25))
+case("lomb", "normalize-bool", lambda A: K(A((N,), F64), A((N,), F32), FREQ, normalize=False, mean_value=0.25))
+case("lomb", "3d-row-means", lambda A: K(A((N,), F64), A((2, 2, N), F32), FREQ, mean_value=np.array([0.25, -0.5, 0.0, 1.0])))
+case("lomb", "strided-rows", lambda A: K(A((N,), F64), A((3, N + 3), F32)[:, :N], FREQ, mean_value=0.25))
+case("lomb", "rows-0", lambda A: K(A((N,), F64), A((0, N), F32), FREQ, mean_value=0.25))
+case("lomb", "f-tensor", lambda A: K(A((N,), F64), A((N,), F32), torch.from_numpy(FREQ.copy()), mean_value=0.25))
+case("lomb", "t-f32", lambda A: K(A((N,), F32), A((N,), F32), FREQ, mean_value=0.25))
+case("lomb", "y-f64", lambda A: K(A((N,), F64), A((N,), F64), FREQ, mean_value=0.25))
+case("lomb", "weights-f32", lambda A: K(A((N,), F64), A((N,), F32), FREQ, weights=squared(A((N,), F32)), mean_value=0.25))
+case("lomb", "host-y", lambda A: K(A((N,), F64), A((N,), F32, host=True), FREQ, mean_value=0.25))
+case("lomb", "host-weights", lambda A: K(A((N,), F64), A((N,), F32), FREQ, weights=squared(A((N,), F64, host=True)), mean_value=0.25))
+case("lomb", "normalize-refused", lambda A: K(A((N,), F64), A((N,), F32), FREQ, normalize="psd", mean_value=0.25))
+case("lomb", "y-none-refused", lambda A: K(A((N,), F64), None, FREQ, mean_value=0.25))
+case("lomb", "y-length-refused", lambda A: K(A((N,), F64), A((N - 1,), F32), FREQ, mean_value=0.25))
+case("lomb", "t-2d-refused", lambda A: K(A((2, N), F64), A((2, N), F32), FREQ, mean_value=0.25))
+case("lomb", "weights-shape-refused", lambda A: K(A((N,), F64), A((N,), F32), FREQ, weights=squared(A((N - 1,), F64)), mean_value=0.25))
+case("lomb", "mean-count-refused", lambda A: K(A((N,), F64), A((2, N), F32), FREQ, mean_value=[0.25, 0.5, 0.75]))
+case("lomb", "mean-nonfinite-refused", lambda A: K(A((N,), F64), A((2, N), F32), FREQ, mean_value=float("nan")))
+case("lomb", "f-empty-refused", lambda A: K(A((N,), F64), A((N,), F32), FREQ[:0], mean_value=0.25))
+case("lomb", "f-nonfinite-refused", lambda A: K(A((N,), F64), A((N,), F32), [0.1, float("inf")], mean_value=0.25))
+case("lomb", "t-ref-refused", lambda A: K(A((N,), F64), A((N,), F32), FREQ, t_ref=float("inf"), mean_value=0.25))
+case("lomb", "t-empty-refused", lambda A: K(A((0,), F64), A((0,), F32), FREQ, mean_value=0.25))
+case("lomb_sums", "plain", lambda A: K(A((N,), F64), A((2, N), F32), FREQ, mean_value=0.25))
+case("lomb_sums", "y-none", lambda A: K(A((N,), F64), None, FREQ, mean_value=0.0))
+case("lomb_sums", "weights-wnorm-t-ref", lambda A: K(A((N,), F64), A((N,), F32), FREQ, weights=squared(A((N,), F64)), t_ref=0.5,
+                                                      mean_value=0.25, wnorm=2.0))
+case("lomb_sums", "3d-row-means", lambda A: K(A((N,), F64), A((2, 2, N), F32), FREQ, mean_value=np.array([0.25, -0.5, 0.0, 1.0])))
+case("lomb_sums", "strided-rows", lambda A: K(A((N,), F64), A((3, N + 3), F32)[:, :N], FREQ, mean_value=0.25))
+case("lomb_sums", "rows-0", lambda A: K(A((N,), F64), A((0, N), F32), FREQ, mean_value=0.25))
+case("lomb_sums", "t-f32", lambda A: K(A((N,), F32), A((N,), F32), FREQ, mean_value=0.25))
+case("lomb_sums", "wnorm-refused", lambda A: K(A((N,), F64), A((N,), F32), FREQ, mean_value=0.25, wnorm=0.0))
+case("lomb_sums", "host-y", lambda A: K(A((N,), F64), A((N,), F32, host=True), FREQ, mean_value=0.25))
+case("lomb_sums", "y-length-refused", lambda A: K(A((N,), F64), A((N - 1,), F32), FREQ, mean_value=0.25))
+
+
+def sums(A, lead=(2,), dt=F64, mean=None, nf=NF):
+    """a LombSums as lomb_sums leaves it for rows of the shape `lead`"""
+    rows = int(np.prod(lead))
+    mean = np.linspace(0.25, 0.5, rows) if mean is None else np.asarray(mean, dtype=np.float64)
+    return engine.LombSums(A((nf, 4), dt), A(tuple(lead) + (nf, 2), dt), A((1 + 2 * rows,), dt), mean, 0.5, N)
+
+
+for nz in ("power", "normalize", "amplitude"):
+    case("lomb_finish", nz, lambda A, nz=nz: K(sums(A), FREQ, normalize=nz))
+case("lomb_finish", "fixed-mean-int", lambda A: K(sums(A), FREQ, floating_mean=False, normalize=2))
+case("lomb_finish", "lead", lambda A: K(sums(A, (2, 2)), FREQ))
+case("lomb_finish", "rows-0", lambda A: K(sums(A, (0,)), FREQ))
+case("lomb_finish", "f32-sums", lambda A: K(sums(A, dt=F32), FREQ))
+case("lomb_finish", "strided-sums", lambda A: K(engine.LombSums(A((NF, 8), F64)[:, :4], A((2, NF, 4), F64)[..., :2], A((10,), F64)[::2],
+                                                                np.array([0.25, 0.5]), 0.5, N), FREQ))
+case("lomb_finish", "other-f-refused", lambda A: K(sums(A), FREQ[:-1]))
+case("lomb_finish", "totals-refused", lambda A: K(sums(A)._replace(totals=A((4,), F64)), FREQ))
+case("lomb_finish", "no-rows-refused", lambda A: K(sums(A)._replace(rows=None), FREQ))
+case("lomb_finish", "not-sums-refused", lambda A: K((A((NF, 4), F64), A((2, NF, 2), F64), A((5,), F64)), FREQ))
+case("lomb_finish", "normalize-refused", lambda A: K(sums(A), FREQ, normalize="psd"))
+case("lomb_finish", "mean-nonfinite-refused", lambda A: K(sums(A, mean=[0.25, float("nan")]), FREQ))
+case("lomb_finish", "N-refused", lambda A: K(sums(A)._replace(N=0), FREQ))
+
+FUNCTIONS = ("fft", "mean","welch_psd", "welch_accum", "welch_export", "welch_apply", "welch_finish", "welch_csd", "csd_matrix",
              "channel_means", "stft_frames", "istft_frames", "bispectrum", "multitaper", "czt", "zoom_welch", "ddc", "upfirdn", "pfb",
              "pfb_synth", "stft_cog", "hilbert_rows", "frame_sum", "spectral_filter_rows", "xcorr_normalised", "xcorr_frames", "skf",
-             "welch_blocks", "cwt", "icwt_sum", "eigh", "fir_filter", "biquad_filter", "sos_filter", "sos_filtfilt", "csd_epilogue")
+             "welch_blocks", "cwt", "icwt_sum", "eigh", "fir_filter", "biquad_filter", "sos_filter", "sos_filtfilt", "csd_epilogue",
+             "wct_time", "wct_scale", "ssq", "ssq_bands", "ssq_sum", "wvd", "cyclic", "lomb", "lomb_sums", "lomb_finish")

@@ -4,8 +4,8 @@ values in device tensors (mem = 1, the caller's own pointers).
 The calls are the case table of tests/engine_trace.py (CASES: every engine function, records of 512 samples, 64-point frames) and
 the cases below it here, which reach what the table does not: the long path of sp_welch_csd (a window of 4097 points, the shortest
 that one workgroup does not transform), sp_welch_finish and sp_welch_apply with a given mean / state next to an odd and an even
-number of bins (one- and two-sided), every subset of the four optional outputs of sp_cwt and sp_ssq, and the wavelet-coherence and
-synchrosqueezing entries the table leaves out.  The values come from a generator seeded by the case, the same in both modes, so a
+number of bins (one- and two-sided), every subset of the four optional outputs of sp_cwt and sp_ssq, and the row means sp_cyclic,
+sp_lomb and sp_lomb_sums compute by default and read back from the device (every lomb case of the table gives mean_value).  The values come from a generator seeded by the case, the same in both modes, so a
 piece copied from a wrong offset reads other values.
 
 Per case: a refusal the golden engine trace records for a mode (raised by engine.py before the library is reached; the two modes
@@ -65,17 +65,13 @@ for m in range(16):
     tag = "".join(c for c, on in zip("TPIG", b) if on) or "none"
     extra("ssq", "subset-" + tag, lambda A, b=b: T.K(A((2, N), F32), SSQ_H, SSQ_DH, HOP, -NFFT // 2, NFR, th=SSQ_TH, T=b[0], P=b[1],
                                                       IF=b[2], GD=b[3], rel=1e-3))
-extra("ssq", "c64-band", lambda A: T.K(A((N,), C64), SSQ_H, SSQ_DH, HOP, 0, NFR, th=SSQ_TH, b0=60, nb=9, P=True, IF=True))
-# the entries of include/spectral_tfr.h the table leaves out
-EDGES = [[2.0, 9.5], [9.5, 30.0]]
-extra("ssq_bands", "fixed-edges", lambda A: T.K(A((2, N), F32), SSQ_H, SSQ_DH, HOP, -NFFT // 2, NFR, EDGES, scale=0.5))
-extra("ssq_bands", "frame-edges", lambda A: T.K(A((N,), C64), SSQ_H, SSQ_DH, HOP, 0, NFR, np.tile(np.array(EDGES)[:, None, :], (1, NFR, 1))))
-extra("ssq_sum", "fixed-edges", lambda A: T.K(A((2, NFR, NFFT // 2 + 1), C64), NFFT, EDGES, half=True))
-extra("ssq_sum", "frame-edges", lambda A: T.K(A((NFR, 20), C64), NFFT, np.tile(np.array(EDGES)[:, None, :], (1, NFR, 1)), b0=3, scale=2.0))
-extra("wct_time", "coherence", lambda A: T.K(A((2, 400), F32), A((2, 400), F32), T.SCALES, "morlet", 6.0, T.CL, T.CM, 16))
-extra("wct_time", "xwt-c64", lambda A: T.K(A((400,), C64), A((400,), C64), T.SCALES, "paul", 4.0, T.CL, T.CM, xwt=True))
-extra("wct_scale", "r2-phase", lambda A: T.K(A((2, 3, 400, 4), F32), [0.25, 0.5, 0.25]))
-extra("wct_scale", "spectra", lambda A: T.K(A((3, 401, 4), F32), [0.25, 0.5, 0.25], spectra=True))
+# the row means sp_cyclic, sp_lomb and sp_lomb_sums take off by default: computed on the device, read back and judged in Python
+extra("cyclic", "own-means", lambda A: T.K(A((2, N), F32), WIN, HOP, NFR, T.NU))
+extra("cyclic", "own-means-y-c64", lambda A: T.K(A((2, N), C64), WIN, HOP, NFR, T.NU, y=A((2, N), C64), conj=True))
+extra("lomb", "own-means", lambda A: T.K(A((N,), F64), A((2, N), F32), T.FREQ))
+extra("lomb", "own-means-weights-3d", lambda A: T.K(A((N,), F64), A((2, 2, N), F32), T.FREQ, weights=T.squared(A((N,), F64)),
+                                                     normalize="amplitude"))
+extra("lomb_sums", "own-means", lambda A: T.K(A((N,), F64), A((2, N), F32), T.FREQ))
 
 ALL = list(T.CASES) + EXTRA
 IDS = ["%s/%s" % (c[1], c[0]) for c in ALL]
@@ -183,7 +179,7 @@ def golden_refusals():
 
 
 def test_the_cases_reach_what_the_table_does_not():
-    assert len(T.CASES) == 251 and len({c[1] for c in T.CASES}) == 36
+    assert len(T.CASES) == 425 and len({c[1] for c in T.CASES}) == 46
     # one workgroup transforms powers of two up to max_wg_fft() and, by Bluestein, other lengths n with 2 n - 1 below it
     assert LWIN.size == 4097 and 2 * 4096 - 1 <= E.max_wg_fft() < 2 * LWIN.size - 1
     assert len({i for i in IDS if i.startswith(("cwt/subset-", "ssq/subset-"))}) == 32

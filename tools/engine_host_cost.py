@@ -3,7 +3,10 @@
 samples (nfft 256, hop 128) and the same on a numpy array, perf_counter around each loop with a torch.cuda.synchronize() before and
 after it.  One line: label, microseconds per call on the device tensor and on the host array.
 
-  python tools/engine_host_cost.py [TREE [LABEL]]
+  python tools/engine_host_cost.py [TREE [LABEL [ENTRY]]]
+
+ENTRY (default welch_psd) may also be cyclic (the same record and frames, 4 cycle frequencies, mean_value given so that it is one
+library call) or ssq (the same record and frames, T only).
 
 TREE (default: this repository) is where pyfft_amd is imported from, so that the Python files of another commit, unpacked elsewhere and
 pointed at the same library with SP_LIB_PATH, can be timed in the same session: profiles/engine_host_cost.txt."""
@@ -13,6 +16,7 @@ import time
 
 root = os.path.abspath(sys.argv[1] if len(sys.argv) > 1 else os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 label = sys.argv[2] if len(sys.argv) > 2 else root
+entry = sys.argv[3] if len(sys.argv) > 3 else "welch_psd"
 sys.path.insert(0, root)
 import numpy as np
 import torch
@@ -25,14 +29,18 @@ rng = np.random.default_rng(0)
 xh = (rng.standard_normal(n) + 1j * rng.standard_normal(n)).astype(np.complex64)
 xd = torch.from_numpy(xh).cuda()
 win = np.hanning(nfft)
+dwin = np.gradient(win)
+call = {"welch_psd": lambda x: E.welch_psd(x, win, hop, nframes),
+        "cyclic": lambda x: E.cyclic(x, win, hop, nframes, [0.0, 0.05, 0.1, 0.25], mean_value=0.0),
+        "ssq": lambda x: E.ssq(x, win, dwin, hop, 0, nframes)}[entry]
 us = []
 for x in (xd, xh):
     for _ in range(200):
-        E.welch_psd(x, win, hop, nframes)
+        call(x)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(K):
-        E.welch_psd(x, win, hop, nframes)
+        call(x)
     torch.cuda.synchronize()
     us.append((time.perf_counter() - t0) / K * 1e6)
-print("%s welch_psd us/call: device %.2f host %.2f" % (label, us[0], us[1]), flush=True)
+print("%s %s us/call: device %.2f host %.2f" % (label, entry, us[0], us[1]), flush=True)
