@@ -129,8 +129,16 @@ UNEVEN_SIGNATURES = {
     "sp_lomb_plan": (_i, [_i64, _i64, _i64, _vp]),
 }
 
-# the six tables, in the order of their headers
+# the seventh table: must list every symbol include/spectral_wbic.h declares, and none of the other six
+WBIC_SIGNATURES = {
+    "sp_wbic": (_i, [_vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i, _i, _i, _d, _i, _i, _i64, _i64, _i64, _i64, _vp, _vp, _vp, C.POINTER(_i), _i]),
+    "sp_wbic_plan": (_i, [_i64, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i, _i, _vp]),
+}
+
+# the six tables the engine trace counts, in the order of their headers
 TABLES = (SIGNATURES, EXT_SIGNATURES, TFR_SIGNATURES, QUAD_SIGNATURES, CYCLO_SIGNATURES, UNEVEN_SIGNATURES)
+# the tables added since: bound like the six, outside the trace
+MORE_TABLES = (WBIC_SIGNATURES,)
 
 
 class SpectralError(RuntimeError):
@@ -146,7 +154,7 @@ def load_library():
         raise SpectralError("libspectral.so not found at %s -- run `make` (or __graft_entry__.build()); "
                             "pyfft_amd has no CPU fallback" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for table in TABLES:
+    for table in TABLES + MORE_TABLES:
         for name, (res, args) in table.items():
             fn = getattr(lib, name)      # AttributeError if the .so lacks a declared symbol
             fn.restype = res

@@ -36,6 +36,7 @@ namespace sp {
 //   SP_LOMB_FREQS (int: a cap on the frequencies per pass of sp_lomb / sp_lomb_sums, before the partials fill their budget)
 //   SP_LOMB_SPLIT (int: the sample runs sp_lomb deals a record into, so that a small record walks the sum over the runs)
 //   (the last six: unset or <= 0 leaves the budget alone; sp_last_passes reports the passes a call made)
+//   SP_WBIC_CHUNK (int: a cap on the samples per pass of sp_wbic, which reports its passes itself; unset or <= 0: the budget alone)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
     return v && v[0] && v[0] != '0';
@@ -1038,6 +1039,33 @@ int launch_lomb_reduce(LaunchCtx c, const double *partial, int R, int64_t groups
 int launch_lomb_finish(LaunchCtx c, const double *common, const double *rows, int64_t rows_ld, const double *totals, const double *mean,
                        const double *f, int fcount, int64_t batch, int64_t N, double t_ref, int floating_mean, int normalize, void *P,
                        int64_t p_ld);
+
+// wavelet bispectrum and bicoherence (k_wbic.hip): the contraction over time of wavelet transforms in the layout k_cwt writes, X, Y, Z
+// [S][ld] complex64, row i the frequency (k_lo + i) df.  A group is a run of at most WBIC_GROUP consecutive samples of one cell (a
+// block, or the `step` samples overlapping blocks share); `start` is the absolute sample index, the column of X, Y, Z is start - shift.
+//   part[(tile * ngroups + g)][3][64 * 64]  fp32 sums over the group of Re, Im of X[i] Y[j] conj(Z[i + j + k_lo]) and of |X[i] Y[j]|^2
+//   ppart[g][S]                             float64 sums over the group of |Z[m]|^2
+// launch_wbic_cells adds the groups gA .. gB - 1 (the ones the launches above covered) in ascending order into the float64 sums of
+// their cells, acc[cell][tile][3][4096] and pcell[cell][S] (zeroed by the caller before the first pass); gfirst[c] = the first group of
+// cell c, gfirst[ncells] = the number of groups.  launch_wbic_finish forms block b from the cells b .. b + cpb - 1:
+// B = sum / T (complex128), b2 = |B|^2 / (D P[m]) (0 where D P = 0), NaN where m = i + j + k_lo >= S, P[b][m]; sym: only tiles tj <= ti
+// are held and (i, j) with j > i reads (j, i).  No atomics, every order fixed.
+#define WBIC_TILE 64
+#define WBIC_GROUP 2048
+#define WBIC_PART (3 * WBIC_TILE * WBIC_TILE)       // floats per (tile, group), float64 sums per (cell, tile)
+#define WBIC_MAX_S 512
+#define WBIC_MAX_PASS_GROUPS 32768
+struct WbicGroup {
+    int64_t start;
+    int cell, len;
+};
+int launch_wbic_tile(LaunchCtx c, const cf *X, const cf *Y, const cf *Z, int S, int k_lo, int64_t ld, int64_t shift, const WbicGroup *groups,
+                     int ngroups, const int2 *tiles, int ntiles, float *part);
+int launch_wbic_pz(LaunchCtx c, const cf *Z, int S, int64_t ld, int64_t shift, const WbicGroup *groups, int ngroups, double *ppart);
+int launch_wbic_cells(LaunchCtx c, const float *part, const double *ppart, const int *gfirst, int64_t cell0, int64_t ncells, int64_t gA,
+                      int64_t gB, int ntiles, int S, double *acc, double *pcell);
+int launch_wbic_finish(LaunchCtx c, const double *acc, const double *pcell, const int *tmap, int ntd, int ntiles, int S, int k_lo, int sym,
+                       int64_t nblocks, int64_t cpb, int64_t T, void *B, double *b2, double *P);
 
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;

@@ -5,6 +5,7 @@
 #include "../../include/spectral_quad.h"
 #include "../../include/spectral_cyclo.h"
 #include "../../include/spectral_uneven.h"
+#include "../../include/spectral_wbic.h"
 #include "launch.h"
 #include "stage.h"
 #include "table_cache.h"
@@ -93,6 +94,7 @@ struct Ctx {
     Scratch sosY, sosZ;                            // cascaded sections: sosfiltfilt's forward output, staged zi / zf
     Scratch bsIn, bsS, bsP, bsA;                    // bispectrum: staged inputs, spectra, fp32 partials, float64 sums
     Scratch mtS;                                    // multitaper: the per-taper cross spectra behind the weighted one
+    Scratch wbW, wbP, wbA;                          // wavelet bispectrum: the transforms of a pass, its fp32 partials, the float64 cell sums
     Scratch cmS, cmT, cmG, cmH, cmO;               // CSD matrix: spectra, bin-major spectra, float64 accumulator, packed-spectra sums, one-pass means state
     std::map<int64_t, BigTw> bigtw;           // N -> two-level twiddle tables of the multi-pass FFT
     std::map<int64_t, BlueTab> blue_big;      // n -> chirp[n], FFT_L(chirp*) (unscaled) for multi-pass Bluestein
@@ -1388,6 +1390,9 @@ void sp_shutdown(void) {
     g.blueB.release();
     g.longrec.release();
     g.mtS.release();
+    g.wbW.release();
+    g.wbP.release();
+    g.wbA.release();
     for (auto &kv : g.bigtw) {
         (void)hipFree((void *)kv.second.hi);
         (void)hipFree((void *)kv.second.lo);
@@ -4241,6 +4246,228 @@ int sp_lomb_finish(const double *common, const double *rows, const double *total
         return fail("%s: the finish step was refused", who);
     HIPCHK(hipGetLastError());
     if (!st.host) HIPCHK(hipStreamSynchronize(g.stream));       // f and mean are the caller's again
+    return st.finish();
+}
+
+// ---- wavelet bispectrum and bicoherence (k_wbic.hip; include/spectral_wbic.h) ------------------------------------
+#define WBIC_MAX_M 3072
+#define WBIC_W_BYTES ((size_t)128 << 20)            // the transforms of a pass
+#define WBIC_PART_BYTES ((size_t)128 << 20)         // the fp32 partials of a pass
+#define WBIC_OUT_BYTES ((size_t)1 << 30)            // B and b2
+#define WBIC_ACC_BYTES ((size_t)2 << 30)            // the float64 cell sums
+
+struct WbicPlan {
+    int ntd, ntiles;
+    int64_t ncells, cell_len, cpb, chunk, span_max, pass_groups_max;
+    std::vector<WbicGroup> groups;
+    std::vector<int> gfirst;            // [ncells + 1]: the first group of every cell, then the number of groups
+    std::vector<int64_t> pass;          // [passes + 1]: the first group of every pass, then the number of groups
+    std::vector<int> tbl;               // [tmap | the tile list as int2]
+    size_t nmap, w_bytes, part_bytes, acc_bytes;
+};
+
+// the checks sp_wbic and sp_wbic_plan share; 0 or the message's tail
+static const char *wbic_shape(int64_t nsig, int S, int k_lo, int L, int M, int64_t n0, int64_t block, int64_t step, int64_t nblocks,
+                              int nrec, bool sym) {
+    if (S < 2 || S > WBIC_MAX_S) return "nscales must lie in 2 .. 512";
+    if (k_lo < 1) return "k_lo must be at least 1";
+    if (k_lo > S - 1) return "k_lo is above nscales - 1: no pair is valid";
+    if (M > WBIC_MAX_M) return "M is above 3072: a scale does not fuse, and there is no composed path here";
+    if (const char *why = cwt_shape(nsig, S, 1, L, M)) return why;
+    if (nrec < 1 || nrec > 3) return "1 .. 3 distinct records";
+    if (block < 1 || step < 1) return "block and step must be at least 1";
+    if (step < block && block % step != 0) return "either step >= block or block % step == 0";
+    if (nblocks < 1) return "nblocks must be at least 1";
+    if ((size_t)nblocks > WBIC_OUT_BYTES / ((size_t)S * (size_t)S * 24)) return "nblocks S^2 24 bytes are above 1 GiB";
+    if (n0 < 0 || n0 >= nsig || block > nsig || (double)n0 + (double)(nblocks - 1) * (double)step + (double)block > (double)nsig ||
+        n0 + (nblocks - 1) * step + block > nsig)
+        return "a block lies outside the record";
+    const int64_t cpb = step < block ? block / step : 1, ncells = nblocks - 1 + cpb;
+    const int ntd = (S + WBIC_TILE - 1) / WBIC_TILE;
+    const size_t tiles_most = (size_t)(sym ? ntd * (ntd + 1) / 2 : ntd * ntd);
+    if ((size_t)ncells > WBIC_ACC_BYTES / (tiles_most * sizeof(double) * WBIC_PART)) return "the float64 cell sums are above 2 GiB";
+    const int64_t cell_len = step < block ? step : block;
+    if ((double)ncells * (double)((cell_len + WBIC_GROUP - 1) / WBIC_GROUP) > (double)(1 << 30)) return "more than 2^30 groups";
+    return nullptr;
+}
+
+// cells, groups, passes and tiles of an accepted shape
+static WbicPlan wbic_plan_of(int64_t nsig, int S, int k_lo, int M, int64_t n0, int64_t block, int64_t step, int64_t nblocks, int nrec,
+                             bool sym) {
+    WbicPlan p;
+    p.cpb = step < block ? block / step : 1;
+    p.ncells = nblocks - 1 + p.cpb;
+    p.cell_len = step < block ? step : block;
+    // the tiles that hold a valid pair (tj <= ti in the auto form) and the map (ti, tj) -> tile number (-1: none)
+    p.ntd = (S + WBIC_TILE - 1) / WBIC_TILE;
+    p.tbl.assign((size_t)p.ntd * p.ntd, -1);
+    std::vector<int> tl;
+    for (int ti = 0; ti < p.ntd; ++ti)
+        for (int tj = 0; tj < (sym ? ti + 1 : p.ntd); ++tj) {
+            if (ti * WBIC_TILE + tj * WBIC_TILE + k_lo > S - 1) continue;
+            p.tbl[(size_t)ti * p.ntd + tj] = (int)tl.size() / 2;
+            tl.push_back(ti);
+            tl.push_back(tj);
+        }
+    p.ntiles = (int)tl.size() / 2;
+    p.nmap = p.tbl.size() + (p.tbl.size() & 1);          // the int2 list starts 8-byte aligned
+    p.tbl.resize(p.nmap, -1);
+    p.tbl.insert(p.tbl.end(), tl.begin(), tl.end());
+    // groups: every cell in runs of WBIC_GROUP samples, the last one ragged
+    p.gfirst.reserve((size_t)p.ncells + 1);
+    for (int64_t c = 0; c < p.ncells; ++c) {
+        p.gfirst.push_back((int)p.groups.size());
+        const int64_t s0 = n0 + c * step;
+        for (int64_t o = 0; o < p.cell_len; o += WBIC_GROUP)
+            p.groups.push_back(WbicGroup{s0 + o, (int)c, (int)std::min<int64_t>(WBIC_GROUP, p.cell_len - o)});
+    }
+    p.gfirst.push_back((int)p.groups.size());
+    // passes: runs of whole groups that span at most `chunk` samples, hold at most pass_groups_max groups, and at least one
+    p.chunk = std::max<int64_t>(1, (int64_t)(WBIC_W_BYTES / (sizeof(cf) * (size_t)S * (size_t)nrec)));
+    p.chunk = hook_cap("SP_WBIC_CHUNK", p.chunk);
+    const size_t group_part = sizeof(float) * WBIC_PART * (size_t)std::max(p.ntiles, 1);
+    const int64_t gcap = std::max<int64_t>(1, std::min<int64_t>(WBIC_MAX_PASS_GROUPS, (int64_t)(WBIC_PART_BYTES / group_part)));
+    const int64_t ng = (int64_t)p.groups.size();
+    p.span_max = p.pass_groups_max = 0;
+    for (int64_t gA = 0; gA < ng;) {
+        int64_t gB = gA + 1;
+        while (gB < ng && gB - gA < gcap && p.groups[(size_t)gB].start + p.groups[(size_t)gB].len - p.groups[(size_t)gA].start <= p.chunk) ++gB;
+        p.pass.push_back(gA);
+        const int64_t a = p.groups[(size_t)gA].start, b = p.groups[(size_t)gB - 1].start + p.groups[(size_t)gB - 1].len;
+        p.span_max = std::max(p.span_max, std::min(b + M, nsig) - std::max<int64_t>(a - M, 0));
+        p.pass_groups_max = std::max(p.pass_groups_max, gB - gA);
+        gA = gB;
+    }
+    p.pass.push_back(ng);
+    p.w_bytes = sizeof(cf) * (size_t)nrec * (size_t)S * (size_t)p.span_max;
+    p.part_bytes = (size_t)p.pass_groups_max * (group_part + sizeof(double) * (size_t)S);
+    p.acc_bytes = (size_t)p.ncells * sizeof(double) * (WBIC_PART * (size_t)std::max(p.ntiles, 1) + (size_t)S);
+    return p;
+}
+
+int sp_wbic_plan(int64_t nsig, int nscales, int k_lo, int L, int M, int64_t n0, int64_t block, int64_t step, int64_t nblocks, int nrec,
+                 int sym, int64_t out[8]) {
+    if (!out || wbic_shape(nsig, nscales, k_lo, L, M, n0, block, step, nblocks, nrec, sym != 0)) return -1;
+    const WbicPlan p = wbic_plan_of(nsig, nscales, k_lo, M, n0, block, step, nblocks, nrec, sym != 0);
+    out[0] = p.ncells;
+    out[1] = p.cell_len;
+    out[2] = (int64_t)p.groups.size();
+    out[3] = (int64_t)p.pass.size() - 1;
+    out[4] = (int64_t)p.groups.size() * p.ntiles;
+    out[5] = (int64_t)(p.w_bytes + p.part_bytes + p.acc_bytes);
+    out[6] = p.chunk;
+    out[7] = p.ntiles;
+    return 0;
+}
+
+int sp_wbic(const void *x, const void *y, const void *z, int x_dtype, int y_dtype, int z_dtype, int64_t nsig, const double *scales,
+            int nscales, int k_lo, int family, double p0, int L, int M, int64_t n0, int64_t block, int64_t step, int64_t nblocks, void *B,
+            double *b2, double *P, int *passes, int mem) {
+    // every refusal comes before the device is touched
+    if (!x || !scales || !B || !b2 || !P) return fail("sp_wbic: x, scales, B, b2 and P are required");
+    if (x_dtype != SP_DTYPE_F32 && x_dtype != SP_DTYPE_C64) return fail("sp_wbic: dtype must be float32 or complex64, got %d", x_dtype);
+    if ((y && y_dtype != x_dtype) || (z && z_dtype != x_dtype))
+        return fail("sp_wbic: the records differ in dtype (x %d, y %d, z %d)", x_dtype, y_dtype, z_dtype);
+    // the records that are transformed: x, then y and z where they are other pointers
+    const void *src[3] = {x, y ? y : x, z ? z : x};
+    int rec[3] = {0, 0, 0}, nrec = 1;
+    if (src[1] != src[0]) rec[1] = nrec++;
+    if (src[2] != src[0]) rec[2] = src[2] == src[1] ? rec[1] : nrec++;
+    const bool sym = rec[1] == 0;
+    if (const char *why = wbic_shape(nsig, nscales, k_lo, L, M, n0, block, step, nblocks, nrec, sym))
+        return fail("sp_wbic: %s (nscales %d, k_lo %d, L %d, M %d, nsig %lld, n0 %lld, block %lld, step %lld, nblocks %lld)", why, nscales,
+                    k_lo, L, M, (long long)nsig, (long long)n0, (long long)block, (long long)step, (long long)nblocks);
+    if (family != SP_CWT_MORLET && family != SP_CWT_PAUL) return fail("sp_wbic: family %d is neither SP_CWT_MORLET nor SP_CWT_PAUL", family);
+    if (!isfinite(p0) || !(p0 > 0.0) || p0 > 64.0 || (family == SP_CWT_PAUL && p0 < 1.0))
+        return fail("sp_wbic: parameter p0 = %g must lie in (0, 64] (Morlet's w0) or [1, 64] (Paul's m)", p0);
+    for (int s = 0; s < nscales; ++s)
+        if (!isfinite(scales[s]) || !(scales[s] > 0.0) || scales[s] > 1e9)
+            return fail("sp_wbic: scales[%d] = %g must be positive and finite", s, scales[s]);
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const WbicPlan p = wbic_plan_of(nsig, nscales, k_lo, M, n0, block, step, nblocks, nrec, sym);
+    const bool cplx = x_dtype == SP_DTYPE_C64;
+    const size_t esz = cplx ? 8 : 4, S = (size_t)nscales;
+    // the scales' filter constants, as sp_cwt forms them
+    const double lognorm = family == SP_CWT_MORLET ? -0.25 * log(M_PI) : p0 * log(2.0) - 0.5 * (log(p0) + lgamma(2.0 * p0));
+    std::vector<float> sc(2 * S);
+    for (size_t s = 0; s < S; ++s) {
+        sc[2 * s] = (float)(2.0 * M_PI * scales[s] / (double)L);
+        sc[2 * s + 1] = (float)(lognorm + 0.5 * log(2.0 * M_PI * scales[s]) - log((double)L));
+    }
+    // the call's small tables: [tmap | tiles] and [gfirst | groups]
+    const size_t nfirst = p.gfirst.size() + (p.gfirst.size() & 1);      // the groups start 8-byte aligned
+    std::vector<char> gt(sizeof(int) * nfirst + sizeof(WbicGroup) * p.groups.size(), 0);
+    memcpy(gt.data(), p.gfirst.data(), sizeof(int) * p.gfirst.size());
+    memcpy(gt.data() + sizeof(int) * nfirst, p.groups.data(), sizeof(WbicGroup) * p.groups.size());
+    void *sc_d = nullptr, *tab_d = nullptr, *gt_d = nullptr;
+    if (get_table(15, sc.data(), sizeof(float) * sc.size(), &sc_d, nullptr)) return -1;
+    if (get_table(26, p.tbl.data(), sizeof(int) * p.tbl.size(), &tab_d, nullptr)) return -1;
+    if (get_table(27, gt.data(), gt.size(), &gt_d, nullptr)) return -1;
+    const int *tmap_d = (const int *)tab_d;
+    const int2 *tiles_d = (const int2 *)((const int *)tab_d + p.nmap);
+    const int *gfirst_d = (const int *)gt_d;
+    const WbicGroup *groups_d = (const WbicGroup *)((const char *)gt_d + sizeof(int) * nfirst);
+    const cf *tw;
+    if (get_twiddles(L, &tw)) return -1;
+    Stage st(mem);
+    const void *xd[3] = {nullptr, nullptr, nullptr};
+    void *Bd;
+    double *b2d, *Pd;
+    for (int k = 0; k < 3; ++k)
+        if (k == 0 || rec[k] > rec[k - 1]) st.in(g.bsIn, src[k], esz * (size_t)nsig, &xd[rec[k]]);
+    const size_t nn = (size_t)nblocks * S * S;
+    st.out(g.out0, B, 2 * sizeof(double) * nn, &Bd);
+    st.out(g.out0, b2, sizeof(double) * nn, &b2d);
+    st.out(g.out0, P, sizeof(double) * (size_t)nblocks * S, &Pd);
+    if (st.commit()) return -1;
+    if (g.wbW.ensure(p.w_bytes) || g.wbP.ensure(p.part_bytes) || g.wbA.ensure(p.acc_bytes)) return -1;
+    float *part = (float *)g.wbP.p;
+    double *ppart = (double *)(part + (size_t)p.pass_groups_max * WBIC_PART * (size_t)p.ntiles);
+    double *acc = (double *)g.wbA.p, *pcell = acc + (size_t)p.ncells * WBIC_PART * (size_t)p.ntiles;
+    HIPCHK(hipMemsetAsync(g.wbA.p, 0, p.acc_bytes, g.stream));
+    CwtArgs a{};
+    a.cplx = cplx ? 1 : 0;
+    a.sc = (const float *)sc_d;
+    a.p = family == SP_CWT_PAUL ? (float)p0 : 0.f;
+    a.a = family == SP_CWT_MORLET ? 0.5f : 0.f;
+    a.b = family == SP_CWT_PAUL ? 1.f : 0.f;
+    a.u0 = family == SP_CWT_MORLET ? (float)p0 : 0.f;
+    a.S = nscales;
+    a.M = M;
+    const int npass = (int)p.pass.size() - 1;
+    for (int q = 0; q < npass; ++q) {
+        const int64_t gA = p.pass[(size_t)q], gB = p.pass[(size_t)q + 1];
+        const WbicGroup &first = p.groups[(size_t)gA], &last = p.groups[(size_t)gB - 1];
+        const int64_t sub0 = std::max<int64_t>(first.start - M, 0), sub1 = std::min<int64_t>(last.start + last.len + M, nsig);
+        const int64_t nsub = sub1 - sub0;
+        // the transforms of the samples [sub0, sub1) of every distinct record, [S][nsub] each: k_cwt on the sub-record
+        const CwtPlan pl = cwt_plan_of(L, M, nsub, nscales, 1, false, false, g.ncu, env_int("SP_CWT_CHUNK", 0));
+        cf *W[3];
+        for (int k = 0; k < nrec; ++k) {
+            W[k] = (cf *)g.wbW.p + (size_t)k * S * (size_t)nsub;
+            a.x = (const char *)xd[k] + esz * (size_t)sub0;
+            a.nsig = a.x_ld = nsub;
+            a.nframes = pl.frames;
+            a.chunk = pl.chunk;
+            a.hop = pl.hop;
+            a.W = W[k];
+            if (launch_cwt(lc(), a, L, tw, pl, 1) != 0)
+                return fail("sp_wbic: the transform's launch was refused (L %d, M %d, nscales %d, %lld samples)", L, M, nscales, (long long)nsub);
+            HIPCHK(hipGetLastError());
+        }
+        {
+            ProfScope ps;
+            LAUNCHCHK(launch_wbic_tile(lc(), W[rec[0]], W[rec[1]], W[rec[2]], nscales, k_lo, nsub, sub0, groups_d + gA, (int)(gB - gA), tiles_d,
+                                       p.ntiles, part));
+            g.last_kernel = "k_wbic_tile";
+        }
+        LAUNCHCHK(launch_wbic_pz(lc(), W[rec[2]], nscales, nsub, sub0, groups_d + gA, (int)(gB - gA), ppart));
+        LAUNCHCHK(launch_wbic_cells(lc(), part, ppart, gfirst_d, first.cell, (int64_t)last.cell - first.cell + 1, gA, gB, p.ntiles, nscales, acc,
+                                    pcell));
+    }
+    LAUNCHCHK(launch_wbic_finish(lc(), acc, pcell, tmap_d, p.ntd, p.ntiles, nscales, k_lo, sym ? 1 : 0, nblocks, p.cpb, block, Bd, b2d, Pd));
+    if (passes) *passes = npass;
     return st.finish();
 }
 

@@ -1764,6 +1764,116 @@ def lomb_plan(N, M, rows=1):
                  rows)
 
 
+WBIC_MAX_S, WBIC_MAX_M, WBIC_TILE, WBIC_GROUP = 512, 3072, 64, 2048
+WBIC_OUT_BYTES, WBIC_ACC_BYTES = 1 << 30, 2 << 30
+
+
+class WbicRefused(ValueError, NotImplementedError):
+    """A shape the wavelet bispectrum does not take: outside the limits, and what is not built (scales whose margin is above 3072 samples
+    -- there is no composed path here --, leading axes, blocks that neither tile nor overlap in whole steps, wavelets that are not analytic)."""
+
+
+def wbic_check(who, nsig, scales, k_lo, family, param, L, M, n0, block, step, nblocks, nrec=1, sym=True):
+    """Every refusal of sp_wbic's shape, before the library is touched -> (scales float64, family code, param)."""
+    nsig, k_lo, L, M, n0, block, step, nblocks = (int(v) for v in (nsig, k_lo, L, M, n0, block, step, nblocks))
+    sc = np.ascontiguousarray(np.asarray(scales, dtype=np.float64))
+    if sc.ndim != 1 or sc.size < 2 or sc.size > WBIC_MAX_S:
+        raise WbicRefused("%s: scales must be one-dimensional and hold 2 .. %d scales" % (who, WBIC_MAX_S))
+    S = int(sc.size)
+    if k_lo < 1 or k_lo > S - 1:
+        raise WbicRefused("%s: k_lo = %d must lie in 1 .. S - 1 = %d (beyond it no pair is valid)" % (who, k_lo, S - 1))
+    if not np.all(np.isfinite(sc)) or not np.all(sc > 0) or np.any(sc > 1e9):
+        raise WbicRefused("%s: every scale must be positive and finite" % who)
+    _range_check(WbicRefused, who, length=("L", L, CWT_MIN_L, CWT_MAX_L))
+    if M > WBIC_MAX_M:
+        raise WbicRefused("%s: M = %d is above %d: a scale does not fuse, and there is no composed path here" % (who, M, WBIC_MAX_M))
+    if M < 0 or 2 * M >= L or L - 2 * M < L // 4:
+        raise WbicRefused("%s: M = %d must lie in 0 .. L / 2 - 1 and leave hop = L - 2 M at L / 4 = %d or more" % (who, M, L // 4))
+    if not isinstance(family, str) or family.lower() not in CWT_FAMILIES:
+        raise WbicRefused("%s: family %r is not built: 'morlet' or 'paul' (analytic wavelets)" % (who, family))
+    param = float(param)
+    code = CWT_FAMILIES[family.lower()]
+    if not np.isfinite(param) or not (0.0 < param <= 64.0) or (code == _ffi.CWT_PAUL and param < 1.0):
+        raise WbicRefused("%s: the %s parameter %r is outside (0, 64] (Morlet's w0) or [1, 64] (Paul's m)" % (who, family, param))
+    if nsig < 1:
+        raise WbicRefused("%s: the record must hold at least one sample" % who)
+    if nrec < 1 or nrec > 3:
+        raise WbicRefused("%s: 1 .. 3 distinct records" % who)
+    if block < 1 or step < 1:
+        raise WbicRefused("%s: block = %d and step = %d must be at least 1" % (who, block, step))
+    if step < block and block % step:
+        raise WbicRefused("%s: either step >= block (disjoint blocks) or block %% step == 0 (overlapping blocks); block %d, step %d"
+                          % (who, block, step))
+    if nblocks < 1:
+        raise WbicRefused("%s: nblocks = %d must be at least 1" % (who, nblocks))
+    if nblocks * S * S * 24 > WBIC_OUT_BYTES:
+        raise WbicRefused("%s: %d blocks of %d x %d pairs are above 1 GiB of B and b2" % (who, nblocks, S, S))
+    if n0 < 0 or n0 + (nblocks - 1) * step + block > nsig:
+        raise WbicRefused("%s: %d blocks of %d samples at step %d from %d on reach outside the %d samples of the record"
+                          % (who, nblocks, block, step, n0, nsig))
+    cpb = block // step if step < block else 1
+    ntd = -(-S // WBIC_TILE)
+    tiles = ntd * (ntd + 1) // 2 if sym else ntd * ntd
+    if (nblocks - 1 + cpb) * tiles * 8 * 3 * WBIC_TILE * WBIC_TILE > WBIC_ACC_BYTES:
+        raise WbicRefused("%s: the float64 sums of %d cells and %d tiles are above 2 GiB" % (who, nblocks - 1 + cpb, tiles))
+    return sc, code, param
+
+
+def _wbic_records(who, md, x, y, z):
+    """-> [x, y, z] as contiguous samples, the same object where they are the same record (None and x itself mean x)"""
+    xs = md.samples(x)
+    if xs.ndim != 1:
+        raise WbicRefused("%s: one record per call: leading axes are not built" % who)
+    out = [xs]
+    for v, earlier in ((y, ((x, 0),)), (z, ((x, 0), (y, 1)))):
+        same = [k for w, k in earlier if v is w]
+        if v is None or same:
+            out.append(out[same[0]] if same else xs)
+            continue
+        if _mode(v) is not md:
+            raise TypeError("%s: the records must all be numpy arrays or all device tensors" % who)
+        vs = md.samples(v)
+        if tuple(vs.shape) != tuple(xs.shape) or not md.alike(xs, vs):
+            raise WbicRefused("%s: the records must share x's %s" % (who, md.ALIKE))
+        out.append(vs)
+    return out
+
+
+def wbic(x, scales, k_lo, family, param, L, M, n0, block, step, nblocks, y=None, z=None):
+    """Wavelet bispectrum of one record, or of a triple of records (sp_wbic): the rows i of `scales` (in samples) stand for the frequencies
+    (k_lo + i) df, block b covers the `block` samples from n0 + b step on, and over it
+        B[b, i, j] = mean_n Wx[i, n] Wy[j, n] conj(Wz[m, n]),  m = i + j + k_lo,   b2 = |B|^2 / (mean |Wx Wy|^2 mean |Wz[m]|^2),
+        P[b, m] = mean_n |Wz[m, n]|^2
+    with W the transforms `cwt` defines (family, param, frames of L samples with margin M).  y and z default to x; a record given
+    twice (the same object) is transformed once.  Returns a dict: 'B' complex128 [nblocks, S, S] and 'b2' float64 (NaN where
+    m > S - 1), 'P' float64 [nblocks, S], 'passes' the passes over the record the call made.  numpy in -> numpy out; device tensors
+    in -> device tensors on x's stream."""
+    md = _mode(x)
+    xs, ys, zs = _wbic_records("wbic", md, x, y, z)
+    nsig = int(xs.shape[-1])
+    nrec = 1 + (ys is not xs) + (zs is not xs and zs is not ys)
+    sc, code, param = wbic_check("wbic", nsig, scales, k_lo, family, param, L, M, n0, block, step, nblocks, nrec, ys is xs)
+    S, nblocks = int(sc.size), int(nblocks)
+    md.bind(xs)
+    B = md.empty((nblocks, S, S), "complex128", xs)
+    b2 = md.empty((nblocks, S, S), "float64", xs)
+    P = md.empty((nblocks, S), "float64", xs)
+    passes = _ffi.C.c_int(0)
+    md.call(lib().sp_wbic, md.addr(xs), None if ys is xs else md.addr(ys), None if zs is xs else md.addr(zs), md.code(xs), md.code(ys),
+            md.code(zs), nsig, ptr(sc), S, int(k_lo), code, param, int(L), int(M), int(n0), int(block), int(step), nblocks, md.addr(B),
+            md.addr(b2), md.addr(P), _ffi.C.byref(passes))
+    return dict(B=B, b2=b2, P=P, passes=int(passes.value))
+
+
+def wbic_plan(nsig, nscales, k_lo, L, M, n0, block, step, nblocks, nrec=1, sym=True):
+    """sp_wbic_plan as a dict (host only): cells, cell_len (samples of a cell), groups, passes, workgroups (of the tile kernel, over all
+    passes), scratch (bytes: transforms, partials and cell sums), chunk (samples a pass may span), tiles."""
+    wbic_check("wbic_plan", nsig, np.ones(max(int(nscales), 0)), k_lo, "morlet", 6.0, L, M, n0, block, step, nblocks, int(nrec), bool(sym))
+    return _plan(lib().sp_wbic_plan, ("cells", "cell_len", "groups", "passes", "workgroups", "scratch", "chunk", "tiles"), WbicRefused,
+                 "wbic_plan", int(nsig), int(nscales), int(k_lo), int(L), int(M), int(n0), int(block), int(step), int(nblocks), int(nrec),
+                 1 if sym else 0)
+
+
 EIGH_MAX_N = 64
 
 
