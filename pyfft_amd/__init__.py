@@ -64,3 +64,5 @@ from .lomb import lombscargle, ls_periodogram, ls_window, ls_grid, ls_level, ls_
 from . import wbicoherence as _wbic_mod                        # noqa: F401
 from .wbicoherence import (wbic_freqs, wavelet_bispectrum, wavelet_bicoherence, summed_bicoherence,   # noqa: F401
                            total_bicoherence, wbic_plan)
+from . import fam as _fam_mod                                  # noqa: F401
+from .fam import FamPlane, fam_pairs, fam_axes, scd_fam, fam_coherence, fam_profile, fam_cells, fam_plan     # noqa: F401

@@ -135,10 +135,16 @@ WBIC_SIGNATURES = {
     "sp_wbic_plan": (_i, [_i64, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i, _i, _vp]),
 }
 
+# the eighth table: must list every symbol include/spectral_fam.h declares, and none of the other seven
+FAM_SIGNATURES = {
+    "sp_fam": (_i, [_vp, _vp, _i, _i64, _vp, _i, _i64, _vp, _i, _i64, _vp, _i64, _i, _vp, _vp, _d, _vp, _vp, _vp, _i]),
+    "sp_fam_plan": (_i, [_i, _i, _i, _i64, _i, _i64, _i64, _vp]),
+}
+
 # the six tables the engine trace counts, in the order of their headers
 TABLES = (SIGNATURES, EXT_SIGNATURES, TFR_SIGNATURES, QUAD_SIGNATURES, CYCLO_SIGNATURES, UNEVEN_SIGNATURES)
 # the tables added since: bound like the six, outside the trace
-MORE_TABLES = (WBIC_SIGNATURES,)
+MORE_TABLES = (WBIC_SIGNATURES, FAM_SIGNATURES)
 
 
 class SpectralError(RuntimeError):

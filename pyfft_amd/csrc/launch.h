@@ -37,6 +37,7 @@ namespace sp {
 //   SP_LOMB_SPLIT (int: the sample runs sp_lomb deals a record into, so that a small record walks the sum over the runs)
 //   (the last six: unset or <= 0 leaves the budget alone; sp_last_passes reports the passes a call made)
 //   SP_WBIC_CHUNK (int: a cap on the samples per pass of sp_wbic, which reports its passes itself; unset or <= 0: the budget alone)
+//   SP_FAM_BLOCKS (int: a cap on the blocks per pass of sp_fam; unset or <= 0: the budget alone; sp_last_passes(5) reports the passes)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
     return v && v[0] && v[0] != '0';
@@ -1066,6 +1067,27 @@ int launch_wbic_cells(LaunchCtx c, const float *part, const double *ppart, const
                       int64_t gB, int ntiles, int S, double *acc, double *pcell);
 int launch_wbic_finish(LaunchCtx c, const double *acc, const double *pcell, const int *tmap, int ntd, int ntiles, int S, int k_lo, int sym,
                        int64_t nblocks, int64_t cpb, int64_t T, void *B, double *b2, double *P);
+
+// FFT accumulation method (k_fam.hip): Y, X [np][ld] complex64 are the frames of a pass bin-major, as the STFT kernel and a transposition
+// leave them (frame-referenced); nb blocks of P frames from column 0 on.  pairs[npairs] = (k, l): row k of Y against row l of X.  The
+// pair kernel sums the blocks of the pass in float32 and the passes in float64 through acc[npairs][2Q][2] (`first`: nothing to add;
+// `last`: S = scale sum, complex64 [npairs][2Q]; a call of one pass never touches acc).  launch_fam_pw: Pw[k] = scale sum_f g[f mod P]
+// |Z[k][f]|^2 over the frames of all passes, float64 throughout, through acc[np].
+#define SP_FAM_MAX_P 8192
+#define SP_FAM_MAX_PAIRS ((int64_t)1 << 22)
+struct FamArgs {
+    const cf *Y, *X;
+    const float *g;
+    const int2 *pairs;
+    double *acc;
+    cf *S;
+    int64_t ld, nb, npairs;
+    double scale;
+    int twoQ, conj, first, last;
+};
+int launch_fam(LaunchCtx c, const FamArgs &a, int P, const cf *tw);
+int launch_fam_pw(LaunchCtx c, const cf *Z, int np, int64_t ld, int64_t nframes, int P, const float *g, double *acc, bool first, bool last,
+                  double scale, float *Pw);
 
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;

@@ -6,6 +6,7 @@
 #include "../../include/spectral_cyclo.h"
 #include "../../include/spectral_uneven.h"
 #include "../../include/spectral_wbic.h"
+#include "../../include/spectral_fam.h"
 #include "launch.h"
 #include "stage.h"
 #include "table_cache.h"
@@ -95,6 +96,7 @@ struct Ctx {
     Scratch bsIn, bsS, bsP, bsA;                    // bispectrum: staged inputs, spectra, fp32 partials, float64 sums
     Scratch mtS;                                    // multitaper: the per-taper cross spectra behind the weighted one
     Scratch wbW, wbP, wbA;                          // wavelet bispectrum: the transforms of a pass, its fp32 partials, the float64 cell sums
+    Scratch famZ, famA;                             // FFT accumulation: the bin-major frames of a pass, the float64 sums across passes
     Scratch cmS, cmT, cmG, cmH, cmO;               // CSD matrix: spectra, bin-major spectra, float64 accumulator, packed-spectra sums, one-pass means state
     std::map<int64_t, BigTw> bigtw;           // N -> two-level twiddle tables of the multi-pass FFT
     std::map<int64_t, BlueTab> blue_big;      // n -> chirp[n], FFT_L(chirp*) (unscaled) for multi-pass Bluestein
@@ -227,9 +229,10 @@ TableCache g_tables;
 
 // sp_last_passes: [0] the passes of the current call's outermost frame-chunk loop, [1] the most slice passes one
 // dev_fft_any / sp_czt loop made inside it, [2] the passes over the cycle-frequency list of sp_cyclic, [3] the passes over the
-// frequency list of sp_lomb / sp_lomb_sums, [4] the most launches the row groups of one such pass were dealt to.  All are zeroed
+// frequency list of sp_lomb / sp_lomb_sums, [4] the most launches the row groups of one such pass were dealt to, [5] the passes over the
+// blocks of sp_fam.  All are zeroed
 // where a call begins (ApiLock), so that a test can assert that the shape it chose really walks a loop past its first pass.
-int g_passes[5] = {0, 0, 0, 0, 0};
+int g_passes[6] = {0, 0, 0, 0, 0, 0};
 inline void note_slices(int64_t n) {
     if (n > g_passes[1]) g_passes[1] = (int)n;
 }
@@ -245,7 +248,7 @@ struct ApiLock {
     std::lock_guard<std::mutex> lk;
     ApiLock() : lk(g.mu) {
         g_tables.begin_call();
-        g_passes[0] = g_passes[1] = g_passes[2] = g_passes[3] = g_passes[4] = 0;
+        g_passes[0] = g_passes[1] = g_passes[2] = g_passes[3] = g_passes[4] = g_passes[5] = 0;
     }
 };
 
@@ -1329,7 +1332,7 @@ int sp_max_wg_fft(void) { return SP_MAX_WG_FFT; }
 const char *sp_last_error(void) { return g_err.c_str(); }
 int sp_last_passes(int which) {
     std::lock_guard<std::mutex> lk(g.mu);
-    return which >= 0 && which <= 4 ? g_passes[which] : 0;
+    return which >= 0 && which <= 5 ? g_passes[which] : 0;
 }
 
 int sp_init(int device_id) {
@@ -1393,6 +1396,8 @@ void sp_shutdown(void) {
     g.wbW.release();
     g.wbP.release();
     g.wbA.release();
+    g.famZ.release();
+    g.famA.release();
     for (auto &kv : g.bigtw) {
         (void)hipFree((void *)kv.second.hi);
         (void)hipFree((void *)kv.second.lo);
@@ -4468,6 +4473,167 @@ int sp_wbic(const void *x, const void *y, const void *z, int x_dtype, int y_dtyp
     }
     LAUNCHCHK(launch_wbic_finish(lc(), acc, pcell, tmap_d, p.ntd, p.ntiles, nscales, k_lo, sym ? 1 : 0, nblocks, p.cpb, block, Bd, b2d, Pd));
     if (passes) *passes = npass;
+    return st.finish();
+}
+
+// ---- FFT accumulation method (k_fam.hip; include/spectral_fam.h) -------------------------------------------------
+#define FAM_PASS_BYTES ((size_t)256 << 20)          // the bin-major frames of a pass
+#define FAM_ACC_BYTES ((size_t)2 << 30)             // the float64 sums of a call of several passes
+
+struct FamPlan {
+    int64_t twoQ, bpp, passes, workgroups;
+    size_t z_bytes, acc_bytes;
+};
+
+// the checks sp_fam and sp_fam_plan share; 0 or the message's tail
+static const char *fam_shape(int dtype, int np, int64_t hop, int P, int64_t nblocks, int64_t npairs) {
+    if (dtype != SP_DTYPE_F32 && dtype != SP_DTYPE_C64) return "dtype must be float32 or complex64";
+    if (np < 32 || np > SP_MAX_WG_FFT || !is_pow2(np)) return "np must be a power of two from 32 to 8192";
+    if (P < 32 || P > SP_FAM_MAX_P || !is_pow2(P)) return "P must be a power of two from 32 to 8192";
+    if (hop < 1 || hop > np || !is_pow2(hop)) return "hop must be a power of two from 1 to np";
+    if ((int64_t)P * hop < 2 * (int64_t)np) return "P hop is below 2 np: no bin lies within half a channel spacing";
+    if (nblocks < 0) return "nblocks must not be negative";
+    if (npairs < 1 || npairs > SP_FAM_MAX_PAIRS) return "npairs must lie in 1 .. 2^22";
+    return nullptr;
+}
+
+// blocks per pass and passes of an accepted shape
+static FamPlan fam_plan_of(int nrec, int np, int64_t hop, int P, int64_t nblocks, int64_t npairs) {
+    FamPlan p;
+    p.twoQ = (int64_t)P * hop / np;
+    const size_t block_bytes = sizeof(cf) * (size_t)nrec * (size_t)np * (size_t)P;
+    p.bpp = std::max<int64_t>(1, (int64_t)(FAM_PASS_BYTES / block_bytes));
+    p.bpp = std::min(hook_cap("SP_FAM_BLOCKS", p.bpp), nblocks);
+    p.passes = nblocks > 0 ? (nblocks + p.bpp - 1) / p.bpp : 0;
+    p.workgroups = p.passes * ((npairs + fpw_of(P) - 1) / fpw_of(P));
+    p.z_bytes = block_bytes * (size_t)p.bpp;
+    p.acc_bytes = p.passes > 1 ? 2 * sizeof(double) * (size_t)npairs * (size_t)p.twoQ : 0;
+    return p;
+}
+
+int sp_fam_plan(int dtype, int cross, int np, int64_t hop, int P, int64_t nblocks, int64_t npairs, int64_t out[5]) {
+    if (!out || fam_shape(dtype, np, hop, P, nblocks, npairs)) return -1;
+    const FamPlan p = fam_plan_of(cross ? 2 : 1, np, hop, P, nblocks, npairs);
+    if (p.acc_bytes > FAM_ACC_BYTES) return -1;
+    out[0] = p.twoQ / 2;
+    out[1] = p.bpp;
+    out[2] = p.passes;
+    out[3] = p.workgroups;
+    out[4] = (int64_t)p.z_bytes;
+    return 0;
+}
+
+int sp_fam(const void *x, const void *y, int dtype, int64_t nsig, const float *a, int np, int64_t hop, const float *taper, int P,
+           int64_t nblocks, const int32_t *pairs, int64_t npairs, int conj, const double *mean_x, const double *mean_y, double scale,
+           void *S, void *Pwx, void *Pwy, int mem) {
+    // every refusal comes before the device is touched
+    if (const char *why = fam_shape(dtype, np, hop, P, nblocks, npairs))
+        return fail("sp_fam: %s (dtype %d, np %d, hop %lld, P %d, nblocks %lld, npairs %lld)", why, dtype, np, (long long)hop, P,
+                    (long long)nblocks, (long long)npairs);
+    if (nblocks > 0 && (nsig < np || nblocks > ((nsig - np) / hop + 1) / P))
+        return fail("sp_fam: nblocks = %lld blocks of P = %d frames of np = %d at hop %lld reach outside the nsig = %lld samples of the row",
+                    (long long)nblocks, P, np, (long long)hop, (long long)nsig);
+    if (!isfinite(scale)) return fail("sp_fam: scale must be finite");
+    for (int c = 0; c < 2; ++c)
+        if ((mean_x && !isfinite(mean_x[c])) || (mean_y && !isfinite(mean_y[c]))) return fail("sp_fam: mean_x and mean_y must be finite");
+    if (!x) return fail("sp_fam: x is required");
+    if (!a) return fail("sp_fam: a is required");
+    if (!taper) return fail("sp_fam: g is required");
+    if (!pairs) return fail("sp_fam: pairs is required");
+    if (!S && !Pwx && !Pwy) return fail("sp_fam: no output: one of S, Pwx and Pwy is required");
+    for (int64_t i = 0; i < 2 * npairs; ++i)
+        if (pairs[i] < 0 || pairs[i] >= np)
+            return fail("sp_fam: pairs[%lld][%d] = %d lies outside the channels 0 .. %d", (long long)(i / 2), (int)(i & 1), pairs[i], np - 1);
+    const bool cross = y != nullptr, cplx = dtype == SP_DTYPE_C64;
+    const int nrec = cross ? 2 : 1;
+    const FamPlan p = fam_plan_of(nrec, np, hop, P, nblocks, npairs);
+    if (p.acc_bytes > FAM_ACC_BYTES)
+        return fail("sp_fam: npairs = %lld pairs of %lld bins in %lld passes need float64 sums above 2 GiB", (long long)npairs, (long long)p.twoQ,
+                    (long long)p.passes);
+    if (nblocks == 0) return 0;
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    Xf xf;
+    if (get_xf(np, &xf)) return -1;
+    const cf *twP;
+    if (get_twiddles(P, &twP)) return -1;
+    const size_t esz = cplx ? sizeof(cf) : sizeof(float);
+    const int64_t nframes = nblocks * P;
+    const size_t used = (size_t)((nframes - 1) * hop + np);           // the samples the frames reach
+    Stage st(mem);
+    const void *xd[2] = {nullptr, nullptr};
+    cf *S_d;
+    float *Pw_d[2];
+    st.in(g.in0, x, esz * used, &xd[0]);
+    st.in(g.in1, y, esz * used, &xd[1]);
+    st.out(g.out0, S, sizeof(cf) * (size_t)npairs * (size_t)p.twoQ, &S_d);
+    st.out(g.out0, Pwx, sizeof(float) * (size_t)np, &Pw_d[0]);
+    st.out(g.out0, Pwy, sizeof(float) * (size_t)np, &Pw_d[1]);
+    if (st.commit()) return -1;
+    // small tables: both windows, the pair table, the means as trend records (x, then y)
+    void *a_d = nullptr, *g_d = nullptr, *pairs_d = nullptr;
+    if (get_table(1, a, sizeof(float) * (size_t)np, &a_d, nullptr)) return -1;
+    if (get_table(1, taper, sizeof(float) * (size_t)P, &g_d, nullptr)) return -1;
+    if (get_table(28, pairs, sizeof(int32_t) * 2 * (size_t)npairs, &pairs_d, nullptr)) return -1;
+    TrendBuf tb;
+    if (get_trendbuf(2, &tb)) return -1;
+    if (set_trend(tb, 0, xd[0], cplx, nsig, 0, mean_x ? mean_x[0] : 0.0, mean_x && cplx ? mean_x[1] : 0.0)) return -1;
+    if (cross && set_trend(tb, 1, xd[1], cplx, nsig, 0, mean_y ? mean_y[0] : 0.0, mean_y && cplx ? mean_y[1] : 0.0)) return -1;
+    // scratch: the bin-major frames of a pass (x, then y), the frame-major frames of one record before their transposition, the
+    // float64 sums (S across passes; the channel powers of x and y)
+    const int64_t ld = p.bpp * P;
+    const size_t rec_elems = (size_t)np * (size_t)ld;
+    if (g.famZ.ensure(sizeof(cf) * rec_elems * (size_t)nrec) || g.work.ensure(sizeof(cf) * rec_elems)) return -1;
+    if (g.famA.ensure(p.acc_bytes + 2 * sizeof(double) * (size_t)np)) return -1;
+    double *pw_acc = (double *)g.famA.p, *s_acc = pw_acc + 2 * (size_t)np;
+    cf *Z[2] = {(cf *)g.famZ.p, (cf *)g.famZ.p + rec_elems};
+    const bool pair = !cplx && !env_flag("SP_NO_REALPAIR");
+    FamArgs fa{};
+    fa.g = (const float *)g_d;
+    fa.pairs = (const int2 *)pairs_d;
+    fa.acc = p.passes > 1 ? s_acc : nullptr;
+    fa.S = S_d;
+    fa.npairs = npairs;
+    fa.scale = scale;
+    fa.twoQ = (int)p.twoQ;
+    fa.conj = conj ? 1 : 0;
+    for (int64_t b0 = 0; b0 < nblocks; b0 += p.bpp, ++g_passes[5]) {
+        const int64_t nb = std::min(p.bpp, nblocks - b0), m = nb * P;
+        const bool first = b0 == 0, last = b0 + nb == nblocks;
+        for (int r = 0; r < nrec; ++r) {
+            const void *xr = (const char *)xd[r] + esz * (size_t)(b0 * P * hop);
+            if (pair) {
+                const RunPart rp = run_partition(xf.L, m / 2, g.ncu);
+                LAUNCHCHK(launch_stft_rp(lc(), (const float *)xr, (const float *)a_d, (int)hop, m, tb.f + 4 * r, false, xf, rp, SIDED_RAW, 1.f,
+                                         0, g.work.p, nullptr));
+            } else {
+                const RunPart rp = run_partition(xf.L, m, g.ncu);
+                LAUNCHCHK(launch_stft(lc(), xr, cplx, (const float *)a_d, (int)hop, m, tb.f + 4 * r, false, xf, rp, SIDED_RAW, 1.f, 0,
+                                      g.work.p, nullptr));
+            }
+            // [m][np] -> [np][m]: the rows of a short last pass keep the pitch of their own frame count
+            LAUNCHCHK(launch_transpose(lc(), g.work.p, Z[r], m, (int64_t)np, (int)sizeof(cf)));
+            if (Pw_d[r]) LAUNCHCHK(launch_fam_pw(lc(), Z[r], np, m, m, P, (const float *)g_d, pw_acc + (size_t)r * np, first, last, scale, Pw_d[r]));
+        }
+        // y = x: Pwy is Pwx, copied where both are asked for
+        if (!cross && Pw_d[1] && !Pw_d[0])
+            LAUNCHCHK(launch_fam_pw(lc(), Z[0], np, m, m, P, (const float *)g_d, pw_acc + (size_t)np, first, last, scale, Pw_d[1]));
+        if (!cross && Pw_d[1] && Pw_d[0] && last)
+            HIPCHK(hipMemcpyAsync(Pw_d[1], Pw_d[0], sizeof(float) * (size_t)np, hipMemcpyDeviceToDevice, g.stream));
+        if (S_d) {
+            fa.Y = Z[cross ? 1 : 0];
+            fa.X = Z[0];
+            fa.ld = m;
+            fa.nb = nb;
+            fa.first = first ? 1 : 0;
+            fa.last = last ? 1 : 0;
+            ProfScope ps;
+            if (launch_fam(lc(), fa, P, twP) != 0)
+                return fail("sp_fam: the launch was refused (P %d, %lld pairs, %lld blocks)", P, (long long)npairs, (long long)nb);
+            HIPCHK(hipGetLastError());
+            g.last_kernel = "k_fam";
+        }
+    }
     return st.finish();
 }
 

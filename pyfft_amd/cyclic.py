@@ -15,8 +15,8 @@ at frame starts give un-normalised S that add up (pass each part its own `first`
 noverlap defaults to 3/4 of nperseg, not scipy's 1/2: Antoni (2007) shows that the cyclic periodogram under a Hann window at 50 % overlap
 leaks cyclic power (the window's own periodicity at fs / hop aliases into alpha); 2/3 or more is needed, 3/4 is the customary choice.
 
-What is not here: the FFT-accumulation and strip-spectral-correlation estimators that tile the whole (f, alpha) plane at once; the cyclic
-modulation spectrum and Fast-SC (an FFT along the frames of an STFT: compose stft_frames and engine.fft); segments that are no power
+What is not here: the estimators that tile the whole (f, alpha) plane at once (the FFT accumulation method is pyfft_amd.fam, the blind
+search that tells which alpha to pass here; the strip spectral correlation analyzer is not built); the cyclic modulation spectrum and Fast-SC (an FFT along the frames of an STFT: compose stft_frames and engine.fft); segments that are no power
 of two or longer than 8192; per-segment detrending.  Those raise CyclicRefused, which is a ValueError and a NotImplementedError.
 """
 import numpy as np

@@ -259,7 +259,7 @@ def last_passes(which=0):
     """Passes the last call's loops made: which=0 its outermost frame-chunk loop, which=1 the most slice passes of one batch of
     long transforms inside it, which=2 (CYC_PASSES) the passes of `cyclic` over its list of cycle frequencies, which=3 (LOMB_PASSES)
     the passes of `lomb` and `lomb_sums` over their frequencies, which=4 (LOMB_LAUNCHES) the most launches the row groups of one such
-    pass were dealt to; 0 where the call had no such loop (sp_last_passes)."""
+    pass were dealt to, which=5 (FAM_PASSES) the passes of `fam` over its blocks; 0 where the call had no such loop (sp_last_passes)."""
     return int(lib().sp_last_passes(int(which)))
 
 
@@ -1872,6 +1872,94 @@ def wbic_plan(nsig, nscales, k_lo, L, M, n0, block, step, nblocks, nrec=1, sym=T
     return _plan(lib().sp_wbic_plan, ("cells", "cell_len", "groups", "passes", "workgroups", "scratch", "chunk", "tiles"), WbicRefused,
                  "wbic_plan", int(nsig), int(nscales), int(k_lo), int(L), int(M), int(n0), int(block), int(step), int(nblocks), int(nrec),
                  1 if sym else 0)
+
+
+FAM_MIN_N, FAM_MAX_N, FAM_MAX_PAIRS, FAM_PASSES, FAM_ACC_BYTES = 32, 8192, 1 << 22, 5, 2 << 30
+
+
+class FamRefused(ValueError, NotImplementedError):
+    """A shape the FFT accumulation method does not take: outside the limits, and what is not built (channel counts, block lengths and
+    hops that are no power of two, hop above the channel count, leading axes)."""
+
+
+def fam_check(who, np_, hop, P, nblocks, npairs, nsig=None, pairs=None, scale=1.0):
+    """The refusals of sp_fam and sp_fam_plan, before the library is touched -> Q."""
+    _range_check(FamRefused, who, ("np", np_, FAM_MIN_N, FAM_MAX_N))
+    _range_check(FamRefused, who, ("P", P, FAM_MIN_N, FAM_MAX_N))
+    if hop < 1 or hop > np_ or hop & (hop - 1):
+        raise FamRefused("%s: hop = %d must be a power of two from 1 to np = %d" % (who, hop, np_))
+    if P * hop < 2 * np_:
+        raise FamRefused("%s: P hop = %d is below 2 np = %d: no bin lies within half a channel spacing" % (who, P * hop, 2 * np_))
+    _range_check(FamRefused, who, count=("nblocks", nblocks))
+    if nsig is not None and nblocks > 0 and (nsig < np_ or nblocks * P > (nsig - np_) // hop + 1):
+        raise FamRefused("%s: nblocks = %d blocks of %d frames of %d at hop %d reach outside the nsig = %d samples of the row"
+                         % (who, nblocks, P, np_, hop, nsig))
+    if npairs < 1 or npairs > FAM_MAX_PAIRS:
+        raise FamRefused("%s: npairs = %d is outside 1 .. 2^22" % (who, npairs))
+    if pairs is not None and (pairs.min() < 0 or pairs.max() >= np_):
+        raise FamRefused("%s: a channel of pairs lies outside 0 .. np - 1 = %d" % (who, np_ - 1))
+    _range_check(FamRefused, who, scale=scale)
+    return P * hop // (2 * np_)
+
+
+def fam(x, a, hop, g, nblocks, pairs, y=None, conj=False, detrend=True, mean_value=None, scale=1.0, S=True, Pw=True):
+    """The FFT accumulation method on one record, or one pair of records (sp_fam): the channelizer window a (np taps) at step hop, the
+    taper g (P taps) over the frames of a block, nblocks disjoint blocks of P frames, and for every pair (k, l) of pairs[npairs, 2]
+        S[i, j] = scale sum_b sum_p g[p] Y[bP + p, k] conj(X[bP + p, l]) e(-(j - Q) p / P),  j < 2Q,  Q = P hop / (2 np)
+    with X, Y the channelizer outputs demodulated to absolute time (conj: X without the conjugate), Pwx[k] = scale sum g |X[., k]|^2
+    and Pwy alike.  y None: y = x.  Returns (S complex64 [npairs, 2Q], Pwx, Pwy float32 [np]), None for what was not asked for (Pw
+    asks for both powers).  detrend: True removes the record's mean (computed on the device), mean_value a given constant (a pair
+    (mx, my) in the cross form), False nothing.  numpy in -> numpy out; device tensors in -> device tensors on x's stream."""
+    hop, nblocks, scale = int(hop), int(nblocks), float(scale)
+    aw, gw = _win32(a), _win32(g)
+    pr = np.ascontiguousarray(np.asarray(pairs), dtype=np.int32)
+    md = _mode(x)
+    x = md.checked(x)
+    if x.ndim != 1:
+        raise FamRefused("fam: x must be one record: leading axes are not built")
+    if aw.ndim != 1 or gw.ndim != 1 or pr.ndim != 2 or pr.shape[1] != 2:
+        raise FamRefused("fam: a and g need exactly one axis, pairs the shape [npairs, 2]")
+    if not (np.all(np.isfinite(aw)) and np.all(np.isfinite(gw))):
+        raise FamRefused("fam: the windows a and g must be finite")
+    n, P, nsig, npairs = int(aw.size), int(gw.size), int(x.shape[-1]), int(pr.shape[0])
+    Q = fam_check("fam", n, hop, P, nblocks, npairs, nsig, pr if npairs else None, scale)
+    if not (S or Pw):
+        raise FamRefused("fam: no output is asked for")
+    y = _second_record("fam", FamRefused, md, x, y)
+    cross = y is not None
+    md.bind(x)
+    xs = md.samples(x)
+    ys = md.samples(y) if cross else None
+    means = []
+    for i, v in enumerate((xs, ys) if cross else (xs,)):
+        m = np.zeros(1, dtype=np.complex128)
+        if detrend not in (None, False, 0, "none"):
+            if mean_value is not None:
+                m[0] = complex(mean_value[i] if isinstance(mean_value, (tuple, list)) else mean_value)
+            else:
+                m[0] = mean(v)
+        if not np.isfinite(m[0]):
+            raise FamRefused("fam: the mean of the record is not finite")
+        means.append(m)
+    outs = [md.empty((npairs, 2 * Q), "complex64", xs) if S else None, md.empty(n, "float32", xs) if Pw else None,
+            md.empty(n, "float32", xs) if Pw else None]
+    if nblocks == 0:                        # a sum over no blocks: the library launches nothing and leaves the outputs as they are
+        for o in outs:
+            if o is not None:
+                o[...] = 0
+        return tuple(outs)
+    md.call(lib().sp_fam, md.addr(xs), md.addr(ys), md.code(xs), nsig, ptr(aw), n, hop, ptr(gw), P, nblocks, ptr(pr), npairs,
+            1 if conj else 0, ptr(means[0]), ptr(means[1]) if cross else None, scale, md.addr(outs[0]), md.addr(outs[1]), md.addr(outs[2]))
+    return tuple(outs)
+
+
+def fam_plan(np_, hop, P, nblocks, npairs, cplx=False, cross=False):
+    """sp_fam_plan as a dict (host only): Q, blocks_per_pass, passes, workgroups (of the pair kernel, over all passes), scratch (bytes of
+    the bin-major frames of a pass)."""
+    np_, hop, P, nblocks, npairs = int(np_), int(hop), int(P), int(nblocks), int(npairs)
+    fam_check("fam_plan", np_, hop, P, nblocks, npairs)
+    return _plan(lib().sp_fam_plan, ("Q", "blocks_per_pass", "passes", "workgroups", "scratch"), FamRefused, "fam_plan",
+                 _ffi.DTYPE_C64 if cplx else _ffi.DTYPE_F32, 1 if cross else 0, np_, hop, P, nblocks, npairs)
 
 
 EIGH_MAX_N = 64
