@@ -141,10 +141,17 @@ FAM_SIGNATURES = {
     "sp_fam_plan": (_i, [_i, _i, _i, _i64, _i, _i64, _i64, _vp]),
 }
 
+# the ninth table: must list every symbol include/spectral_nufft.h declares, and none of the other eight
+NUFFT_SIGNATURES = {
+    "sp_nufft1": (_i, [_vp, _vp, _i64, _i64, _i64, _d, _d, _d, _i64, _i, _vp, _i]),
+    "sp_lomb_sums_grid": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _d, _d, _d, _d, _i64, _vp, _vp, _vp, _vp, _i]),
+    "sp_nufft1_plan": (_i, [_i64, _i64, _i64, _vp]),
+}
+
 # the six tables the engine trace counts, in the order of their headers
 TABLES = (SIGNATURES, EXT_SIGNATURES, TFR_SIGNATURES, QUAD_SIGNATURES, CYCLO_SIGNATURES, UNEVEN_SIGNATURES)
 # the tables added since: bound like the six, outside the trace
-MORE_TABLES = (WBIC_SIGNATURES, FAM_SIGNATURES)
+MORE_TABLES = (WBIC_SIGNATURES, FAM_SIGNATURES, NUFFT_SIGNATURES)
 
 
 class SpectralError(RuntimeError):

@@ -3,6 +3,7 @@
 #include <limits.h>
 #include <stdlib.h>
 #include "kernels.h"
+#include "nufft_plan.h"
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -38,6 +39,8 @@ namespace sp {
 //   (the last six: unset or <= 0 leaves the budget alone; sp_last_passes reports the passes a call made)
 //   SP_WBIC_CHUNK (int: a cap on the samples per pass of sp_wbic, which reports its passes itself; unset or <= 0: the budget alone)
 //   SP_FAM_BLOCKS (int: a cap on the blocks per pass of sp_fam; unset or <= 0: the budget alone; sp_last_passes(5) reports the passes)
+//   SP_NUFFT_ROWS (int: a cap on the rows per pass of sp_nufft1 / sp_lomb_sums_grid, before the fine grids fill their budget; unset or
+//                  <= 0: the budget alone; sp_last_passes(6) reports the passes)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
     return v && v[0] && v[0] != '0';
@@ -1088,6 +1091,62 @@ struct FamArgs {
 int launch_fam(LaunchCtx c, const FamArgs &a, int P, const cf *tw);
 int launch_fam_pw(LaunchCtx c, const cf *Z, int np, int64_t ld, int64_t nframes, int P, const float *g, double *acc, bool first, bool last,
                   double scale, float *Pw);
+
+// Type-1 NUFFT and the Lomb-Scargle sums on a uniform frequency grid (k_nufft.hip; the arithmetic: nufft_plan.h).  A pass holds the
+// fine grids grid[rows of the pass][nf] complex64 of as many rows as NUFFT_GRID_BYTES take.
+#define NUFFT_GRID_BYTES ((size_t)256 << 20)
+// ls_periodogram / ls_window with method="auto" take the fast path for a uniform grid of N samples x M frequencies from so many
+// (sample, frequency) pairs on.  Measured (tools/nufft_bench.py -> profiles/nufft_bench.txt, the "crossing" lines, N = M = 2^k): with one
+// row the direct sums win up to k = 14 (0.27 against 0.34 ms) and lose from k = 15 on (0.66 against 0.34 ms); with eight rows they
+// lose from k = 14 on.  2^30 pairs is the first measured point from which the fast path wins at both row counts.
+#define LOMB_FAST_MIN_PAIRS ((int64_t)1 << 30)
+#define NUFFT_HIST 2048                   // up to so many tiles a workgroup counts its samples per tile in LDS first
+#define NUFFT_PREP_SPT 8                  // samples per thread of k_nufft_prep and k_nufft_fill: 2048 per workgroup
+inline int nufft_rowmax_blocks(int64_t N) { return (int)(N < 4096 * 64 ? (N + 4095) / 4096 : 64); }
+struct NufftRec {                         // a prepared sample: the first cell of its footprint, the offset in it, the centre phase
+    int i0;
+    float dx, pc, ps;
+};
+// the strengths of row q at sample j: complex rows c_ld apart, or (c null) the prepared Lomb record: row 0 = head[j].w, row q >= 1 = row
+// q - 1 of wy[groups][npad][RP] (R rows to a group), all real
+struct NufftSrc {
+    const cf *c;
+    int64_t c_ld;
+    const LombHead *head;
+    const float *wy;
+    int64_t npad;
+    int R, RP;
+};
+struct NufftPrepArgs {
+    const double *t;
+    int64_t N, nf, tiles;
+    double t_ref;
+    int sets;                             // position sets: 1, or 2 for the Lomb sums (phi and 2 phi)
+    double q[2], fc[2];                   // per set: the position is frac(q tau), the centre phase frac(fc tau)
+    NufftRec *rec;                        // [sets][N]
+    unsigned *count;                      // [sets][tiles], zeroed by the caller
+    int *status;                          // [2]: a time (or a product with it) that is not finite; set by launch_nufft_rowshift: a strength that is not
+};
+struct NufftSpreadArgs {
+    NufftSrc src;
+    int64_t row0;                         // first row of the pass
+    int nrows;                            // rows of the pass
+    int64_t nf;
+    const NufftRec *rec;
+    const int64_t *off;                   // [tiles + 1]
+    const int *list;
+    const int *shift;                     // [rows]
+    cf *grid;                             // [nrows][nf]
+};
+int launch_nufft_prep(LaunchCtx c, const NufftPrepArgs &a);
+// part: [rows][nufft_rowmax_blocks(N)] floats of scratch
+int launch_nufft_rowshift(LaunchCtx c, const NufftSrc &src, int64_t rows, int64_t N, float *part, int *shift, int *status);
+// the counts of one set scanned into off[tiles + 1] (and zeroed), then every sample entered into list (2 N entries at most)
+int launch_nufft_bin(LaunchCtx c, const NufftRec *rec, int64_t N, int64_t nf, unsigned *count, int64_t *off, int *list);
+int launch_nufft_spread(LaunchCtx c, const NufftSpreadArgs &a);
+// row r of the transformed grid -> dst + r * row_ld + m * stride: complex64 elements (f32) or pairs of float64
+int launch_nufft_pick(LaunchCtx c, const cf *grid, int64_t nf, int64_t M, int64_t nrows, const NufftQuad &q, bool f32, void *dst,
+                      int64_t row_ld, int64_t stride);
 
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;

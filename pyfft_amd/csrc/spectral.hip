@@ -7,6 +7,7 @@
 #include "../../include/spectral_uneven.h"
 #include "../../include/spectral_wbic.h"
 #include "../../include/spectral_fam.h"
+#include "../../include/spectral_nufft.h"
 #include "launch.h"
 #include "stage.h"
 #include "table_cache.h"
@@ -97,6 +98,7 @@ struct Ctx {
     Scratch mtS;                                    // multitaper: the per-taper cross spectra behind the weighted one
     Scratch wbW, wbP, wbA;                          // wavelet bispectrum: the transforms of a pass, its fp32 partials, the float64 cell sums
     Scratch famZ, famA;                             // FFT accumulation: the bin-major frames of a pass, the float64 sums across passes
+    Scratch nuRec, nuGrid;                          // type-1 NUFFT: the prepared samples, tile lists and shifts of a call; the fine grids of a pass
     Scratch cmS, cmT, cmG, cmH, cmO;               // CSD matrix: spectra, bin-major spectra, float64 accumulator, packed-spectra sums, one-pass means state
     std::map<int64_t, BigTw> bigtw;           // N -> two-level twiddle tables of the multi-pass FFT
     std::map<int64_t, BlueTab> blue_big;      // n -> chirp[n], FFT_L(chirp*) (unscaled) for multi-pass Bluestein
@@ -230,9 +232,9 @@ TableCache g_tables;
 // sp_last_passes: [0] the passes of the current call's outermost frame-chunk loop, [1] the most slice passes one
 // dev_fft_any / sp_czt loop made inside it, [2] the passes over the cycle-frequency list of sp_cyclic, [3] the passes over the
 // frequency list of sp_lomb / sp_lomb_sums, [4] the most launches the row groups of one such pass were dealt to, [5] the passes over the
-// blocks of sp_fam.  All are zeroed
+// blocks of sp_fam, [6] the passes over the rows of sp_nufft1 / sp_lomb_sums_grid.  All are zeroed
 // where a call begins (ApiLock), so that a test can assert that the shape it chose really walks a loop past its first pass.
-int g_passes[6] = {0, 0, 0, 0, 0, 0};
+int g_passes[7] = {0, 0, 0, 0, 0, 0, 0};
 inline void note_slices(int64_t n) {
     if (n > g_passes[1]) g_passes[1] = (int)n;
 }
@@ -248,7 +250,7 @@ struct ApiLock {
     std::lock_guard<std::mutex> lk;
     ApiLock() : lk(g.mu) {
         g_tables.begin_call();
-        g_passes[0] = g_passes[1] = g_passes[2] = g_passes[3] = g_passes[4] = g_passes[5] = 0;
+        g_passes[0] = g_passes[1] = g_passes[2] = g_passes[3] = g_passes[4] = g_passes[5] = g_passes[6] = 0;
     }
 };
 
@@ -1332,7 +1334,7 @@ int sp_max_wg_fft(void) { return SP_MAX_WG_FFT; }
 const char *sp_last_error(void) { return g_err.c_str(); }
 int sp_last_passes(int which) {
     std::lock_guard<std::mutex> lk(g.mu);
-    return which >= 0 && which <= 5 ? g_passes[which] : 0;
+    return which >= 0 && which <= 6 ? g_passes[which] : 0;
 }
 
 int sp_init(int device_id) {
@@ -1398,6 +1400,8 @@ void sp_shutdown(void) {
     g.wbA.release();
     g.famZ.release();
     g.famA.release();
+    g.nuRec.release();
+    g.nuGrid.release();
     for (auto &kv : g.bigtw) {
         (void)hipFree((void *)kv.second.hi);
         (void)hipFree((void *)kv.second.lo);
@@ -4071,17 +4075,65 @@ int sp_lomb_plan(int64_t N, int64_t M, int64_t batch, int64_t out[5]) {
     return 0;
 }
 
-// f[M] and mean[batch] behind one another at `at` in g_lombRec (sized by the caller), on the stream
+// f[M] (null: none) and mean[batch] behind one another at `at` in g_lombRec (sized by the caller), on the stream
 static int lomb_upload(size_t at, const double *f, int64_t M, const double *mean, int64_t batch, const double **f_d, const double **mean_d) {
     char *base = (char *)g_lombRec.p + at;
-    HIPCHK(hipMemcpyAsync(base, f, sizeof(double) * (size_t)M, hipMemcpyHostToDevice, g.stream));
-    *f_d = (const double *)base;
+    if (f) HIPCHK(hipMemcpyAsync(base, f, sizeof(double) * (size_t)M, hipMemcpyHostToDevice, g.stream));
+    *f_d = f ? (const double *)base : nullptr;
     *mean_d = nullptr;
     if (mean && batch > 0) {
         char *mp = base + lomb_up(sizeof(double) * (size_t)M);
         HIPCHK(hipMemcpyAsync(mp, mean, sizeof(double) * (size_t)batch, hipMemcpyHostToDevice, g.stream));
         *mean_d = (const double *)mp;
     }
+    return 0;
+}
+
+// the record prepared in g_lombRec beside the call's small tables (f null: no frequency list), and what it must not hold looked
+// for: 0, -1, or SP_LOMB_BAD_RECORD with nothing written anywhere else
+struct LombRec {
+    LombPrepArgs pa;
+    const double *f_d, *mean_d;
+};
+static int lomb_prepare(const char *who, const LombPlan &p, const double *t_d, const double *w_d, const float *y_d, int64_t y_ld, int64_t N,
+                        int64_t batch, double t_ref, double wnorm, const double *f, int64_t M, const double *mean, LombRec *out) {
+    const int64_t npad = lomb_npad(N), nt = 1 + 2 * batch;
+    // the prepared record and the call's small tables, each at a multiple of 256 bytes
+    const size_t o_head = 0, o_wy = o_head + lomb_up(sizeof(LombHead) * (size_t)npad);
+    const size_t o_wpart = o_wy + lomb_up(sizeof(float) * (size_t)p.groups * (size_t)npad * (size_t)p.RP);
+    const size_t o_tpart = o_wpart + lomb_up(sizeof(double) * LOMB_PREP_BLOCKS);
+    const size_t o_tot = o_tpart + lomb_up(sizeof(double) * (size_t)nt * LOMB_PREP_BLOCKS);
+    const size_t o_status = o_tot + lomb_up(sizeof(double) * (size_t)nt);
+    const size_t o_f = o_status + 256;
+    const size_t total = o_f + lomb_up(sizeof(double) * (size_t)M) + lomb_up(sizeof(double) * (size_t)(batch + 1));
+    if (g_lombRec.ensure(total)) return -1;
+    char *rec = (char *)g_lombRec.p;
+    const double *f_d, *mean_d;
+    if (lomb_upload(o_f, f, M, mean, batch, &f_d, &mean_d)) return -1;
+    LombPrepArgs pa{};
+    pa.t = t_d, pa.w = w_d, pa.y = y_d;
+    pa.y_ld = y_ld, pa.N = N, pa.npad = npad, pa.batch = batch, pa.rows_padded = p.R ? p.groups * p.RP : 0;
+    pa.R = p.R, pa.RP = p.RP;
+    pa.t_ref = t_ref, pa.wnorm = wnorm;
+    pa.mean = mean_d;
+    pa.blocks = p.prep_blocks, pa.len = p.prep_len;
+    pa.wpart = (double *)(rec + o_wpart);
+    pa.head = (LombHead *)(rec + o_head);
+    pa.wy = p.RP ? (float *)(rec + o_wy) : nullptr;
+    pa.tpart = (double *)(rec + o_tpart);
+    pa.totals = (double *)(rec + o_tot);
+    pa.status = (int *)(rec + o_status);
+    HIPCHK(hipMemsetAsync(pa.status, 0, 4 * sizeof(int), g.stream));
+    if (launch_lomb_prep(lc(), pa) != 0) return fail("%s: the record could not be prepared (N %lld, batch %lld)", who, (long long)N, (long long)batch);
+    HIPCHK(hipGetLastError());
+    int flags[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(flags, pa.status, sizeof flags, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    if (flags[0]) return fail("%s: t holds a value that is not finite", who), SP_LOMB_BAD_RECORD;
+    if (flags[1]) return fail("%s: w holds a weight that is negative or not finite", who), SP_LOMB_BAD_RECORD;
+    if (flags[2]) return fail("%s: the weights (w, or wnorm) do not sum to a positive finite value", who), SP_LOMB_BAD_RECORD;
+    if (flags[3]) return fail("%s: y holds a value that is not finite", who), SP_LOMB_BAD_RECORD;
+    out->pa = pa, out->f_d = f_d, out->mean_d = mean_d;
     return 0;
 }
 
@@ -4125,41 +4177,10 @@ static int lomb_run(const char *who, const double *t, const double *w, const flo
         st.out(g.out0, (char *)P, esz * (size_t)batch * (size_t)M, &P_d);
     }
     if (st.commit()) return -1;
-    // the prepared record and the call's small tables, each at a multiple of 256 bytes
-    const size_t o_head = 0, o_wy = o_head + lomb_up(sizeof(LombHead) * (size_t)npad);
-    const size_t o_wpart = o_wy + lomb_up(sizeof(float) * (size_t)p.groups * (size_t)npad * (size_t)p.RP);
-    const size_t o_tpart = o_wpart + lomb_up(sizeof(double) * LOMB_PREP_BLOCKS);
-    const size_t o_tot = o_tpart + lomb_up(sizeof(double) * (size_t)nt * LOMB_PREP_BLOCKS);
-    const size_t o_status = o_tot + lomb_up(sizeof(double) * (size_t)nt);
-    const size_t o_f = o_status + 256;
-    const size_t total = o_f + lomb_up(sizeof(double) * (size_t)M) + lomb_up(sizeof(double) * (size_t)(batch + 1));
-    if (g_lombRec.ensure(total)) return -1;
-    char *rec = (char *)g_lombRec.p;
-    const double *f_d, *mean_d;
-    if (lomb_upload(o_f, f, M, mean, batch, &f_d, &mean_d)) return -1;
-    LombPrepArgs pa{};
-    pa.t = t_d, pa.w = w_d, pa.y = y_d;
-    pa.y_ld = y_ld, pa.N = N, pa.npad = npad, pa.batch = batch, pa.rows_padded = p.R ? p.groups * p.RP : 0;
-    pa.R = p.R, pa.RP = p.RP;
-    pa.t_ref = t_ref, pa.wnorm = wnorm;
-    pa.mean = mean_d;
-    pa.blocks = p.prep_blocks, pa.len = p.prep_len;
-    pa.wpart = (double *)(rec + o_wpart);
-    pa.head = (LombHead *)(rec + o_head);
-    pa.wy = p.RP ? (float *)(rec + o_wy) : nullptr;
-    pa.tpart = (double *)(rec + o_tpart);
-    pa.totals = (double *)(rec + o_tot);
-    pa.status = (int *)(rec + o_status);
-    HIPCHK(hipMemsetAsync(pa.status, 0, 4 * sizeof(int), g.stream));
-    if (launch_lomb_prep(lc(), pa) != 0) return fail("%s: the record could not be prepared (N %lld, batch %lld)", who, (long long)N, (long long)batch);
-    HIPCHK(hipGetLastError());
-    int flags[4] = {0, 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(flags, pa.status, sizeof flags, hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream));
-    if (flags[0]) return fail("%s: t holds a value that is not finite", who), SP_LOMB_BAD_RECORD;
-    if (flags[1]) return fail("%s: w holds a weight that is negative or not finite", who), SP_LOMB_BAD_RECORD;
-    if (flags[2]) return fail("%s: the weights (w, or wnorm) do not sum to a positive finite value", who), SP_LOMB_BAD_RECORD;
-    if (flags[3]) return fail("%s: y holds a value that is not finite", who), SP_LOMB_BAD_RECORD;
+    LombRec rec;
+    if (const int rc = lomb_prepare(who, p, t_d, w_d, y_d, y_ld, N, batch, t_ref, wnorm, f, M, mean, &rec)) return rc;
+    const LombPrepArgs &pa = rec.pa;
+    const double *f_d = rec.f_d, *mean_d = rec.mean_d;
     if (sums_only) HIPCHK(hipMemcpyAsync(totals_d, pa.totals, sizeof(double) * (size_t)nt, hipMemcpyDeviceToDevice, g.stream));
     if (g.work.ensure(sizeof(double) * (size_t)p.gpl * (size_t)p.split * (size_t)p.nv * (size_t)p.fpass)) return -1;
     double *sc_common = nullptr, *sc_rows = nullptr;
@@ -4251,6 +4272,212 @@ int sp_lomb_finish(const double *common, const double *rows, const double *total
         return fail("%s: the finish step was refused", who);
     HIPCHK(hipGetLastError());
     if (!st.host) HIPCHK(hipStreamSynchronize(g.stream));       // f and mean are the caller's again
+    return st.finish();
+}
+
+// ---- type-1 NUFFT and the Lomb-Scargle sums on a uniform frequency grid (k_nufft.hip; include/spectral_nufft.h) ----------
+static const char *nufft_shape(int64_t N, int64_t M, int64_t batch) {
+    if (const char *why = lomb_shape(N, M, batch)) return why;
+    if (nufft_nf(M) > NUFFT_MAX_NF) return "the fine grid of next_pow2(2 M) cells is beyond 2^26";
+    return nullptr;
+}
+// fc = f0 + (M / 2) df, the centre of the modes; 0 or the message's tail
+static const char *nufft_grid_args(double t_ref, double f0, double df, int64_t M, double *fc) {
+    if (!isfinite(t_ref)) return "t_ref must be finite";
+    if (!isfinite(f0)) return "f0 must be finite";
+    if (!isfinite(df)) return "df must be finite";
+    if (df == 0.0) return "df must not be zero";
+    *fc = f0 + (double)(M / 2) * df;
+    if (!isfinite(2.0 * *fc) || !isfinite(f0 + (double)M * df)) return "f0 + M df must be finite";
+    return nullptr;
+}
+static NufftPlan nufft_plan_now(int64_t M, int64_t rows) { return nufft_plan_of(M, rows, NUFFT_GRID_BYTES, env_int("SP_NUFFT_ROWS", 0)); }
+
+int sp_nufft1_plan(int64_t N, int64_t M, int64_t batch, int64_t out[8]) {
+    if (!out || nufft_shape(N, M, batch)) return -1;
+    const NufftPlan p = nufft_plan_now(M, batch);
+    out[0] = p.nf;
+    out[1] = NUFFT_W;
+    out[2] = p.tiles;
+    out[3] = NUFFT_TILE;
+    out[4] = p.rpp;
+    out[5] = p.passes;
+    out[6] = p.workgroups;
+    out[7] = LOMB_FAST_MIN_PAIRS;
+    return 0;
+}
+
+struct NufftWork {
+    NufftRec *rec;                  // [sets][N]
+    unsigned *count;                // [sets][tiles]
+    int64_t *off;                   // [sets][tiles + 1]
+    int *list;                      // [sets][2 N]
+    int *shift;                     // [rows]
+    int flags[2];                   // read back: a time, a strength that is not finite
+};
+// the samples of `sets` position sets prepared and entered into their tile lists, the shifts of `rows` rows taken, and the status read
+// back (one synchronisation): everything the passes share
+static int nufft_prepare(const char *who, const double *t_d, int64_t N, double t_ref, int sets, const double *q, const double *fc,
+                         const NufftPlan &p, const NufftSrc &src, int64_t rows, NufftWork *w) {
+    const size_t o_rec = 0, o_list = o_rec + lomb_up(sizeof(NufftRec) * (size_t)sets * (size_t)N);
+    const size_t o_count = o_list + lomb_up(sizeof(int) * (size_t)sets * 2 * (size_t)N);
+    const size_t o_off = o_count + lomb_up(sizeof(unsigned) * (size_t)sets * (size_t)p.tiles);
+    const size_t o_shift = o_off + lomb_up(sizeof(int64_t) * (size_t)sets * (size_t)(p.tiles + 1));
+    const size_t o_part = o_shift + lomb_up(sizeof(int) * (size_t)rows);
+    const size_t o_status = o_part + lomb_up(sizeof(float) * (size_t)rows * (size_t)nufft_rowmax_blocks(N));
+    if (g.nuRec.ensure(o_status + 256)) return -1;
+    char *base = (char *)g.nuRec.p;
+    w->rec = (NufftRec *)(base + o_rec);
+    w->list = (int *)(base + o_list);
+    w->count = (unsigned *)(base + o_count);
+    w->off = (int64_t *)(base + o_off);
+    w->shift = (int *)(base + o_shift);
+    int *status = (int *)(base + o_status);
+    HIPCHK(hipMemsetAsync(w->count, 0, sizeof(unsigned) * (size_t)sets * (size_t)p.tiles, g.stream));
+    HIPCHK(hipMemsetAsync(status, 0, 2 * sizeof(int), g.stream));
+    NufftPrepArgs a{};
+    a.t = t_d, a.N = N, a.nf = p.nf, a.tiles = p.tiles, a.t_ref = t_ref, a.sets = sets;
+    for (int s = 0; s < sets; ++s) a.q[s] = q[s], a.fc[s] = fc[s];
+    a.rec = w->rec, a.count = w->count, a.status = status;
+    if (launch_nufft_prep(lc(), a) != 0) return fail("%s: the samples could not be prepared (N %lld, nf %lld)", who, (long long)N, (long long)p.nf);
+    HIPCHK(hipGetLastError());
+    if (launch_nufft_rowshift(lc(), src, rows, N, (float *)(base + o_part), w->shift, status) != 0) return fail("%s: the rows' shifts could not be taken", who);
+    HIPCHK(hipGetLastError());
+    for (int s = 0; s < sets; ++s) {
+        if (launch_nufft_bin(lc(), w->rec + (int64_t)s * N, N, p.nf, w->count + (int64_t)s * p.tiles, w->off + (int64_t)s * (p.tiles + 1),
+                             w->list + (int64_t)s * 2 * N) != 0)
+            return fail("%s: the tile lists could not be filled", who);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(w->flags, status, sizeof w->flags, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    return 0;
+}
+// rows row0 .. row0 + nrows - 1 of position set `set` spread onto the pass's grids and transformed in place
+static int nufft_grids(const char *who, const NufftWork &w, int set, const NufftSrc &src, int64_t N, int64_t row0, int64_t nrows,
+                       const NufftPlan &p, bool timed) {
+    NufftSpreadArgs a{};
+    a.src = src, a.row0 = row0, a.nrows = (int)nrows, a.nf = p.nf;
+    a.rec = w.rec + (int64_t)set * N, a.off = w.off + (int64_t)set * (p.tiles + 1), a.list = w.list + (int64_t)set * 2 * N;
+    a.shift = w.shift, a.grid = (cf *)g.nuGrid.p;
+    int rc;
+    if (timed) {                    // the profile keeps the spread of the rows, not the one-row spread of A2 behind it
+        ProfScope ps;
+        rc = launch_nufft_spread(lc(), a);
+    } else {
+        rc = launch_nufft_spread(lc(), a);
+    }
+    if (rc != 0)
+        return fail("%s: the spread was refused (%lld rows from %lld on %lld cells)", who, (long long)nrows, (long long)row0, (long long)p.nf);
+    HIPCHK(hipGetLastError());
+    g.last_kernel = "k_nufft_spread";
+    return dev_fft_any(a.grid, a.grid, p.nf, nrows, 0);
+}
+
+int sp_nufft1(const double *t, const void *c, int64_t c_ld, int64_t N, int64_t batch, double t_ref, double f0, double df, int64_t M,
+              int sign, void *out, int mem) {
+    const char *who = "sp_nufft1";
+    if (const char *why = nufft_shape(N, M, batch))
+        return fail("%s: %s (N %lld, M %lld, batch %lld)", who, why, (long long)N, (long long)M, (long long)batch);
+    if (c_ld < N) return fail("%s: c_ld = %lld is below N = %lld", who, (long long)c_ld, (long long)N);
+    if (sign != 1 && sign != -1) return fail("%s: sign = %d must be +1 or -1", who, sign);
+    double fc;
+    if (const char *why = nufft_grid_args(t_ref, f0, df, M, &fc)) return fail("%s: %s", who, why);
+    if (!t) return fail("%s: t is required", who);
+    if (!c) return fail("%s: c is required", who);
+    if (!out) return fail("%s: out is required", who);
+    if (batch == 0) return 0;
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const NufftPlan p = nufft_plan_now(M, batch);
+    Stage st(mem);
+    const double *t_d;
+    const cf *c_d;
+    cf *out_d;
+    st.in(g.in0, t, sizeof(double) * (size_t)N, &t_d);
+    st.in(g.in0, (const cf *)c, sizeof(cf) * (size_t)((batch - 1) * c_ld + N), &c_d);
+    st.out(g.out0, (cf *)out, sizeof(cf) * (size_t)batch * (size_t)M, &out_d);
+    if (st.commit()) return -1;
+    NufftSrc src{};
+    src.c = c_d, src.c_ld = c_ld;
+    const double q = -(double)sign * df, fcs = (double)sign * fc;
+    NufftWork w;
+    if (nufft_prepare(who, t_d, N, t_ref, 1, &q, &fcs, p, src, batch, &w)) return -1;
+    if (w.flags[0]) return fail("%s: t holds a value that is not finite, or one whose product with df or f0 is not", who), SP_NUFFT_BAD_RECORD;
+    if (w.flags[1]) return fail("%s: c holds a value that is not finite", who), SP_NUFFT_BAD_RECORD;
+    if (g.nuGrid.ensure(sizeof(cf) * (size_t)p.rpp * (size_t)p.nf)) return -1;
+    const NufftQuad quad = nufft_quad(p.nf);
+    for (int64_t r0 = 0; r0 < batch; r0 += p.rpp, ++g_passes[6]) {
+        const int64_t nr = std::min<int64_t>(p.rpp, batch - r0);
+        if (nufft_grids(who, w, 0, src, N, r0, nr, p, true)) return -1;
+        if (launch_nufft_pick(lc(), (const cf *)g.nuGrid.p, p.nf, M, nr, quad, true, out_d + r0 * M, M, 1) != 0)
+            return fail("%s: the pick was refused", who);
+        HIPCHK(hipGetLastError());
+    }
+    return st.finish();
+}
+
+int sp_lomb_sums_grid(const double *t, const double *w, const float *y, int64_t y_ld, int64_t N, int64_t batch, double t_ref, double wnorm,
+                      double f0, double df, int64_t M, const double *mean, double *common, double *rows, double *totals, int mem) {
+    const char *who = "sp_lomb_sums_grid";
+    if (const char *why = nufft_shape(N, M, batch))
+        return fail("%s: %s (N %lld, M %lld, batch %lld)", who, why, (long long)N, (long long)M, (long long)batch);
+    if (batch > 0 && y_ld < N) return fail("%s: y_ld = %lld is below N = %lld", who, (long long)y_ld, (long long)N);
+    double fc;
+    if (const char *why = nufft_grid_args(t_ref, f0, df, M, &fc)) return fail("%s: %s", who, why);
+    if (!isfinite(wnorm)) return fail("%s: wnorm must be finite", who);
+    for (int64_t b = 0; mean && b < batch; ++b)
+        if (!isfinite(mean[b])) return fail("%s: every mean must be finite (index %lld)", who, (long long)b);
+    if (!t) return fail("%s: t is required", who);
+    if (batch > 0 && !y) return fail("%s: y is required", who);
+    if (!common) return fail("%s: common is required", who);
+    if (!totals) return fail("%s: totals is required", who);
+    if (batch > 0 && !rows) return fail("%s: rows is required", who);
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const LombPlan lp = lomb_plan_now(N, M, batch);                 // its row groups and prep blocks: the record sp_lomb_sums prepares
+    const NufftPlan p = nufft_plan_now(M, 1 + batch);
+    if (batch == 0) y = nullptr;
+    const int64_t nt = 1 + 2 * batch;
+    Stage st(mem);
+    const double *t_d, *w_d;
+    const float *y_d;
+    double *common_d = nullptr, *rows_d = nullptr, *totals_d = nullptr;
+    st.in(g.in0, t, sizeof(double) * (size_t)N, &t_d);
+    st.in(g.in0, w, sizeof(double) * (size_t)N, &w_d);
+    st.in(g.in0, y, sizeof(float) * (size_t)((batch - 1) * y_ld + N), &y_d);
+    st.out(g.out0, common, sizeof(double) * 4 * (size_t)M, &common_d);
+    st.out(g.out0, batch > 0 ? rows : nullptr, sizeof(double) * 2 * (size_t)batch * (size_t)M, &rows_d);
+    st.out(g.out0, totals, sizeof(double) * (size_t)nt, &totals_d);
+    if (st.commit()) return -1;
+    LombRec rec;
+    if (const int rc = lomb_prepare(who, lp, t_d, w_d, y_d, y_ld, N, batch, t_ref, wnorm, nullptr, 0, mean, &rec)) return rc;
+    NufftSrc src{};
+    src.head = rec.pa.head, src.wy = rec.pa.wy, src.npad = rec.pa.npad, src.R = lp.R ? lp.R : 1, src.RP = lp.RP ? lp.RP : 1;
+    const double q[2] = {-df, -2.0 * df}, fcs[2] = {fc, 2.0 * fc};
+    NufftWork wk;
+    if (nufft_prepare(who, t_d, N, t_ref, 2, q, fcs, p, src, 1 + batch, &wk)) return -1;
+    if (wk.flags[0]) return fail("%s: a time's product with df or f0 is not finite", who), SP_LOMB_BAD_RECORD;
+    if (wk.flags[1]) return fail("%s: a weight or a value leaves float32 once the weights are normalised", who), SP_LOMB_BAD_RECORD;
+    HIPCHK(hipMemcpyAsync(totals_d, rec.pa.totals, sizeof(double) * (size_t)nt, hipMemcpyDeviceToDevice, g.stream));
+    if (g.nuGrid.ensure(sizeof(cf) * (size_t)p.rpp * (size_t)p.nf)) return -1;
+    const cf *grid = (const cf *)g.nuGrid.p;
+    const NufftQuad quad = nufft_quad(p.nf);
+    // A1 and the B_r: row 0 is w32, row 1 + r is wy32_r, under the positions of phi
+    for (int64_t r0 = 0; r0 < 1 + batch; r0 += p.rpp, ++g_passes[6]) {
+        const int64_t nr = std::min<int64_t>(p.rpp, 1 + batch - r0);
+        if (nufft_grids(who, wk, 0, src, N, r0, nr, p, true)) return -1;
+        const int64_t lead = r0 == 0 ? 1 : 0;                       // the pass's rows that go to common
+        if (lead && launch_nufft_pick(lc(), grid, p.nf, M, 1, quad, false, common_d, 0, 4) != 0) return fail("%s: the pick was refused", who);
+        if (nr > lead &&
+            launch_nufft_pick(lc(), grid + lead * p.nf, p.nf, M, nr - lead, quad, false, rows_d + 2 * M * (r0 + lead - 1), 2 * M, 2) != 0)
+            return fail("%s: the pick was refused", who);
+        HIPCHK(hipGetLastError());
+    }
+    // A2: w32 under the doubled positions, on the same grid length
+    if (nufft_grids(who, wk, 1, src, N, 0, 1, p, false)) return -1;
+    if (launch_nufft_pick(lc(), grid, p.nf, M, 1, quad, false, common_d + 2, 0, 4) != 0) return fail("%s: the pick was refused", who);
+    HIPCHK(hipGetLastError());
     return st.finish();
 }
 

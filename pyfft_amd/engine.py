@@ -259,7 +259,8 @@ def last_passes(which=0):
     """Passes the last call's loops made: which=0 its outermost frame-chunk loop, which=1 the most slice passes of one batch of
     long transforms inside it, which=2 (CYC_PASSES) the passes of `cyclic` over its list of cycle frequencies, which=3 (LOMB_PASSES)
     the passes of `lomb` and `lomb_sums` over their frequencies, which=4 (LOMB_LAUNCHES) the most launches the row groups of one such
-    pass were dealt to, which=5 (FAM_PASSES) the passes of `fam` over its blocks; 0 where the call had no such loop (sp_last_passes)."""
+    pass were dealt to, which=5 (FAM_PASSES) the passes of `fam` over its blocks, which=6 (NUFFT_PASSES) the passes of `nufft1` and
+    `lomb_sums_grid` over their rows; 0 where the call had no such loop (sp_last_passes)."""
     return int(lib().sp_last_passes(int(which)))
 
 
@@ -1762,6 +1763,105 @@ def lomb_plan(N, M, rows=1):
     lomb_check("lomb_plan", N, M, rows)
     return _plan(lib().sp_lomb_plan, ("rows_per_group", "freqs_per_pass", "passes", "split", "workgroups"), LombRefused, "lomb_plan", N, M,
                  rows)
+
+
+NUFFT_W, NUFFT_TILE, NUFFT_MAX_M, NUFFT_MAX_ROWS, NUFFT_PASSES, NUFFT_BAD_RECORD = 8, 1024, 1 << 24, 65535, 6, -2
+
+
+class NufftRefused(ValueError, NotImplementedError):
+    """A record or a frequency grid the type-1 NUFFT does not take: outside the limits, values a record must not hold, and what is
+    not built (float64 strengths on the device, rows with times of their own, types 2 and 3, more than one dimension)."""
+
+
+def nufft_check(who, N, M, rows, c_ld=None, t_ref=0.0, f0=0.0, df=1.0, sign=1, Refused=NufftRefused):
+    """The refusals of sp_nufft1, sp_lomb_sums_grid and sp_nufft1_plan, before the library is touched."""
+    if N < 1 or N >= 1 << 31:
+        raise Refused("%s: N = %d samples are outside 1 .. 2^31 - 1" % (who, N))
+    if M < 1 or M > NUFFT_MAX_M:
+        raise Refused("%s: M = %d frequencies are outside 1 .. 2^24" % (who, M))
+    _range_check(Refused, who, rows=(rows, NUFFT_MAX_ROWS))
+    if c_ld is not None and rows > 0 and c_ld < N:
+        raise Refused("%s: the rows' pitch %d is below N = %d" % (who, c_ld, N))
+    if not (np.isfinite(t_ref) and np.isfinite(f0) and np.isfinite(df)) or df == 0 or not np.isfinite(2.0 * (f0 + M * df)):
+        raise Refused("%s: t_ref, f0 and df must be finite, df not zero, and f0 + M df within float64" % who)
+    if sign not in (1, -1):
+        raise Refused("%s: sign must be +1 or -1, not %r" % (who, sign))
+
+
+def _bad_record_call(md, Refused, entry, *args):
+    """md.call, with the return code of a record the device refused (-2) raised as `Refused`"""
+    md.init()
+    rc = entry(*args, md.mem)
+    if rc == NUFFT_BAD_RECORD:
+        raise Refused((lib().sp_last_error() or b"the record was refused").decode())
+    check(rc)
+
+
+def nufft1(t, c, f0, df, M, sign=1, t_ref=None):
+    """The type-1 NUFFT (sp_nufft1): F[..., m] = sum_j c[..., j] exp(2 pi i sign (f0 + m df) (t_j - t_ref)), m = 0 .. M - 1, of
+    complex strengths c[..., N] at the times t[N] (float64, any order, duplicates allowed, shared by the rows).  t_ref: the origin the
+    phases are taken from (default t[0]; pass 0.0 for phases from the origin of t itself).  Returns complex64 [..., M]; a permutation
+    of the samples changes no bit of it.  numpy in -> numpy out; device tensors in (t float64, c complex64) -> a device tensor."""
+    who = "nufft1"
+    md = _mode(t)
+    if _mode(c) is not md:
+        raise TypeError("%s: t and c must both be numpy arrays or both device tensors" % who)
+    if md.dev:
+        if t.dtype != torch.float64 or c.dtype != torch.complex64:
+            raise NufftRefused("%s: on the device times are float64 and strengths complex64 tensors" % who)
+        tv = t.contiguous()
+        tdim, N = tv.dim(), int(tv.shape[-1]) if tv.dim() else 0
+    else:
+        tv = np.ascontiguousarray(np.asarray(t), dtype=np.float64)
+        c = np.ascontiguousarray(np.asarray(c), dtype=np.complex64)
+        tdim, N = tv.ndim, int(tv.shape[-1]) if tv.ndim else 0
+    if tdim != 1 or len(c.shape) < 1 or int(c.shape[-1]) != N:
+        raise NufftRefused("%s: t needs exactly one axis, and the last axis of c its %d samples" % (who, N))
+    f0, df, M, sign = float(f0), float(df), int(M), int(sign) if sign in (1, -1) else sign
+    lead, rows = _lead_rows(c.shape)
+    if N >= 1 and t_ref is None:
+        t_ref = float(tv[0])
+    nufft_check(who, N, M, rows, None, 0.0 if t_ref is None else float(t_ref), f0, df, sign)
+    t_ref = float(t_ref)
+    if not md.dev and not (np.all(np.isfinite(tv)) and np.all(np.isfinite(c))):
+        raise NufftRefused("%s: t and c must be finite" % who)
+    md.bind(tv)
+    out = md.empty(lead + (M,), "complex64", tv)
+    if rows:
+        cs, ld = md.rows(c.reshape(rows, N) if len(c.shape) != 2 else c)
+        nufft_check(who, N, M, rows, ld, t_ref, f0, df, sign)
+        _bad_record_call(md, NufftRefused, lib().sp_nufft1, md.addr(tv), md.addr(cs), ld, N, rows, t_ref, f0, df, M, sign, md.addr(out))
+    return out
+
+
+def lomb_sums_grid(t, y, f0, df, M, weights=None, t_ref=None, mean_value=None, wnorm=None):
+    """`lomb_sums` at the frequencies f0 + m df, m = 0 .. M - 1, by three type-1 NUFFTs (sp_lomb_sums_grid): O(N + M log M) in place of
+    O(N M).  The LombSums differ from lomb_sums' by rounding only, go to `lomb_finish` unchanged and add up like them; the totals
+    are bitwise lomb_sums'.  A permutation of the samples changes no bit of common and rows, given equal weights or a wnorm and a
+    mean_value."""
+    who = "lomb_sums_grid"
+    wn = 0.0 if wnorm is None else float(wnorm)
+    if not np.isfinite(wn) or (wnorm is not None and wn <= 0):
+        raise LombRefused("%s: wnorm must be positive and finite" % who)
+    f0, df, M = float(f0), float(df), int(M)
+    nufft_check(who, 1, M, 0, None, 0.0, f0, df, 1, LombRefused)           # the grid, before the record is looked at
+    md, tv, wv, ys, ld, lead, N, rows, _, t_ref, mv = _lomb_record(who, t, y, np.array([f0, df]), weights, t_ref, mean_value)
+    nufft_check(who, N, M, rows, ld, t_ref, f0, df, 1, LombRefused)
+    common = md.empty((M, 4), "float64", tv)
+    sums = md.empty(lead + (M, 2), "float64", tv) if rows else None
+    totals = md.empty((1 + 2 * rows,), "float64", tv)
+    _bad_record_call(md, LombRefused, lib().sp_lomb_sums_grid, md.addr(tv), md.addr(wv), md.addr(ys), ld, N, rows, t_ref, wn, f0, df, M, ptr(mv),
+                     md.addr(common), md.addr(sums), md.addr(totals))
+    return LombSums(common, sums, totals, mv, t_ref, N)
+
+
+def nufft_plan(N, M, rows=1):
+    """sp_nufft1_plan as a dict (host only): nf (fine-grid cells), width (kernel cells), tiles, tile (cells of one), rows_per_pass,
+    passes, workgroups (of the spread kernel), fast_min_pairs (the N M from which ls_periodogram's method='auto' takes the fast path)."""
+    N, M, rows = int(N), int(M), int(rows)
+    nufft_check("nufft_plan", N, M, rows)
+    return _plan(lib().sp_nufft1_plan, ("nf", "width", "tiles", "tile", "rows_per_pass", "passes", "workgroups", "fast_min_pairs"),
+                 NufftRefused, "nufft_plan", N, M, rows)
 
 
 WBIC_MAX_S, WBIC_MAX_M, WBIC_TILE, WBIC_GROUP = 512, 3072, 64, 2048

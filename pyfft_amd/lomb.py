@@ -6,7 +6,8 @@ without inventing data.
 At every frequency the periodogram is the least-squares fit of a sinusoid (with `floating_mean`, of a sinusoid and a constant) to the
 weighted samples.  One kernel (engine.lomb, sp_lomb) takes three complex sums per frequency in one pass over the samples, one lane
 per frequency, and a float64 finish step applies scipy's body to them; scipy's own O(N M) float64 product on the host materialises
-N x M arrays.  Times are float64 and may come in any order, with duplicates; the phases are taken from an origin near the record
+N x M arrays.  On a uniform frequency grid the same sums are three type-1 NUFFTs (engine.lomb_sums_grid, sp_lomb_sums_grid; Press &
+Rybicki 1989 in its modern form): O(N + M log M), taken with method='fast', or with method='auto' from the measured crossover on.  Times are float64 and may come in any order, with duplicates; the phases are taken from an origin near the record
 (`t_ref`, by default the first sample), so a far time origin costs nothing.  Results are bitwise reproducible.
 
     lombscargle     scipy's signature and semantics (angular frequencies, one row)
@@ -14,9 +15,10 @@ N x M arrays.  Times are float64 and may come in any order, with duplicates; the
     ls_window       the spectral window |sum w e^{2 pi i f t}|^2 of the sampling pattern: what to look at first in a gapped record
     ls_grid         a frequency grid from the record's span and mean rate
     ls_level        the level the normalised periodogram exceeds with probability p under white Gaussian noise
-    ls_plan         how a shape is dealt to the device
+    ls_plan         how a shape is dealt to the device, and which path it takes
+    uniform_grid    whether a frequency list is a uniform grid for a record: what method='fast' needs
 
-What is not here: the NUFFT / Press-Rybicki fast form for uniform frequency grids; cross spectra and coherence between unevenly
+What is not here: cross spectra and coherence between unevenly
 sampled channels (the complex 'amplitude' form of several rows over one t is what to build them from); a segment-averaged
 Lomb-Scargle; float64 or complex values on the device; rows with times of their own in one call; multi-term and multi-band models;
 bootstrap false-alarm levels.  What is refused raises LombRefused, which is a ValueError and a NotImplementedError.
@@ -66,21 +68,81 @@ def lombscargle(x, y, freqs, precenter=False, normalize=False, *, weights=None, 
     return _engine.lomb(xs, ys, fr / TWO_PI, weights=ws, floating_mean=bool(floating_mean), normalize=normalize)
 
 
-def ls_periodogram(t, y, f, weights=None, floating_mean=True, normalize="normalize", t_ref=None):
+UNIFORM_TURNS = 1e-9          # method='fast': every f[k] within so many turns over the record's span of f[0] + k df
+
+
+def _span(t):
+    if _is_torch(t):
+        return float(t.max() - t.min()) if t.numel() else 0.0
+    tt = np.asarray(t, dtype=np.float64)
+    return float(np.max(tt) - np.min(tt)) if tt.size else 0.0
+
+
+def uniform_grid(t, f):
+    """(f0, df, M) where the frequencies f are a uniform grid for the record t -- every |f[k] - (f[0] + k df)| span at most 1e-9 turns,
+    df = (f[-1] - f[0]) / (M - 1) not zero -- and None where they are not (one frequency is a grid of any step)."""
+    fv = np.asarray(f.detach().cpu().numpy() if _is_torch(f) else f, dtype=np.float64)
+    if fv.ndim != 1 or fv.size < 1 or not np.all(np.isfinite(fv)):
+        return None
+    M = int(fv.size)
+    if M == 1:
+        return float(fv[0]), 1.0, 1
+    df = float((fv[-1] - fv[0]) / (M - 1))
+    if df == 0 or not np.isfinite(df):
+        return None
+    span = _span(t)
+    if not np.isfinite(span) or np.max(np.abs(fv - (fv[0] + df * np.arange(M)))) * span > UNIFORM_TURNS:
+        return None
+    return float(fv[0]), df, M
+
+
+def _path(who, method, t, f):
+    """None for the direct sums, (f0, df, M) for the fast ones"""
+    if method == "direct":
+        return None
+    if method not in ("fast", "auto"):
+        raise LombRefused("%s: method must be 'direct', 'fast' or 'auto', not %r" % (who, method))
+    grid = uniform_grid(t, f)
+    if method == "fast":
+        if grid is None:
+            raise LombRefused("%s: method='fast' needs a uniform frequency grid: every f[k] within 1e-9 turns over the record's span "
+                              "of f[0] + k df, df not zero" % who)
+        return grid
+    if grid is None:
+        return None
+    N = int(t.shape[-1]) if len(t.shape) else 0
+    if N < 1 or N >= 1 << 31 or grid[2] > _engine.NUFFT_MAX_M:
+        return None
+    return grid if N * grid[2] >= _engine.nufft_plan(N, grid[2])["fast_min_pairs"] else None
+
+
+def ls_periodogram(t, y, f, weights=None, floating_mean=True, normalize="normalize", t_ref=None, method="direct"):
     """The periodogram P [..., M] of the rows y[..., N] over one axis of times t[N] at the frequencies f[M] in Hz (cycles per unit of
     t); float32, or complex64 for normalize='amplitude': the best-fit a + ib of a cos + b sin referred to the origin of t.
     Accuracy: about 1e-6 of a row's largest value (held on the device to 6e-6) at frequencies from 1 / span on.  Below 1 / span a
     floating-mean fit is nearly degenerate -- the sinusoid, the constant and the record's window are close to collinear -- and
     amplifies the float32 rounding: at 1 / (5 span) the 'amplitude' form is good to 6e-5 of the row's largest value only (float32
-    restatement, tests/test_host_lomb.py).  Those bins carry no independent information; scipy's float64 is what to use for them."""
-    return _engine.lomb(t, y, f, weights=weights, floating_mean=floating_mean, normalize=normalize, t_ref=t_ref)
+    restatement, tests/test_host_lomb.py).  Those bins carry no independent information; scipy's float64 is what to use for them.
+    method: 'direct' (the default: one (sample, frequency) pair at a time, any frequencies), 'fast' (three type-1 NUFFTs; f must be a
+    uniform grid, see uniform_grid, and the result is that of the grid f[0] + k df itself; it differs from 'direct' by rounding,
+    about 1e-6 of a row's largest value) or 'auto' ('fast' where f is uniform and N M is beyond the measured crossover)."""
+    grid = _path("ls_periodogram", method, t if _is_torch(t) else np.asarray(t), f)
+    if grid is None:
+        return _engine.lomb(t, y, f, weights=weights, floating_mean=floating_mean, normalize=normalize, t_ref=t_ref)
+    if y is None:
+        raise LombRefused("ls_periodogram: y is required (ls_window takes the window's sums without rows)")
+    f0, df, M = grid
+    sums = _engine.lomb_sums_grid(t, y, f0, df, M, weights=weights, t_ref=t_ref)
+    return _engine.lomb_finish(sums, f0 + df * np.arange(M), floating_mean=floating_mean, normalize=normalize)
 
 
-def ls_window(t, f, weights=None):
+def ls_window(t, f, weights=None, method="direct"):
     """The spectral window of the sampling pattern, |sum_n wn e^{2 pi i f (t_n - t_0)}|^2 with the weights normalised to sum to one
     (float64 [M]): 1 at f = 0, and near 1 again wherever the sampling repeats -- at the multiples of the rate of an even clock.  A
-    line at f0 in the record shows up at f0 plus every peak of the window.  From the device's sums without rows."""
-    s = _engine.lomb_sums(t, None, f, weights=weights)
+    line at f0 in the record shows up at f0 plus every peak of the window.  From the device's sums without rows; method as in
+    ls_periodogram."""
+    grid = _path("ls_window", method, t if _is_torch(t) else np.asarray(t), f)
+    s = _engine.lomb_sums(t, None, f, weights=weights) if grid is None else _engine.lomb_sums_grid(t, None, *grid, weights=weights)
     W = s.totals[0]
     return (s.common[:, 0] ** 2 + s.common[:, 1] ** 2) / (W * W)
 
@@ -115,7 +177,19 @@ def ls_level(N, p, nindep=1):
     return float(1.0 - p1 ** (2.0 / (N - 3)))
 
 
-def ls_plan(N, M, rows=1):
+def ls_plan(N, M, rows=1, method=None):
     """How engine.lomb deals N samples, M frequencies and `rows` rows to the device (sp_lomb_plan, host only): rows_per_group,
-    freqs_per_pass, passes, split (sample runs), workgroups."""
-    return _engine.lomb_plan(N, M, rows)
+    freqs_per_pass, passes, split (sample runs), workgroups.  With a method ('direct', 'fast', 'auto') also `path`, the path a uniform
+    grid of that shape takes ('direct' or 'fast': 'auto' goes by N M against the measured crossover), and under `fast` the plan of the
+    fast path's 1 + rows transforms (engine.nufft_plan)."""
+    plan = _engine.lomb_plan(N, M, rows)
+    if method is None:
+        return plan
+    if method not in ("direct", "fast", "auto"):
+        raise LombRefused("ls_plan: method must be 'direct', 'fast' or 'auto', not %r" % (method,))
+    try:
+        fast = _engine.nufft_plan(N, M, int(rows) + 1)
+    except _engine.NufftRefused as exc:
+        raise LombRefused(str(exc))
+    take = method == "fast" or (method == "auto" and int(N) * int(M) >= fast["fast_min_pairs"])
+    return dict(plan, path="fast" if take else "direct", fast=fast)
