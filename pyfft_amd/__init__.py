@@ -62,7 +62,8 @@ from .cyclic import (scd, cyclic_coherence, cyclic_spectra, cyclic_profile, alph
 from . import lomb as _lomb_mod                                # noqa: F401
 from .lomb import lombscargle, ls_periodogram, ls_window, ls_grid, ls_level, ls_plan     # noqa: F401
 from . import nufft as _nufft_mod                              # noqa: F401
-from .nufft import nufft1, nufft1_modes, nufft_plan            # noqa: F401
+from .nufft import (nufft1, nufft1_modes, nufft_plan, nufft2, nufft2_modes, nufft2_plan, nufft_fit, regrid,   # noqa: F401
+                    NufftFit)
 from . import wbicoherence as _wbic_mod                        # noqa: F401
 from .wbicoherence import (wbic_freqs, wavelet_bispectrum, wavelet_bicoherence, summed_bicoherence,   # noqa: F401
                            total_bicoherence, wbic_plan)

@@ -148,10 +148,16 @@ NUFFT_SIGNATURES = {
     "sp_nufft1_plan": (_i, [_i64, _i64, _i64, _vp]),
 }
 
+# the tenth table: must list every symbol include/spectral_nufft2.h declares, and none of the other nine
+NUFFT2_SIGNATURES = {
+    "sp_nufft2": (_i, [_vp, _vp, _i64, _i64, _i64, _d, _d, _d, _i64, _i, _vp, _i64, _i]),
+    "sp_nufft2_plan": (_i, [_i64, _i64, _i64, _vp]),
+}
+
 # the six tables the engine trace counts, in the order of their headers
 TABLES = (SIGNATURES, EXT_SIGNATURES, TFR_SIGNATURES, QUAD_SIGNATURES, CYCLO_SIGNATURES, UNEVEN_SIGNATURES)
 # the tables added since: bound like the six, outside the trace
-MORE_TABLES = (WBIC_SIGNATURES, FAM_SIGNATURES, NUFFT_SIGNATURES)
+MORE_TABLES = (WBIC_SIGNATURES, FAM_SIGNATURES, NUFFT_SIGNATURES, NUFFT2_SIGNATURES)
 
 
 class SpectralError(RuntimeError):

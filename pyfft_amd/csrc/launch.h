@@ -39,7 +39,7 @@ namespace sp {
 //   (the last six: unset or <= 0 leaves the budget alone; sp_last_passes reports the passes a call made)
 //   SP_WBIC_CHUNK (int: a cap on the samples per pass of sp_wbic, which reports its passes itself; unset or <= 0: the budget alone)
 //   SP_FAM_BLOCKS (int: a cap on the blocks per pass of sp_fam; unset or <= 0: the budget alone; sp_last_passes(5) reports the passes)
-//   SP_NUFFT_ROWS (int: a cap on the rows per pass of sp_nufft1 / sp_lomb_sums_grid, before the fine grids fill their budget; unset or
+//   SP_NUFFT_ROWS (int: a cap on the rows per pass of sp_nufft1 / sp_nufft2 / sp_lomb_sums_grid, before the fine grids fill their budget; unset or
 //                  <= 0: the budget alone; sp_last_passes(6) reports the passes)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
@@ -1147,6 +1147,27 @@ int launch_nufft_spread(LaunchCtx c, const NufftSpreadArgs &a);
 // row r of the transformed grid -> dst + r * row_ld + m * stride: complex64 elements (f32) or pairs of float64
 int launch_nufft_pick(LaunchCtx c, const cf *grid, int64_t nf, int64_t M, int64_t nrows, const NufftQuad &q, bool f32, void *dst,
                       int64_t row_ld, int64_t stride);
+
+// Type-2 NUFFT (k_nufft2.hip): the adjoint of the above over the same prepared samples, tile lists, kernel and fine grids.
+// Rows of a row group of k_nufft2_interp: a workgroup stages NUFFT_TILE + NUFFT_W - 1 = 1031 cells per row (held at a pitch of
+// NUFFT2_PITCH = 1032, so that every row starts on 16 bytes).  4 rows are 33 KB: well within the 64 KiB a launch gets unasked, four
+// workgroups (16 waves) to a CU's 160 KiB, and the 8 kernel values of a sample are shared by 4 rows.  7 rows would fit the 64 KiB and
+// leave two workgroups to a CU, too few to hide the latency of the scattered LDS reads and the global stores.
+#define NUFFT2_RG 4
+#define NUFFT2_PITCH (NUFFT_TILE + NUFFT_W)
+struct Nufft2InterpArgs {
+    const cf *grid;                       // [nrows][nf], transformed
+    int nrows;                            // rows of the pass
+    int64_t nf, N;
+    const NufftRec *rec;
+    const int64_t *off;                   // [tiles + 1]
+    const int *list;
+    cf *out;                              // row r of the pass at out + r * out_ld, sample j at + j
+    int64_t out_ld;
+};
+// grid[r][(m - M / 2) mod nf] = F[r * F_ld + m] / phihat(m - M / 2), every other cell of grid[nrows][nf] zero: each cell written once
+int launch_nufft2_place(LaunchCtx c, const cf *F, int64_t F_ld, int64_t M, int64_t nrows, int64_t nf, const NufftQuad &q, cf *grid);
+int launch_nufft2_interp(LaunchCtx c, const Nufft2InterpArgs &a);
 
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;

@@ -8,6 +8,7 @@
 #include "../../include/spectral_wbic.h"
 #include "../../include/spectral_fam.h"
 #include "../../include/spectral_nufft.h"
+#include "../../include/spectral_nufft2.h"
 #include "launch.h"
 #include "stage.h"
 #include "table_cache.h"
@@ -232,7 +233,7 @@ TableCache g_tables;
 // sp_last_passes: [0] the passes of the current call's outermost frame-chunk loop, [1] the most slice passes one
 // dev_fft_any / sp_czt loop made inside it, [2] the passes over the cycle-frequency list of sp_cyclic, [3] the passes over the
 // frequency list of sp_lomb / sp_lomb_sums, [4] the most launches the row groups of one such pass were dealt to, [5] the passes over the
-// blocks of sp_fam, [6] the passes over the rows of sp_nufft1 / sp_lomb_sums_grid.  All are zeroed
+// blocks of sp_fam, [6] the passes over the rows of sp_nufft1 / sp_lomb_sums_grid / sp_nufft2.  All are zeroed
 // where a call begins (ApiLock), so that a test can assert that the shape it chose really walks a loop past its first pass.
 int g_passes[7] = {0, 0, 0, 0, 0, 0, 0};
 inline void note_slices(int64_t n) {
@@ -4316,15 +4317,16 @@ struct NufftWork {
     int flags[2];                   // read back: a time, a strength that is not finite
 };
 // the samples of `sets` position sets prepared and entered into their tile lists, the shifts of `rows` rows taken, and the status read
-// back (one synchronisation): everything the passes share
+// back (one synchronisation): everything the passes share.  src_n: the elements of a row of src the shift and the check for values that
+// are not finite look at: N for strengths at the samples, M for the modes of the type-2 transform
 static int nufft_prepare(const char *who, const double *t_d, int64_t N, double t_ref, int sets, const double *q, const double *fc,
-                         const NufftPlan &p, const NufftSrc &src, int64_t rows, NufftWork *w) {
+                         const NufftPlan &p, const NufftSrc &src, int64_t rows, int64_t src_n, NufftWork *w) {
     const size_t o_rec = 0, o_list = o_rec + lomb_up(sizeof(NufftRec) * (size_t)sets * (size_t)N);
     const size_t o_count = o_list + lomb_up(sizeof(int) * (size_t)sets * 2 * (size_t)N);
     const size_t o_off = o_count + lomb_up(sizeof(unsigned) * (size_t)sets * (size_t)p.tiles);
     const size_t o_shift = o_off + lomb_up(sizeof(int64_t) * (size_t)sets * (size_t)(p.tiles + 1));
     const size_t o_part = o_shift + lomb_up(sizeof(int) * (size_t)rows);
-    const size_t o_status = o_part + lomb_up(sizeof(float) * (size_t)rows * (size_t)nufft_rowmax_blocks(N));
+    const size_t o_status = o_part + lomb_up(sizeof(float) * (size_t)rows * (size_t)nufft_rowmax_blocks(src_n));
     if (g.nuRec.ensure(o_status + 256)) return -1;
     char *base = (char *)g.nuRec.p;
     w->rec = (NufftRec *)(base + o_rec);
@@ -4341,7 +4343,7 @@ static int nufft_prepare(const char *who, const double *t_d, int64_t N, double t
     a.rec = w->rec, a.count = w->count, a.status = status;
     if (launch_nufft_prep(lc(), a) != 0) return fail("%s: the samples could not be prepared (N %lld, nf %lld)", who, (long long)N, (long long)p.nf);
     HIPCHK(hipGetLastError());
-    if (launch_nufft_rowshift(lc(), src, rows, N, (float *)(base + o_part), w->shift, status) != 0) return fail("%s: the rows' shifts could not be taken", who);
+    if (launch_nufft_rowshift(lc(), src, rows, src_n, (float *)(base + o_part), w->shift, status) != 0) return fail("%s: the rows' shifts could not be taken", who);
     HIPCHK(hipGetLastError());
     for (int s = 0; s < sets; ++s) {
         if (launch_nufft_bin(lc(), w->rec + (int64_t)s * N, N, p.nf, w->count + (int64_t)s * p.tiles, w->off + (int64_t)s * (p.tiles + 1),
@@ -4402,7 +4404,7 @@ int sp_nufft1(const double *t, const void *c, int64_t c_ld, int64_t N, int64_t b
     src.c = c_d, src.c_ld = c_ld;
     const double q = -(double)sign * df, fcs = (double)sign * fc;
     NufftWork w;
-    if (nufft_prepare(who, t_d, N, t_ref, 1, &q, &fcs, p, src, batch, &w)) return -1;
+    if (nufft_prepare(who, t_d, N, t_ref, 1, &q, &fcs, p, src, batch, N, &w)) return -1;
     if (w.flags[0]) return fail("%s: t holds a value that is not finite, or one whose product with df or f0 is not", who), SP_NUFFT_BAD_RECORD;
     if (w.flags[1]) return fail("%s: c holds a value that is not finite", who), SP_NUFFT_BAD_RECORD;
     if (g.nuGrid.ensure(sizeof(cf) * (size_t)p.rpp * (size_t)p.nf)) return -1;
@@ -4456,7 +4458,7 @@ int sp_lomb_sums_grid(const double *t, const double *w, const float *y, int64_t 
     src.head = rec.pa.head, src.wy = rec.pa.wy, src.npad = rec.pa.npad, src.R = lp.R ? lp.R : 1, src.RP = lp.RP ? lp.RP : 1;
     const double q[2] = {-df, -2.0 * df}, fcs[2] = {fc, 2.0 * fc};
     NufftWork wk;
-    if (nufft_prepare(who, t_d, N, t_ref, 2, q, fcs, p, src, 1 + batch, &wk)) return -1;
+    if (nufft_prepare(who, t_d, N, t_ref, 2, q, fcs, p, src, 1 + batch, N, &wk)) return -1;
     if (wk.flags[0]) return fail("%s: a time's product with df or f0 is not finite", who), SP_LOMB_BAD_RECORD;
     if (wk.flags[1]) return fail("%s: a weight or a value leaves float32 once the weights are normalised", who), SP_LOMB_BAD_RECORD;
     HIPCHK(hipMemcpyAsync(totals_d, rec.pa.totals, sizeof(double) * (size_t)nt, hipMemcpyDeviceToDevice, g.stream));
@@ -4478,6 +4480,87 @@ int sp_lomb_sums_grid(const double *t, const double *w, const float *y, int64_t 
     if (nufft_grids(who, wk, 1, src, N, 0, 1, p, false)) return -1;
     if (launch_nufft_pick(lc(), grid, p.nf, M, 1, quad, false, common_d + 2, 0, 4) != 0) return fail("%s: the pick was refused", who);
     HIPCHK(hipGetLastError());
+    return st.finish();
+}
+
+// ---- type-2 NUFFT (k_nufft2.hip; include/spectral_nufft2.h): the parts of type 1 above, run the other way ------------------------
+static int64_t nufft2_workgroups(const NufftPlan &p, int64_t rows) {
+    int64_t n = 0;
+    for (int64_t r0 = 0; r0 < rows; r0 += p.rpp) n += p.tiles * ((std::min<int64_t>(p.rpp, rows - r0) + NUFFT2_RG - 1) / NUFFT2_RG);
+    return n;
+}
+
+int sp_nufft2_plan(int64_t N, int64_t M, int64_t batch, int64_t out[8]) {
+    if (!out || nufft_shape(N, M, batch)) return -1;
+    const NufftPlan p = nufft_plan_now(M, batch);
+    out[0] = p.nf;
+    out[1] = NUFFT_W;
+    out[2] = p.tiles;
+    out[3] = NUFFT_TILE;
+    out[4] = p.rpp;
+    out[5] = p.passes;
+    out[6] = nufft2_workgroups(p, batch);
+    out[7] = NUFFT2_RG;
+    return 0;
+}
+
+int sp_nufft2(const double *t, const void *F, int64_t F_ld, int64_t N, int64_t batch, double t_ref, double f0, double df, int64_t M,
+              int sign, void *out, int64_t out_ld, int mem) {
+    const char *who = "sp_nufft2";
+    if (const char *why = nufft_shape(N, M, batch))
+        return fail("%s: %s (N %lld, M %lld, batch %lld)", who, why, (long long)N, (long long)M, (long long)batch);
+    if (F_ld < M) return fail("%s: F_ld = %lld is below M = %lld", who, (long long)F_ld, (long long)M);
+    if (out_ld < N) return fail("%s: out_ld = %lld is below N = %lld", who, (long long)out_ld, (long long)N);
+    if (sign != 1 && sign != -1) return fail("%s: sign = %d must be +1 or -1", who, sign);
+    double fc;
+    if (const char *why = nufft_grid_args(t_ref, f0, df, M, &fc)) return fail("%s: %s", who, why);
+    if (!t) return fail("%s: t is required", who);
+    if (!F) return fail("%s: F is required", who);
+    if (!out) return fail("%s: out is required", who);
+    if (batch == 0) return 0;
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const NufftPlan p = nufft_plan_now(M, batch);
+    Stage st(mem);
+    const double *t_d;
+    const cf *F_d, *out_in;
+    cf *out_d;
+    const size_t out_bytes = sizeof(cf) * (size_t)((batch - 1) * out_ld + N);
+    st.in(g.in0, t, sizeof(double) * (size_t)N, &t_d);
+    st.in(g.in0, (const cf *)F, sizeof(cf) * (size_t)((batch - 1) * F_ld + M), &F_d);
+    // host rows further apart than N: the columns between them are the caller's, carried there and back unchanged
+    if (out_ld > N) st.inout(g.out0, (const cf *)out, (cf *)out, out_bytes, &out_in, &out_d);
+    else st.out(g.out0, (cf *)out, out_bytes, &out_d);
+    if (st.commit()) return -1;
+    NufftSrc src{};
+    src.c = F_d, src.c_ld = F_ld;                                   // the row-shift step's source: its status word finds modes that are not finite
+    const double q = -(double)sign * df, fcs = (double)sign * fc;
+    NufftWork w;
+    if (nufft_prepare(who, t_d, N, t_ref, 1, &q, &fcs, p, src, batch, M, &w)) return -1;
+    if (w.flags[0]) return fail("%s: t holds a value that is not finite, or one whose product with df or f0 is not", who), SP_NUFFT_BAD_RECORD;
+    if (w.flags[1]) return fail("%s: F holds a value that is not finite", who), SP_NUFFT_BAD_RECORD;
+    if (g.nuGrid.ensure(sizeof(cf) * (size_t)p.rpp * (size_t)p.nf)) return -1;
+    const NufftQuad quad = nufft_quad(p.nf);
+    cf *grid = (cf *)g.nuGrid.p;
+    for (int64_t r0 = 0; r0 < batch; r0 += p.rpp, ++g_passes[6]) {
+        const int64_t nr = std::min<int64_t>(p.rpp, batch - r0);
+        if (launch_nufft2_place(lc(), F_d + r0 * F_ld, F_ld, M, nr, p.nf, quad, grid) != 0) return fail("%s: the placing of the modes was refused", who);
+        HIPCHK(hipGetLastError());
+        if (dev_fft_any(grid, grid, p.nf, nr, 0)) return -1;
+        Nufft2InterpArgs a{};
+        a.grid = grid, a.nrows = (int)nr, a.nf = p.nf, a.N = N;
+        a.rec = w.rec, a.off = w.off, a.list = w.list;
+        a.out = out_d + r0 * out_ld, a.out_ld = out_ld;
+        int rc;
+        {
+            ProfScope ps;
+            rc = launch_nufft2_interp(lc(), a);
+        }
+        if (rc != 0)
+            return fail("%s: the interpolation was refused (%lld rows from %lld on %lld cells)", who, (long long)nr, (long long)r0, (long long)p.nf);
+        HIPCHK(hipGetLastError());
+        g.last_kernel = "k_nufft2_interp";
+    }
     return st.finish();
 }
 

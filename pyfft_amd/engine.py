@@ -259,8 +259,8 @@ def last_passes(which=0):
     """Passes the last call's loops made: which=0 its outermost frame-chunk loop, which=1 the most slice passes of one batch of
     long transforms inside it, which=2 (CYC_PASSES) the passes of `cyclic` over its list of cycle frequencies, which=3 (LOMB_PASSES)
     the passes of `lomb` and `lomb_sums` over their frequencies, which=4 (LOMB_LAUNCHES) the most launches the row groups of one such
-    pass were dealt to, which=5 (FAM_PASSES) the passes of `fam` over its blocks, which=6 (NUFFT_PASSES) the passes of `nufft1` and
-    `lomb_sums_grid` over their rows; 0 where the call had no such loop (sp_last_passes)."""
+    pass were dealt to, which=5 (FAM_PASSES) the passes of `fam` over its blocks, which=6 (NUFFT_PASSES) the passes of `nufft1`, `nufft2`
+    and `lomb_sums_grid` over their rows; 0 where the call had no such loop (sp_last_passes)."""
     return int(lib().sp_last_passes(int(which)))
 
 
@@ -1769,8 +1769,8 @@ NUFFT_W, NUFFT_TILE, NUFFT_MAX_M, NUFFT_MAX_ROWS, NUFFT_PASSES, NUFFT_BAD_RECORD
 
 
 class NufftRefused(ValueError, NotImplementedError):
-    """A record or a frequency grid the type-1 NUFFT does not take: outside the limits, values a record must not hold, and what is
-    not built (float64 strengths on the device, rows with times of their own, types 2 and 3, more than one dimension)."""
+    """A record or a frequency grid the type-1 and type-2 NUFFT do not take: outside the limits, values a record must not hold, and what is
+    not built (float64 strengths on the device, rows with times of their own, type 3, more than one dimension)."""
 
 
 def nufft_check(who, N, M, rows, c_ld=None, t_ref=0.0, f0=0.0, df=1.0, sign=1, Refused=NufftRefused):
@@ -1832,6 +1832,55 @@ def nufft1(t, c, f0, df, M, sign=1, t_ref=None):
         nufft_check(who, N, M, rows, ld, t_ref, f0, df, sign)
         _bad_record_call(md, NufftRefused, lib().sp_nufft1, md.addr(tv), md.addr(cs), ld, N, rows, t_ref, f0, df, M, sign, md.addr(out))
     return out
+
+
+def nufft2(t, F, f0, df, sign=1, t_ref=None):
+    """The type-2 NUFFT (sp_nufft2): c[..., j] = sum_m F[..., m] exp(2 pi i sign (f0 + m df) (t_j - t_ref)), j = 0 .. N - 1, of the
+    modes F[..., M] (complex, M taken from it) at the times t[N] (float64, any order, duplicates allowed, shared by the rows): the
+    adjoint of `nufft1` with the other sign.  t_ref: the origin the phases are taken from (default t[0]; 0.0 for the origin of t
+    itself).  Returns complex64 [..., N]; an output depends on its own sample alone, so a permutation of the samples permutes it bit
+    for bit.  numpy in -> numpy out; device tensors in (t float64, F complex64) -> a device tensor."""
+    who = "nufft2"
+    md = _mode(t)
+    if _mode(F) is not md:
+        raise TypeError("%s: t and F must both be numpy arrays or both device tensors" % who)
+    if md.dev:
+        if t.dtype != torch.float64 or F.dtype != torch.complex64:
+            raise NufftRefused("%s: on the device times are float64 and modes complex64 tensors" % who)
+        tv = t.contiguous()
+        tdim, N = tv.dim(), int(tv.shape[-1]) if tv.dim() else 0
+    else:
+        tv = np.ascontiguousarray(np.asarray(t), dtype=np.float64)
+        F = np.ascontiguousarray(np.asarray(F), dtype=np.complex64)
+        tdim, N = tv.ndim, int(tv.shape[-1]) if tv.ndim else 0
+    if tdim != 1 or len(F.shape) < 1:
+        raise NufftRefused("%s: t needs exactly one axis, and F at least one: its last holds the modes" % who)
+    M = int(F.shape[-1])
+    f0, df, sign = float(f0), float(df), int(sign) if sign in (1, -1) else sign
+    lead, rows = _lead_rows(F.shape)
+    if N >= 1 and t_ref is None:
+        t_ref = float(tv[0])
+    nufft_check(who, N, M, rows, None, 0.0 if t_ref is None else float(t_ref), f0, df, sign)
+    t_ref = float(t_ref)
+    if not md.dev and not (np.all(np.isfinite(tv)) and np.all(np.isfinite(F))):
+        raise NufftRefused("%s: t and F must be finite" % who)
+    md.bind(tv)
+    out = md.empty(lead + (N,), "complex64", tv)
+    if rows:
+        Fs, ld = md.rows(F.reshape(rows, M) if len(F.shape) != 2 else F)
+        if ld < M:
+            raise NufftRefused("%s: the rows' pitch %d is below M = %d" % (who, ld, M))
+        _bad_record_call(md, NufftRefused, lib().sp_nufft2, md.addr(tv), md.addr(Fs), ld, N, rows, t_ref, f0, df, M, sign, md.addr(out), N)
+    return out
+
+
+def nufft2_plan(N, M, rows=1):
+    """sp_nufft2_plan as a dict (host only): nf (fine-grid cells), width (kernel cells), tiles, tile (cells of one), rows_per_pass,
+    passes, workgroups (of the interpolation kernel), row_group (rows a workgroup stages)."""
+    N, M, rows = int(N), int(M), int(rows)
+    nufft_check("nufft2_plan", N, M, rows)
+    return _plan(lib().sp_nufft2_plan, ("nf", "width", "tiles", "tile", "rows_per_pass", "passes", "workgroups", "row_group"),
+                 NufftRefused, "nufft2_plan", N, M, rows)
 
 
 def lomb_sums_grid(t, y, f0, df, M, weights=None, t_ref=None, mean_value=None, wnorm=None):
