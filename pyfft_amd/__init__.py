@@ -64,6 +64,9 @@ from .lomb import lombscargle, ls_periodogram, ls_window, ls_grid, ls_level, ls_
 from . import nufft as _nufft_mod                              # noqa: F401
 from .nufft import (nufft1, nufft1_modes, nufft_plan, nufft2, nufft2_modes, nufft2_plan, nufft_fit, regrid,   # noqa: F401
                     NufftFit)
+from . import parametric as _parametric_mod                    # noqa: F401
+from .parametric import (arburg, aryule, pburg, pyulear, ar_spectrogram, ar_psd, ar_order, ar_stepup, ar_poles, ar_plan,   # noqa: F401
+                         ArRefused)
 from . import wbicoherence as _wbic_mod                        # noqa: F401
 from .wbicoherence import (wbic_freqs, wavelet_bispectrum, wavelet_bicoherence, summed_bicoherence,   # noqa: F401
                            total_bicoherence, wbic_plan)

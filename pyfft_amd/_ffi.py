@@ -154,10 +154,19 @@ NUFFT2_SIGNATURES = {
     "sp_nufft2_plan": (_i, [_i64, _i64, _i64, _vp]),
 }
 
+# the eleventh table: must list every symbol include/spectral_ar.h declares, and none of the other ten
+_AR_FIT = (_i, [_vp, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i, _i, _d, _d, _vp, _vp, _vp, _i64, _i])
+AR_SIGNATURES = {
+    "sp_burg": _AR_FIT,
+    "sp_yule": _AR_FIT,
+    "sp_ar_psd": (_i, [_vp, _i, _i64, _vp, _i64, _i, _i64, _i64, _d, _d, _d, _i, _vp, _i64, _i]),
+    "sp_ar_plan": (_i, [_i, _i, _i64, _i, _i64, _i64, _vp]),
+}
+
 # the six tables the engine trace counts, in the order of their headers
 TABLES = (SIGNATURES, EXT_SIGNATURES, TFR_SIGNATURES, QUAD_SIGNATURES, CYCLO_SIGNATURES, UNEVEN_SIGNATURES)
 # the tables added since: bound like the six, outside the trace
-MORE_TABLES = (WBIC_SIGNATURES, FAM_SIGNATURES, NUFFT_SIGNATURES, NUFFT2_SIGNATURES)
+MORE_TABLES = (WBIC_SIGNATURES, FAM_SIGNATURES, NUFFT_SIGNATURES, NUFFT2_SIGNATURES, AR_SIGNATURES)
 
 
 class SpectralError(RuntimeError):

@@ -4,6 +4,7 @@
 #include <stdlib.h>
 #include "kernels.h"
 #include "nufft_plan.h"
+#include "ar_plan.h"
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -41,6 +42,8 @@ namespace sp {
 //   SP_FAM_BLOCKS (int: a cap on the blocks per pass of sp_fam; unset or <= 0: the budget alone; sp_last_passes(5) reports the passes)
 //   SP_NUFFT_ROWS (int: a cap on the rows per pass of sp_nufft1 / sp_nufft2 / sp_lomb_sums_grid, before the fine grids fill their budget; unset or
 //                  <= 0: the budget alone; sp_last_passes(6) reports the passes)
+//   SP_AR_SEGS (int: a cap on the segments per pass of sp_burg / sp_yule; unset or <= 0: the budget alone; sp_last_passes(7) reports the passes)
+//   SP_BURG_FORM (int: 1 the wave form of k_burg wherever a segment fits it, 2 the workgroup form at every length; unset or 0: by length)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
     return v && v[0] && v[0] != '0';
@@ -1168,6 +1171,35 @@ struct Nufft2InterpArgs {
 // grid[r][(m - M / 2) mod nf] = F[r * F_ld + m] / phihat(m - M / 2), every other cell of grid[nrows][nf] zero: each cell written once
 int launch_nufft2_place(LaunchCtx c, const cf *F, int64_t F_ld, int64_t M, int64_t nrows, int64_t nf, const NufftQuad &q, cf *grid);
 int launch_nufft2_interp(LaunchCtx c, const Nufft2InterpArgs &a);
+
+// Autoregressive fits and spectra (k_burg.hip; include/spectral_ar.h; the host's arithmetic in ar_plan.h).  Segment s of a pass is frame
+// g = (seg0 + s) % nframes of row r = (seg0 + s) / nframes: the n samples from x + r x_ld + first + g hop on.  Model s of the pass is
+// written at a + s out_ld (p + 1 coefficients, float64 or complex128), e + s out_ld (p + 1 prediction-error powers) and k + s out_ld
+// (p reflection coefficients): the pointers are the pass's own.
+// BURG_WAVE_MAX (ar_plan.h) is where the two forms of k_burg meet; profiles/burg_variants.txt has both forms on either side of it.
+struct ArArgs {
+    const void *x;                        // float32 or complex64 rows
+    bool cplx;
+    int64_t x_ld, first, hop, nframes, n;
+    int p, detrend;                       // detrend: 0 nothing, 1 the segment's own mean, 2 the constant (mre, mim)
+    double mre, mim;
+    int64_t seg0, nseg;                   // the pass
+    void *a;
+    double *e;
+    void *k;
+    int64_t out_ld;
+};
+// sums[nseg][tiles] (re, im) of the tiles' samples in float64 (nullptr: not wanted); *flag = 1 where a sample is not finite
+int launch_ar_scan(LaunchCtx c, const ArArgs &a, int64_t chunk, int64_t tiles, double *sums, int *flag);
+// mean[nseg] (re, im): the tiles' sums added in order over n, the given constant, or zero
+int launch_ar_mean(LaunchCtx c, const ArArgs &a, int64_t tiles, const double *sums, double *mean);
+int launch_burg(LaunchCtx c, const ArArgs &a, int spl, int nw);
+// part[nseg][tiles][p + 1] float64 or complex128: sum over the tile's i of x[i] conj(x[i - l]), detrended with mean[seg]
+int launch_ar_lags(LaunchCtx c, const ArArgs &a, int64_t chunk, int64_t tiles, const double *mean, void *part);
+int launch_levinson(LaunchCtx c, const ArArgs &a, int64_t tiles, const void *part);
+// P[model][q] = scale e[model e_ld] / |sum_j a[model a_ld + j] e(-j (start + q step))|^2, q = 0 .. m - 1; float32, or float64 with out64
+int launch_ar_psd(LaunchCtx c, const void *a, bool cplx, int64_t a_ld, const double *e, int64_t e_ld, int p, int64_t nmodels, int64_t m,
+                  double start, double step, double scale, bool out64, void *P, int64_t P_ld);
 
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;

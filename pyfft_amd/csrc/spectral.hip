@@ -9,6 +9,7 @@
 #include "../../include/spectral_fam.h"
 #include "../../include/spectral_nufft.h"
 #include "../../include/spectral_nufft2.h"
+#include "../../include/spectral_ar.h"
 #include "launch.h"
 #include "stage.h"
 #include "table_cache.h"
@@ -100,6 +101,7 @@ struct Ctx {
     Scratch wbW, wbP, wbA;                          // wavelet bispectrum: the transforms of a pass, its fp32 partials, the float64 cell sums
     Scratch famZ, famA;                             // FFT accumulation: the bin-major frames of a pass, the float64 sums across passes
     Scratch nuRec, nuGrid;                          // type-1 NUFFT: the prepared samples, tile lists and shifts of a call; the fine grids of a pass
+    Scratch arPart, arSmall;                        // autoregressive fits: the per-tile partial lags of a pass; the flag, the tiles' sums and the means
     Scratch cmS, cmT, cmG, cmH, cmO;               // CSD matrix: spectra, bin-major spectra, float64 accumulator, packed-spectra sums, one-pass means state
     std::map<int64_t, BigTw> bigtw;           // N -> two-level twiddle tables of the multi-pass FFT
     std::map<int64_t, BlueTab> blue_big;      // n -> chirp[n], FFT_L(chirp*) (unscaled) for multi-pass Bluestein
@@ -233,9 +235,10 @@ TableCache g_tables;
 // sp_last_passes: [0] the passes of the current call's outermost frame-chunk loop, [1] the most slice passes one
 // dev_fft_any / sp_czt loop made inside it, [2] the passes over the cycle-frequency list of sp_cyclic, [3] the passes over the
 // frequency list of sp_lomb / sp_lomb_sums, [4] the most launches the row groups of one such pass were dealt to, [5] the passes over the
-// blocks of sp_fam, [6] the passes over the rows of sp_nufft1 / sp_lomb_sums_grid / sp_nufft2.  All are zeroed
+// blocks of sp_fam, [6] the passes over the rows of sp_nufft1 / sp_lomb_sums_grid / sp_nufft2, [7] the passes over
+// the segments of sp_burg / sp_yule.  All are zeroed
 // where a call begins (ApiLock), so that a test can assert that the shape it chose really walks a loop past its first pass.
-int g_passes[7] = {0, 0, 0, 0, 0, 0, 0};
+int g_passes[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 inline void note_slices(int64_t n) {
     if (n > g_passes[1]) g_passes[1] = (int)n;
 }
@@ -251,7 +254,7 @@ struct ApiLock {
     std::lock_guard<std::mutex> lk;
     ApiLock() : lk(g.mu) {
         g_tables.begin_call();
-        g_passes[0] = g_passes[1] = g_passes[2] = g_passes[3] = g_passes[4] = g_passes[5] = g_passes[6] = 0;
+        g_passes[0] = g_passes[1] = g_passes[2] = g_passes[3] = g_passes[4] = g_passes[5] = g_passes[6] = g_passes[7] = 0;
     }
 };
 
@@ -1335,7 +1338,7 @@ int sp_max_wg_fft(void) { return SP_MAX_WG_FFT; }
 const char *sp_last_error(void) { return g_err.c_str(); }
 int sp_last_passes(int which) {
     std::lock_guard<std::mutex> lk(g.mu);
-    return which >= 0 && which <= 6 ? g_passes[which] : 0;
+    return which >= 0 && which <= 7 ? g_passes[which] : 0;
 }
 
 int sp_init(int device_id) {
@@ -1403,6 +1406,8 @@ void sp_shutdown(void) {
     g.famA.release();
     g.nuRec.release();
     g.nuGrid.release();
+    g.arPart.release();
+    g.arSmall.release();
     for (auto &kv : g.bigtw) {
         (void)hipFree((void *)kv.second.hi);
         (void)hipFree((void *)kv.second.lo);
@@ -4561,6 +4566,184 @@ int sp_nufft2(const double *t, const void *F, int64_t F_ld, int64_t N, int64_t b
         HIPCHK(hipGetLastError());
         g.last_kernel = "k_nufft2_interp";
     }
+    return st.finish();
+}
+
+// ---- autoregressive fits and spectra (k_burg.hip; include/spectral_ar.h; the host's arithmetic in ar_plan.h) --------------------
+static ArPlan ar_plan_now(int method, bool cplx, int64_t n, int order, int64_t segs) {
+    return ar_plan_of(method, cplx, n, order, segs, env_int("SP_BURG_FORM", 0), env_int("SP_AR_SEGS", 0));
+}
+
+int sp_ar_plan(int method, int dtype, int64_t n, int order, int64_t batch, int64_t nframes, int64_t out[8]) {
+    if (!out || (dtype != SP_DTYPE_F32 && dtype != SP_DTYPE_C64) || ar_shape(method, n, order, batch, nframes)) return -1;
+    const ArPlan p = ar_plan_now(method, dtype == SP_DTYPE_C64, n, order, batch * nframes);
+    out[0] = p.form;
+    out[1] = p.segs_per_wg;
+    out[2] = method == AR_METHOD_BURG ? p.spl : p.chunk;
+    out[3] = p.lds_bytes;
+    out[4] = p.workgroups;
+    out[5] = p.passes;
+    out[6] = p.threads;
+    out[7] = p.tiles;
+    return 0;
+}
+
+static int ar_fit(const char *who, int method, const void *x, int dtype, int64_t x_ld, int64_t nsig, int64_t batch, int64_t n, int64_t hop,
+                  int64_t first, int64_t nframes, int order, int detrend, double mean_re, double mean_im, void *a, double *evar, void *k,
+                  int64_t out_ld, int mem) {
+    if (dtype != SP_DTYPE_F32 && dtype != SP_DTYPE_C64) return fail("%s: dtype = %d must be SP_DTYPE_F32 or SP_DTYPE_C64", who, dtype);
+    if (const char *why = ar_shape(method, n, order, batch, nframes))
+        return fail("%s: %s (n %lld, order %d, batch %lld, nframes %lld)", who, why, (long long)n, order, (long long)batch, (long long)nframes);
+    if (hop < 1) return fail("%s: hop = %lld must be at least 1", who, (long long)hop);
+    if (first < 0) return fail("%s: first = %lld must not be negative", who, (long long)first);
+    if (nsig < 1 || nsig > ((int64_t)1 << 40)) return fail("%s: nsig = %lld must lie in 1 .. 2^40", who, (long long)nsig);
+    if (nframes > 0 && (first > nsig - n || (nframes - 1) > (nsig - n - first) / hop))
+        return fail("%s: %lld frames of %lld at hop %lld from %lld on reach outside the %lld samples of a row", who, (long long)nframes, (long long)n,
+                    (long long)hop, (long long)first, (long long)nsig);
+    if (x_ld < nsig) return fail("%s: x_ld = %lld is below nsig = %lld", who, (long long)x_ld, (long long)nsig);
+    if (out_ld < order + 1) return fail("%s: out_ld = %lld is below order + 1 = %d", who, (long long)out_ld, order + 1);
+    if (detrend != SP_DETREND_CONST && detrend != SP_DETREND_SEGMEAN) return fail("%s: detrend = %d must be SP_DETREND_CONST or SP_DETREND_SEGMEAN", who, detrend);
+    if (!std::isfinite(mean_re) || !std::isfinite(mean_im)) return fail("%s: the mean must be finite", who);
+    if (!x) return fail("%s: x is required", who);
+    if (!a) return fail("%s: a is required", who);
+    if (!evar) return fail("%s: evar is required", who);
+    if (!k) return fail("%s: k is required", who);
+    const int64_t segs = batch * nframes;
+    if (segs == 0) return 0;
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const bool cplx = dtype == SP_DTYPE_C64;
+    const ArPlan p = ar_plan_now(method, cplx, n, order, segs);
+    const size_t xel = cplx ? 8 : 4, el = cplx ? 16 : 8;
+    Stage st(mem);
+    const char *x_d, *a_in, *k_in;
+    const double *e_in;
+    char *a_d, *k_d;
+    double *e_d;
+    st.in(g.in0, (const char *)x, xel * (size_t)((batch - 1) * x_ld + nsig), &x_d);
+    // host models further apart than they are long: what lies between them is the caller's, carried there and back unchanged
+    const size_t a_bytes = el * (size_t)((segs - 1) * out_ld + order + 1), e_bytes = 8 * (size_t)((segs - 1) * out_ld + order + 1);
+    const size_t k_bytes = el * (size_t)((segs - 1) * out_ld + order);
+    if (out_ld > order + 1) {
+        st.inout(g.out0, (const char *)a, (char *)a, a_bytes, &a_in, &a_d);
+        st.inout(g.out0, (const double *)evar, evar, e_bytes, &e_in, &e_d);
+    } else {
+        st.out(g.out0, (char *)a, a_bytes, &a_d);
+        st.out(g.out0, evar, e_bytes, &e_d);
+    }
+    if (segs > 1) st.inout(g.out0, (const char *)k, (char *)k, k_bytes, &k_in, &k_d);
+    else st.out(g.out0, (char *)k, k_bytes, &k_d);
+    if (st.commit()) return -1;
+    const bool yule = method == AR_METHOD_YULE;
+    const bool want_sums = yule && detrend == SP_DETREND_SEGMEAN;
+    // the small scratch: the flag; for Yule-Walker then the means of a pass and its tiles' sums (k_burg forms its own mean)
+    const size_t o_mean = 256, o_sums = o_mean + lomb_up(16 * (size_t)p.spp);
+    if (g.arSmall.ensure(yule ? o_sums + 16 * (size_t)p.spp * (size_t)p.tiles + 256 : o_mean)) return -1;
+    int *flag = (int *)g.arSmall.p;
+    double *mean = (double *)((char *)g.arSmall.p + o_mean), *sums = (double *)((char *)g.arSmall.p + o_sums);
+    if (yule && g.arPart.ensure(el * (size_t)p.spp * (size_t)p.tiles * (size_t)(order + 1))) return -1;
+    ArArgs A{};
+    A.x = x_d, A.cplx = cplx, A.x_ld = x_ld, A.first = first, A.hop = hop, A.nframes = nframes, A.n = n;
+    A.p = order;
+    A.detrend = detrend == SP_DETREND_SEGMEAN ? 1 : ((mean_re != 0.0 || mean_im != 0.0) ? 2 : 0);
+    A.mre = mean_re, A.mim = mean_im;
+    A.out_ld = out_ld;
+    auto pass = [&](int64_t s0) {
+        A.seg0 = s0, A.nseg = std::min<int64_t>(p.spp, segs - s0);
+        A.a = a_d + el * (size_t)(s0 * out_ld), A.e = e_d + s0 * out_ld, A.k = k_d + el * (size_t)(s0 * out_ld);
+    };
+    // every segment is looked at before anything is written; one pass keeps the sums of that look
+    HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), g.stream));
+    for (int64_t s0 = 0; s0 < segs; s0 += p.spp) {
+        pass(s0);
+        if (launch_ar_scan(lc(), A, p.chunk, p.tiles, p.passes == 1 && want_sums ? sums : nullptr, flag) != 0)
+            return fail("%s: the look at the record was refused", who);
+        HIPCHK(hipGetLastError());
+    }
+    int bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    if (bad) return fail("%s: x holds a value that is not finite", who), SP_AR_BAD_RECORD;
+    for (int64_t s0 = 0; s0 < segs; s0 += p.spp, ++g_passes[7]) {
+        pass(s0);
+        int rc;
+        if (yule) {
+            if (want_sums && p.passes > 1) {
+                if (launch_ar_scan(lc(), A, p.chunk, p.tiles, sums, flag) != 0) return fail("%s: the tiles' sums were refused", who);
+                HIPCHK(hipGetLastError());
+            }
+            if (launch_ar_mean(lc(), A, p.tiles, want_sums ? sums : nullptr, mean) != 0) return fail("%s: the means were refused", who);
+            HIPCHK(hipGetLastError());
+            {
+                ProfScope ps;
+                rc = launch_ar_lags(lc(), A, p.chunk, p.tiles, mean, g.arPart.p);
+            }
+            if (rc != 0) return fail("%s: the lags were refused (%lld segments of %lld in %lld tiles)", who, (long long)A.nseg, (long long)n, (long long)p.tiles);
+            HIPCHK(hipGetLastError());
+            if (launch_levinson(lc(), A, p.tiles, g.arPart.p) != 0) return fail("%s: the Levinson recursion was refused", who);
+            HIPCHK(hipGetLastError());
+            g.last_kernel = "k_ar_lags";
+        } else {
+            {
+                ProfScope ps;
+                rc = launch_burg(lc(), A, p.spl, p.nw);
+            }
+            if (rc != 0) return fail("%s: no kernel for %lld samples (%d per lane, %d waves)", who, (long long)n, p.spl, p.nw);
+            HIPCHK(hipGetLastError());
+            g.last_kernel = "k_burg";
+        }
+    }
+    return st.finish();
+}
+
+int sp_burg(const void *x, int dtype, int64_t x_ld, int64_t nsig, int64_t batch, int64_t n, int64_t hop, int64_t first, int64_t nframes,
+            int order, int detrend, double mean_re, double mean_im, void *a, double *evar, void *k, int64_t out_ld, int mem) {
+    return ar_fit("sp_burg", AR_METHOD_BURG, x, dtype, x_ld, nsig, batch, n, hop, first, nframes, order, detrend, mean_re, mean_im, a, evar, k,
+                  out_ld, mem);
+}
+
+int sp_yule(const void *x, int dtype, int64_t x_ld, int64_t nsig, int64_t batch, int64_t n, int64_t hop, int64_t first, int64_t nframes,
+            int order, int detrend, double mean_re, double mean_im, void *a, double *evar, void *k, int64_t out_ld, int mem) {
+    return ar_fit("sp_yule", AR_METHOD_YULE, x, dtype, x_ld, nsig, batch, n, hop, first, nframes, order, detrend, mean_re, mean_im, a, evar, k,
+                  out_ld, mem);
+}
+
+int sp_ar_psd(const void *a, int cplx, int64_t a_ld, const double *e, int64_t e_ld, int order, int64_t nmodels, int64_t m, double start,
+              double step, double scale, int out64, void *P, int64_t P_ld, int mem) {
+    const char *who = "sp_ar_psd";
+    if (order < 0 || order > AR_MAX_ORDER) return fail("%s: order = %d must lie in 0 .. 256", who, order);
+    if (a_ld < order + 1) return fail("%s: a_ld = %lld is below order + 1 = %d", who, (long long)a_ld, order + 1);
+    if (e_ld < 1) return fail("%s: e_ld = %lld must be at least 1", who, (long long)e_ld);
+    if (m < 1 || m > 0x7fffffff) return fail("%s: m = %lld must lie in 1 .. 2^31 - 1", who, (long long)m);
+    if (P_ld < m) return fail("%s: P_ld = %lld is below m = %lld", who, (long long)P_ld, (long long)m);
+    if (nmodels < 0 || (nmodels > 0 && (m + 255) / 256 > 0x7fffffff / nmodels))
+        return fail("%s: nmodels = %lld must not be negative, nor nmodels x ceil(m / 256) exceed 2^31 - 1", who, (long long)nmodels);
+    if (!std::isfinite(start) || !std::isfinite(step) || !std::isfinite(scale)) return fail("%s: start, step and scale must be finite", who);
+    if (!a) return fail("%s: a is required", who);
+    if (!e) return fail("%s: e is required", who);
+    if (!P) return fail("%s: P is required", who);
+    if (nmodels == 0) return 0;
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const size_t el = cplx ? 16 : 8, pel = out64 ? 8 : 4;
+    Stage st(mem);
+    const char *a_d, *P_in;
+    const double *e_d;
+    char *P_d;
+    st.in(g.in0, (const char *)a, el * (size_t)((nmodels - 1) * a_ld + order + 1), &a_d);
+    st.in(g.in0, e, 8 * (size_t)((nmodels - 1) * e_ld + 1), &e_d);
+    const size_t P_bytes = pel * (size_t)((nmodels - 1) * P_ld + m);
+    if (P_ld > m) st.inout(g.out0, (const char *)P, (char *)P, P_bytes, &P_in, &P_d);
+    else st.out(g.out0, (char *)P, P_bytes, &P_d);
+    if (st.commit()) return -1;
+    int rc;
+    {
+        ProfScope ps;
+        rc = launch_ar_psd(lc(), a_d, cplx != 0, a_ld, e_d, e_ld, order, nmodels, m, start, step, scale, out64 != 0, P_d, P_ld);
+    }
+    if (rc != 0) return fail("%s: the launch was refused (%lld models, %lld bins)", who, (long long)nmodels, (long long)m);
+    HIPCHK(hipGetLastError());
+    g.last_kernel = "k_ar_psd";
     return st.finish();
 }
 

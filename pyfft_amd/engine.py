@@ -260,7 +260,8 @@ def last_passes(which=0):
     long transforms inside it, which=2 (CYC_PASSES) the passes of `cyclic` over its list of cycle frequencies, which=3 (LOMB_PASSES)
     the passes of `lomb` and `lomb_sums` over their frequencies, which=4 (LOMB_LAUNCHES) the most launches the row groups of one such
     pass were dealt to, which=5 (FAM_PASSES) the passes of `fam` over its blocks, which=6 (NUFFT_PASSES) the passes of `nufft1`, `nufft2`
-    and `lomb_sums_grid` over their rows; 0 where the call had no such loop (sp_last_passes)."""
+    and `lomb_sums_grid` over their rows; 0 where the call had no such loop (sp_last_passes).
+    which=7 (AR_PASSES): the passes of `burg` and `yule` over their segments."""
     return int(lib().sp_last_passes(int(which)))
 
 
@@ -2109,6 +2110,148 @@ def fam_plan(np_, hop, P, nblocks, npairs, cplx=False, cross=False):
     fam_check("fam_plan", np_, hop, P, nblocks, npairs)
     return _plan(lib().sp_fam_plan, ("Q", "blocks_per_pass", "passes", "workgroups", "scratch"), FamRefused, "fam_plan",
                  _ffi.DTYPE_C64 if cplx else _ffi.DTYPE_F32, 1 if cross else 0, np_, hop, P, nblocks, npairs)
+
+
+AR_MAX_ORDER, BURG_MAX_N, BURG_WAVE_MAX, YULE_MAX_N, AR_PASSES, AR_BAD_RECORD = 256, 16384, 1024, (1 << 31) - 1, 7, -2
+AR_METHODS = {"burg": 0, "yule": 1}
+
+
+class ArRefused(ValueError, NotImplementedError):
+    """A segment, an order or a model the autoregressive fits and spectra do not take: outside the limits, values a record must not
+    hold, and what is not built (a Burg fit of a segment beyond 16384 samples, orders beyond 256, float64 samples)."""
+
+
+def ar_check(who, method, n, hop, first, nframes, order, rows, nsig=None, x_ld=None, mean=0j):
+    """The refusals of sp_burg, sp_yule and sp_ar_plan, before the library is touched."""
+    if method not in (0, 1):
+        raise ArRefused("%s: method must be 0 (Burg) or 1 (Yule-Walker)" % who)
+    if order < 1 or order > AR_MAX_ORDER:
+        raise ArRefused("%s: order = %d is outside 1 .. %d" % (who, order, AR_MAX_ORDER))
+    most = BURG_MAX_N if method == 0 else YULE_MAX_N
+    if n < 2 or n > most:
+        raise ArRefused("%s: n = %d samples of a segment are outside 2 .. %d" % (who, n, most))
+    if order > n // 2:
+        raise ArRefused("%s: order = %d exceeds n / 2 = %d" % (who, order, n // 2))
+    _range_check(ArRefused, who, hop=hop, count=("nframes", nframes), rows=(rows, (1 << 31) - 1))
+    if nframes > (1 << 31) - 1 or rows * nframes > 1 << 40:
+        raise ArRefused("%s: %d rows of %d frames are more segments than 2^40" % (who, rows, nframes))
+    if first < 0:
+        raise ArRefused("%s: first = %d must not be negative" % (who, first))
+    if nsig is not None and nframes > 0 and first + (nframes - 1) * hop + n > nsig:
+        raise ArRefused("%s: %d frames of %d at hop %d from %d on reach outside the %d samples of a row" % (who, nframes, n, hop, first, nsig))
+    if x_ld is not None:
+        _range_check(ArRefused, who, nsig=nsig, x_ld=x_ld)
+    if not (math.isfinite(mean.real) and math.isfinite(mean.imag)):
+        raise ArRefused("%s: mean_value must be finite" % who)
+
+
+def _ar_detrend(who, detrend, mean_value):
+    """-> (the C ABI's detrend code, the constant): True every segment's own mean, or with an explicit mean_value that constant; False
+    or None nothing, and then a mean_value is refused"""
+    flag = isinstance(detrend, (bool, np.bool_))
+    if detrend is None or (flag and not detrend):
+        if mean_value is not None:
+            raise ArRefused("%s: mean_value = %r is given, but detrend is off" % (who, mean_value))
+        return _ffi.DETREND_CONST, 0j
+    if not flag:
+        raise ArRefused("%s: detrend must be True (every segment's own mean, or mean_value) or False, not %r" % (who, detrend))
+    if mean_value is not None:
+        return _ffi.DETREND_CONST, complex(mean_value)
+    return _ffi.DETREND_SEGMEAN, 0j
+
+
+def _ar_fit(who, method, x, n, hop, first, nframes, order, detrend, mean_value):
+    n, hop, first, nframes, order = int(n), int(hop), int(first), int(nframes), int(order)
+    md = _enter(x)
+    x = md.checked(x)
+    if x.ndim < 1:
+        raise ArRefused("%s: x needs at least one axis" % who)
+    code, mean = _ar_detrend(who, detrend, mean_value)
+    lead, rows = _lead_rows(x.shape)
+    nsig = int(x.shape[-1])
+    ar_check(who, method, n, hop, first, nframes, order, rows, nsig, None, mean)
+    cplx = md.code(x) == _ffi.DTYPE_C64
+    if not cplx and mean.imag != 0.0:
+        raise ArRefused("%s: a real record takes a real mean_value" % who)
+    if not md.dev and not np.all(np.isfinite(x)):
+        raise ArRefused("%s: x must be finite" % who)
+    if md.dev and x.ndim != 2:
+        x = x.reshape(rows, nsig)
+    xs, xld = md.rows(x)
+    dt = "complex128" if cplx else "float64"
+    a = md.empty(lead + (nframes, order + 1), dt, xs)
+    e = md.empty(lead + (nframes, order + 1), "float64", xs)
+    k = md.empty(lead + (nframes, order + 1), dt, xs)               # the three share one pitch: k is handed out as a view of order columns
+    if rows * nframes:
+        _bad_record_call(md, ArRefused, lib().sp_burg if method == 0 else lib().sp_yule, md.addr(xs), md.code(xs), xld, nsig, rows, n, hop,
+                         first, nframes, order, code, mean.real, mean.imag, md.addr(a), md.addr(e), md.addr(k), order + 1)
+    return a, e, k[..., :order]
+
+
+def burg(x, n, hop, first, nframes, order, detrend=True, mean_value=None):
+    """Burg's autoregressive fit (sp_burg; MATLAB's arburg) of the segments x[..., first + g hop + i], i < n, g < nframes, of every row:
+    -> (a, evar, k): the polynomial a[..., g, 0 .. order] with a[..., 0] = 1, the prediction-error power by order evar[..., g, 0 .. order]
+    and the reflection coefficients k[..., g, 0 .. order - 1]; float64 for float32 rows, complex128 (evar float64) for complex64 rows.
+    detrend: True every segment's own mean, mean_value a given constant, False nothing.  n <= 16384, order <= 256 and <= n / 2.
+    numpy in -> numpy out; device tensors in -> device tensors on x's stream; the two agree bitwise."""
+    return _ar_fit("burg", 0, x, n, hop, first, nframes, order, detrend, mean_value)
+
+
+def yule(x, n, hop, first, nframes, order, detrend=True, mean_value=None):
+    """The Yule-Walker fit (sp_yule; MATLAB's aryule) of the same segments as `burg`, from the biased lags by Levinson-Durbin:
+    the same triple.  n up to 2^31 - 1."""
+    return _ar_fit("yule", 1, x, n, hop, first, nframes, order, detrend, mean_value)
+
+
+def ar_psd(a, e, m, start, step, scale=1.0, out64=False):
+    """The spectra of all-pole models (sp_ar_psd): P[..., q] = scale e[...] / |sum_j a[..., j] exp(-2 pi i j (start + q step))|^2,
+    q = 0 .. m - 1, frequencies in cycles per sample (the start, step, m of `czt`).  a[..., order + 1] float64 or complex128, e[...]
+    float64 of a's leading shape.  float32 [..., m], or float64 with out64.  e == 0 gives zeros; a row padded with zeros is a model of
+    lower order.  numpy in -> numpy out; device tensors in -> a device tensor."""
+    who = "ar_psd"
+    m, start, step, scale = int(m), float(start), float(step), float(scale)
+    md = _enter(a)
+    if _mode(e) is not md:
+        raise TypeError("%s: a and e must both be numpy arrays or both device tensors" % who)
+    if md.dev:
+        if a.dtype not in (torch.float64, torch.complex128) or e.dtype != torch.float64:
+            raise ArRefused("%s: on the device a is a float64 or complex128 tensor and e float64" % who)
+        a, e = a.contiguous(), e.contiguous()
+        cplx = a.dtype == torch.complex128
+    else:
+        a = np.asarray(a)
+        cplx = np.iscomplexobj(a)
+        a = np.ascontiguousarray(a, dtype=np.complex128 if cplx else np.float64)
+        e = np.ascontiguousarray(np.asarray(e), dtype=np.float64)
+    if len(a.shape) < 1 or tuple(a.shape[:-1]) != tuple(e.shape):
+        raise ArRefused("%s: a needs at least one axis and e the shape of a's leading axes" % who)
+    order = int(a.shape[-1]) - 1
+    if order < 0 or order > AR_MAX_ORDER:
+        raise ArRefused("%s: %d coefficients are outside 1 .. %d" % (who, order + 1, AR_MAX_ORDER + 1))
+    if m < 1 or m > (1 << 31) - 1:
+        raise ArRefused("%s: m = %d bins are outside 1 .. 2^31 - 1" % (who, m))
+    if not (math.isfinite(start) and math.isfinite(step) and math.isfinite(scale)):
+        raise ArRefused("%s: start, step and scale must be finite" % who)
+    lead, models = _lead_rows(a.shape)
+    if models * -(-m // 256) > (1 << 31) - 1:
+        raise ArRefused("%s: %d models of %d bins are more than one launch takes" % (who, models, m))
+    if not md.dev and not (np.all(np.isfinite(a)) and np.all(np.isfinite(e))):
+        raise ArRefused("%s: a and e must be finite" % who)
+    P = md.empty(lead + (m,), "float64" if out64 else "float32", a)
+    if models:
+        md.call(lib().sp_ar_psd, md.addr(a), 1 if cplx else 0, order + 1, md.addr(e), 1, order, models, m, start, step, scale,
+                1 if out64 else 0, md.addr(P), m)
+    return P
+
+
+def ar_plan(method, n, order, rows=1, nframes=1, cplx=False):
+    """sp_ar_plan as a dict (host only): form (0 the wave form of k_burg, 1 its workgroup form, 2 lags and Levinson), segs_per_wg,
+    samples (per lane of k_burg, or per tile of the lags), lds_bytes, workgroups (over all passes), passes, threads, tiles."""
+    method = AR_METHODS.get(method, method)
+    n, order, rows, nframes = int(n), int(order), int(rows), int(nframes)
+    ar_check("ar_plan", method, n, 1, 0, nframes, order, rows)
+    return _plan(lib().sp_ar_plan, ("form", "segs_per_wg", "samples", "lds_bytes", "workgroups", "passes", "threads", "tiles"), ArRefused,
+                 "ar_plan", method, _ffi.DTYPE_C64 if cplx else _ffi.DTYPE_F32, n, order, rows, nframes)
 
 
 EIGH_MAX_N = 64
