@@ -59,6 +59,7 @@ int sp_wct_plan(int64_t nsig, int nscales, int64_t batch, int L, int Mw, int Mg,
  *      were dealt to; which = 5: the passes sp_fam (spectral_fam.h) made over its blocks; which = 6: the passes sp_nufft1, sp_nufft2 (spectral_nufft2.h) and
  *      sp_lomb_sums_grid (spectral_nufft.h) made over their rows (for the latter 1 + batch of them: the weights' row and the values').
  *      which = 7: the passes sp_burg and sp_yule (spectral_ar.h) made over their segments.
+ *      which = 8: the passes sp_covmat and sp_ar_ls (spectral_sub.h) made over their segments.
  *      0 where the call had no such loop, or for another `which`.
  *      All are reset where a call that touches the device begins.  The budgets behind the loops can be capped
  *      through the environment, read on every call (unset or <= 0: no cap): SP_LONG_CHUNK_FRAMES (frames of a long chunk),

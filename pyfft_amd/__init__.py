@@ -66,7 +66,10 @@ from .nufft import (nufft1, nufft1_modes, nufft_plan, nufft2, nufft2_modes, nuff
                     NufftFit)
 from . import parametric as _parametric_mod                    # noqa: F401
 from .parametric import (arburg, aryule, pburg, pyulear, ar_spectrogram, ar_psd, ar_order, ar_stepup, ar_poles, ar_plan,   # noqa: F401
-                         ArRefused)
+                         ArRefused, arcov, armcov, pcov, pmcov)
+from . import subspace as _subspace_mod                        # noqa: F401
+from .subspace import (corrmtx_cov, pmusic, peig, subspace_spectrogram, subspace_order, esprit, subspace_plan,   # noqa: F401
+                       SubRefused)
 from . import wbicoherence as _wbic_mod                        # noqa: F401
 from .wbicoherence import (wbic_freqs, wavelet_bispectrum, wavelet_bicoherence, summed_bicoherence,   # noqa: F401
                            total_bicoherence, wbic_plan)

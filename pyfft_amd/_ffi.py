@@ -163,10 +163,19 @@ AR_SIGNATURES = {
     "sp_ar_plan": (_i, [_i, _i, _i64, _i, _i64, _i64, _vp]),
 }
 
+# the twelfth table: must list every symbol include/spectral_sub.h declares, and none of the other eleven
+_SUB_REC = [_vp, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i64]
+SUB_SIGNATURES = {
+    "sp_covmat": (_i, _SUB_REC + [_i, _i, _i, _d, _d, _vp, _i64, _i]),
+    "sp_ar_ls": (_i, _SUB_REC + [_i, _i, _i, _d, _d, _vp, _vp, _vp, _i64, _i]),
+    "sp_pseudospectrum": (_i, [_vp, _i64, _vp, _i, _i, _i64, _i, _i64, _d, _d, _i, _vp, _i64, _vp, _i]),
+    "sp_sub_plan": (_i, [_i, _i, _i64, _i, _i64, _i64, _vp]),
+}
+
 # the six tables the engine trace counts, in the order of their headers
 TABLES = (SIGNATURES, EXT_SIGNATURES, TFR_SIGNATURES, QUAD_SIGNATURES, CYCLO_SIGNATURES, UNEVEN_SIGNATURES)
 # the tables added since: bound like the six, outside the trace
-MORE_TABLES = (WBIC_SIGNATURES, FAM_SIGNATURES, NUFFT_SIGNATURES, NUFFT2_SIGNATURES, AR_SIGNATURES)
+MORE_TABLES = (WBIC_SIGNATURES, FAM_SIGNATURES, NUFFT_SIGNATURES, NUFFT2_SIGNATURES, SUB_SIGNATURES, AR_SIGNATURES)
 
 
 class SpectralError(RuntimeError):

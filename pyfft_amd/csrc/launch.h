@@ -5,6 +5,7 @@
 #include "kernels.h"
 #include "nufft_plan.h"
 #include "ar_plan.h"
+#include "sub_plan.h"
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -43,6 +44,7 @@ namespace sp {
 //   SP_NUFFT_ROWS (int: a cap on the rows per pass of sp_nufft1 / sp_nufft2 / sp_lomb_sums_grid, before the fine grids fill their budget; unset or
 //                  <= 0: the budget alone; sp_last_passes(6) reports the passes)
 //   SP_AR_SEGS (int: a cap on the segments per pass of sp_burg / sp_yule; unset or <= 0: the budget alone; sp_last_passes(7) reports the passes)
+//                  the same cap holds for sp_covmat / sp_ar_ls, whose passes sp_last_passes(8) reports
 //   SP_BURG_FORM (int: 1 the wave form of k_burg wherever a segment fits it, 2 the workgroup form at every length; unset or 0: by length)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
@@ -1200,6 +1202,24 @@ int launch_levinson(LaunchCtx c, const ArArgs &a, int64_t tiles, const void *par
 // P[model][q] = scale e[model e_ld] / |sum_j a[model a_ld + j] e(-j (start + q step))|^2, q = 0 .. m - 1; float32, or float64 with out64
 int launch_ar_psd(LaunchCtx c, const void *a, bool cplx, int64_t a_ld, const double *e, int64_t e_ld, int p, int64_t nmodels, int64_t m,
                   double start, double step, double scale, bool out64, void *P, int64_t P_ld);
+
+// The data covariance matrix, the covariance least-squares fits and the pseudospectrum (k_subspace.hip; include/spectral_sub.h; the host's
+// arithmetic in sub_plan.h).  A holds the segments of a pass as for the fits above (its p, a, e, k, out_ld are not looked at here);
+// matrix s of the pass is written at C + s C_ld, complex128 [m][m].
+struct CovArgs {
+    ArArgs A;
+    int m, fb;                            // the matrix order; 1: the forward-backward (modified) form
+    void *C;
+    int64_t C_ld;
+};
+// part[nseg][tiles][m] float64 or complex128: the tile's share of sum_{t >= m-1} conj(s[t]) s[t - j], detrended with mean[seg]
+int launch_cov_row(LaunchCtx c, const CovArgs &k, int64_t chunk, int64_t tiles, const double *mean, void *part);
+int launch_cov_fill(LaunchCtx c, const CovArgs &k, int64_t tiles, const double *mean, const void *part);
+// a[model out_ld + j], j = 0 .. m - 1 (float64, or complex128 with cplx), e[model], status[model] from C[model C_ld + i m + j]
+int launch_ls_chol(LaunchCtx c, const void *C, int64_t C_ld, int m, int64_t nmodels, bool cplx, void *a, double *e, int *status, int64_t out_ld);
+// P[model P_ld + q] = 1 / sum_{k >= p} g_k |sum_i V[model m V_ld + i V_ld + k] e(-i (start + q step))|^2; status[model]: a weight was not positive
+int launch_pseudo(LaunchCtx c, const void *V, int64_t V_ld, const double *w, int m, int p, int64_t nmodels, bool ev, int64_t nbins, double start, double step,
+                  bool out64, void *P, int64_t P_ld, int *status);
 
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;

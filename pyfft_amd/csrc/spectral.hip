@@ -10,6 +10,7 @@
 #include "../../include/spectral_nufft.h"
 #include "../../include/spectral_nufft2.h"
 #include "../../include/spectral_ar.h"
+#include "../../include/spectral_sub.h"
 #include "launch.h"
 #include "stage.h"
 #include "table_cache.h"
@@ -101,6 +102,7 @@ struct Ctx {
     Scratch wbW, wbP, wbA;                          // wavelet bispectrum: the transforms of a pass, its fp32 partials, the float64 cell sums
     Scratch famZ, famA;                             // FFT accumulation: the bin-major frames of a pass, the float64 sums across passes
     Scratch nuRec, nuGrid;                          // type-1 NUFFT: the prepared samples, tile lists and shifts of a call; the fine grids of a pass
+    Scratch subPart, subMat;                        // covariance matrices: the per-tile partial rows of a pass; the matrices of a pass of fits
     Scratch arPart, arSmall;                        // autoregressive fits: the per-tile partial lags of a pass; the flag, the tiles' sums and the means
     Scratch cmS, cmT, cmG, cmH, cmO;               // CSD matrix: spectra, bin-major spectra, float64 accumulator, packed-spectra sums, one-pass means state
     std::map<int64_t, BigTw> bigtw;           // N -> two-level twiddle tables of the multi-pass FFT
@@ -236,9 +238,9 @@ TableCache g_tables;
 // dev_fft_any / sp_czt loop made inside it, [2] the passes over the cycle-frequency list of sp_cyclic, [3] the passes over the
 // frequency list of sp_lomb / sp_lomb_sums, [4] the most launches the row groups of one such pass were dealt to, [5] the passes over the
 // blocks of sp_fam, [6] the passes over the rows of sp_nufft1 / sp_lomb_sums_grid / sp_nufft2, [7] the passes over
-// the segments of sp_burg / sp_yule.  All are zeroed
+// the segments of sp_burg / sp_yule, [8] the passes over the segments of sp_covmat / sp_ar_ls.  All are zeroed
 // where a call begins (ApiLock), so that a test can assert that the shape it chose really walks a loop past its first pass.
-int g_passes[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+int g_passes[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 inline void note_slices(int64_t n) {
     if (n > g_passes[1]) g_passes[1] = (int)n;
 }
@@ -254,7 +256,7 @@ struct ApiLock {
     std::lock_guard<std::mutex> lk;
     ApiLock() : lk(g.mu) {
         g_tables.begin_call();
-        g_passes[0] = g_passes[1] = g_passes[2] = g_passes[3] = g_passes[4] = g_passes[5] = g_passes[6] = g_passes[7] = 0;
+        g_passes[0] = g_passes[1] = g_passes[2] = g_passes[3] = g_passes[4] = g_passes[5] = g_passes[6] = g_passes[7] = g_passes[8] = 0;
     }
 };
 
@@ -1338,7 +1340,7 @@ int sp_max_wg_fft(void) { return SP_MAX_WG_FFT; }
 const char *sp_last_error(void) { return g_err.c_str(); }
 int sp_last_passes(int which) {
     std::lock_guard<std::mutex> lk(g.mu);
-    return which >= 0 && which <= 7 ? g_passes[which] : 0;
+    return which >= 0 && which <= 8 ? g_passes[which] : 0;
 }
 
 int sp_init(int device_id) {
@@ -1407,6 +1409,8 @@ void sp_shutdown(void) {
     g.nuRec.release();
     g.nuGrid.release();
     g.arPart.release();
+    g.subPart.release();
+    g.subMat.release();
     g.arSmall.release();
     for (auto &kv : g.bigtw) {
         (void)hipFree((void *)kv.second.hi);
@@ -4744,6 +4748,210 @@ int sp_ar_psd(const void *a, int cplx, int64_t a_ld, const double *e, int64_t e_
     if (rc != 0) return fail("%s: the launch was refused (%lld models, %lld bins)", who, (long long)nmodels, (long long)m);
     HIPCHK(hipGetLastError());
     g.last_kernel = "k_ar_psd";
+    return st.finish();
+}
+
+// ---- covariance matrices, covariance least-squares fits and pseudospectra (k_subspace.hip; include/spectral_sub.h; sub_plan.h) ------
+static SubPlan sub_plan_now(int what, bool cplx, int64_t n, int m, int64_t segs) { return sub_plan_of(what, cplx, n, m, segs, env_int("SP_AR_SEGS", 0)); }
+
+int sp_sub_plan(int what, int dtype, int64_t n, int m, int64_t batch, int64_t nframes, int64_t out[8]) {
+    if (!out || (dtype != SP_DTYPE_F32 && dtype != SP_DTYPE_C64) || sub_shape(what, n, m, batch, nframes)) return -1;
+    const SubPlan p = sub_plan_now(what, dtype == SP_DTYPE_C64, n, m, batch * nframes);
+    out[0] = p.chunk;
+    out[1] = p.tiles;
+    out[2] = p.nsub;
+    out[3] = p.lds_bytes;
+    out[4] = p.workgroups;
+    out[5] = p.passes;
+    out[6] = p.seg_bytes;
+    out[7] = p.spp;
+    return 0;
+}
+
+// what the two entries refuse about the record and the matrix order, in one order; 0 or -1
+static int sub_refusals(const char *who, int what, const void *x, int dtype, int64_t x_ld, int64_t nsig, int64_t batch, int64_t n, int64_t hop, int64_t first,
+                        int64_t nframes, int m, int fb, int detrend, double mean_re, double mean_im) {
+    if (dtype != SP_DTYPE_F32 && dtype != SP_DTYPE_C64) return fail("%s: dtype = %d must be SP_DTYPE_F32 or SP_DTYPE_C64", who, dtype);
+    if (const char *why = sub_shape(what, n, m, batch, nframes))
+        return fail("%s: %s (n %lld, %s %d, batch %lld, nframes %lld)", who, why, (long long)n, what == SUB_WHAT_LS ? "order" : "m", what == SUB_WHAT_LS ? m - 1 : m,
+                    (long long)batch, (long long)nframes);
+    if (fb != 0 && fb != 1) return fail("%s: fb = %d must be 0 (covariance) or 1 (modified covariance)", who, fb);
+    if (hop < 1) return fail("%s: hop = %lld must be at least 1", who, (long long)hop);
+    if (first < 0) return fail("%s: first = %lld must not be negative", who, (long long)first);
+    if (nsig < 1 || nsig > ((int64_t)1 << 40)) return fail("%s: nsig = %lld must lie in 1 .. 2^40", who, (long long)nsig);
+    if (nframes > 0 && (first > nsig - n || (nframes - 1) > (nsig - n - first) / hop))
+        return fail("%s: %lld frames of %lld at hop %lld from %lld on reach outside the %lld samples of a row", who, (long long)nframes, (long long)n,
+                    (long long)hop, (long long)first, (long long)nsig);
+    if (x_ld < nsig) return fail("%s: x_ld = %lld is below nsig = %lld", who, (long long)x_ld, (long long)nsig);
+    if (detrend != SP_DETREND_CONST && detrend != SP_DETREND_SEGMEAN) return fail("%s: detrend = %d must be SP_DETREND_CONST or SP_DETREND_SEGMEAN", who, detrend);
+    if (!std::isfinite(mean_re) || !std::isfinite(mean_im)) return fail("%s: the mean must be finite", who);
+    if (!x) return fail("%s: x is required", who);
+    return 0;
+}
+
+// the passes of both entries over staged pointers: the look at the record, then per pass the means, row 0 by tiles, the matrices (into
+// C_d, or into scratch for a fit) and, for a fit, the Cholesky solves
+static int sub_passes(const char *who, int what, const char *x_d, bool cplx, int64_t x_ld, int64_t segs, int64_t n, int64_t hop, int64_t first, int64_t nframes,
+                      int m, int fb, int detrend, double mean_re, double mean_im, char *C_d, int64_t C_ld, char *a_d, double *e_d, int32_t *st_d, int64_t out_ld) {
+    const SubPlan p = sub_plan_now(what, cplx, n, m, segs);
+    const size_t el = cplx ? 16 : 8;
+    const bool ls = what == SUB_WHAT_LS, want_sums = detrend == SP_DETREND_SEGMEAN;
+    const size_t o_mean = 256, o_sums = o_mean + lomb_up(16 * (size_t)p.spp);
+    if (g.arSmall.ensure(o_sums + 16 * (size_t)p.spp * (size_t)p.tiles + 256)) return -1;
+    int *flag = (int *)g.arSmall.p;
+    double *mean = (double *)((char *)g.arSmall.p + o_mean), *sums = (double *)((char *)g.arSmall.p + o_sums);
+    if (g.subPart.ensure(el * (size_t)p.spp * (size_t)p.tiles * (size_t)m)) return -1;
+    if (ls && g.subMat.ensure(16 * (size_t)p.spp * (size_t)m * (size_t)m)) return -1;
+    CovArgs K{};
+    ArArgs &A = K.A;
+    A.x = x_d, A.cplx = cplx, A.x_ld = x_ld, A.first = first, A.hop = hop, A.nframes = nframes, A.n = n;
+    A.p = 1, A.out_ld = 2, A.a = flag, A.e = mean, A.k = flag;           // what k_ar_scan's launch asks for and neither kernel here touches
+    A.detrend = detrend == SP_DETREND_SEGMEAN ? 1 : ((mean_re != 0.0 || mean_im != 0.0) ? 2 : 0);
+    A.mre = mean_re, A.mim = mean_im;
+    K.m = m, K.fb = fb;
+    auto pass = [&](int64_t s0) {
+        A.seg0 = s0, A.nseg = std::min<int64_t>(p.spp, segs - s0);
+        K.C = ls ? (char *)g.subMat.p : C_d + 16 * (size_t)(s0 * C_ld);
+        K.C_ld = ls ? (int64_t)m * m : C_ld;
+    };
+    // every segment is looked at before anything is written; one pass keeps the sums of that look
+    HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), g.stream));
+    for (int64_t s0 = 0; s0 < segs; s0 += p.spp) {
+        pass(s0);
+        if (launch_ar_scan(lc(), A, p.chunk, p.tiles, p.passes == 1 && want_sums ? sums : nullptr, flag) != 0)
+            return fail("%s: the look at the record was refused", who);
+        HIPCHK(hipGetLastError());
+    }
+    int bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    if (bad) return fail("%s: x holds a value that is not finite", who), SP_AR_BAD_RECORD;
+    for (int64_t s0 = 0; s0 < segs; s0 += p.spp, ++g_passes[8]) {
+        pass(s0);
+        if (want_sums && p.passes > 1) {
+            if (launch_ar_scan(lc(), A, p.chunk, p.tiles, sums, flag) != 0) return fail("%s: the tiles' sums were refused", who);
+            HIPCHK(hipGetLastError());
+        }
+        if (launch_ar_mean(lc(), A, p.tiles, want_sums ? sums : nullptr, mean) != 0) return fail("%s: the means were refused", who);
+        HIPCHK(hipGetLastError());
+        int rc;
+        {
+            ProfScope ps;
+            rc = launch_cov_row(lc(), K, p.chunk, p.tiles, mean, g.subPart.p);
+        }
+        if (rc != 0) return fail("%s: row 0 was refused (%lld segments of %lld in %lld tiles, m %d)", who, (long long)A.nseg, (long long)n, (long long)p.tiles, m);
+        HIPCHK(hipGetLastError());
+        if (launch_cov_fill(lc(), K, p.tiles, mean, g.subPart.p) != 0) return fail("%s: the fill of the matrices was refused", who);
+        HIPCHK(hipGetLastError());
+        g.last_kernel = "k_cov_row";
+        if (ls) {
+            if (launch_ls_chol(lc(), K.C, K.C_ld, m, A.nseg, cplx, a_d + el * (size_t)(s0 * out_ld), e_d + s0, st_d + s0, out_ld) != 0)
+                return fail("%s: the Cholesky solve was refused", who);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    return 0;
+}
+
+int sp_covmat(const void *x, int dtype, int64_t x_ld, int64_t nsig, int64_t batch, int64_t n, int64_t hop, int64_t first, int64_t nframes,
+              int m, int fb, int detrend, double mean_re, double mean_im, void *C, int64_t C_ld, int mem) {
+    const char *who = "sp_covmat";
+    if (sub_refusals(who, SUB_WHAT_COVMAT, x, dtype, x_ld, nsig, batch, n, hop, first, nframes, m, fb, detrend, mean_re, mean_im)) return -1;
+    if (C_ld < (int64_t)m * m) return fail("%s: C_ld = %lld is below m m = %d", who, (long long)C_ld, m * m);
+    if (!C) return fail("%s: C is required", who);
+    const int64_t segs = batch * nframes;
+    if (segs == 0) return 0;
+    if (segs > ((int64_t)1 << 40) / C_ld) return fail("%s: %lld matrices %lld apart are more than 2^40 elements", who, (long long)segs, (long long)C_ld);
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const bool cplx = dtype == SP_DTYPE_C64;
+    Stage st(mem);
+    const char *x_d, *C_in;
+    char *C_d;
+    st.in(g.in0, (const char *)x, (cplx ? 8 : 4) * (size_t)((batch - 1) * x_ld + nsig), &x_d);
+    const size_t C_bytes = 16 * (size_t)((segs - 1) * C_ld + (int64_t)m * m);
+    if (C_ld > (int64_t)m * m) st.inout(g.out0, (const char *)C, (char *)C, C_bytes, &C_in, &C_d);
+    else st.out(g.out0, (char *)C, C_bytes, &C_d);
+    if (st.commit()) return -1;
+    if (int rc = sub_passes(who, SUB_WHAT_COVMAT, x_d, cplx, x_ld, segs, n, hop, first, nframes, m, fb, detrend, mean_re, mean_im, C_d, C_ld, nullptr, nullptr,
+                            nullptr, 0))
+        return rc;
+    return st.finish();
+}
+
+int sp_ar_ls(const void *x, int dtype, int64_t x_ld, int64_t nsig, int64_t batch, int64_t n, int64_t hop, int64_t first, int64_t nframes,
+             int order, int fb, int detrend, double mean_re, double mean_im, void *a, double *e, int32_t *status, int64_t out_ld, int mem) {
+    const char *who = "sp_ar_ls";
+    if (order < 1 || order > SUB_MAX_M - 1) return fail("%s: order must lie in 1 .. 63 (order %d)", who, order);
+    const int m = order + 1;
+    if (sub_refusals(who, SUB_WHAT_LS, x, dtype, x_ld, nsig, batch, n, hop, first, nframes, m, fb, detrend, mean_re, mean_im)) return -1;
+    if (out_ld < order + 1) return fail("%s: out_ld = %lld is below order + 1 = %d", who, (long long)out_ld, order + 1);
+    if (!a) return fail("%s: a is required", who);
+    if (!e) return fail("%s: e is required", who);
+    if (!status) return fail("%s: status is required", who);
+    const int64_t segs = batch * nframes;
+    if (segs == 0) return 0;
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const bool cplx = dtype == SP_DTYPE_C64;
+    const size_t el = cplx ? 16 : 8;
+    Stage st(mem);
+    const char *x_d, *a_in;
+    char *a_d;
+    double *e_d;
+    int32_t *s_d;
+    st.in(g.in0, (const char *)x, (cplx ? 8 : 4) * (size_t)((batch - 1) * x_ld + nsig), &x_d);
+    const size_t a_bytes = el * (size_t)((segs - 1) * out_ld + order + 1);
+    if (out_ld > order + 1) st.inout(g.out0, (const char *)a, (char *)a, a_bytes, &a_in, &a_d);
+    else st.out(g.out0, (char *)a, a_bytes, &a_d);
+    st.out(g.out0, e, 8 * (size_t)segs, &e_d);
+    st.out(g.out0, status, 4 * (size_t)segs, &s_d);
+    if (st.commit()) return -1;
+    if (int rc = sub_passes(who, SUB_WHAT_LS, x_d, cplx, x_ld, segs, n, hop, first, nframes, m, fb, detrend, mean_re, mean_im, nullptr, 0, a_d, e_d, s_d, out_ld))
+        return rc;
+    return st.finish();
+}
+
+int sp_pseudospectrum(const void *V, int64_t V_ld, const double *w, int m, int p, int64_t nmodels, int weighting, int64_t nbins, double start,
+                      double step, int out64, void *P, int64_t P_ld, int32_t *status, int mem) {
+    const char *who = "sp_pseudospectrum";
+    if (m < 2 || m > SUB_MAX_M) return fail("%s: m = %d must lie in 2 .. 64", who, m);
+    if (p < 0 || p > m - 1) return fail("%s: p = %d must lie in 0 .. m - 1 = %d", who, p, m - 1);
+    if (V_ld < m) return fail("%s: V_ld = %lld is below m = %d", who, (long long)V_ld, m);
+    if (weighting != SP_SUB_MUSIC && weighting != SP_SUB_EV) return fail("%s: weighting = %d must be SP_SUB_MUSIC or SP_SUB_EV", who, weighting);
+    if (nbins < 1 || nbins > 0x7fffffff) return fail("%s: nbins = %lld must lie in 1 .. 2^31 - 1", who, (long long)nbins);
+    if (P_ld < nbins) return fail("%s: P_ld = %lld is below nbins = %lld", who, (long long)P_ld, (long long)nbins);
+    if (nmodels < 0 || (nmodels > 0 && (nbins + 255) / 256 > 0x7fffffff / nmodels))
+        return fail("%s: nmodels = %lld must not be negative, nor nmodels x ceil(nbins / 256) exceed 2^31 - 1", who, (long long)nmodels);
+    if (!std::isfinite(start) || !std::isfinite(step)) return fail("%s: start and step must be finite", who);
+    if (!V) return fail("%s: V is required", who);
+    if (!w) return fail("%s: w is required", who);
+    if (!P) return fail("%s: P is required", who);
+    if (!status) return fail("%s: status is required", who);
+    if (nmodels == 0) return 0;
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const size_t pel = out64 ? 8 : 4;
+    Stage st(mem);
+    const char *V_d, *P_in;
+    const double *w_d;
+    char *P_d;
+    int32_t *s_d;
+    st.in(g.in0, (const char *)V, 16 * (size_t)((nmodels * m - 1) * V_ld + m), &V_d);
+    st.in(g.in0, w, 8 * (size_t)(nmodels * m), &w_d);
+    const size_t P_bytes = pel * (size_t)((nmodels - 1) * P_ld + nbins);
+    if (P_ld > nbins) st.inout(g.out0, (const char *)P, (char *)P, P_bytes, &P_in, &P_d);
+    else st.out(g.out0, (char *)P, P_bytes, &P_d);
+    st.out(g.out0, status, 4 * (size_t)nmodels, &s_d);
+    if (st.commit()) return -1;
+    int rc;
+    {
+        ProfScope ps;
+        rc = launch_pseudo(lc(), V_d, V_ld, w_d, m, p, nmodels, weighting == SP_SUB_EV, nbins, start, step, out64 != 0, P_d, P_ld, s_d);
+    }
+    if (rc != 0) return fail("%s: the launch was refused (%lld models, %lld bins)", who, (long long)nmodels, (long long)nbins);
+    HIPCHK(hipGetLastError());
+    g.last_kernel = "k_pseudo";
     return st.finish();
 }
 

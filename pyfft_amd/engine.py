@@ -261,7 +261,7 @@ def last_passes(which=0):
     the passes of `lomb` and `lomb_sums` over their frequencies, which=4 (LOMB_LAUNCHES) the most launches the row groups of one such
     pass were dealt to, which=5 (FAM_PASSES) the passes of `fam` over its blocks, which=6 (NUFFT_PASSES) the passes of `nufft1`, `nufft2`
     and `lomb_sums_grid` over their rows; 0 where the call had no such loop (sp_last_passes).
-    which=7 (AR_PASSES): the passes of `burg` and `yule` over their segments."""
+    which=7 (AR_PASSES): the passes of `burg` and `yule` over their segments; which=8 (SUB_PASSES): those of `covmat` and `ar_ls`."""
     return int(lib().sp_last_passes(int(which)))
 
 
@@ -2145,16 +2145,17 @@ def ar_check(who, method, n, hop, first, nframes, order, rows, nsig=None, x_ld=N
         raise ArRefused("%s: mean_value must be finite" % who)
 
 
-def _ar_detrend(who, detrend, mean_value):
+def _ar_detrend(who, detrend, mean_value, Refused=None):
     """-> (the C ABI's detrend code, the constant): True every segment's own mean, or with an explicit mean_value that constant; False
     or None nothing, and then a mean_value is refused"""
+    Refused = Refused or ArRefused
     flag = isinstance(detrend, (bool, np.bool_))
     if detrend is None or (flag and not detrend):
         if mean_value is not None:
-            raise ArRefused("%s: mean_value = %r is given, but detrend is off" % (who, mean_value))
+            raise Refused("%s: mean_value = %r is given, but detrend is off" % (who, mean_value))
         return _ffi.DETREND_CONST, 0j
     if not flag:
-        raise ArRefused("%s: detrend must be True (every segment's own mean, or mean_value) or False, not %r" % (who, detrend))
+        raise Refused("%s: detrend must be True (every segment's own mean, or mean_value) or False, not %r" % (who, detrend))
     if mean_value is not None:
         return _ffi.DETREND_CONST, complex(mean_value)
     return _ffi.DETREND_SEGMEAN, 0j
@@ -2252,6 +2253,160 @@ def ar_plan(method, n, order, rows=1, nframes=1, cplx=False):
     ar_check("ar_plan", method, n, 1, 0, nframes, order, rows)
     return _plan(lib().sp_ar_plan, ("form", "segs_per_wg", "samples", "lds_bytes", "workgroups", "passes", "threads", "tiles"), ArRefused,
                  "ar_plan", method, _ffi.DTYPE_C64 if cplx else _ffi.DTYPE_F32, n, order, rows, nframes)
+
+
+SUB_MAX_M, SUB_PASSES = 64, 8
+SUB_WHAT = {"covmat": 0, "ls": 1}
+SUB_WEIGHTINGS = {"music": 0, "ev": 1}
+
+
+class SubRefused(ValueError, NotImplementedError):
+    """A segment, a matrix order, a signal dimension or an eigendecomposition the covariance matrices, the covariance least-squares
+    fits and the pseudospectra do not take: outside the limits, values a record must not hold, and what is not built (m above 64)."""
+
+
+def sub_check(who, what, n, hop, first, nframes, m, rows, nsig=None, mean=0j):
+    """The refusals of sp_covmat, sp_ar_ls and sp_sub_plan about the record and the matrix order m (order + 1 for a fit), before the
+    library is touched."""
+    if what not in (0, 1):
+        raise SubRefused("%s: what must be 0 (covmat) or 1 (the least-squares fit)" % who)
+    if what == 1 and (m < 2 or m > SUB_MAX_M):
+        raise SubRefused("%s: order = %d is outside 1 .. %d" % (who, m - 1, SUB_MAX_M - 1))
+    if m < 2 or m > SUB_MAX_M:
+        raise SubRefused("%s: m = %d is outside 2 .. %d" % (who, m, SUB_MAX_M))
+    if n < 2 or n > YULE_MAX_N:
+        raise SubRefused("%s: n = %d samples of a segment are outside 2 .. %d" % (who, n, YULE_MAX_N))
+    if what == 1 and m - 1 > n // 2:
+        raise SubRefused("%s: order = %d exceeds n / 2 = %d" % (who, m - 1, n // 2))
+    if m > n:
+        raise SubRefused("%s: m = %d exceeds n = %d" % (who, m, n))
+    _range_check(SubRefused, who, hop=hop, count=("nframes", nframes), rows=(rows, (1 << 31) - 1))
+    if nframes > (1 << 31) - 1 or rows * nframes > 1 << 40:
+        raise SubRefused("%s: %d rows of %d frames are more segments than 2^40" % (who, rows, nframes))
+    if first < 0:
+        raise SubRefused("%s: first = %d must not be negative" % (who, first))
+    if nsig is not None and nframes > 0 and first + (nframes - 1) * hop + n > nsig:
+        raise SubRefused("%s: %d frames of %d at hop %d from %d on reach outside the %d samples of a row" % (who, nframes, n, hop, first, nsig))
+    if not (math.isfinite(mean.real) and math.isfinite(mean.imag)):
+        raise SubRefused("%s: mean_value must be finite" % who)
+
+
+def _sub_record(who, what, x, n, hop, first, nframes, m, detrend, mean_value):
+    """the record of `covmat` and `ar_ls`, judged as `_ar_fit` judges its own -> (md, rows of x, their pitch, nsig, rows, lead, cplx,
+    the detrend code, the constant)"""
+    md = _enter(x)
+    x = md.checked(x)
+    if x.ndim < 1:
+        raise SubRefused("%s: x needs at least one axis" % who)
+    code, mean = _ar_detrend(who, detrend, mean_value, SubRefused)
+    lead, rows = _lead_rows(x.shape)
+    nsig = int(x.shape[-1])
+    sub_check(who, what, n, hop, first, nframes, m, rows, nsig, mean)
+    cplx = md.code(x) == _ffi.DTYPE_C64
+    if not cplx and mean.imag != 0.0:
+        raise SubRefused("%s: a real record takes a real mean_value" % who)
+    if not md.dev and not np.all(np.isfinite(x)):
+        raise SubRefused("%s: x must be finite" % who)
+    if md.dev and x.ndim != 2:
+        x = x.reshape(rows, nsig)
+    xs, xld = md.rows(x)
+    return md, xs, xld, nsig, rows, lead, cplx, code, mean
+
+
+def covmat(x, n, hop, first, nframes, m, fb=True, detrend=True, mean_value=None):
+    """The m x m data covariance matrices (sp_covmat) of the segments x[..., first + g hop + t], t < n, g < nframes, of every row:
+    C[i,j] = (1 / N) sum_{t=m-1}^{n-1} conj(s[t-i]) s[t-j], N = n - m + 1 (fb=False: MATLAB's corrmtx(.., 'covariance') as X'X), or
+    its forward-backward average (C + J conj(C) J) / 2 (fb=True: 'modified').  -> C[..., g, m, m] complex128, exactly Hermitian,
+    what `eigh` takes.  2 <= m <= 64, m <= n.  The detrended samples stay float64 and every sum is float64 in a fixed order.
+    detrend as for `burg`.  numpy in -> numpy out; device tensors in -> a device tensor on x's stream; the two agree bitwise."""
+    who = "covmat"
+    n, hop, first, nframes, m = int(n), int(hop), int(first), int(nframes), int(m)
+    md, xs, xld, nsig, rows, lead, cplx, code, mean = _sub_record(who, 0, x, n, hop, first, nframes, m, detrend, mean_value)
+    C = md.empty(lead + (nframes, m, m), "complex128", xs)
+    if rows * nframes:
+        _bad_record_call(md, SubRefused, lib().sp_covmat, md.addr(xs), md.code(xs), xld, nsig, rows, n, hop, first, nframes, m, 1 if fb else 0, code,
+                         mean.real, mean.imag, md.addr(C), m * m)
+    return C
+
+
+def ar_ls(x, n, hop, first, nframes, order, fb=False, detrend=True, mean_value=None, check=True):
+    """The covariance (fb=False, MATLAB's arcov) or modified-covariance (fb=True, armcov) least-squares fit (sp_ar_ls) of the segments
+    of `covmat`: with C at m = order + 1, sum_j C[i,j] a_j = -C[i,0], i, j = 1 .. order, by Cholesky -> (a, e, status):
+    a[..., g, 0 .. order] with a[..., 0] = 1 (float64 for float32 rows, complex128 for complex64 rows), e[..., g] =
+    Re(C[0,0] + sum_j C[0,j] a_j) and status[..., g] int32: 0, or the 1-based index of the first pivot at or below m 2^-52 C[j,j]
+    (then a = (1, 0 ..) and e = 0).  order <= 63 and <= n / 2.  check=True reads status back and raises numpy.linalg.LinAlgError
+    naming the first singular model, as `eigh` does.  numpy in -> numpy out; device tensors in -> device tensors, the same bits."""
+    who = "ar_ls"
+    n, hop, first, nframes, order = int(n), int(hop), int(first), int(nframes), int(order)
+    md, xs, xld, nsig, rows, lead, cplx, code, mean = _sub_record(who, 1, x, n, hop, first, nframes, order + 1, detrend, mean_value)
+    a = md.empty(lead + (nframes, order + 1), "complex128" if cplx else "float64", xs)
+    e = md.empty(lead + (nframes,), "float64", xs)
+    st = md.empty(lead + (nframes,), "int32", xs)
+    if rows * nframes:
+        _bad_record_call(md, SubRefused, lib().sp_ar_ls, md.addr(xs), md.code(xs), xld, nsig, rows, n, hop, first, nframes, order, 1 if fb else 0, code,
+                         mean.real, mean.imag, md.addr(a), md.addr(e), md.addr(st), order + 1)
+    if check and rows * nframes:                                    # (the read-back of a device tensor waits for the stream)
+        bad = (st.reshape(-1).cpu().numpy() if md.dev else st.reshape(-1)) > 0
+        if bad.any():
+            i = int(np.argmax(bad))
+            raise np.linalg.LinAlgError("ar_ls: model %s (flat index %d) is singular: no positive pivot at row %d of %d"
+                                        % (np.unravel_index(i, lead + (nframes,)), i, int(st.reshape(-1)[i]), order))
+    return a, e, st
+
+
+def pseudospectrum(V, w, p, nbins, start, step, weighting="music", out64=False):
+    """The MUSIC (weighting='music') or eigenvector (weighting='ev') pseudospectrum (sp_pseudospectrum) of the eigendecompositions
+    V[..., m, m] complex128, w[..., m] float64 descending, as `eigh` returns them, with signal dimension 0 <= p < m:
+    P[..., q] = 1 / sum_{k >= p} g_k |sum_i V[..., i, k] exp(-2 pi i nu_q i)|^2 at nu_q = start + q step cycles per sample, g_k = 1
+    or 1 / w_k (g_k = 0 and status 1 where w_k <= 0) -> (P float32 [..., nbins], or float64 with out64; status int32 [...]).
+    numpy in -> numpy out; device tensors in -> device tensors."""
+    who = "pseudospectrum"
+    p, nbins, start, step = int(p), int(nbins), float(start), float(step)
+    if weighting not in SUB_WEIGHTINGS:
+        raise SubRefused("%s: weighting must be 'music' or 'ev', not %r" % (who, weighting))
+    md = _enter(V)
+    if _mode(w) is not md:
+        raise TypeError("%s: V and w must both be numpy arrays or both device tensors" % who)
+    if md.dev:
+        if V.dtype != torch.complex128 or w.dtype != torch.float64:
+            raise SubRefused("%s: on the device V is a complex128 tensor and w float64" % who)
+        V, w = V.contiguous(), w.contiguous()
+    else:
+        V = np.ascontiguousarray(np.asarray(V), dtype=np.complex128)
+        w = np.ascontiguousarray(np.asarray(w), dtype=np.float64)
+    shape = tuple(V.shape)
+    if len(shape) < 2 or shape[-1] != shape[-2] or tuple(w.shape) != shape[:-1]:
+        raise SubRefused("%s: V must be [..., m, m] and w [..., m]" % who)
+    m = int(shape[-1])
+    if m < 2 or m > SUB_MAX_M:
+        raise SubRefused("%s: m = %d is outside 2 .. %d" % (who, m, SUB_MAX_M))
+    if p < 0 or p > m - 1:
+        raise SubRefused("%s: p = %d is outside 0 .. m - 1 = %d" % (who, p, m - 1))
+    if nbins < 1 or nbins > (1 << 31) - 1:
+        raise SubRefused("%s: nbins = %d is outside 1 .. 2^31 - 1" % (who, nbins))
+    if not (math.isfinite(start) and math.isfinite(step)):
+        raise SubRefused("%s: start and step must be finite" % who)
+    lead, models = _lead_rows(shape, 2)
+    if models * -(-nbins // 256) > (1 << 31) - 1:
+        raise SubRefused("%s: %d models of %d bins are more than one launch takes" % (who, models, nbins))
+    if not md.dev and not (np.all(np.isfinite(V)) and np.all(np.isfinite(w))):
+        raise SubRefused("%s: V and w must be finite" % who)
+    P = md.empty(lead + (nbins,), "float64" if out64 else "float32", V)
+    st = md.empty(lead, "int32", V)
+    if models:
+        md.call(lib().sp_pseudospectrum, md.addr(V), m, md.addr(w), m, p, models, SUB_WEIGHTINGS[weighting], nbins, start, step, 1 if out64 else 0,
+                md.addr(P), nbins, md.addr(st))
+    return P, st
+
+
+def sub_plan(what, n, m, rows=1, nframes=1, cplx=False):
+    """sp_sub_plan as a dict (host only): what 'covmat' or 'ls' (m = order + 1) -> chunk (samples of a tile), tiles, shares (of a stage
+    of k_cov_row), lds_bytes, workgroups (of k_cov_row over all passes), passes, seg_bytes (scratch of a segment), segs_per_pass."""
+    what = SUB_WHAT.get(what, what)
+    n, m, rows, nframes = int(n), int(m), int(rows), int(nframes)
+    sub_check("sub_plan", what, n, 1, 0, nframes, m, rows)
+    return _plan(lib().sp_sub_plan, ("chunk", "tiles", "shares", "lds_bytes", "workgroups", "passes", "seg_bytes", "segs_per_pass"), SubRefused,
+                 "sub_plan", what, _ffi.DTYPE_C64 if cplx else _ffi.DTYPE_F32, n, m, rows, nframes)
 
 
 EIGH_MAX_N = 64

@@ -10,7 +10,7 @@ import math
 import numpy as np
 
 from . import engine as E
-from .engine import ArRefused                                      # noqa: F401
+from .engine import ArRefused, SubRefused                          # noqa: F401
 
 try:
     import torch
@@ -18,6 +18,7 @@ except Exception:                                                  # pragma: no 
     torch = None
 
 _FITS = {"burg": E.burg, "yule": E.yule}
+_LS = {"cov": False, "mcov": True}                                 # the least-squares fits (engine.ar_ls): forward, forward-backward
 
 
 def _is_tensor(x):
@@ -51,6 +52,30 @@ def aryule(x, order, detrend=False, evar=False):
     """MATLAB's aryule along the last axis (the biased autocorrelation estimate and Levinson-Durbin): the returns of `arburg`.  Rows of
     any length up to 2^31 - 1."""
     return _fit("aryule", "yule", x, order, detrend, evar)
+
+
+def _ls_fit(who, fb, x, order, detrend, check=True):
+    if not _is_tensor(x):
+        x = np.asarray(x)
+    if len(x.shape) < 1 or int(x.shape[-1]) < 2:
+        raise SubRefused("%s: x needs a last axis of at least two samples" % who)
+    a, e, _ = E.ar_ls(x, int(x.shape[-1]), 1, 0, 1, order, fb=fb, detrend=detrend, check=check)
+    return a[..., 0, :], e[..., 0]
+
+
+def arcov(x, order, detrend=False, check=True):
+    """MATLAB's arcov along the last axis, the covariance (forward least-squares) fit: -> a[..., order + 1] (a[..., 0] = 1), e[...]
+    (the mean square of the forward prediction error over the n - order predicted samples).  No window and no lattice: lines closer
+    than 1 / n that `arburg` merges or splits come apart, and a noiseless sum of order / 2 real sinusoids is fitted exactly (then the
+    normal matrix is singular: numpy.linalg.LinAlgError, or with check=False the model a = (1, 0 ..), e = 0).  order <= 63 and
+    <= n / 2; the model need not be stable."""
+    return _ls_fit("arcov", False, x, order, detrend, check)
+
+
+def armcov(x, order, detrend=False, check=True):
+    """MATLAB's armcov along the last axis, the modified covariance (forward-backward least-squares) fit: the returns of `arcov`; e is
+    the mean of the forward and the backward error powers.  Free of Burg's line splitting and of its phase-dependent bias."""
+    return _ls_fit("armcov", True, x, order, detrend, check)
 
 
 def _axis(who, nfft, fs, onesided, band, m):
@@ -110,14 +135,31 @@ def pyulear(x, order, nfft=256, fs=1.0, return_onesided=True, detrend=False, ban
     return _pxx("pyulear", "yule", x, order, nfft, fs, return_onesided, detrend, band, m, out64)
 
 
+def _pxx_ls(who, fb, x, order, nfft, fs, return_onesided, detrend, band, m, out64):
+    _axis(who, nfft, fs, bool(return_onesided), band, m)
+    a, e = _ls_fit(who, fb, x, order, detrend)
+    return ar_psd(a, e, nfft, fs, return_onesided, band, m, out64)
+
+
+def pcov(x, order, nfft=256, fs=1.0, return_onesided=True, detrend=False, band=None, m=None, out64=False):
+    """MATLAB's pcov along the last axis: -> f, Pxx: `ar_psd` of `arcov`, in the units and the one-sided rule of `pburg`."""
+    return _pxx_ls("pcov", False, x, order, nfft, fs, return_onesided, detrend, band, m, out64)
+
+
+def pmcov(x, order, nfft=256, fs=1.0, return_onesided=True, detrend=False, band=None, m=None, out64=False):
+    """MATLAB's pmcov along the last axis: -> f, Pxx: `ar_psd` of `armcov`."""
+    return _pxx_ls("pmcov", True, x, order, nfft, fs, return_onesided, detrend, band, m, out64)
+
+
 def ar_spectrogram(x, order, nperseg, noverlap=None, method="burg", fs=1.0, nfft=None, detrend=True, return_onesided=True, band=None,
                    m=None, out64=False):
     """A time-resolved autoregressive spectrum: one fit per segment of nperseg samples (noverlap defaults to nperseg // 2) -> f, t,
     Pxx[..., bins, segments] in scipy.signal.spectrogram's orientation and units; column g is `pburg` (`pyulear`) of segment g less
-    its own mean (detrend=False: as it is).  t: the segments' centres.  nfft defaults to nperseg; band=(f1, f2), m= give a zoomed axis."""
+    its own mean (detrend=False: as it is).  t: the segments' centres.  nfft defaults to nperseg; band=(f1, f2), m= give a zoomed axis.
+    method: 'burg', 'yule', or the least-squares fits 'cov' (`pcov`) and 'mcov' (`pmcov`), whose orders end at 63."""
     who = "ar_spectrogram"
-    if method not in _FITS:
-        raise ArRefused("%s: method must be 'burg' or 'yule', not %r" % (who, method))
+    if method not in _FITS and method not in _LS:
+        raise ArRefused("%s: method must be 'burg', 'yule', 'cov' or 'mcov', not %r" % (who, method))
     if not _is_tensor(x):
         x = np.asarray(x)
     nperseg = int(nperseg)
@@ -128,8 +170,12 @@ def ar_spectrogram(x, order, nperseg, noverlap=None, method="burg", fs=1.0, nfft
     nframes = (int(x.shape[-1]) - nperseg) // hop + 1
     cplx = _is_complex(x)
     f, m, start, step, dbl = _axis(who, nperseg if nfft is None else nfft, fs, bool(return_onesided) and not cplx, band, m)
-    a, e, _ = _FITS[method](x, nperseg, hop, 0, nframes, order, detrend=detrend)
-    P = E.ar_psd(a, e[..., -1], m, start, step, 1.0 / float(fs), out64)
+    if method in _LS:
+        a, e1, _ = E.ar_ls(x, nperseg, hop, 0, nframes, order, fb=_LS[method], detrend=detrend)
+    else:
+        a, e, _ = _FITS[method](x, nperseg, hop, 0, nframes, order, detrend=detrend)
+        e1 = e[..., -1]
+    P = E.ar_psd(a, e1, m, start, step, 1.0 / float(fs), out64)
     if dbl is not None:
         if _is_tensor(P) and not isinstance(dbl, slice):
             dbl = torch.as_tensor(dbl, device=P.device)
