@@ -60,6 +60,7 @@ int sp_wct_plan(int64_t nsig, int nscales, int64_t batch, int L, int Mw, int Mg,
  *      sp_lomb_sums_grid (spectral_nufft.h) made over their rows (for the latter 1 + batch of them: the weights' row and the values').
  *      which = 7: the passes sp_burg and sp_yule (spectral_ar.h) made over their segments.
  *      which = 8: the passes sp_covmat and sp_ar_ls (spectral_sub.h) made over their segments.
+ *      which = 9: the passes the tile form of sp_dwt, sp_idwt, sp_modwt and sp_imodwt (spectral_dwt.h) made over their rows (SP_DWT_ROWS caps a pass).
  *      0 where the call had no such loop, or for another `which`.
  *      All are reset where a call that touches the device begins.  The budgets behind the loops can be capped
  *      through the environment, read on every call (unset or <= 0: no cap): SP_LONG_CHUNK_FRAMES (frames of a long chunk),

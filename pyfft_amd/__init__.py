@@ -70,6 +70,9 @@ from .parametric import (arburg, aryule, pburg, pyulear, ar_spectrogram, ar_psd,
 from . import subspace as _subspace_mod                        # noqa: F401
 from .subspace import (corrmtx_cov, pmusic, peig, subspace_spectrogram, subspace_order, esprit, subspace_plan,   # noqa: F401
                        SubRefused)
+from . import dwt as _dwt_mod                                  # noqa: F401
+from .dwt import (wavelet_filters, dwt_max_level, dwt_coeff_len, dwt, idwt, wavedec, waverec, modwt, imodwt, modwt_mra,   # noqa: F401
+                  modwt_variance, wpdec, wprec, dwt_plan, DwtRefused)
 from . import wbicoherence as _wbic_mod                        # noqa: F401
 from .wbicoherence import (wbic_freqs, wavelet_bispectrum, wavelet_bicoherence, summed_bicoherence,   # noqa: F401
                            total_bicoherence, wbic_plan)

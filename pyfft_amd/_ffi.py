@@ -172,10 +172,24 @@ SUB_SIGNATURES = {
     "sp_sub_plan": (_i, [_i, _i, _i64, _i, _i64, _i64, _vp]),
 }
 
+# the thirteenth table: must list every symbol include/spectral_dwt.h declares, and none of the other twelve
+_DWT_ROWS = [_vp, _i, _i64, _i64, _i64, _vp, _vp, _i]                 # rows, dtype, pitch, n, batch, the two filters (host float64), L
+DWT_SIGNATURES = {
+    "sp_dwt": (_i, _DWT_ROWS + [_i, _i, _vp, _i64, _i, _i]),
+    "sp_dwt_level": (_i, _DWT_ROWS + [_i, _vp, _i64, _vp, _i64, _i, _i]),
+    "sp_idwt": (_i, _DWT_ROWS + [_i, _i, _vp, _i64, _i, _i]),
+    "sp_idwt_level": (_i, [_vp, _i64, _vp, _i64, _i, _i64, _i64, _vp, _vp, _i, _i, _vp, _i64, _i, _i]),
+    "sp_modwt": (_i, _DWT_ROWS + [_i, _vp, _i64, _i, _i]),
+    "sp_imodwt": (_i, _DWT_ROWS + [_i, _vp, _i64, _i, _i]),
+    "sp_dwt_plan": (_i, [_i, _i, _i64, _i, _i, _i, _i64, _i, _vp]),
+}
+
 # the six tables the engine trace counts, in the order of their headers
 TABLES = (SIGNATURES, EXT_SIGNATURES, TFR_SIGNATURES, QUAD_SIGNATURES, CYCLO_SIGNATURES, UNEVEN_SIGNATURES)
 # the tables added since: bound like the six, outside the trace
 MORE_TABLES = (WBIC_SIGNATURES, FAM_SIGNATURES, NUFFT_SIGNATURES, NUFFT2_SIGNATURES, SUB_SIGNATURES, AR_SIGNATURES)
+# ... and those added after them, bound alike
+LATER_TABLES = (DWT_SIGNATURES,)
 
 
 class SpectralError(RuntimeError):
@@ -191,7 +205,7 @@ def load_library():
         raise SpectralError("libspectral.so not found at %s -- run `make` (or __graft_entry__.build()); "
                             "pyfft_amd has no CPU fallback" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for table in TABLES + MORE_TABLES:
+    for table in TABLES + MORE_TABLES + LATER_TABLES:
         for name, (res, args) in table.items():
             fn = getattr(lib, name)      # AttributeError if the .so lacks a declared symbol
             fn.restype = res

@@ -6,6 +6,7 @@
 #include "nufft_plan.h"
 #include "ar_plan.h"
 #include "sub_plan.h"
+#include "dwt_plan.h"
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -45,6 +46,8 @@ namespace sp {
 //                  <= 0: the budget alone; sp_last_passes(6) reports the passes)
 //   SP_AR_SEGS (int: a cap on the segments per pass of sp_burg / sp_yule; unset or <= 0: the budget alone; sp_last_passes(7) reports the passes)
 //                  the same cap holds for sp_covmat / sp_ar_ls, whose passes sp_last_passes(8) reports
+//   SP_DWT_ROWS (int: a cap on the rows per pass of the tile form of sp_dwt / sp_idwt / sp_modwt / sp_imodwt; unset or <= 0: the budget alone;
+//                  sp_last_passes(9) reports the passes)
 //   SP_BURG_FORM (int: 1 the wave form of k_burg wherever a segment fits it, 2 the workgroup form at every length; unset or 0: by length)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
@@ -1220,6 +1223,35 @@ int launch_ls_chol(LaunchCtx c, const void *C, int64_t C_ld, int m, int64_t nmod
 // P[model P_ld + q] = 1 / sum_{k >= p} g_k |sum_i V[model m V_ld + i V_ld + k] e(-i (start + q step))|^2; status[model]: a weight was not positive
 int launch_pseudo(LaunchCtx c, const void *V, int64_t V_ld, const double *w, int m, int p, int64_t nmodels, bool ev, int64_t nbins, double start, double step,
                   bool out64, void *P, int64_t P_ld, int *status);
+
+// The discrete wavelet transforms (k_dwt.hip; include/spectral_dwt.h; the host's arithmetic in dwt_plan.h).  Row form: a workgroup runs
+// every level of rpw rows in LDS (lds = dwt_row_lds, cap = dwt_row_cap, lv the levels' lengths and the details' offsets in a row of outD /
+// inD); tile form: one level per launch, DWT_TILE outputs of one row per workgroup.  Pitches count elements.
+static_assert((size_t)DWT_LDS_MAX == SP_LDS_MAX, "dwt_plan.h states the LDS a workgroup may take");
+struct DwtRowArgs {
+    bool cplx;
+    int64_t n, rows;
+    DwtFilt f;
+    int mode, levels, rpw;
+    int64_t cap;
+    size_t lds;
+    DwtLv lv;
+};
+struct DwtTileArgs {
+    bool cplx;
+    int64_t rows;
+    DwtFilt f;
+    int mode;
+};
+int launch_dwt_row(LaunchCtx c, const DwtRowArgs &a, const void *x, int64_t x_ld, void *outA, int64_t a_ld, void *outD, int64_t d_ld);
+int launch_idwt_row(LaunchCtx c, const DwtRowArgs &a, const void *inA, int64_t a_ld, const void *inD, int64_t d_ld, void *x, int64_t x_ld);
+// W[(j - 1) plane + row w_ld + t], j = 1 .. levels, V_levels in the plane behind them
+int launch_modwt_row(LaunchCtx c, const DwtRowArgs &a, const void *x, int64_t x_ld, void *W, int64_t w_ld, int64_t plane);
+int launch_imodwt_row(LaunchCtx c, const DwtRowArgs &a, const void *W, int64_t w_ld, int64_t plane, void *x, int64_t x_ld);
+int launch_dwt_tile(LaunchCtx c, const DwtTileArgs &a, const void *x, int64_t x_ld, int64_t n, void *cA, int64_t a_ld, void *cD, int64_t d_ld);
+int launch_idwt_tile(LaunchCtx c, const DwtTileArgs &a, const void *cA, int64_t a_ld, const void *cD, int64_t d_ld, void *x, int64_t x_ld, int64_t nout);
+int launch_modwt_tile(LaunchCtx c, const DwtTileArgs &a, int level, const void *vin, int64_t in_ld, int64_t n, void *W, int64_t w_ld, void *vout, int64_t out_ld);
+int launch_imodwt_tile(LaunchCtx c, const DwtTileArgs &a, int level, const void *W, int64_t w_ld, const void *vin, int64_t in_ld, int64_t n, void *vout, int64_t out_ld);
 
 // dispatch over the transform: MACRO(XTYPE) with XTYPE = XfPow2<L> or XfBlue<L>
 #define SP_CASE_P(Lv, MACRO) case Lv: { MACRO(XfPow2<Lv>) } break;

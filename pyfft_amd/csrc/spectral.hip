@@ -11,6 +11,7 @@
 #include "../../include/spectral_nufft2.h"
 #include "../../include/spectral_ar.h"
 #include "../../include/spectral_sub.h"
+#include "../../include/spectral_dwt.h"
 #include "launch.h"
 #include "stage.h"
 #include "table_cache.h"
@@ -103,6 +104,7 @@ struct Ctx {
     Scratch famZ, famA;                             // FFT accumulation: the bin-major frames of a pass, the float64 sums across passes
     Scratch nuRec, nuGrid;                          // type-1 NUFFT: the prepared samples, tile lists and shifts of a call; the fine grids of a pass
     Scratch subPart, subMat;                        // covariance matrices: the per-tile partial rows of a pass; the matrices of a pass of fits
+    Scratch dwtS;                                   // discrete wavelet transforms: the approximations between the levels of a pass (tile form)
     Scratch arPart, arSmall;                        // autoregressive fits: the per-tile partial lags of a pass; the flag, the tiles' sums and the means
     Scratch cmS, cmT, cmG, cmH, cmO;               // CSD matrix: spectra, bin-major spectra, float64 accumulator, packed-spectra sums, one-pass means state
     std::map<int64_t, BigTw> bigtw;           // N -> two-level twiddle tables of the multi-pass FFT
@@ -238,9 +240,10 @@ TableCache g_tables;
 // dev_fft_any / sp_czt loop made inside it, [2] the passes over the cycle-frequency list of sp_cyclic, [3] the passes over the
 // frequency list of sp_lomb / sp_lomb_sums, [4] the most launches the row groups of one such pass were dealt to, [5] the passes over the
 // blocks of sp_fam, [6] the passes over the rows of sp_nufft1 / sp_lomb_sums_grid / sp_nufft2, [7] the passes over
-// the segments of sp_burg / sp_yule, [8] the passes over the segments of sp_covmat / sp_ar_ls.  All are zeroed
+// the segments of sp_burg / sp_yule, [8] the passes over the segments of sp_covmat / sp_ar_ls, [9] the passes over the
+// rows of the tile form of sp_dwt / sp_idwt / sp_modwt / sp_imodwt and their single-level entries.  All are zeroed
 // where a call begins (ApiLock), so that a test can assert that the shape it chose really walks a loop past its first pass.
-int g_passes[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+int g_passes[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 inline void note_slices(int64_t n) {
     if (n > g_passes[1]) g_passes[1] = (int)n;
 }
@@ -256,7 +259,7 @@ struct ApiLock {
     std::lock_guard<std::mutex> lk;
     ApiLock() : lk(g.mu) {
         g_tables.begin_call();
-        g_passes[0] = g_passes[1] = g_passes[2] = g_passes[3] = g_passes[4] = g_passes[5] = g_passes[6] = g_passes[7] = g_passes[8] = 0;
+        g_passes[0] = g_passes[1] = g_passes[2] = g_passes[3] = g_passes[4] = g_passes[5] = g_passes[6] = g_passes[7] = g_passes[8] = g_passes[9] = 0;
     }
 };
 
@@ -1340,7 +1343,7 @@ int sp_max_wg_fft(void) { return SP_MAX_WG_FFT; }
 const char *sp_last_error(void) { return g_err.c_str(); }
 int sp_last_passes(int which) {
     std::lock_guard<std::mutex> lk(g.mu);
-    return which >= 0 && which <= 8 ? g_passes[which] : 0;
+    return which >= 0 && which <= 9 ? g_passes[which] : 0;
 }
 
 int sp_init(int device_id) {
@@ -1411,6 +1414,7 @@ void sp_shutdown(void) {
     g.arPart.release();
     g.subPart.release();
     g.subMat.release();
+    g.dwtS.release();
     g.arSmall.release();
     for (auto &kv : g.bigtw) {
         (void)hipFree((void *)kv.second.hi);
@@ -4952,6 +4956,341 @@ int sp_pseudospectrum(const void *V, int64_t V_ld, const double *w, int m, int p
     if (rc != 0) return fail("%s: the launch was refused (%lld models, %lld bins)", who, (long long)nmodels, (long long)nbins);
     HIPCHK(hipGetLastError());
     g.last_kernel = "k_pseudo";
+    return st.finish();
+}
+
+// ---- the discrete wavelet transforms (k_dwt.hip; include/spectral_dwt.h; dwt_plan.h) ----------------------------------------------
+// what every entry refuses about its shape and filters, in one order, and what it then works with; 0 or -1
+struct DwtCall {
+    DwtFilt f;
+    DwtPlan p;
+    bool cplx;
+    size_t el;
+};
+static int dwt_enter(const char *who, int what, int dtype, int64_t n, int64_t batch, const double *lo, const double *hi, int L, int mode, int levels, int form,
+                     DwtCall *c) {
+    if (dtype != SP_DTYPE_F32 && dtype != SP_DTYPE_C64) return fail("%s: dtype = %d must be SP_DTYPE_F32 or SP_DTYPE_C64", who, dtype);
+    if (const char *why = dwt_shape(what, n, L, mode, levels, batch))
+        return fail("%s: %s (n %lld, L %d, mode %d, levels %d, batch %lld)", who, why, (long long)n, L, mode, levels, (long long)batch);
+    if (!lo || !hi) return fail("%s: both filters are required", who);
+    const double scale = what >= DWT_WHAT_MODWT ? 0.70710678118654752440 : 1.0;
+    c->f.L = L;
+    for (int i = 0; i < DWT_MAX_L; ++i) c->f.lo[i] = c->f.hi[i] = 0.f;
+    for (int i = 0; i < L; ++i) {
+        if (!std::isfinite(lo[i]) || !std::isfinite(hi[i])) return fail("%s: the filters must be finite (tap %d)", who, i);
+        c->f.lo[i] = (float)(lo[i] * scale), c->f.hi[i] = (float)(hi[i] * scale);
+    }
+    if (form != SP_DWT_AUTO && form != SP_DWT_ROW && form != SP_DWT_TILE) return fail("%s: form = %d must be 0 (auto), 1 (row) or 2 (tile)", who, form);
+    c->cplx = dtype == SP_DTYPE_C64, c->el = c->cplx ? 8 : 4;
+    c->p = dwt_plan_of(what, c->cplx, n, L, mode, levels, batch, form, env_int("SP_DWT_ROWS", 0));
+    if (form == SP_DWT_ROW && !c->p.row_fits)
+        return fail("%s: the row form does not fit: two buffers of a row of %lld samples take %lld bytes of LDS, a workgroup has %lld", who, (long long)n,
+                    (long long)dwt_row_lds(c->cplx, n, L), (long long)DWT_LDS_MAX);
+    return 0;
+}
+
+int sp_dwt_plan(int what, int dtype, int64_t n, int L, int mode, int levels, int64_t batch, int form, int64_t out[80]) {
+    if (!out || (dtype != SP_DTYPE_F32 && dtype != SP_DTYPE_C64) || dwt_shape(what, n, L, mode, levels, batch)) return -1;
+    if (form != SP_DWT_AUTO && form != SP_DWT_ROW && form != SP_DWT_TILE) return -1;
+    const DwtPlan p = dwt_plan_of(what, dtype == SP_DTYPE_C64, n, L, mode, levels, batch, form, env_int("SP_DWT_ROWS", 0));
+    if (form == SP_DWT_ROW && !p.row_fits) return -1;
+    const int64_t head[10] = {p.form, p.tile, p.lds_bytes, p.workgroups, p.launches, p.passes, p.scratch_bytes, p.rpp, p.max_levels, p.rpw};
+    for (int i = 0; i < 10; ++i) out[i] = head[i];
+    for (int e = 0; e < p.nent; ++e) out[10 + 2 * e] = p.len[e], out[11 + 2 * e] = p.off[e];
+    return 0;
+}
+
+static DwtRowArgs dwt_row_args(const DwtCall &c, int64_t n, int64_t rows, int mode, int levels) {
+    DwtRowArgs a{};
+    a.cplx = c.cplx, a.n = n, a.rows = rows, a.f = c.f, a.mode = mode, a.levels = levels, a.rpw = c.p.rpw, a.cap = c.p.cap;
+    a.lds = (size_t)dwt_row_lds(c.cplx, n, c.f.L), a.lv = c.p.lv;
+    return a;
+}
+
+// the two scratch buffers of a pass of the tile form: the approximation of level j in S[j & 1], its rows buf[j & 1] apart
+static int dwt_scratch(const DwtCall &c, char *S[2]) {
+    const size_t b0 = (c.el * (size_t)c.p.rpp * (size_t)c.p.buf[0] + 255) & ~(size_t)255;
+    if (g.dwtS.ensure(b0 + c.el * (size_t)c.p.rpp * (size_t)c.p.buf[1] + 256)) return -1;
+    S[0] = (char *)g.dwtS.p, S[1] = S[0] + b0;
+    return 0;
+}
+
+// analysis over device pointers: the details of row b at outD + b d_ld + lv.off[j], the last approximation at outA + b a_ld
+static int dwt_run(const char *who, const DwtCall &c, int mode, int levels, const char *x, int64_t x_ld, int64_t n, int64_t batch, char *outA, int64_t a_ld,
+                   char *outD, int64_t d_ld) {
+    const size_t el = c.el;
+    if (c.p.form == DWT_FORM_ROW) {
+        int rc;
+        {
+            ProfScope ps;
+            rc = launch_dwt_row(lc(), dwt_row_args(c, n, batch, mode, levels), x, x_ld, outA, a_ld, outD, d_ld);
+        }
+        if (rc != 0) return fail("%s: the row form's launch was refused (n %lld, L %d, levels %d)", who, (long long)n, c.f.L, levels);
+        HIPCHK(hipGetLastError());
+        g.last_kernel = "k_dwt_row";
+        return 0;
+    }
+    char *S[2];
+    if (dwt_scratch(c, S)) return -1;
+    for (int64_t r0 = 0; r0 < batch; r0 += c.p.rpp, ++g_passes[9]) {
+        DwtTileArgs a{c.cplx, std::min<int64_t>(c.p.rpp, batch - r0), c.f, mode};
+        const char *src = x + el * (size_t)(r0 * x_ld);
+        int64_t sld = x_ld, nj = n;
+        for (int j = 1; j <= levels; ++j) {
+            char *dA = j == levels ? outA + el * (size_t)(r0 * a_ld) : S[j & 1];
+            const int64_t dld = j == levels ? a_ld : c.p.buf[j & 1];
+            int rc;
+            {
+                ProfScope ps;
+                rc = launch_dwt_tile(lc(), a, src, sld, nj, dA, dld, outD + el * (size_t)(r0 * d_ld + c.p.lv.off[j]), d_ld);
+            }
+            if (rc != 0) return fail("%s: the tile form's launch of level %d was refused (%lld samples)", who, j, (long long)nj);
+            HIPCHK(hipGetLastError());
+            src = dA, sld = dld, nj = c.p.lv.len[j];
+        }
+    }
+    g.last_kernel = "k_dwt_tile";
+    return 0;
+}
+
+static int idwt_run(const char *who, const DwtCall &c, int mode, int levels, const char *inA, int64_t a_ld, const char *inD, int64_t d_ld, int64_t n, int64_t batch,
+                    char *x, int64_t x_ld) {
+    const size_t el = c.el;
+    if (c.p.form == DWT_FORM_ROW) {
+        int rc;
+        {
+            ProfScope ps;
+            rc = launch_idwt_row(lc(), dwt_row_args(c, n, batch, mode, levels), inA, a_ld, inD, d_ld, x, x_ld);
+        }
+        if (rc != 0) return fail("%s: the row form's launch was refused (n %lld, L %d, levels %d)", who, (long long)n, c.f.L, levels);
+        HIPCHK(hipGetLastError());
+        g.last_kernel = "k_idwt_row";
+        return 0;
+    }
+    char *S[2];
+    if (dwt_scratch(c, S)) return -1;
+    for (int64_t r0 = 0; r0 < batch; r0 += c.p.rpp, ++g_passes[9]) {
+        DwtTileArgs a{c.cplx, std::min<int64_t>(c.p.rpp, batch - r0), c.f, mode};
+        const char *src = inA + el * (size_t)(r0 * a_ld);
+        int64_t sld = a_ld;
+        for (int j = levels; j >= 1; --j) {
+            char *dst = j == 1 ? x + el * (size_t)(r0 * x_ld) : S[(j - 1) & 1];
+            const int64_t dld = j == 1 ? x_ld : c.p.buf[(j - 1) & 1];
+            int rc;
+            {
+                ProfScope ps;
+                rc = launch_idwt_tile(lc(), a, src, sld, inD + el * (size_t)(r0 * d_ld + c.p.lv.off[j]), d_ld, dst, dld, c.p.lv.len[j - 1]);
+            }
+            if (rc != 0) return fail("%s: the tile form's launch of level %d was refused", who, j);
+            HIPCHK(hipGetLastError());
+            src = dst, sld = dld;
+        }
+    }
+    g.last_kernel = "k_idwt_tile";
+    return 0;
+}
+
+// what the entries refuse about their buffers; `need` elements of a row of each
+static int dwt_buffers(const char *who, const void *in, int64_t in_ld, int64_t in_need, const char *in_name, const void *out, int64_t out_ld, int64_t out_need,
+                       const char *out_name) {
+    if (in_ld < in_need) return fail("%s: %s_ld = %lld is below the %lld elements of a row", who, in_name, (long long)in_ld, (long long)in_need);
+    if (out_ld < out_need) return fail("%s: %s_ld = %lld is below the %lld elements of a row", who, out_name, (long long)out_ld, (long long)out_need);
+    if (in_ld > ((int64_t)1 << 40) || out_ld > ((int64_t)1 << 40)) return fail("%s: a pitch beyond 2^40 elements", who);
+    if (!in) return fail("%s: %s is required", who, in_name);
+    if (!out) return fail("%s: %s is required", who, out_name);
+    return 0;
+}
+
+// an output of `rows` rows of `need` elements, `ld` apart: staged in place where the rows leave room between them
+static void dwt_stage_out(Stage &st, void *h, size_t el, int64_t rows, int64_t ld, int64_t need, const char **in_d, char **out_d) {
+    const size_t bytes = el * (size_t)((rows - 1) * ld + need);
+    if (ld > need) st.inout(g.out0, (const char *)h, (char *)h, bytes, in_d, out_d);
+    else st.out(g.out0, (char *)h, bytes, out_d);
+}
+
+int sp_dwt(const void *x, int dtype, int64_t x_ld, int64_t n, int64_t batch, const double *dec_lo, const double *dec_hi, int L, int mode, int levels,
+           void *out, int64_t out_ld, int form, int mem) {
+    const char *who = "sp_dwt";
+    DwtCall c;
+    if (dwt_enter(who, DWT_WHAT_DWT, dtype, n, batch, dec_lo, dec_hi, L, mode, levels, form, &c)) return -1;
+    if (dwt_buffers(who, x, x_ld, n, "x", out, out_ld, c.p.total, "out")) return -1;
+    if (batch == 0) return 0;
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    Stage st(mem);
+    const char *x_d, *o_in;
+    char *o_d;
+    st.in(g.in0, (const char *)x, c.el * (size_t)((batch - 1) * x_ld + n), &x_d);
+    dwt_stage_out(st, out, c.el, batch, out_ld, c.p.total, &o_in, &o_d);
+    if (st.commit()) return -1;
+    if (int rc = dwt_run(who, c, mode, levels, x_d, x_ld, n, batch, o_d, out_ld, o_d, out_ld)) return rc;
+    return st.finish();
+}
+
+int sp_dwt_level(const void *x, int dtype, int64_t x_ld, int64_t n, int64_t batch, const double *dec_lo, const double *dec_hi, int L, int mode,
+                 void *cA, int64_t a_ld, void *cD, int64_t d_ld, int form, int mem) {
+    const char *who = "sp_dwt_level";
+    DwtCall c;
+    if (dwt_enter(who, DWT_WHAT_DWT, dtype, n, batch, dec_lo, dec_hi, L, mode, 1, form, &c)) return -1;
+    const int64_t K = c.p.lv.len[1];
+    if (dwt_buffers(who, x, x_ld, n, "x", cA, a_ld, K, "cA") || dwt_buffers(who, x, x_ld, n, "x", cD, d_ld, K, "cD")) return -1;
+    if (batch == 0) return 0;
+    const size_t a_bytes = c.el * (size_t)((batch - 1) * a_ld + K), d_bytes = c.el * (size_t)((batch - 1) * d_ld + K);
+    if (!mem && (const char *)cA < (const char *)cD + d_bytes && (const char *)cD < (const char *)cA + a_bytes)
+        return fail("%s: with mem = 0 the rows of cA and cD must not overlap", who);
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    Stage st(mem);
+    const char *x_d, *a_in, *d_in;
+    char *a_d, *d_d;
+    st.in(g.in0, (const char *)x, c.el * (size_t)((batch - 1) * x_ld + n), &x_d);
+    dwt_stage_out(st, cA, c.el, batch, a_ld, K, &a_in, &a_d);
+    dwt_stage_out(st, cD, c.el, batch, d_ld, K, &d_in, &d_d);
+    if (st.commit()) return -1;
+    c.p.lv.off[1] = 0;
+    if (int rc = dwt_run(who, c, mode, 1, x_d, x_ld, n, batch, a_d, a_ld, d_d, d_ld)) return rc;
+    return st.finish();
+}
+
+int sp_idwt(const void *coef, int dtype, int64_t c_ld, int64_t n, int64_t batch, const double *rec_lo, const double *rec_hi, int L, int mode, int levels,
+            void *x, int64_t x_ld, int form, int mem) {
+    const char *who = "sp_idwt";
+    DwtCall c;
+    if (dwt_enter(who, DWT_WHAT_IDWT, dtype, n, batch, rec_lo, rec_hi, L, mode, levels, form, &c)) return -1;
+    if (dwt_buffers(who, coef, c_ld, c.p.total, "coef", x, x_ld, n, "x")) return -1;
+    if (batch == 0) return 0;
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    Stage st(mem);
+    const char *c_d, *x_in;
+    char *x_d;
+    st.in(g.in0, (const char *)coef, c.el * (size_t)((batch - 1) * c_ld + c.p.total), &c_d);
+    dwt_stage_out(st, x, c.el, batch, x_ld, n, &x_in, &x_d);
+    if (st.commit()) return -1;
+    if (int rc = idwt_run(who, c, mode, levels, c_d, c_ld, c_d, c_ld, n, batch, x_d, x_ld)) return rc;
+    return st.finish();
+}
+
+int sp_idwt_level(const void *cA, int64_t a_ld, const void *cD, int64_t d_ld, int dtype, int64_t n, int64_t batch, const double *rec_lo, const double *rec_hi,
+                  int L, int mode, void *x, int64_t x_ld, int form, int mem) {
+    const char *who = "sp_idwt_level";
+    DwtCall c;
+    if (dwt_enter(who, DWT_WHAT_IDWT, dtype, n, batch, rec_lo, rec_hi, L, mode, 1, form, &c)) return -1;
+    const int64_t K = c.p.lv.len[1];
+    if (dwt_buffers(who, cA, a_ld, K, "cA", x, x_ld, n, "x") || dwt_buffers(who, cD, d_ld, K, "cD", x, x_ld, n, "x")) return -1;
+    if (batch == 0) return 0;
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    Stage st(mem);
+    const char *a_d, *d_d, *x_in;
+    char *x_d;
+    st.in(g.in0, (const char *)cA, c.el * (size_t)((batch - 1) * a_ld + K), &a_d);
+    st.in(g.in0, (const char *)cD, c.el * (size_t)((batch - 1) * d_ld + K), &d_d);
+    dwt_stage_out(st, x, c.el, batch, x_ld, n, &x_in, &x_d);
+    if (st.commit()) return -1;
+    c.p.lv.off[1] = 0;
+    if (int rc = idwt_run(who, c, mode, 1, a_d, a_ld, d_d, d_ld, n, batch, x_d, x_ld)) return rc;
+    return st.finish();
+}
+
+int sp_modwt(const void *x, int dtype, int64_t x_ld, int64_t n, int64_t batch, const double *rec_lo, const double *rec_hi, int L, int levels, void *W,
+             int64_t w_ld, int form, int mem) {
+    const char *who = "sp_modwt";
+    DwtCall c;
+    if (dwt_enter(who, DWT_WHAT_MODWT, dtype, n, batch, rec_lo, rec_hi, L, 0, levels, form, &c)) return -1;
+    if (dwt_buffers(who, x, x_ld, n, "x", W, w_ld, n, "W")) return -1;
+    if (batch == 0) return 0;
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const int64_t plane = batch * w_ld;
+    Stage st(mem);
+    const char *x_d, *w_in;
+    char *w_d;
+    st.in(g.in0, (const char *)x, c.el * (size_t)((batch - 1) * x_ld + n), &x_d);
+    dwt_stage_out(st, W, c.el, (int64_t)(levels + 1) * batch, w_ld, n, &w_in, &w_d);
+    if (st.commit()) return -1;
+    if (c.p.form == DWT_FORM_ROW) {
+        int rc;
+        {
+            ProfScope ps;
+            rc = launch_modwt_row(lc(), dwt_row_args(c, n, batch, 0, levels), x_d, x_ld, w_d, w_ld, plane);
+        }
+        if (rc != 0) return fail("%s: the row form's launch was refused (n %lld, L %d, levels %d)", who, (long long)n, L, levels);
+        HIPCHK(hipGetLastError());
+        g.last_kernel = "k_modwt_row";
+        return st.finish();
+    }
+    char *S[2];
+    if (dwt_scratch(c, S)) return -1;
+    for (int64_t r0 = 0; r0 < batch; r0 += c.p.rpp, ++g_passes[9]) {
+        DwtTileArgs a{c.cplx, std::min<int64_t>(c.p.rpp, batch - r0), c.f, 0};
+        const char *src = x_d + c.el * (size_t)(r0 * x_ld);
+        int64_t sld = x_ld;
+        for (int j = 1; j <= levels; ++j) {
+            char *wj = w_d + c.el * (size_t)((j - 1) * plane + r0 * w_ld);
+            char *dst = j == levels ? w_d + c.el * (size_t)(levels * plane + r0 * w_ld) : S[j & 1];
+            const int64_t dld = j == levels ? w_ld : c.p.buf[j & 1];
+            int rc;
+            {
+                ProfScope ps;
+                rc = launch_modwt_tile(lc(), a, j, src, sld, n, wj, w_ld, dst, dld);
+            }
+            if (rc != 0) return fail("%s: the tile form's launch of level %d was refused", who, j);
+            HIPCHK(hipGetLastError());
+            src = dst, sld = dld;
+        }
+    }
+    g.last_kernel = "k_modwt_tile";
+    return st.finish();
+}
+
+int sp_imodwt(const void *W, int dtype, int64_t w_ld, int64_t n, int64_t batch, const double *rec_lo, const double *rec_hi, int L, int levels, void *x,
+              int64_t x_ld, int form, int mem) {
+    const char *who = "sp_imodwt";
+    DwtCall c;
+    if (dwt_enter(who, DWT_WHAT_IMODWT, dtype, n, batch, rec_lo, rec_hi, L, 0, levels, form, &c)) return -1;
+    if (dwt_buffers(who, W, w_ld, n, "W", x, x_ld, n, "x")) return -1;
+    if (batch == 0) return 0;
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const int64_t plane = batch * w_ld;
+    Stage st(mem);
+    const char *w_d, *x_in;
+    char *x_d;
+    st.in(g.in0, (const char *)W, c.el * (size_t)(((int64_t)(levels + 1) * batch - 1) * w_ld + n), &w_d);
+    dwt_stage_out(st, x, c.el, batch, x_ld, n, &x_in, &x_d);
+    if (st.commit()) return -1;
+    if (c.p.form == DWT_FORM_ROW) {
+        int rc;
+        {
+            ProfScope ps;
+            rc = launch_imodwt_row(lc(), dwt_row_args(c, n, batch, 0, levels), w_d, w_ld, plane, x_d, x_ld);
+        }
+        if (rc != 0) return fail("%s: the row form's launch was refused (n %lld, L %d, levels %d)", who, (long long)n, L, levels);
+        HIPCHK(hipGetLastError());
+        g.last_kernel = "k_imodwt_row";
+        return st.finish();
+    }
+    char *S[2];
+    if (dwt_scratch(c, S)) return -1;
+    for (int64_t r0 = 0; r0 < batch; r0 += c.p.rpp, ++g_passes[9]) {
+        DwtTileArgs a{c.cplx, std::min<int64_t>(c.p.rpp, batch - r0), c.f, 0};
+        const char *src = w_d + c.el * (size_t)(levels * plane + r0 * w_ld);
+        int64_t sld = w_ld;
+        for (int j = levels; j >= 1; --j) {
+            char *dst = j == 1 ? x_d + c.el * (size_t)(r0 * x_ld) : S[(j - 1) & 1];
+            const int64_t dld = j == 1 ? x_ld : c.p.buf[(j - 1) & 1];
+            int rc;
+            {
+                ProfScope ps;
+                rc = launch_imodwt_tile(lc(), a, j, w_d + c.el * (size_t)((j - 1) * plane + r0 * w_ld), w_ld, src, sld, n, dst, dld);
+            }
+            if (rc != 0) return fail("%s: the tile form's launch of level %d was refused", who, j);
+            HIPCHK(hipGetLastError());
+            src = dst, sld = dld;
+        }
+    }
+    g.last_kernel = "k_imodwt_tile";
     return st.finish();
 }
 

@@ -261,7 +261,8 @@ def last_passes(which=0):
     the passes of `lomb` and `lomb_sums` over their frequencies, which=4 (LOMB_LAUNCHES) the most launches the row groups of one such
     pass were dealt to, which=5 (FAM_PASSES) the passes of `fam` over its blocks, which=6 (NUFFT_PASSES) the passes of `nufft1`, `nufft2`
     and `lomb_sums_grid` over their rows; 0 where the call had no such loop (sp_last_passes).
-    which=7 (AR_PASSES): the passes of `burg` and `yule` over their segments; which=8 (SUB_PASSES): those of `covmat` and `ar_ls`."""
+    which=7 (AR_PASSES): the passes of `burg` and `yule` over their segments; which=8 (SUB_PASSES): those of `covmat` and `ar_ls`;
+    which=9 (DWT_PASSES): the passes of the tile form of `dwt`, `idwt`, `modwt`, `imodwt` and the single-level entries over their rows."""
     return int(lib().sp_last_passes(int(which)))
 
 
@@ -2407,6 +2408,254 @@ def sub_plan(what, n, m, rows=1, nframes=1, cplx=False):
     sub_check("sub_plan", what, n, 1, 0, nframes, m, rows)
     return _plan(lib().sp_sub_plan, ("chunk", "tiles", "shares", "lds_bytes", "workgroups", "passes", "seg_bytes", "segs_per_pass"), SubRefused,
                  "sub_plan", what, _ffi.DTYPE_C64 if cplx else _ffi.DTYPE_F32, n, m, rows, nframes)
+
+
+DWT_MAX_L, DWT_MAX_LEVELS, DWT_MODWT_MAX_LEVELS, DWT_PASSES, DWT_MAX_N = 64, 32, 30, 9, (1 << 31) - 1
+DWT_MODES = {"zero": 0, "constant": 1, "symmetric": 2, "reflect": 3, "periodic": 4, "periodization": 5}
+DWT_FORMS = {"auto": 0, "row": 1, "tile": 2}
+DWT_WHAT = {"dwt": 0, "idwt": 1, "modwt": 2, "imodwt": 3}
+
+
+class DwtRefused(ValueError, NotImplementedError):
+    """A filter bank, an extension mode, a depth or a layout the discrete wavelet transforms do not take: outside the limits, and what is
+    not built (the extrapolating modes 'smooth', 'antisymmetric' and 'antireflect', which are not index maps; filters beyond 64 taps)."""
+
+
+def dwt_coeff_len(n, L, mode="symmetric"):
+    """coefficients of one analysis level of n samples: floor((n + L - 1) / 2), ceil(n / 2) for 'periodization'"""
+    return (n + 1) // 2 if DWT_MODES.get(mode, mode) == 5 else (n + L - 1) // 2
+
+
+def dwt_max_levels(n, L, mode="symmetric"):
+    """the deepest level the library takes: the one at which a row has one coefficient, 32 at the most"""
+    j = 0
+    while j < DWT_MAX_LEVELS:
+        n, j = dwt_coeff_len(n, L, mode), j + 1
+        if n <= 1:
+            break
+    return j
+
+
+def _dwt_code(who, table, what, value):
+    if isinstance(value, str):
+        if value in ("smooth", "antisymmetric", "antireflect") and table is DWT_MODES:
+            raise DwtRefused("%s: mode %r extrapolates the row, which is not a map of the index: not built" % (who, value))
+        if value not in table:
+            raise DwtRefused("%s: %s must be one of %s, not %r" % (who, what, ", ".join(table), value))
+        return table[value]
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or int(value) not in table.values():
+        raise DwtRefused("%s: %s must be one of %s, not %r" % (who, what, ", ".join(table), value))
+    return int(value)
+
+
+def _dwt_filters(who, lo, hi):
+    """the two filters of a call as contiguous float64 arrays of one even length 2 .. 64, finite"""
+    lo, hi = np.ascontiguousarray(lo, dtype=np.float64), np.ascontiguousarray(hi, dtype=np.float64)
+    if lo.ndim != 1 or hi.ndim != 1 or lo.size != hi.size:
+        raise DwtRefused("%s: the two filters must be one-dimensional and of one length" % who)
+    L = int(lo.size)
+    if L < 2 or L > DWT_MAX_L or L % 2:
+        raise DwtRefused("%s: the filter length L = %d must be even and lie in 2 .. %d" % (who, L, DWT_MAX_L))
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi))):
+        raise DwtRefused("%s: the filters must be finite" % who)
+    return lo, hi, L
+
+
+def dwt_check(who, what, n, L, mode, levels, rows):
+    """The refusals of the C entries about the shape (dwt_plan.h's dwt_shape), before the library is touched."""
+    if n < 1 or n > DWT_MAX_N:
+        raise DwtRefused("%s: n = %d samples of a row are outside 1 .. 2^31 - 1" % (who, n))
+    if rows < 0 or rows > DWT_MAX_N:
+        raise DwtRefused("%s: %d rows are outside 0 .. 2^31 - 1" % (who, rows))
+    if what >= 2:
+        if levels < 1 or levels > DWT_MODWT_MAX_LEVELS or (1 << (levels - 1)) * (L - 1) >= 1 << 31:
+            raise DwtRefused("%s: levels = %d is outside 1 .. 30, or its dilated filter 2^(levels-1) (L - 1) reaches 2^31" % (who, levels))
+    elif levels < 1 or levels > dwt_max_levels(n, L, mode):
+        raise DwtRefused("%s: levels = %d is outside 1 .. %d, the level at which a row of %d samples has one coefficient"
+                         % (who, levels, dwt_max_levels(n, L, mode), n))
+
+
+def dwt_layout(n, L, mode, levels):
+    """-> (lens, entries, total): lens[j] the samples of the approximation of level j (lens[0] = n); entries the (length, offset) of
+    cA_J, cD_J, .., cD_1 in a row of the pyramid; total its elements"""
+    lens = [int(n)]
+    for _ in range(levels):
+        lens.append(dwt_coeff_len(lens[-1], L, mode))
+    entries, o = [], 0
+    for e in range(levels + 1):
+        ln = lens[levels if e == 0 else levels - e + 1]
+        entries.append((ln, o))
+        o += ln
+    return lens, entries, o
+
+
+def _dwt_rows(who, x):
+    """the rows of a call -> (md, rows as the mode takes them, their pitch, lead, rows, the last axis)"""
+    md = _enter(x)
+    x = md.checked(x)
+    if x.ndim < 1:
+        raise DwtRefused("%s: the array needs at least one axis" % who)
+    lead, rows = _lead_rows(x.shape)
+    n = int(x.shape[-1])
+    if n < 1:
+        raise DwtRefused("%s: the rows must hold at least one sample" % who)
+    if md.dev and x.ndim != 2:
+        x = x.reshape(rows, n)
+    xs, xld = md.rows(x)
+    return md, xs, xld, lead, rows, n
+
+
+def dwt(x, dec_lo, dec_hi, mode="symmetric", levels=1, form="auto"):
+    """The pyramid (sp_dwt) of every row x[..., n] under the analysis filters (dec_lo, dec_hi) -> out[..., total] =
+    [cA_J | cD_J | .. | cD_1] at the offsets of `dwt_layout`.  One level of n samples: cA[k] = sum_m dec_lo[m] xe[2k + 1 - m], k <
+    floor((n + L - 1) / 2), xe the row extended by `mode` ('zero', 'constant', 'symmetric', 'reflect', 'periodic'; 'periodization':
+    cA[k] = sum_m dec_lo[m] x[(2k + L / 2 - m) mod n'], k < n' / 2, an odd row repeating its last sample).  float32 FMAs with the taps
+    ascending; complex rows take the real taps on both parts.  form 'row' (every level in LDS, one launch), 'tile' (a launch per
+    level, any length) or 'auto' (the row form wherever it fits).  numpy in -> numpy out; device tensors in -> a device tensor on x's
+    stream; the two, and the two forms, agree bitwise."""
+    who = "dwt"
+    lo, hi, L = _dwt_filters(who, dec_lo, dec_hi)
+    mode, form, levels = _dwt_code(who, DWT_MODES, "mode", mode), _dwt_code(who, DWT_FORMS, "form", form), int(levels)
+    md, xs, xld, lead, rows, n = _dwt_rows(who, x)
+    dwt_check(who, 0, n, L, mode, levels, rows)
+    total = dwt_layout(n, L, mode, levels)[2]
+    out = md.empty(lead + (total,), "complex64" if md.code(xs) == _ffi.DTYPE_C64 else "float32", xs)
+    if rows:
+        md.call(lib().sp_dwt, md.addr(xs), md.code(xs), xld, n, rows, ptr(lo), ptr(hi), L, mode, levels, md.addr(out), total, form)
+    return out
+
+
+def dwt_level(x, dec_lo, dec_hi, mode="symmetric", form="auto", interleave=False):
+    """One analysis level (sp_dwt_level) of every row -> (cA, cD), each [..., K]; interleave=True -> one array [..., 2, K] holding cA
+    and cD side by side (the children 2p and 2p + 1 of a packet node; on the device the kernel writes it in place)."""
+    who = "dwt_level"
+    lo, hi, L = _dwt_filters(who, dec_lo, dec_hi)
+    mode, form = _dwt_code(who, DWT_MODES, "mode", mode), _dwt_code(who, DWT_FORMS, "form", form)
+    md, xs, xld, lead, rows, n = _dwt_rows(who, x)
+    dwt_check(who, 0, n, L, mode, 1, rows)
+    K = dwt_coeff_len(n, L, mode)
+    dt = "complex64" if md.code(xs) == _ffi.DTYPE_C64 else "float32"
+    if interleave and md.dev:
+        out = md.empty(lead + (2, K), dt, xs)
+        if rows:
+            md.call(lib().sp_dwt_level, md.addr(xs), md.code(xs), xld, n, rows, ptr(lo), ptr(hi), L, mode, ptr(out.data_ptr()), 2 * K,
+                    ptr(out.data_ptr() + K * out.element_size()), 2 * K, form)
+        return out
+    cA, cD = md.empty(lead + (K,), dt, xs), md.empty(lead + (K,), dt, xs)
+    if rows:
+        md.call(lib().sp_dwt_level, md.addr(xs), md.code(xs), xld, n, rows, ptr(lo), ptr(hi), L, mode, md.addr(cA), K, md.addr(cD), K, form)
+    return np.stack((cA, cD), axis=-2) if interleave else (cA, cD)
+
+
+def idwt(coef, n, rec_lo, rec_hi, mode="symmetric", levels=1, form="auto"):
+    """The inverse of `dwt` (sp_idwt): rows of n samples from pyramids coef[..., total] laid out as `dwt` writes them for the same
+    (n, L, mode, levels).  One level: x[i] = sum_q rec_lo[p + 2q] cA[k0 - q] + sum_q rec_hi[p + 2q] cD[k0 - q], t = i + L - 2, p = t mod 2,
+    k0 = floor(t / 2) ('periodization': t = i + L / 2 - 1, k0 - q mod K); an approximation one longer than the detail it meets drops
+    its last sample."""
+    who = "idwt"
+    lo, hi, L = _dwt_filters(who, rec_lo, rec_hi)
+    mode, form, levels, n = _dwt_code(who, DWT_MODES, "mode", mode), _dwt_code(who, DWT_FORMS, "form", form), int(levels), int(n)
+    md, cs, cld, lead, rows, total = _dwt_rows(who, coef)
+    dwt_check(who, 1, n, L, mode, levels, rows)
+    if total != dwt_layout(n, L, mode, levels)[2]:
+        raise DwtRefused("%s: a pyramid of %d levels of %d samples has %d coefficients, not %d" % (who, levels, n, dwt_layout(n, L, mode, levels)[2], total))
+    x = md.empty(lead + (n,), "complex64" if md.code(cs) == _ffi.DTYPE_C64 else "float32", cs)
+    if rows:
+        md.call(lib().sp_idwt, md.addr(cs), md.code(cs), cld, n, rows, ptr(lo), ptr(hi), L, mode, levels, md.addr(x), n, form)
+    return x
+
+
+def idwt_level(cA, cD, n, rec_lo, rec_hi, mode="symmetric", form="auto"):
+    """The inverse of `dwt_level` (sp_idwt_level): rows of n samples from cA[..., K] and cD[..., K], K the coefficients n samples have.
+    cD=None: cA is the interleaved [..., 2, K] of `dwt_level`."""
+    who = "idwt_level"
+    lo, hi, L = _dwt_filters(who, rec_lo, rec_hi)
+    mode, form, n = _dwt_code(who, DWT_MODES, "mode", mode), _dwt_code(who, DWT_FORMS, "form", form), int(n)
+    if cD is None:
+        if cA.ndim < 2 or cA.shape[-2] != 2:
+            raise DwtRefused("%s: the interleaved coefficients must be [..., 2, K]" % who)
+        if _is_torch(cA):
+            K = int(cA.shape[-1])
+            pair = cA.contiguous().reshape(-1, 2, K)
+            cA, cD, lead = pair[:, 0, :], pair[:, 1, :], tuple(map(int, cA.shape[:-2]))
+        else:
+            cA, cD, lead = cA[..., 0, :], cA[..., 1, :], None
+    else:
+        lead = None
+    md, As, ald, lead_a, rows, K = _dwt_rows(who, cA)
+    if _mode(cD) is not md:
+        raise TypeError("%s: cA and cD must both be numpy arrays or both device tensors" % who)
+    cD = md.checked(cD)
+    if tuple(cD.shape) != tuple(cA.shape) or not md.alike(As, cD):
+        raise DwtRefused("%s: cD must share cA's shape, %s" % (who, md.ALIKE))
+    if md.dev and cD.ndim != 2:
+        cD = cD.reshape(max(rows, 1), K)
+    Ds, dld = md.rows(cD)
+    lead = lead_a if lead is None else lead
+    dwt_check(who, 1, n, L, mode, 1, rows)
+    if K != dwt_coeff_len(n, L, mode):
+        raise DwtRefused("%s: %d samples have %d coefficients, not %d" % (who, n, dwt_coeff_len(n, L, mode), K))
+    x = md.empty(lead + (n,), "complex64" if md.code(As) == _ffi.DTYPE_C64 else "float32", As)
+    if rows:
+        md.call(lib().sp_idwt_level, md.addr(As), ald, md.addr(Ds), dld, md.code(As), n, rows, ptr(lo), ptr(hi), L, mode, md.addr(x), n, form)
+    return x
+
+
+def modwt(x, rec_lo, rec_hi, levels, form="auto"):
+    """The maximal-overlap transform (sp_modwt) of every row x[..., n], circular, any n: with g = rec_lo / sqrt 2, h = rec_hi / sqrt 2 and
+    V_0 = x, W_j[t] = sum_l h[l] V_{j-1}[(t - 2^(j-1) l) mod n] and V_j the same with g -> W[levels + 1, ..., n] = W_1 .. W_J, V_J."""
+    who = "modwt"
+    lo, hi, L = _dwt_filters(who, rec_lo, rec_hi)
+    form, levels = _dwt_code(who, DWT_FORMS, "form", form), int(levels)
+    md, xs, xld, lead, rows, n = _dwt_rows(who, x)
+    dwt_check(who, 2, n, L, 0, levels, rows)
+    W = md.empty((levels + 1,) + lead + (n,), "complex64" if md.code(xs) == _ffi.DTYPE_C64 else "float32", xs)
+    if rows:
+        md.call(lib().sp_modwt, md.addr(xs), md.code(xs), xld, n, rows, ptr(lo), ptr(hi), L, levels, md.addr(W), n, form)
+    return W
+
+
+def imodwt(W, rec_lo, rec_hi, form="auto"):
+    """The inverse of `modwt` (sp_imodwt): x[..., n] from W[levels + 1, ..., n]:
+    V_{j-1}[t] = sum_l h[l] W_j[(t + 2^(j-1) l) mod n] + sum_l g[l] V_j[(t + 2^(j-1) l) mod n]."""
+    who = "imodwt"
+    lo, hi, L = _dwt_filters(who, rec_lo, rec_hi)
+    form = _dwt_code(who, DWT_FORMS, "form", form)
+    md = _enter(W)
+    W = md.samples(md.checked(W))
+    if W.ndim < 2 or W.shape[0] < 2:
+        raise DwtRefused("%s: W must be [levels + 1, ..., n] with at least one level" % who)
+    levels, n = int(W.shape[0]) - 1, int(W.shape[-1])
+    lead, rows = _lead_rows(W.shape[1:])
+    if n < 1:
+        raise DwtRefused("%s: the rows must hold at least one sample" % who)
+    dwt_check(who, 3, n, L, 0, levels, rows)
+    x = md.empty(lead + (n,), "complex64" if md.code(W) == _ffi.DTYPE_C64 else "float32", W)
+    if rows:
+        md.call(lib().sp_imodwt, md.addr(W), md.code(W), n, n, rows, ptr(lo), ptr(hi), L, levels, md.addr(x), n, form)
+    return x
+
+
+DWT_PLAN_NAMES = ("form", "tile", "lds_bytes", "workgroups", "launches", "passes", "scratch_bytes", "rows_per_pass", "max_levels", "rows_per_workgroup")
+
+
+def dwt_plan(what, n, L, mode="symmetric", levels=1, rows=1, cplx=False, form="auto"):
+    """sp_dwt_plan as a dict (host only): what 'dwt', 'idwt', 'modwt' or 'imodwt' -> form (1 row, 2 tile), tile (outputs of a tile),
+    lds_bytes, workgroups, launches, passes, scratch_bytes, rows_per_pass, max_levels, rows_per_workgroup, and `entries`: the
+    (length, offset) of every entry of the output in its order."""
+    who = "dwt_plan"
+    what = _dwt_code(who, DWT_WHAT, "what", what)
+    mode = 0 if what >= 2 else _dwt_code(who, DWT_MODES, "mode", mode)
+    form, n, L, levels, rows = _dwt_code(who, DWT_FORMS, "form", form), int(n), int(L), int(levels), int(rows)
+    if L < 2 or L > DWT_MAX_L or L % 2:
+        raise DwtRefused("%s: the filter length L = %d must be even and lie in 2 .. %d" % (who, L, DWT_MAX_L))
+    dwt_check(who, what, n, L, mode, levels, rows)
+    out = np.zeros(80, dtype=np.int64)
+    if lib().sp_dwt_plan(what, _ffi.DTYPE_C64 if cplx else _ffi.DTYPE_F32, n, L, mode, levels, rows, form, ptr(out)) != 0:
+        raise DwtRefused("%s: the shape is refused (a forced row form that does not fit)" % who)
+    d = dict(zip(DWT_PLAN_NAMES, (int(v) for v in out[:10])))
+    d["entries"] = [(int(out[10 + 2 * e]), int(out[11 + 2 * e])) for e in range(levels + 1)]
+    return d
 
 
 EIGH_MAX_N = 64
