@@ -73,6 +73,9 @@ from .subspace import (corrmtx_cov, pmusic, peig, subspace_spectrogram, subspace
 from . import dwt as _dwt_mod                                  # noqa: F401
 from .dwt import (wavelet_filters, dwt_max_level, dwt_coeff_len, dwt, idwt, wavedec, waverec, modwt, imodwt, modwt_mra,   # noqa: F401
                   modwt_variance, wpdec, wprec, dwt_plan, DwtRefused)
+from . import beamform as _beamform_mod                        # noqa: F401
+from .beamform import (array_spectrum, mode_spectrum, beam_scan, slowness_scan, array_pattern, beam_peaks, beam_plan,   # noqa: F401
+                       BeamRefused)
 from . import wbicoherence as _wbic_mod                        # noqa: F401
 from .wbicoherence import (wbic_freqs, wavelet_bispectrum, wavelet_bicoherence, summed_bicoherence,   # noqa: F401
                            total_bicoherence, wbic_plan)

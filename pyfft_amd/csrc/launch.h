@@ -7,6 +7,7 @@
 #include "ar_plan.h"
 #include "sub_plan.h"
 #include "dwt_plan.h"
+#include "beam_plan.h"
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -48,6 +49,8 @@ namespace sp {
 //                  the same cap holds for sp_covmat / sp_ar_ls, whose passes sp_last_passes(8) reports
 //   SP_DWT_ROWS (int: a cap on the rows per pass of the tile form of sp_dwt / sp_idwt / sp_modwt / sp_imodwt; unset or <= 0: the budget alone;
 //                  sp_last_passes(9) reports the passes)
+//   SP_BEAM_GRID (int: a cap on the workgroups of sp_beamscan, so that a small call walks the loop over its (model, tile) items past the
+//                  first; unset or <= 0: the plan's own grid)
 //   SP_BURG_FORM (int: 1 the wave form of k_burg wherever a segment fits it, 2 the workgroup form at every length; unset or 0: by length)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
@@ -1223,6 +1226,12 @@ int launch_ls_chol(LaunchCtx c, const void *C, int64_t C_ld, int m, int64_t nmod
 // P[model P_ld + q] = 1 / sum_{k >= p} g_k |sum_i V[model m V_ld + i V_ld + k] e(-i (start + q step))|^2; status[model]: a weight was not positive
 int launch_pseudo(LaunchCtx c, const void *V, int64_t V_ld, const double *w, int m, int p, int64_t nmodels, bool ev, int64_t nbins, double start, double step,
                   bool out64, void *P, int64_t P_ld, int *status);
+
+// The array scan (k_beam.hip; include/spectral_array.h; the host's arithmetic in beam_plan.h): P[model P_ld + q] from V, w as k_eigh writes
+// them and the device copies of the host tables pos[m][ndim], kv[nk][ndim], scale[nmodels] (or nullptr); `grid` workgroups walk the
+// nmodels x ceil(nk / BEAM_TQ) items.  status[model]: a weight that was needed had a denominator that was not positive.
+int launch_beam(LaunchCtx c, const void *V, int64_t V_ld, const double *w, int m, int64_t nmodels, const double *pos, int ndim, const double *kv, int64_t nk,
+                const double *scale, int method, int p, double loading, bool out64, void *P, int64_t P_ld, int *status, int64_t grid);
 
 // The discrete wavelet transforms (k_dwt.hip; include/spectral_dwt.h; the host's arithmetic in dwt_plan.h).  Row form: a workgroup runs
 // every level of rpw rows in LDS (lds = dwt_row_lds, cap = dwt_row_cap, lv the levels' lengths and the details' offsets in a row of outD /

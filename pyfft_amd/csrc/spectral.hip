@@ -12,6 +12,7 @@
 #include "../../include/spectral_ar.h"
 #include "../../include/spectral_sub.h"
 #include "../../include/spectral_dwt.h"
+#include "../../include/spectral_array.h"
 #include "launch.h"
 #include "stage.h"
 #include "table_cache.h"
@@ -4956,6 +4957,71 @@ int sp_pseudospectrum(const void *V, int64_t V_ld, const double *w, int m, int p
     if (rc != 0) return fail("%s: the launch was refused (%lld models, %lld bins)", who, (long long)nmodels, (long long)nbins);
     HIPCHK(hipGetLastError());
     g.last_kernel = "k_pseudo";
+    return st.finish();
+}
+
+// ---- the array scan: Bartlett, Capon, MUSIC and eigenvector spectra over steering vectors (k_beam.hip; include/spectral_array.h; beam_plan.h) ----
+int sp_beamscan_plan(int m, int ndim, int64_t nk, int64_t nmodels, int method, int p, int64_t out[8]) {
+    if (!out || beam_shape(m, ndim, nk, nmodels, method, p)) return -1;
+    const BeamPlan b = beam_plan_of(m, nk, nmodels, method, p, env_int("SP_BEAM_GRID", 0));
+    out[0] = b.tq;
+    out[1] = b.tiles;
+    out[2] = b.ks;
+    out[3] = b.lds_bytes;
+    out[4] = b.grid;
+    out[5] = b.per_wg;
+    out[6] = b.stages;
+    out[7] = 0;
+    return 0;
+}
+
+int sp_beamscan(const void *V, int64_t V_ld, const double *w, int m, int64_t nmodels, const double *pos, int ndim, const double *kv, int64_t nk,
+                const double *scale, int method, int p, double loading, int out64, void *P, int64_t P_ld, int32_t *status, int mem) {
+    const char *who = "sp_beamscan";
+    if (const char *why = beam_shape(m, ndim, nk, nmodels, method, p))
+        return fail("%s: %s (m %d, ndim %d, nk %lld, nmodels %lld, method %d, p %d)", who, why, m, ndim, (long long)nk, (long long)nmodels, method, p);
+    if (V_ld < m) return fail("%s: V_ld = %lld is below m = %d", who, (long long)V_ld, m);
+    if (P_ld < nk) return fail("%s: P_ld = %lld is below nk = %lld", who, (long long)P_ld, (long long)nk);
+    if (!(loading >= 0.0) || !std::isfinite(loading)) return fail("%s: loading must be finite and not negative", who);
+    if (!V) return fail("%s: V is required", who);
+    if (!w) return fail("%s: w is required", who);
+    if (!pos) return fail("%s: pos is required", who);
+    if (!kv) return fail("%s: kv is required", who);
+    if (!P) return fail("%s: P is required", who);
+    if (!status) return fail("%s: status is required", who);
+    if (!beam_finite(pos, (int64_t)m * ndim)) return fail("%s: pos must be finite", who);
+    if (!beam_finite(kv, nk * ndim)) return fail("%s: kv must be finite", who);
+    if (scale && !beam_finite(scale, nmodels)) return fail("%s: scale must be finite", who);
+    if (nmodels == 0) return 0;
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const BeamPlan b = beam_plan_of(m, nk, nmodels, method, p, env_int("SP_BEAM_GRID", 0));
+    void *pos_d = nullptr, *kv_d = nullptr, *sc_d = nullptr;
+    if (get_table(29, pos, sizeof(double) * (size_t)m * ndim, &pos_d, nullptr)) return -1;
+    if (get_table(30, kv, sizeof(double) * (size_t)nk * ndim, &kv_d, nullptr)) return -1;
+    if (scale && get_table(31, scale, sizeof(double) * (size_t)nmodels, &sc_d, nullptr)) return -1;
+    const size_t pel = out64 ? 8 : 4;
+    Stage st(mem);
+    const char *V_d, *P_in;
+    const double *w_d;
+    char *P_d;
+    int32_t *s_d;
+    st.in(g.in0, (const char *)V, 16 * (size_t)((nmodels * m - 1) * V_ld + m), &V_d);
+    st.in(g.in0, w, 8 * (size_t)(nmodels * m), &w_d);
+    const size_t P_bytes = pel * (size_t)((nmodels - 1) * P_ld + nk);
+    if (P_ld > nk) st.inout(g.out0, (const char *)P, (char *)P, P_bytes, &P_in, &P_d);
+    else st.out(g.out0, (char *)P, P_bytes, &P_d);
+    st.out(g.out0, status, 4 * (size_t)nmodels, &s_d);
+    if (st.commit()) return -1;
+    int rc;
+    {
+        ProfScope ps;
+        rc = launch_beam(lc(), V_d, V_ld, w_d, m, nmodels, (const double *)pos_d, ndim, (const double *)kv_d, nk, (const double *)sc_d, method, p, loading,
+                         out64 != 0, P_d, P_ld, s_d, b.grid);
+    }
+    if (rc != 0) return fail("%s: the launch was refused (%lld models, %lld scan points, %lld bytes of LDS)", who, (long long)nmodels, (long long)nk, (long long)b.lds_bytes);
+    HIPCHK(hipGetLastError());
+    g.last_kernel = "k_beam";
     return st.finish();
 }
 

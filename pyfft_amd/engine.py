@@ -2410,6 +2410,111 @@ def sub_plan(what, n, m, rows=1, nframes=1, cplx=False):
                  "sub_plan", what, _ffi.DTYPE_C64 if cplx else _ffi.DTYPE_F32, n, m, rows, nframes)
 
 
+BEAM_MAX_M, BEAM_TQ = 64, 64
+BEAM_METHODS = {"bartlett": 0, "capon": 1, "music": 2, "ev": 3}
+BEAM_PLAN_NAMES = ("tq", "tiles", "stage_vectors", "lds_bytes", "workgroups", "items_per_workgroup", "stages", "spare")
+
+
+class BeamRefused(ValueError, NotImplementedError):
+    """An array, a scan grid, a method or an eigendecomposition the array scan does not take: outside the limits, tables that are not
+    finite, and what is not built (more than 64 sensors)."""
+
+
+def _beam_table(who, name, t, cols=None):
+    """a host table as contiguous float64 [rows, ndim]; a device tensor is read back (the tables are host arrays, as windows are)"""
+    if _is_torch(t):
+        t = t.detach().cpu().numpy()
+    t = np.ascontiguousarray(np.asarray(t), dtype=np.float64)
+    if t.ndim == 1:
+        t = t.reshape(-1, 1)
+    if t.ndim != 2 or t.shape[1] < 1 or t.shape[1] > 3 or (cols is not None and t.shape[1] != cols):
+        raise BeamRefused("%s: %s must be [n] or [n, ndim] with ndim 1 .. 3, the same for pos and kv" % (who, name))
+    if not np.all(np.isfinite(t)):
+        raise BeamRefused("%s: %s must be finite" % (who, name))
+    return t
+
+
+def beam_check(who, m, ndim, nk, models, method, p, loading=0.0):
+    """The refusals of sp_beamscan and sp_beamscan_plan about the shape, before the library is touched -> the method's code."""
+    if method not in BEAM_METHODS:
+        raise BeamRefused("%s: method must be 'bartlett', 'capon', 'music' or 'ev', not %r" % (who, method))
+    code = BEAM_METHODS[method]
+    if m < 2 or m > BEAM_MAX_M:
+        raise BeamRefused("%s: m = %d sensors are outside 2 .. %d" % (who, m, BEAM_MAX_M))
+    if ndim < 1 or ndim > 3:
+        raise BeamRefused("%s: ndim = %d is outside 1 .. 3" % (who, ndim))
+    if nk < 1 or nk > (1 << 31) - 1:
+        raise BeamRefused("%s: nk = %d is outside 1 .. 2^31 - 1" % (who, nk))
+    if code >= 2 and (p < 0 or p > m - 1):
+        raise BeamRefused("%s: p = %d is outside 0 .. m - 1 = %d" % (who, p, m - 1))
+    if models < 0 or models * -(-nk // BEAM_TQ) > 1 << 40:
+        raise BeamRefused("%s: %d models of %d scan points are more than 2^40 tiles" % (who, models, nk))
+    if not (math.isfinite(loading) and loading >= 0.0):
+        raise BeamRefused("%s: loading must be finite and not negative" % who)
+    return code
+
+
+def beamscan(V, w, pos, kv, method="bartlett", p=0, loading=0.0, scale=None, out64=False):
+    """The scan of a sensor array over steering vectors (sp_beamscan) from the eigendecompositions V[..., m, m] complex128, w[..., m]
+    float64 descending, as `eigh` returns them for the array's cross-spectral-density matrices.  pos[m] or [m, ndim] are the sensor
+    positions, kv[nk] or [nk, ndim] the scan vectors in TURNS per unit of pos, scale[...] (one number per model, or None = 1) multiplies
+    the phase: a_q[i] = exp(2 pi i scale pos[i] . kv[q]), which is `pseudospectrum`'s steering vector for pos = 0, 1, ..  With
+    D = sum_k g_k |a_q^H v_k|^2:
+      'bartlett'  g_k = w_k,                 P = D / m^2      (a^H G a / m^2)
+      'capon'     g_k = 1 / (w_k + delta),   P = 1 / D        (1 / a^H (G + delta I)^-1 a), delta = loading max(trace, 0) / m
+      'music'     g_k = 1, k >= p,           P = 1 / D
+      'ev'        g_k = 1 / w_k, k >= p,     P = 1 / D
+    -> (P float32 [..., nk], or float64 with out64; status int32 [...]: 1 where a weight that was needed had a denominator <= 0 and
+    was left out).  pos, kv and scale are host tables (a device tensor is read back).  numpy in -> numpy out; device tensors in ->
+    device tensors on torch's current stream; the two agree bitwise."""
+    who = "beamscan"
+    p, loading = int(p), float(loading)
+    md = _enter(V)
+    if _mode(w) is not md:
+        raise TypeError("%s: V and w must both be numpy arrays or both device tensors" % who)
+    if md.dev:
+        if V.dtype != torch.complex128 or w.dtype != torch.float64:
+            raise BeamRefused("%s: on the device V is a complex128 tensor and w float64" % who)
+        V, w = V.contiguous(), w.contiguous()
+    else:
+        V = np.ascontiguousarray(np.asarray(V), dtype=np.complex128)
+        w = np.ascontiguousarray(np.asarray(w), dtype=np.float64)
+    shape = tuple(V.shape)
+    if len(shape) < 2 or shape[-1] != shape[-2] or tuple(w.shape) != shape[:-1]:
+        raise BeamRefused("%s: V must be [..., m, m] and w [..., m]" % who)
+    m = int(shape[-1])
+    pos = _beam_table(who, "pos", pos)
+    kv = _beam_table(who, "kv", kv, pos.shape[1])
+    ndim, nk = int(pos.shape[1]), int(kv.shape[0])
+    lead, models = _lead_rows(shape, 2)
+    code = beam_check(who, m, ndim, nk, models, method, p, loading)
+    if pos.shape[0] != m:
+        raise BeamRefused("%s: pos holds %d sensors, V has order %d" % (who, pos.shape[0], m))
+    if scale is not None:
+        if _is_torch(scale):
+            scale = scale.detach().cpu().numpy()
+        scale = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64), lead)).reshape(-1)
+        if not np.all(np.isfinite(scale)):
+            raise BeamRefused("%s: scale must be finite" % who)
+    if not md.dev and not (np.all(np.isfinite(V)) and np.all(np.isfinite(w))):
+        raise BeamRefused("%s: V and w must be finite" % who)
+    P = md.empty(lead + (nk,), "float64" if out64 else "float32", V)
+    st = md.empty(lead, "int32", V)
+    if models:
+        md.call(lib().sp_beamscan, md.addr(V), m, md.addr(w), m, models, ptr(pos), ndim, ptr(kv), nk, ptr(scale), code, p, loading, 1 if out64 else 0,
+                md.addr(P), nk, md.addr(st))
+    return P, st
+
+
+def beam_plan(m, nk, models=1, method="bartlett", p=0, ndim=1):
+    """sp_beamscan_plan as a dict (host only): tq (steering vectors of a tile), tiles (of a model), stage_vectors (eigenvectors staged in
+    LDS at a time), lds_bytes (of a workgroup), workgroups (launched), items_per_workgroup (the most (model, tile) items one walks),
+    stages (of a tile), spare."""
+    m, nk, models, p, ndim = int(m), int(nk), int(models), int(p), int(ndim)
+    code = beam_check("beam_plan", m, ndim, nk, models, method, p)
+    return _plan(lib().sp_beamscan_plan, BEAM_PLAN_NAMES, BeamRefused, "beam_plan", m, ndim, nk, models, code, p)
+
+
 DWT_MAX_L, DWT_MAX_LEVELS, DWT_MODWT_MAX_LEVELS, DWT_PASSES, DWT_MAX_N = 64, 32, 30, 9, (1 << 31) - 1
 DWT_MODES = {"zero": 0, "constant": 1, "symmetric": 2, "reflect": 3, "periodic": 4, "periodization": 5}
 DWT_FORMS = {"auto": 0, "row": 1, "tile": 2}
