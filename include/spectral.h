@@ -16,6 +16,8 @@
  *  - complex = interleaved float re,im (numpy complex64).  Reduced spectra (Welch
  *    accumulators) are returned in double.
  *  - return value: 0 = ok, <0 = error; sp_last_error() gives the message (thread-local).
+ *  - a call's results depend on its arguments alone, never on what the library ran before it (other shapes, NaN or huge
+ *    samples, other streams), and a refused call leaves no trace.
  *  - one global context per process / one device per process (multi-GPU = one process per
  *    GPU, torch.distributed/RCCL reduces the accumulators; see pyfft_amd/dist.py).
  *  - Transform convention (dft.py:108-133, :242-290): forward unnormalised e^{-j2pi nk/N},

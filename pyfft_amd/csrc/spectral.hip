@@ -97,6 +97,7 @@ struct Ctx {
     std::map<int64_t, BlueTab> blue;    // n -> Bluestein tables
     Scratch in0, in1, out0, work, small, trends, onepass, ticket, epi;
     Scratch pend_trend;                       // trend record a pending sp_welch_accum keeps until sp_welch_finish
+    Scratch pend_x;                           // ... and the staged record of a host-memory sp_welch_accum: sp_welch_finish reads its edge blocks
     Scratch bigA, bigB, bigT, blueA, blueB, longrec;   // long (multi-kernel) paths
     Scratch sosY, sosZ;                            // cascaded sections: sosfiltfilt's forward output, staged zi / zf
     Scratch bsIn, bsS, bsP, bsA;                    // bispectrum: staged inputs, spectra, fp32 partials, float64 sums
@@ -1393,6 +1394,7 @@ void sp_shutdown(void) {
     g.ticket.release();
     g.epi.release();
     g.pend_trend.release();
+    g.pend_x.release();
     g.cmS.release();
     g.cmT.release();
     g.cmG.release();
@@ -1627,7 +1629,9 @@ int sp_welch_accum(const void *x, int x_dtype, int64_t nsig, const float *win, i
     const size_t esz = cplx ? 8 : 4;
     Stage st(mem);
     const void *xd;
-    st.in(g.in0, x, esz * (size_t)nsig, &xd);
+    // staged in a scratch of its own, not in g.in0: the pending state keeps xd (k_op_finish reads the record's edge blocks), and every
+    // host-memory call between sp_welch_accum and sp_welch_finish stages into g.in0 (and may grow it, which frees it)
+    st.in(g.pend_x, x, esz * (size_t)nsig, &xd);
     if (st.commit()) return -1;
     if (welch_accum_locked(xd, cplx, nsig, win, nfft, hop, nframes, nmean, true)) return -1;
     if (!sum_out) return 0;
