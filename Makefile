@@ -8,7 +8,7 @@ FLAGS   := -O3 -std=c++17 -fPIC -fno-slp-vectorize --offload-arch=$(ARCH) -Iincl
 
 SRCS    := $(wildcard $(CSRC)/*.hip)
 OBJS    := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
-HDRS    := $(wildcard $(CSRC)/*.h) include/spectral.h include/spectral_ext.h include/spectral_tfr.h include/spectral_quad.h include/spectral_cyclo.h include/spectral_uneven.h include/spectral_wbic.h include/spectral_fam.h include/spectral_nufft.h include/spectral_nufft2.h include/spectral_ar.h include/spectral_sub.h include/spectral_dwt.h include/spectral_array.h
+HDRS    := $(wildcard $(CSRC)/*.h) include/spectral.h include/spectral_ext.h include/spectral_tfr.h include/spectral_quad.h include/spectral_cyclo.h include/spectral_uneven.h include/spectral_wbic.h include/spectral_fam.h include/spectral_nufft.h include/spectral_nufft2.h include/spectral_ar.h include/spectral_sub.h include/spectral_dwt.h include/spectral_array.h include/spectral_mimo.h
 
 all: $(LIBDIR)/libspectral.so
 

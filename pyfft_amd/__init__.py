@@ -76,6 +76,9 @@ from .dwt import (wavelet_filters, dwt_max_level, dwt_coeff_len, dwt, idwt, wave
 from . import beamform as _beamform_mod                        # noqa: F401
 from .beamform import (array_spectrum, mode_spectrum, beam_scan, slowness_scan, array_pattern, beam_peaks, beam_plan,   # noqa: F401
                        BeamRefused)
+from . import mimo as _mimo_mod                                # noqa: F401
+from .mimo import (cond, cond_plan, mimo_frf, multiple_coherence, partial_coherence, conditioned_spectra, ordered_spectra,   # noqa: F401
+                   multiple_coherence_level, CondRefused, CondResult)
 from . import wbicoherence as _wbic_mod                        # noqa: F401
 from .wbicoherence import (wbic_freqs, wavelet_bispectrum, wavelet_bicoherence, summed_bicoherence,   # noqa: F401
                            total_bicoherence, wbic_plan)

@@ -190,6 +190,13 @@ ARRAY_SIGNATURES = {
     "sp_beamscan_plan": (_i, [_i, _i, _i64, _i64, _i, _i, _vp]),
 }
 
+# the fifteenth table: must list every symbol include/spectral_mimo.h declares, and none of the other fourteen
+_u = C.c_uint                          # the bit mask of wanted outputs
+MIMO_SIGNATURES = {
+    "sp_cond": (_i, [_vp, _i64, _i, _i64, _vp, _i, _u, _d, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i]),
+    "sp_cond_plan": (_i, [_i, _i, _i64, _u, _vp]),
+}
+
 # the six tables the engine trace counts, in the order of their headers
 TABLES = (SIGNATURES, EXT_SIGNATURES, TFR_SIGNATURES, QUAD_SIGNATURES, CYCLO_SIGNATURES, UNEVEN_SIGNATURES)
 # the tables added since: bound like the six, outside the trace
@@ -198,6 +205,8 @@ MORE_TABLES = (WBIC_SIGNATURES, FAM_SIGNATURES, NUFFT_SIGNATURES, NUFFT2_SIGNATU
 LATER_TABLES = (DWT_SIGNATURES,)
 # ... and the array scan, in a tuple of its own: the three above stay as they are
 ARRAY_TABLES = (ARRAY_SIGNATURES,)
+# ... and conditioned spectral analysis, alike
+MIMO_TABLES = (MIMO_SIGNATURES,)
 
 
 class SpectralError(RuntimeError):
@@ -213,7 +222,7 @@ def load_library():
         raise SpectralError("libspectral.so not found at %s -- run `make` (or __graft_entry__.build()); "
                             "pyfft_amd has no CPU fallback" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for table in TABLES + MORE_TABLES + LATER_TABLES + ARRAY_TABLES:
+    for table in TABLES + MORE_TABLES + LATER_TABLES + ARRAY_TABLES + MIMO_TABLES:
         for name, (res, args) in table.items():
             fn = getattr(lib, name)      # AttributeError if the .so lacks a declared symbol
             fn.restype = res

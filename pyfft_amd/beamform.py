@@ -24,7 +24,7 @@ import numpy as np
 
 from . import engine as E
 from .engine import BeamRefused, _is_torch                         # noqa: F401
-from .windows import get_window
+from .spod import csd_segments, one_sided_csd
 
 METHODS = ("bartlett", "capon", "music", "ev")
 TWO_PI = 2.0 * math.pi
@@ -105,39 +105,11 @@ def array_spectrum(x, positions, k, fs=1.0, method="capon", nsources=None, loadi
         raise BeamRefused("%s: x must be [nch, nsig]" % who)
     nch, nsig = int(x.shape[0]), int(x.shape[1])
     pos, kv, p = _judge(who, nch, positions, k, method, nsources, loading)
-    nperseg, fs = int(nperseg), float(fs)
-    if not (fs > 0 and math.isfinite(fs)):
-        raise BeamRefused("%s: fs must be positive" % who)
-    noverlap = nperseg // 2 if noverlap is None else int(noverlap)
-    if nperseg < 2 or not 0 <= noverlap < nperseg or nsig < nperseg:
-        raise BeamRefused("%s: need 2 <= nperseg <= nsig and 0 <= noverlap < nperseg" % who)
-    if isinstance(window, (str, tuple)):
-        win = np.asarray(get_window(window, nperseg), dtype=np.float64)
-    else:
-        win = np.asarray(window, dtype=np.float64)
-    if win.shape != (nperseg,) or not np.all(np.isfinite(win)) or not np.sum(win * win) > 0:
-        raise BeamRefused("%s: window must be a name or nperseg = %d finite values with some weight" % (who, nperseg))
-    freq = np.fft.rfftfreq(nperseg, 1.0 / fs)
-    nb = nperseg // 2 + 1
-    b0, b1 = 0, nb
-    if band is not None:
-        f1, f2 = float(band[0]), float(band[1])
-        inside = np.nonzero((freq >= f1) & (freq <= f2))[0] if math.isfinite(f1) and math.isfinite(f2) else ()
-        if len(inside) == 0:
-            raise BeamRefused("%s: band = (f1, f2) holds no bin" % who)
-        b0, b1 = int(inside[0]), int(inside[-1]) + 1
-    hop = nperseg - noverlap
-    nframes = 1 + (nsig - nperseg) // hop
-    G = E.csd_matrix(x, win, hop, nframes, detrend=bool(detrend), scale=1.0 / (fs * float(np.sum(win * win))))
-    bins = np.arange(nb)
-    dbl = np.where((bins >= 1) & (bins <= (nperseg - 1) // 2), 2.0, 1.0)[b0:b1]
-    if _is_torch(G):
-        import torch
-        dbl = torch.as_tensor(dbl, dtype=torch.float64, device=G.device)
-    G = G[b0:b1] * dbl[:, None, None]
+    win, hop, nframes, freq, b0, b1 = csd_segments(who, BeamRefused, nsig, fs, window, nperseg, noverlap, band)
+    G = one_sided_csd(x, win, hop, nframes, float(fs), detrend, b0, b1)
     w, V, _ = E.eigh(G)
     P, _ = E.beamscan(V, w, pos, kv, method, p, loading, None, out64)
-    return freq[b0:b1], P
+    return freq, P
 
 
 def mode_spectrum(x, angles, modes, fs=1.0, method="capon", nsources=None, loading=0.0, window="hann", nperseg=256, noverlap=None, detrend=True,

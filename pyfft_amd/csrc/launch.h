@@ -8,6 +8,7 @@
 #include "sub_plan.h"
 #include "dwt_plan.h"
 #include "beam_plan.h"
+#include "cond_plan.h"
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -51,6 +52,8 @@ namespace sp {
 //                  sp_last_passes(9) reports the passes)
 //   SP_BEAM_GRID (int: a cap on the workgroups of sp_beamscan, so that a small call walks the loop over its (model, tile) items past the
 //                  first; unset or <= 0: the plan's own grid)
+//   SP_COND_GRID (int: a cap on the workgroups of sp_cond, so that a small call walks the loop over its matrices past the first; unset or
+//                  <= 0: the plan's own grid)
 //   SP_BURG_FORM (int: 1 the wave form of k_burg wherever a segment fits it, 2 the workgroup form at every length; unset or 0: by length)
 inline bool env_flag(const char *name) {
     const char *v = getenv(name);
@@ -1232,6 +1235,26 @@ int launch_pseudo(LaunchCtx c, const void *V, int64_t V_ld, const double *w, int
 // nmodels x ceil(nk / BEAM_TQ) items.  status[model]: a weight that was needed had a denominator that was not positive.
 int launch_beam(LaunchCtx c, const void *V, int64_t V_ld, const double *w, int m, int64_t nmodels, const double *pos, int ndim, const double *kv, int64_t nk,
                 const double *scale, int method, int p, double loading, bool out64, void *P, int64_t P_ld, int *status, int64_t grid);
+
+// Conditioned spectral analysis (k_cond.hip; include/spectral_mimo.h; the host's arithmetic in cond_plan.h): one Cholesky factor of
+// A = G[order][:, order] + delta I per matrix, and what `want` names of H [r][q], Gc [r][r], mcoh [r], piv [n], P [n][n] (r = n - q) at
+// their pitches per matrix; pointers of outputs that are not wanted are never touched.  The permutation travels by value.
+struct CondOrder {
+    unsigned char p[COND_MAX_N];
+};
+struct CondArgs {
+    const double2 *G;
+    int64_t G_ld, count;
+    int n, q;
+    unsigned want;
+    double loading;
+    double2 *H, *Gc, *P;
+    double *mcoh, *piv;
+    int64_t H_ld, Gc_ld, mcoh_ld, piv_ld, P_ld;
+    int *status;
+    CondOrder order;
+};
+int launch_cond(LaunchCtx c, const CondArgs &a, const CondPlan &pl);
 
 // The discrete wavelet transforms (k_dwt.hip; include/spectral_dwt.h; the host's arithmetic in dwt_plan.h).  Row form: a workgroup runs
 // every level of rpw rows in LDS (lds = dwt_row_lds, cap = dwt_row_cap, lv the levels' lengths and the details' offsets in a row of outD /

@@ -13,6 +13,7 @@
 #include "../../include/spectral_sub.h"
 #include "../../include/spectral_dwt.h"
 #include "../../include/spectral_array.h"
+#include "../../include/spectral_mimo.h"
 #include "launch.h"
 #include "stage.h"
 #include "table_cache.h"
@@ -5026,6 +5027,89 @@ int sp_beamscan(const void *V, int64_t V_ld, const double *w, int m, int64_t nmo
     if (rc != 0) return fail("%s: the launch was refused (%lld models, %lld scan points, %lld bytes of LDS)", who, (long long)nmodels, (long long)nk, (long long)b.lds_bytes);
     HIPCHK(hipGetLastError());
     g.last_kernel = "k_beam";
+    return st.finish();
+}
+
+// ---- conditioned spectral analysis: MIMO responses, multiple and partial coherence (k_cond.hip; include/spectral_mimo.h; cond_plan.h) ----
+int sp_cond_plan(int n, int q, int64_t count, unsigned want, int64_t out[8]) {
+    if (!out || cond_shape(n, q, count, want)) return -1;
+    const CondPlan p = cond_plan_of(n, count, want, env_int("SP_COND_GRID", 0));
+    const bool wantP = (want & COND_WANT_P) != 0;
+    out[0] = p.pitch;
+    out[1] = p.wg;
+    out[2] = p.lds_bytes;
+    out[3] = p.raised;
+    out[4] = p.grid;
+    out[5] = p.per_wg;
+    out[6] = wantP ? cond_off_w(n) : 0;
+    out[7] = cond_off_diag(n, wantP);
+    return 0;
+}
+
+int sp_cond(const void *G, int64_t G_ld, int n, int64_t count, const int32_t *order, int q, unsigned want, double loading, void *H, int64_t H_ld,
+            void *Gc, int64_t Gc_ld, double *mcoh, int64_t mcoh_ld, double *piv, int64_t piv_ld, void *P, int64_t P_ld, int32_t *status, int mem) {
+    const char *who = "sp_cond";
+    if (const char *why = cond_shape(n, q, count, want))
+        return fail("%s: %s (n %d, q %d, count %lld, want %u)", who, why, n, q, (long long)count, want);
+    const int64_t r = n - q, nn = (int64_t)n * n;
+    const bool wH = (want & COND_WANT_H) && r * q > 0, wG = (want & COND_WANT_GC) && r > 0, wM = (want & COND_WANT_MCOH) && r > 0;
+    const bool wV = (want & COND_WANT_PIV) != 0, wP = (want & COND_WANT_P) != 0;
+    if (G_ld < nn) return fail("%s: G_ld = %lld is below n^2 = %lld", who, (long long)G_ld, (long long)nn);
+    if (wH && H_ld < r * q) return fail("%s: H_ld = %lld is below r q = %lld", who, (long long)H_ld, (long long)(r * q));
+    if (wG && Gc_ld < r * r) return fail("%s: Gc_ld = %lld is below r^2 = %lld", who, (long long)Gc_ld, (long long)(r * r));
+    if (wM && mcoh_ld < r) return fail("%s: mcoh_ld = %lld is below r = %lld", who, (long long)mcoh_ld, (long long)r);
+    if (wV && piv_ld < n) return fail("%s: piv_ld = %lld is below n = %d", who, (long long)piv_ld, n);
+    if (wP && P_ld < nn) return fail("%s: P_ld = %lld is below n^2 = %lld", who, (long long)P_ld, (long long)nn);
+    if (!(loading >= 0.0) || !std::isfinite(loading)) return fail("%s: loading must be finite and not negative", who);
+    if (order && !cond_is_perm(order, n)) return fail("%s: order is not a permutation of 0 .. n - 1", who);
+    if (count == 0) return 0;
+    if (!G) return fail("%s: G is required", who);
+    if (!status) return fail("%s: status is required", who);
+    if (wH && !H) return fail("%s: H is wanted and NULL", who);
+    if (wG && !Gc) return fail("%s: Gc is wanted and NULL", who);
+    if (wM && !mcoh) return fail("%s: mcoh is wanted and NULL", who);
+    if (wV && !piv) return fail("%s: piv is wanted and NULL", who);
+    if (wP && !P) return fail("%s: P is wanted and NULL", who);
+    if (ensure_init()) return -1;
+    ApiLock lk;
+    const CondPlan pl = cond_plan_of(n, count, want, env_int("SP_COND_GRID", 0));
+    CondArgs a{};
+    a.G_ld = G_ld, a.count = count, a.n = n, a.q = q, a.loading = loading;
+    a.want = (wH ? COND_WANT_H : 0u) | (wG ? COND_WANT_GC : 0u) | (wM ? COND_WANT_MCOH : 0u) | (wV ? COND_WANT_PIV : 0u) | (wP ? COND_WANT_P : 0u);
+    a.H_ld = H_ld, a.Gc_ld = Gc_ld, a.mcoh_ld = mcoh_ld, a.piv_ld = piv_ld, a.P_ld = P_ld;
+    for (int i = 0; i < COND_MAX_N; ++i) a.order.p[i] = (unsigned char)(i < n ? (order ? order[i] : i) : 0);
+    Stage st(mem);
+    const char *G_d, *H_in, *Gc_in, *P_in;
+    const double *m_in, *v_in;
+    char *H_d = nullptr, *Gc_d = nullptr, *P_d = nullptr;
+    double *m_d = nullptr, *v_d = nullptr;
+    int32_t *s_d;
+    st.in(g.in0, (const char *)G, 16 * (size_t)((count - 1) * G_ld + nn), &G_d);
+    // an output with room between its matrices is staged in both directions, so that the room comes back as it was
+    auto piece = [&](bool wanted, auto *host, size_t el, int64_t ld, int64_t len, auto **in_d, auto **out_d) {
+        if (!wanted) return;
+        const size_t bytes = el * (size_t)((count - 1) * ld + len);
+        using T = std::remove_pointer_t<std::remove_pointer_t<decltype(out_d)>>;
+        if (ld > len) st.inout(g.out0, (const T *)host, (T *)host, bytes, in_d, out_d);
+        else st.out(g.out0, (T *)host, bytes, out_d);
+    };
+    piece(wH, (char *)H, 16, H_ld, r * q, &H_in, &H_d);
+    piece(wG, (char *)Gc, 16, Gc_ld, r * r, &Gc_in, &Gc_d);
+    piece(wM, mcoh, 8, mcoh_ld, r, &m_in, &m_d);
+    piece(wV, piv, 8, piv_ld, n, &v_in, &v_d);
+    piece(wP, (char *)P, 16, P_ld, nn, &P_in, &P_d);
+    st.out(g.out0, status, 4 * (size_t)count, &s_d);
+    if (st.commit()) return -1;
+    a.G = (const double2 *)G_d;
+    a.H = (double2 *)H_d, a.Gc = (double2 *)Gc_d, a.P = (double2 *)P_d, a.mcoh = m_d, a.piv = v_d, a.status = s_d;
+    int rc;
+    {
+        ProfScope ps;
+        rc = launch_cond(lc(), a, pl);
+    }
+    if (rc != 0) return fail("%s: the launch was refused (n %d, %lld matrices, %lld bytes of LDS)", who, n, (long long)count, (long long)pl.lds_bytes);
+    HIPCHK(hipGetLastError());
+    g.last_kernel = "k_cond";
     return st.finish();
 }
 

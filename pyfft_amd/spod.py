@@ -12,6 +12,7 @@ k_eigh.hip (sp_eigh: parallel cyclic Jacobi in float64, one bin per workgroup), 
 axis is made on the host.  The array is limited to 64 channels by the eigensolver.  The CSD matrix is Hermitian only to about 1e-6
 (float32 spectra): the solver reads its lower triangle, as numpy.linalg.eigh does."""
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -36,6 +37,54 @@ def _weights(who, weights, nch):
     if w.shape != (nch,) or not np.all(np.isfinite(w)) or not np.all(w > 0):
         raise ValueError("%s: weights must be %d positive finite numbers" % (who, nch))
     return w
+
+
+def csd_segments(who, Refused, nsig, fs, window, nperseg, noverlap, band=None):
+    """What the record front ends that take a `band` (`array_spectrum`, `mimo_frf` and their kin) refuse about the segments, in one order
+    and in one set of words, and what they then work with -> (win float64 [nperseg], hop, nframes, freq of the kept bins, b0, b1):
+    segments of nperseg under `window` every nperseg - noverlap samples (noverlap defaults to nperseg // 2); band = (f1, f2) keeps the
+    bins f1 <= f <= f2 of rfftfreq(nperseg, 1 / fs)."""
+    nperseg, fs = int(nperseg), float(fs)
+    if not (fs > 0 and math.isfinite(fs)):
+        raise Refused("%s: fs must be positive" % who)
+    noverlap = nperseg // 2 if noverlap is None else int(noverlap)
+    if nperseg < 2 or not 0 <= noverlap < nperseg or nsig < nperseg:
+        raise Refused("%s: need 2 <= nperseg <= nsig and 0 <= noverlap < nperseg" % who)
+    if isinstance(window, (str, tuple)):
+        win = np.asarray(get_window(window, nperseg), dtype=np.float64)
+    else:
+        win = np.asarray(window, dtype=np.float64)
+    if win.shape != (nperseg,) or not np.all(np.isfinite(win)) or not np.sum(win * win) > 0:
+        raise Refused("%s: window must be a name or nperseg = %d finite values with some weight" % (who, nperseg))
+    freq = np.fft.rfftfreq(nperseg, 1.0 / fs)
+    b0, b1 = 0, nperseg // 2 + 1
+    if band is not None:
+        f1, f2 = float(band[0]), float(band[1])
+        inside = np.nonzero((freq >= f1) & (freq <= f2))[0] if math.isfinite(f1) and math.isfinite(f2) else ()
+        if len(inside) == 0:
+            raise Refused("%s: band = (f1, f2) holds no bin" % who)
+        b0, b1 = int(inside[0]), int(inside[-1]) + 1
+    hop = nperseg - noverlap
+    return win, hop, 1 + (nsig - nperseg) // hop, freq[b0:b1], b0, b1
+
+
+def one_sided_csd(x, win, hop, nframes, fs, detrend=True, b0=0, b1=None, doubling=True):
+    """The CSD matrices G[b0:b1] of the real channels x[nch, nsig] under the one convention of `spod`, `array_spectrum` and `mimo_frf`:
+    `engine.csd_matrix` scaled to a density, 1 / (fs sum w^2), with the interior bins doubled for a one-sided spectrum.  A device
+    tensor in -> a device tensor, and the matrices never visit the host."""
+    from . import engine
+    nperseg = int(win.shape[0])
+    nb = nperseg // 2 + 1
+    b1 = nb if b1 is None else b1
+    G = engine.csd_matrix(x, win, hop, nframes, detrend=bool(detrend), scale=1.0 / (fs * float(np.sum(win * win))))
+    if not doubling:
+        return G if (b0, b1) == (0, nb) else G[b0:b1]
+    k = np.arange(nb)
+    dbl = np.where((k >= 1) & (k <= (nperseg - 1) // 2), 2.0, 1.0)[b0:b1]
+    if _is_torch(G):
+        import torch
+        dbl = torch.as_tensor(dbl, dtype=torch.float64, device=G.device)
+    return (G if (b0, b1) == (0, nb) else G[b0:b1]) * dbl[:, None, None]
 
 
 def spod_plan(nch, nmodes=None, nb=1):
@@ -98,18 +147,14 @@ def spod(x, fs=1.0, window="hann", nperseg=256, noverlap=None, detrend=True, nmo
     wts = _weights("spod", weights, nch)
     hop = nperseg - noverlap
     nframes = 1 + (nsig - nperseg) // hop
-    nb = nperseg // 2 + 1
     freq = np.fft.rfftfreq(nperseg, 1.0 / fs)
-    G = engine.csd_matrix(x, win, hop, nframes, detrend=bool(detrend), scale=1.0 / (fs * float(np.sum(win * win))))
+    G = one_sided_csd(x, win, hop, nframes, fs, detrend, doubling=onesided_doubling)
     dev = _is_torch(G)
     if dev:
         import torch
         host = lambda a: torch.as_tensor(a, dtype=torch.float64, device=G.device)      # noqa: E731
     else:
         host = lambda a: a                                                              # noqa: E731
-    if onesided_doubling:
-        k = np.arange(nb)
-        G = G * host(np.where((k >= 1) & (k <= (nperseg - 1) // 2), 2.0, 1.0))[:, None, None]
     Gw = G
     if wts is not None:
         rw = host(np.sqrt(wts))
