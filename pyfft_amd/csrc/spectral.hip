@@ -292,6 +292,16 @@ struct Stage {
         *dout = (D *)h_out;
         if (host) plan.add(&s, h_in, h_out, bytes, dout, din);
     }
+    // an output of `count` rows of `len` elements of `el` bytes, `ld` apart.  Rows further apart than they are long leave room
+    // between them that is the caller's: then the piece is staged in both directions, so that the room comes back as it was.
+    // `both` states that choice where a site makes another one
+    template <class H, class D> void rows(Scratch &s, H *h, size_t el, int64_t count, int64_t ld, int64_t len, D **dev, bool both) {
+        *dev = (D *)h;
+        if (host) plan.add(&s, both ? h : nullptr, h, el * (size_t)((count - 1) * ld + len), dev);
+    }
+    template <class H, class D> void rows(Scratch &s, H *h, size_t el, int64_t count, int64_t ld, int64_t len, D **dev) {
+        rows(s, h, el, count, ld, len, dev, ld > len);
+    }
     int commit() {
         if (!host) return 0;
         if (plan.err) return fail("staging: %s", plan.err);
@@ -4542,14 +4552,11 @@ int sp_nufft2(const double *t, const void *F, int64_t F_ld, int64_t N, int64_t b
     const NufftPlan p = nufft_plan_now(M, batch);
     Stage st(mem);
     const double *t_d;
-    const cf *F_d, *out_in;
+    const cf *F_d;
     cf *out_d;
-    const size_t out_bytes = sizeof(cf) * (size_t)((batch - 1) * out_ld + N);
     st.in(g.in0, t, sizeof(double) * (size_t)N, &t_d);
     st.in(g.in0, (const cf *)F, sizeof(cf) * (size_t)((batch - 1) * F_ld + M), &F_d);
-    // host rows further apart than N: the columns between them are the caller's, carried there and back unchanged
-    if (out_ld > N) st.inout(g.out0, (const cf *)out, (cf *)out, out_bytes, &out_in, &out_d);
-    else st.out(g.out0, (cf *)out, out_bytes, &out_d);
+    st.rows(g.out0, (cf *)out, sizeof(cf), batch, out_ld, N, &out_d);
     if (st.commit()) return -1;
     NufftSrc src{};
     src.c = F_d, src.c_ld = F_ld;                                   // the row-shift step's source: its status word finds modes that are not finite
@@ -4602,12 +4609,12 @@ int sp_ar_plan(int method, int dtype, int64_t n, int order, int64_t batch, int64
     return 0;
 }
 
-static int ar_fit(const char *who, int method, const void *x, int dtype, int64_t x_ld, int64_t nsig, int64_t batch, int64_t n, int64_t hop,
-                  int64_t first, int64_t nframes, int order, int detrend, double mean_re, double mean_im, void *a, double *evar, void *k,
-                  int64_t out_ld, int mem) {
-    if (dtype != SP_DTYPE_F32 && dtype != SP_DTYPE_C64) return fail("%s: dtype = %d must be SP_DTYPE_F32 or SP_DTYPE_C64", who, dtype);
-    if (const char *why = ar_shape(method, n, order, batch, nframes))
-        return fail("%s: %s (n %lld, order %d, batch %lld, nframes %lld)", who, why, (long long)n, order, (long long)batch, (long long)nframes);
+// The front of the entries that work on a framed record -- the fits here, the covariance entries below: what they refuse about the
+// record, the look at it, and what opens every pass.
+//
+// the refusals about the frames, the pitch, the detrending and the record itself, in one order; 0 or -1
+static int frames_refusals(const char *who, const void *x, int64_t x_ld, int64_t nsig, int64_t n, int64_t hop, int64_t first, int64_t nframes, int detrend,
+                           double mean_re, double mean_im) {
     if (hop < 1) return fail("%s: hop = %lld must be at least 1", who, (long long)hop);
     if (first < 0) return fail("%s: first = %lld must not be negative", who, (long long)first);
     if (nsig < 1 || nsig > ((int64_t)1 << 40)) return fail("%s: nsig = %lld must lie in 1 .. 2^40", who, (long long)nsig);
@@ -4615,10 +4622,61 @@ static int ar_fit(const char *who, int method, const void *x, int dtype, int64_t
         return fail("%s: %lld frames of %lld at hop %lld from %lld on reach outside the %lld samples of a row", who, (long long)nframes, (long long)n,
                     (long long)hop, (long long)first, (long long)nsig);
     if (x_ld < nsig) return fail("%s: x_ld = %lld is below nsig = %lld", who, (long long)x_ld, (long long)nsig);
-    if (out_ld < order + 1) return fail("%s: out_ld = %lld is below order + 1 = %d", who, (long long)out_ld, order + 1);
     if (detrend != SP_DETREND_CONST && detrend != SP_DETREND_SEGMEAN) return fail("%s: detrend = %d must be SP_DETREND_CONST or SP_DETREND_SEGMEAN", who, detrend);
     if (!std::isfinite(mean_re) || !std::isfinite(mean_im)) return fail("%s: the mean must be finite", who);
     if (!x) return fail("%s: x is required", who);
+    return 0;
+}
+
+// the small scratch (g.arSmall): the flag of the look; with `means` behind it, at 256, the means of a pass and then its tiles' sums
+struct ArSmall {
+    int *flag;
+    double *mean, *sums;
+};
+
+extern "C++" {   // two templates: p is the entry's plan (ArPlan, SubPlan), pass a lambda of the entry
+// the look at the record: every segment is looked at before anything is written; one pass keeps the sums of that look.  pass(s0)
+// sets A to the pass that begins with segment s0.  0, -1 or SP_AR_BAD_RECORD
+template <class Plan, class Pass>
+static int ar_look(const char *who, const ArArgs &A, Pass pass, int64_t segs, const Plan &p, bool means, bool want_sums, ArSmall *s) {
+    const size_t o_mean = 256, o_sums = o_mean + lomb_up(16 * (size_t)p.spp);
+    if (g.arSmall.ensure(means ? o_sums + 16 * (size_t)p.spp * (size_t)p.tiles + 256 : o_mean)) return -1;
+    s->flag = (int *)g.arSmall.p;
+    s->mean = (double *)((char *)g.arSmall.p + o_mean), s->sums = (double *)((char *)g.arSmall.p + o_sums);
+    HIPCHK(hipMemsetAsync(s->flag, 0, sizeof(int), g.stream));
+    for (int64_t s0 = 0; s0 < segs; s0 += p.spp) {
+        pass(s0);
+        if (launch_ar_scan(lc(), A, p.chunk, p.tiles, p.passes == 1 && want_sums ? s->sums : nullptr, s->flag) != 0)
+            return fail("%s: the look at the record was refused", who);
+        HIPCHK(hipGetLastError());
+    }
+    int bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, s->flag, sizeof(int), hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    if (bad) return fail("%s: x holds a value that is not finite", who), SP_AR_BAD_RECORD;
+    return 0;
+}
+
+// what opens a pass: the tiles' sums if there are several passes, then the means
+template <class Plan> static int ar_pass_means(const char *who, const ArArgs &A, const Plan &p, bool want_sums, const ArSmall &s) {
+    if (want_sums && p.passes > 1) {
+        if (launch_ar_scan(lc(), A, p.chunk, p.tiles, s.sums, s.flag) != 0) return fail("%s: the tiles' sums were refused", who);
+        HIPCHK(hipGetLastError());
+    }
+    if (launch_ar_mean(lc(), A, p.tiles, want_sums ? s.sums : nullptr, s.mean) != 0) return fail("%s: the means were refused", who);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+}   // extern "C++"
+
+static int ar_fit(const char *who, int method, const void *x, int dtype, int64_t x_ld, int64_t nsig, int64_t batch, int64_t n, int64_t hop,
+                  int64_t first, int64_t nframes, int order, int detrend, double mean_re, double mean_im, void *a, double *evar, void *k,
+                  int64_t out_ld, int mem) {
+    if (dtype != SP_DTYPE_F32 && dtype != SP_DTYPE_C64) return fail("%s: dtype = %d must be SP_DTYPE_F32 or SP_DTYPE_C64", who, dtype);
+    if (const char *why = ar_shape(method, n, order, batch, nframes))
+        return fail("%s: %s (n %lld, order %d, batch %lld, nframes %lld)", who, why, (long long)n, order, (long long)batch, (long long)nframes);
+    if (frames_refusals(who, x, x_ld, nsig, n, hop, first, nframes, detrend, mean_re, mean_im)) return -1;
+    if (out_ld < order + 1) return fail("%s: out_ld = %lld is below order + 1 = %d", who, (long long)out_ld, order + 1);
     if (!a) return fail("%s: a is required", who);
     if (!evar) return fail("%s: evar is required", who);
     if (!k) return fail("%s: k is required", who);
@@ -4630,31 +4688,16 @@ static int ar_fit(const char *who, int method, const void *x, int dtype, int64_t
     const ArPlan p = ar_plan_now(method, cplx, n, order, segs);
     const size_t xel = cplx ? 8 : 4, el = cplx ? 16 : 8;
     Stage st(mem);
-    const char *x_d, *a_in, *k_in;
-    const double *e_in;
+    const char *x_d;
     char *a_d, *k_d;
     double *e_d;
     st.in(g.in0, (const char *)x, xel * (size_t)((batch - 1) * x_ld + nsig), &x_d);
-    // host models further apart than they are long: what lies between them is the caller's, carried there and back unchanged
-    const size_t a_bytes = el * (size_t)((segs - 1) * out_ld + order + 1), e_bytes = 8 * (size_t)((segs - 1) * out_ld + order + 1);
-    const size_t k_bytes = el * (size_t)((segs - 1) * out_ld + order);
-    if (out_ld > order + 1) {
-        st.inout(g.out0, (const char *)a, (char *)a, a_bytes, &a_in, &a_d);
-        st.inout(g.out0, (const double *)evar, evar, e_bytes, &e_in, &e_d);
-    } else {
-        st.out(g.out0, (char *)a, a_bytes, &a_d);
-        st.out(g.out0, evar, e_bytes, &e_d);
-    }
-    if (segs > 1) st.inout(g.out0, (const char *)k, (char *)k, k_bytes, &k_in, &k_d);
-    else st.out(g.out0, (char *)k, k_bytes, &k_d);
+    st.rows(g.out0, (char *)a, el, segs, out_ld, order + 1, &a_d);
+    st.rows(g.out0, evar, 8, segs, out_ld, order + 1, &e_d);
+    st.rows(g.out0, (char *)k, el, segs, out_ld, order, &k_d, segs > 1);   // rows of `order` at a pitch of at least order + 1: room wherever there are two
     if (st.commit()) return -1;
     const bool yule = method == AR_METHOD_YULE;
     const bool want_sums = yule && detrend == SP_DETREND_SEGMEAN;
-    // the small scratch: the flag; for Yule-Walker then the means of a pass and its tiles' sums (k_burg forms its own mean)
-    const size_t o_mean = 256, o_sums = o_mean + lomb_up(16 * (size_t)p.spp);
-    if (g.arSmall.ensure(yule ? o_sums + 16 * (size_t)p.spp * (size_t)p.tiles + 256 : o_mean)) return -1;
-    int *flag = (int *)g.arSmall.p;
-    double *mean = (double *)((char *)g.arSmall.p + o_mean), *sums = (double *)((char *)g.arSmall.p + o_sums);
     if (yule && g.arPart.ensure(el * (size_t)p.spp * (size_t)p.tiles * (size_t)(order + 1))) return -1;
     ArArgs A{};
     A.x = x_d, A.cplx = cplx, A.x_ld = x_ld, A.first = first, A.hop = hop, A.nframes = nframes, A.n = n;
@@ -4666,31 +4709,16 @@ static int ar_fit(const char *who, int method, const void *x, int dtype, int64_t
         A.seg0 = s0, A.nseg = std::min<int64_t>(p.spp, segs - s0);
         A.a = a_d + el * (size_t)(s0 * out_ld), A.e = e_d + s0 * out_ld, A.k = k_d + el * (size_t)(s0 * out_ld);
     };
-    // every segment is looked at before anything is written; one pass keeps the sums of that look
-    HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), g.stream));
-    for (int64_t s0 = 0; s0 < segs; s0 += p.spp) {
-        pass(s0);
-        if (launch_ar_scan(lc(), A, p.chunk, p.tiles, p.passes == 1 && want_sums ? sums : nullptr, flag) != 0)
-            return fail("%s: the look at the record was refused", who);
-        HIPCHK(hipGetLastError());
-    }
-    int bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream));
-    if (bad) return fail("%s: x holds a value that is not finite", who), SP_AR_BAD_RECORD;
+    ArSmall sm;                                                     // Yule-Walker keeps means there; k_burg forms its own
+    if (int rc = ar_look(who, A, pass, segs, p, yule, want_sums, &sm)) return rc;
     for (int64_t s0 = 0; s0 < segs; s0 += p.spp, ++g_passes[7]) {
         pass(s0);
         int rc;
         if (yule) {
-            if (want_sums && p.passes > 1) {
-                if (launch_ar_scan(lc(), A, p.chunk, p.tiles, sums, flag) != 0) return fail("%s: the tiles' sums were refused", who);
-                HIPCHK(hipGetLastError());
-            }
-            if (launch_ar_mean(lc(), A, p.tiles, want_sums ? sums : nullptr, mean) != 0) return fail("%s: the means were refused", who);
-            HIPCHK(hipGetLastError());
+            if (ar_pass_means(who, A, p, want_sums, sm)) return -1;
             {
                 ProfScope ps;
-                rc = launch_ar_lags(lc(), A, p.chunk, p.tiles, mean, g.arPart.p);
+                rc = launch_ar_lags(lc(), A, p.chunk, p.tiles, sm.mean, g.arPart.p);
             }
             if (rc != 0) return fail("%s: the lags were refused (%lld segments of %lld in %lld tiles)", who, (long long)A.nseg, (long long)n, (long long)p.tiles);
             HIPCHK(hipGetLastError());
@@ -4741,14 +4769,12 @@ int sp_ar_psd(const void *a, int cplx, int64_t a_ld, const double *e, int64_t e_
     ApiLock lk;
     const size_t el = cplx ? 16 : 8, pel = out64 ? 8 : 4;
     Stage st(mem);
-    const char *a_d, *P_in;
+    const char *a_d;
     const double *e_d;
     char *P_d;
     st.in(g.in0, (const char *)a, el * (size_t)((nmodels - 1) * a_ld + order + 1), &a_d);
     st.in(g.in0, e, 8 * (size_t)((nmodels - 1) * e_ld + 1), &e_d);
-    const size_t P_bytes = pel * (size_t)((nmodels - 1) * P_ld + m);
-    if (P_ld > m) st.inout(g.out0, (const char *)P, (char *)P, P_bytes, &P_in, &P_d);
-    else st.out(g.out0, (char *)P, P_bytes, &P_d);
+    st.rows(g.out0, (char *)P, pel, nmodels, P_ld, m, &P_d);
     if (st.commit()) return -1;
     int rc;
     {
@@ -4786,17 +4812,7 @@ static int sub_refusals(const char *who, int what, const void *x, int dtype, int
         return fail("%s: %s (n %lld, %s %d, batch %lld, nframes %lld)", who, why, (long long)n, what == SUB_WHAT_LS ? "order" : "m", what == SUB_WHAT_LS ? m - 1 : m,
                     (long long)batch, (long long)nframes);
     if (fb != 0 && fb != 1) return fail("%s: fb = %d must be 0 (covariance) or 1 (modified covariance)", who, fb);
-    if (hop < 1) return fail("%s: hop = %lld must be at least 1", who, (long long)hop);
-    if (first < 0) return fail("%s: first = %lld must not be negative", who, (long long)first);
-    if (nsig < 1 || nsig > ((int64_t)1 << 40)) return fail("%s: nsig = %lld must lie in 1 .. 2^40", who, (long long)nsig);
-    if (nframes > 0 && (first > nsig - n || (nframes - 1) > (nsig - n - first) / hop))
-        return fail("%s: %lld frames of %lld at hop %lld from %lld on reach outside the %lld samples of a row", who, (long long)nframes, (long long)n,
-                    (long long)hop, (long long)first, (long long)nsig);
-    if (x_ld < nsig) return fail("%s: x_ld = %lld is below nsig = %lld", who, (long long)x_ld, (long long)nsig);
-    if (detrend != SP_DETREND_CONST && detrend != SP_DETREND_SEGMEAN) return fail("%s: detrend = %d must be SP_DETREND_CONST or SP_DETREND_SEGMEAN", who, detrend);
-    if (!std::isfinite(mean_re) || !std::isfinite(mean_im)) return fail("%s: the mean must be finite", who);
-    if (!x) return fail("%s: x is required", who);
-    return 0;
+    return frames_refusals(who, x, x_ld, nsig, n, hop, first, nframes, detrend, mean_re, mean_im);
 }
 
 // the passes of both entries over staged pointers: the look at the record, then per pass the means, row 0 by tiles, the matrices (into
@@ -4806,44 +4822,26 @@ static int sub_passes(const char *who, int what, const char *x_d, bool cplx, int
     const SubPlan p = sub_plan_now(what, cplx, n, m, segs);
     const size_t el = cplx ? 16 : 8;
     const bool ls = what == SUB_WHAT_LS, want_sums = detrend == SP_DETREND_SEGMEAN;
-    const size_t o_mean = 256, o_sums = o_mean + lomb_up(16 * (size_t)p.spp);
-    if (g.arSmall.ensure(o_sums + 16 * (size_t)p.spp * (size_t)p.tiles + 256)) return -1;
-    int *flag = (int *)g.arSmall.p;
-    double *mean = (double *)((char *)g.arSmall.p + o_mean), *sums = (double *)((char *)g.arSmall.p + o_sums);
     if (g.subPart.ensure(el * (size_t)p.spp * (size_t)p.tiles * (size_t)m)) return -1;
     if (ls && g.subMat.ensure(16 * (size_t)p.spp * (size_t)m * (size_t)m)) return -1;
     CovArgs K{};
     ArArgs &A = K.A;
     A.x = x_d, A.cplx = cplx, A.x_ld = x_ld, A.first = first, A.hop = hop, A.nframes = nframes, A.n = n;
-    A.p = 1, A.out_ld = 2, A.a = flag, A.e = mean, A.k = flag;           // what k_ar_scan's launch asks for and neither kernel here touches
     A.detrend = detrend == SP_DETREND_SEGMEAN ? 1 : ((mean_re != 0.0 || mean_im != 0.0) ? 2 : 0);
     A.mre = mean_re, A.mim = mean_im;
     K.m = m, K.fb = fb;
+    ArSmall sm;                                                     // carved by the look, before it sets its first pass
     auto pass = [&](int64_t s0) {
         A.seg0 = s0, A.nseg = std::min<int64_t>(p.spp, segs - s0);
+        A.p = 1, A.out_ld = 2, A.a = sm.flag, A.e = sm.mean, A.k = sm.flag;   // what k_ar_scan's launch asks for and neither kernel here touches
         K.C = ls ? (char *)g.subMat.p : C_d + 16 * (size_t)(s0 * C_ld);
         K.C_ld = ls ? (int64_t)m * m : C_ld;
     };
-    // every segment is looked at before anything is written; one pass keeps the sums of that look
-    HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), g.stream));
-    for (int64_t s0 = 0; s0 < segs; s0 += p.spp) {
-        pass(s0);
-        if (launch_ar_scan(lc(), A, p.chunk, p.tiles, p.passes == 1 && want_sums ? sums : nullptr, flag) != 0)
-            return fail("%s: the look at the record was refused", who);
-        HIPCHK(hipGetLastError());
-    }
-    int bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream));
-    if (bad) return fail("%s: x holds a value that is not finite", who), SP_AR_BAD_RECORD;
+    if (int rc = ar_look(who, A, pass, segs, p, true, want_sums, &sm)) return rc;
+    double *mean = sm.mean;
     for (int64_t s0 = 0; s0 < segs; s0 += p.spp, ++g_passes[8]) {
         pass(s0);
-        if (want_sums && p.passes > 1) {
-            if (launch_ar_scan(lc(), A, p.chunk, p.tiles, sums, flag) != 0) return fail("%s: the tiles' sums were refused", who);
-            HIPCHK(hipGetLastError());
-        }
-        if (launch_ar_mean(lc(), A, p.tiles, want_sums ? sums : nullptr, mean) != 0) return fail("%s: the means were refused", who);
-        HIPCHK(hipGetLastError());
+        if (ar_pass_means(who, A, p, want_sums, sm)) return -1;
         int rc;
         {
             ProfScope ps;
@@ -4876,12 +4874,10 @@ int sp_covmat(const void *x, int dtype, int64_t x_ld, int64_t nsig, int64_t batc
     ApiLock lk;
     const bool cplx = dtype == SP_DTYPE_C64;
     Stage st(mem);
-    const char *x_d, *C_in;
+    const char *x_d;
     char *C_d;
     st.in(g.in0, (const char *)x, (cplx ? 8 : 4) * (size_t)((batch - 1) * x_ld + nsig), &x_d);
-    const size_t C_bytes = 16 * (size_t)((segs - 1) * C_ld + (int64_t)m * m);
-    if (C_ld > (int64_t)m * m) st.inout(g.out0, (const char *)C, (char *)C, C_bytes, &C_in, &C_d);
-    else st.out(g.out0, (char *)C, C_bytes, &C_d);
+    st.rows(g.out0, (char *)C, 16, segs, C_ld, (int64_t)m * m, &C_d);
     if (st.commit()) return -1;
     if (int rc = sub_passes(who, SUB_WHAT_COVMAT, x_d, cplx, x_ld, segs, n, hop, first, nframes, m, fb, detrend, mean_re, mean_im, C_d, C_ld, nullptr, nullptr,
                             nullptr, 0))
@@ -4906,14 +4902,12 @@ int sp_ar_ls(const void *x, int dtype, int64_t x_ld, int64_t nsig, int64_t batch
     const bool cplx = dtype == SP_DTYPE_C64;
     const size_t el = cplx ? 16 : 8;
     Stage st(mem);
-    const char *x_d, *a_in;
+    const char *x_d;
     char *a_d;
     double *e_d;
     int32_t *s_d;
     st.in(g.in0, (const char *)x, (cplx ? 8 : 4) * (size_t)((batch - 1) * x_ld + nsig), &x_d);
-    const size_t a_bytes = el * (size_t)((segs - 1) * out_ld + order + 1);
-    if (out_ld > order + 1) st.inout(g.out0, (const char *)a, (char *)a, a_bytes, &a_in, &a_d);
-    else st.out(g.out0, (char *)a, a_bytes, &a_d);
+    st.rows(g.out0, (char *)a, el, segs, out_ld, order + 1, &a_d);
     st.out(g.out0, e, 8 * (size_t)segs, &e_d);
     st.out(g.out0, status, 4 * (size_t)segs, &s_d);
     if (st.commit()) return -1;
@@ -4943,15 +4937,13 @@ int sp_pseudospectrum(const void *V, int64_t V_ld, const double *w, int m, int p
     ApiLock lk;
     const size_t pel = out64 ? 8 : 4;
     Stage st(mem);
-    const char *V_d, *P_in;
+    const char *V_d;
     const double *w_d;
     char *P_d;
     int32_t *s_d;
     st.in(g.in0, (const char *)V, 16 * (size_t)((nmodels * m - 1) * V_ld + m), &V_d);
     st.in(g.in0, w, 8 * (size_t)(nmodels * m), &w_d);
-    const size_t P_bytes = pel * (size_t)((nmodels - 1) * P_ld + nbins);
-    if (P_ld > nbins) st.inout(g.out0, (const char *)P, (char *)P, P_bytes, &P_in, &P_d);
-    else st.out(g.out0, (char *)P, P_bytes, &P_d);
+    st.rows(g.out0, (char *)P, pel, nmodels, P_ld, nbins, &P_d);
     st.out(g.out0, status, 4 * (size_t)nmodels, &s_d);
     if (st.commit()) return -1;
     int rc;
@@ -5007,15 +4999,13 @@ int sp_beamscan(const void *V, int64_t V_ld, const double *w, int m, int64_t nmo
     if (scale && get_table(31, scale, sizeof(double) * (size_t)nmodels, &sc_d, nullptr)) return -1;
     const size_t pel = out64 ? 8 : 4;
     Stage st(mem);
-    const char *V_d, *P_in;
+    const char *V_d;
     const double *w_d;
     char *P_d;
     int32_t *s_d;
     st.in(g.in0, (const char *)V, 16 * (size_t)((nmodels * m - 1) * V_ld + m), &V_d);
     st.in(g.in0, w, 8 * (size_t)(nmodels * m), &w_d);
-    const size_t P_bytes = pel * (size_t)((nmodels - 1) * P_ld + nk);
-    if (P_ld > nk) st.inout(g.out0, (const char *)P, (char *)P, P_bytes, &P_in, &P_d);
-    else st.out(g.out0, (char *)P, P_bytes, &P_d);
+    st.rows(g.out0, (char *)P, pel, nmodels, P_ld, nk, &P_d);
     st.out(g.out0, status, 4 * (size_t)nmodels, &s_d);
     if (st.commit()) return -1;
     int rc;
@@ -5079,25 +5069,16 @@ int sp_cond(const void *G, int64_t G_ld, int n, int64_t count, const int32_t *or
     a.H_ld = H_ld, a.Gc_ld = Gc_ld, a.mcoh_ld = mcoh_ld, a.piv_ld = piv_ld, a.P_ld = P_ld;
     for (int i = 0; i < COND_MAX_N; ++i) a.order.p[i] = (unsigned char)(i < n ? (order ? order[i] : i) : 0);
     Stage st(mem);
-    const char *G_d, *H_in, *Gc_in, *P_in;
-    const double *m_in, *v_in;
+    const char *G_d;
     char *H_d = nullptr, *Gc_d = nullptr, *P_d = nullptr;
     double *m_d = nullptr, *v_d = nullptr;
     int32_t *s_d;
     st.in(g.in0, (const char *)G, 16 * (size_t)((count - 1) * G_ld + nn), &G_d);
-    // an output with room between its matrices is staged in both directions, so that the room comes back as it was
-    auto piece = [&](bool wanted, auto *host, size_t el, int64_t ld, int64_t len, auto **in_d, auto **out_d) {
-        if (!wanted) return;
-        const size_t bytes = el * (size_t)((count - 1) * ld + len);
-        using T = std::remove_pointer_t<std::remove_pointer_t<decltype(out_d)>>;
-        if (ld > len) st.inout(g.out0, (const T *)host, (T *)host, bytes, in_d, out_d);
-        else st.out(g.out0, (T *)host, bytes, out_d);
-    };
-    piece(wH, (char *)H, 16, H_ld, r * q, &H_in, &H_d);
-    piece(wG, (char *)Gc, 16, Gc_ld, r * r, &Gc_in, &Gc_d);
-    piece(wM, mcoh, 8, mcoh_ld, r, &m_in, &m_d);
-    piece(wV, piv, 8, piv_ld, n, &v_in, &v_d);
-    piece(wP, (char *)P, 16, P_ld, nn, &P_in, &P_d);
+    if (wH) st.rows(g.out0, (char *)H, 16, count, H_ld, r * q, &H_d);
+    if (wG) st.rows(g.out0, (char *)Gc, 16, count, Gc_ld, r * r, &Gc_d);
+    if (wM) st.rows(g.out0, mcoh, 8, count, mcoh_ld, r, &m_d);
+    if (wV) st.rows(g.out0, piv, 8, count, piv_ld, n, &v_d);
+    if (wP) st.rows(g.out0, (char *)P, 16, count, P_ld, nn, &P_d);
     st.out(g.out0, status, 4 * (size_t)count, &s_d);
     if (st.commit()) return -1;
     a.G = (const double2 *)G_d;
@@ -5255,13 +5236,6 @@ static int dwt_buffers(const char *who, const void *in, int64_t in_ld, int64_t i
     return 0;
 }
 
-// an output of `rows` rows of `need` elements, `ld` apart: staged in place where the rows leave room between them
-static void dwt_stage_out(Stage &st, void *h, size_t el, int64_t rows, int64_t ld, int64_t need, const char **in_d, char **out_d) {
-    const size_t bytes = el * (size_t)((rows - 1) * ld + need);
-    if (ld > need) st.inout(g.out0, (const char *)h, (char *)h, bytes, in_d, out_d);
-    else st.out(g.out0, (char *)h, bytes, out_d);
-}
-
 int sp_dwt(const void *x, int dtype, int64_t x_ld, int64_t n, int64_t batch, const double *dec_lo, const double *dec_hi, int L, int mode, int levels,
            void *out, int64_t out_ld, int form, int mem) {
     const char *who = "sp_dwt";
@@ -5272,10 +5246,10 @@ int sp_dwt(const void *x, int dtype, int64_t x_ld, int64_t n, int64_t batch, con
     if (ensure_init()) return -1;
     ApiLock lk;
     Stage st(mem);
-    const char *x_d, *o_in;
+    const char *x_d;
     char *o_d;
     st.in(g.in0, (const char *)x, c.el * (size_t)((batch - 1) * x_ld + n), &x_d);
-    dwt_stage_out(st, out, c.el, batch, out_ld, c.p.total, &o_in, &o_d);
+    st.rows(g.out0, (char *)out, c.el, batch, out_ld, c.p.total, &o_d);
     if (st.commit()) return -1;
     if (int rc = dwt_run(who, c, mode, levels, x_d, x_ld, n, batch, o_d, out_ld, o_d, out_ld)) return rc;
     return st.finish();
@@ -5295,11 +5269,11 @@ int sp_dwt_level(const void *x, int dtype, int64_t x_ld, int64_t n, int64_t batc
     if (ensure_init()) return -1;
     ApiLock lk;
     Stage st(mem);
-    const char *x_d, *a_in, *d_in;
+    const char *x_d;
     char *a_d, *d_d;
     st.in(g.in0, (const char *)x, c.el * (size_t)((batch - 1) * x_ld + n), &x_d);
-    dwt_stage_out(st, cA, c.el, batch, a_ld, K, &a_in, &a_d);
-    dwt_stage_out(st, cD, c.el, batch, d_ld, K, &d_in, &d_d);
+    st.rows(g.out0, (char *)cA, c.el, batch, a_ld, K, &a_d);
+    st.rows(g.out0, (char *)cD, c.el, batch, d_ld, K, &d_d);
     if (st.commit()) return -1;
     c.p.lv.off[1] = 0;
     if (int rc = dwt_run(who, c, mode, 1, x_d, x_ld, n, batch, a_d, a_ld, d_d, d_ld)) return rc;
@@ -5316,10 +5290,10 @@ int sp_idwt(const void *coef, int dtype, int64_t c_ld, int64_t n, int64_t batch,
     if (ensure_init()) return -1;
     ApiLock lk;
     Stage st(mem);
-    const char *c_d, *x_in;
+    const char *c_d;
     char *x_d;
     st.in(g.in0, (const char *)coef, c.el * (size_t)((batch - 1) * c_ld + c.p.total), &c_d);
-    dwt_stage_out(st, x, c.el, batch, x_ld, n, &x_in, &x_d);
+    st.rows(g.out0, (char *)x, c.el, batch, x_ld, n, &x_d);
     if (st.commit()) return -1;
     if (int rc = idwt_run(who, c, mode, levels, c_d, c_ld, c_d, c_ld, n, batch, x_d, x_ld)) return rc;
     return st.finish();
@@ -5336,11 +5310,11 @@ int sp_idwt_level(const void *cA, int64_t a_ld, const void *cD, int64_t d_ld, in
     if (ensure_init()) return -1;
     ApiLock lk;
     Stage st(mem);
-    const char *a_d, *d_d, *x_in;
+    const char *a_d, *d_d;
     char *x_d;
     st.in(g.in0, (const char *)cA, c.el * (size_t)((batch - 1) * a_ld + K), &a_d);
     st.in(g.in0, (const char *)cD, c.el * (size_t)((batch - 1) * d_ld + K), &d_d);
-    dwt_stage_out(st, x, c.el, batch, x_ld, n, &x_in, &x_d);
+    st.rows(g.out0, (char *)x, c.el, batch, x_ld, n, &x_d);
     if (st.commit()) return -1;
     c.p.lv.off[1] = 0;
     if (int rc = idwt_run(who, c, mode, 1, a_d, a_ld, d_d, d_ld, n, batch, x_d, x_ld)) return rc;
@@ -5358,10 +5332,10 @@ int sp_modwt(const void *x, int dtype, int64_t x_ld, int64_t n, int64_t batch, c
     ApiLock lk;
     const int64_t plane = batch * w_ld;
     Stage st(mem);
-    const char *x_d, *w_in;
+    const char *x_d;
     char *w_d;
     st.in(g.in0, (const char *)x, c.el * (size_t)((batch - 1) * x_ld + n), &x_d);
-    dwt_stage_out(st, W, c.el, (int64_t)(levels + 1) * batch, w_ld, n, &w_in, &w_d);
+    st.rows(g.out0, (char *)W, c.el, (int64_t)(levels + 1) * batch, w_ld, n, &w_d);
     if (st.commit()) return -1;
     if (c.p.form == DWT_FORM_ROW) {
         int rc;
@@ -5409,10 +5383,10 @@ int sp_imodwt(const void *W, int dtype, int64_t w_ld, int64_t n, int64_t batch, 
     ApiLock lk;
     const int64_t plane = batch * w_ld;
     Stage st(mem);
-    const char *w_d, *x_in;
+    const char *w_d;
     char *x_d;
     st.in(g.in0, (const char *)W, c.el * (size_t)(((int64_t)(levels + 1) * batch - 1) * w_ld + n), &w_d);
-    dwt_stage_out(st, x, c.el, batch, x_ld, n, &x_in, &x_d);
+    st.rows(g.out0, (char *)x, c.el, batch, x_ld, n, &x_d);
     if (st.commit()) return -1;
     if (c.p.form == DWT_FORM_ROW) {
         int rc;

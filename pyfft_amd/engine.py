@@ -251,6 +251,62 @@ def _range_check(Refused, who, length=None, hop=None, count=None, rows=None, nsi
         raise Refused("%s: scale must be finite" % who)
 
 
+def _frames_check(Refused, who, n, hop, first, nframes, rows, nsig, x_ld, mean):
+    """The refusals about the frames of a record that `ar_check` and `sub_check` end in, in this order."""
+    _range_check(Refused, who, hop=hop, count=("nframes", nframes), rows=(rows, (1 << 31) - 1))
+    if nframes > (1 << 31) - 1 or rows * nframes > 1 << 40:
+        raise Refused("%s: %d rows of %d frames are more segments than 2^40" % (who, rows, nframes))
+    if first < 0:
+        raise Refused("%s: first = %d must not be negative" % (who, first))
+    if nsig is not None and nframes > 0 and first + (nframes - 1) * hop + n > nsig:
+        raise Refused("%s: %d frames of %d at hop %d from %d on reach outside the %d samples of a row" % (who, nframes, n, hop, first, nsig))
+    if x_ld is not None:
+        _range_check(Refused, who, nsig=nsig, x_ld=x_ld)
+    if not (math.isfinite(mean.real) and math.isfinite(mean.imag)):
+        raise Refused("%s: mean_value must be finite" % who)
+
+
+def _framed_record(who, Refused, x, detrend, mean_value, judge):
+    """The record of the fits (`burg`, `yule`) and of the covariance entries (`covmat`, `ar_ls`) -> (md, rows of x, their pitch, nsig,
+    rows, lead, cplx, the detrend code, the constant).  judge(rows, nsig, mean) holds the entry's own refusals about the shape."""
+    md = _enter(x)
+    x = md.checked(x)
+    if x.ndim < 1:
+        raise Refused("%s: x needs at least one axis" % who)
+    code, mean = _ar_detrend(who, detrend, mean_value, Refused)
+    lead, rows = _lead_rows(x.shape)
+    nsig = int(x.shape[-1])
+    judge(rows, nsig, mean)
+    cplx = md.code(x) == _ffi.DTYPE_C64
+    if not cplx and mean.imag != 0.0:
+        raise Refused("%s: a real record takes a real mean_value" % who)
+    if not md.dev and not np.all(np.isfinite(x)):
+        raise Refused("%s: x must be finite" % who)
+    if md.dev and x.ndim != 2:
+        x = x.reshape(rows, nsig)
+    xs, xld = md.rows(x)
+    return md, xs, xld, nsig, rows, lead, cplx, code, mean
+
+
+def _eigen_models(who, Refused, V, w):
+    """The eigendecompositions `pseudospectrum` and `beamscan` take, V[..., m, m] complex128 and w[..., m] float64 as `eigh` returns
+    them -> (md, V, w, V's shape, m), both contiguous"""
+    md = _enter(V)
+    if _mode(w) is not md:
+        raise TypeError("%s: V and w must both be numpy arrays or both device tensors" % who)
+    if md.dev:
+        if V.dtype != torch.complex128 or w.dtype != torch.float64:
+            raise Refused("%s: on the device V is a complex128 tensor and w float64" % who)
+        V, w = V.contiguous(), w.contiguous()
+    else:
+        V = np.ascontiguousarray(np.asarray(V), dtype=np.complex128)
+        w = np.ascontiguousarray(np.asarray(w), dtype=np.float64)
+    shape = tuple(V.shape)
+    if len(shape) < 2 or shape[-1] != shape[-2] or tuple(w.shape) != shape[:-1]:
+        raise Refused("%s: V must be [..., m, m] and w [..., m]" % who)
+    return md, V, w, shape, int(shape[-1])
+
+
 def max_wg_fft():
     return int(lib().sp_max_wg_fft())
 
@@ -2133,23 +2189,12 @@ def ar_check(who, method, n, hop, first, nframes, order, rows, nsig=None, x_ld=N
         raise ArRefused("%s: n = %d samples of a segment are outside 2 .. %d" % (who, n, most))
     if order > n // 2:
         raise ArRefused("%s: order = %d exceeds n / 2 = %d" % (who, order, n // 2))
-    _range_check(ArRefused, who, hop=hop, count=("nframes", nframes), rows=(rows, (1 << 31) - 1))
-    if nframes > (1 << 31) - 1 or rows * nframes > 1 << 40:
-        raise ArRefused("%s: %d rows of %d frames are more segments than 2^40" % (who, rows, nframes))
-    if first < 0:
-        raise ArRefused("%s: first = %d must not be negative" % (who, first))
-    if nsig is not None and nframes > 0 and first + (nframes - 1) * hop + n > nsig:
-        raise ArRefused("%s: %d frames of %d at hop %d from %d on reach outside the %d samples of a row" % (who, nframes, n, hop, first, nsig))
-    if x_ld is not None:
-        _range_check(ArRefused, who, nsig=nsig, x_ld=x_ld)
-    if not (math.isfinite(mean.real) and math.isfinite(mean.imag)):
-        raise ArRefused("%s: mean_value must be finite" % who)
+    _frames_check(ArRefused, who, n, hop, first, nframes, rows, nsig, x_ld, mean)
 
 
-def _ar_detrend(who, detrend, mean_value, Refused=None):
+def _ar_detrend(who, detrend, mean_value, Refused):
     """-> (the C ABI's detrend code, the constant): True every segment's own mean, or with an explicit mean_value that constant; False
     or None nothing, and then a mean_value is refused"""
-    Refused = Refused or ArRefused
     flag = isinstance(detrend, (bool, np.bool_))
     if detrend is None or (flag and not detrend):
         if mean_value is not None:
@@ -2164,22 +2209,8 @@ def _ar_detrend(who, detrend, mean_value, Refused=None):
 
 def _ar_fit(who, method, x, n, hop, first, nframes, order, detrend, mean_value):
     n, hop, first, nframes, order = int(n), int(hop), int(first), int(nframes), int(order)
-    md = _enter(x)
-    x = md.checked(x)
-    if x.ndim < 1:
-        raise ArRefused("%s: x needs at least one axis" % who)
-    code, mean = _ar_detrend(who, detrend, mean_value)
-    lead, rows = _lead_rows(x.shape)
-    nsig = int(x.shape[-1])
-    ar_check(who, method, n, hop, first, nframes, order, rows, nsig, None, mean)
-    cplx = md.code(x) == _ffi.DTYPE_C64
-    if not cplx and mean.imag != 0.0:
-        raise ArRefused("%s: a real record takes a real mean_value" % who)
-    if not md.dev and not np.all(np.isfinite(x)):
-        raise ArRefused("%s: x must be finite" % who)
-    if md.dev and x.ndim != 2:
-        x = x.reshape(rows, nsig)
-    xs, xld = md.rows(x)
+    md, xs, xld, nsig, rows, lead, cplx, code, mean = _framed_record(
+        who, ArRefused, x, detrend, mean_value, lambda rows, nsig, mean: ar_check(who, method, n, hop, first, nframes, order, rows, nsig, None, mean))
     dt = "complex128" if cplx else "float64"
     a = md.empty(lead + (nframes, order + 1), dt, xs)
     e = md.empty(lead + (nframes, order + 1), "float64", xs)
@@ -2281,37 +2312,13 @@ def sub_check(who, what, n, hop, first, nframes, m, rows, nsig=None, mean=0j):
         raise SubRefused("%s: order = %d exceeds n / 2 = %d" % (who, m - 1, n // 2))
     if m > n:
         raise SubRefused("%s: m = %d exceeds n = %d" % (who, m, n))
-    _range_check(SubRefused, who, hop=hop, count=("nframes", nframes), rows=(rows, (1 << 31) - 1))
-    if nframes > (1 << 31) - 1 or rows * nframes > 1 << 40:
-        raise SubRefused("%s: %d rows of %d frames are more segments than 2^40" % (who, rows, nframes))
-    if first < 0:
-        raise SubRefused("%s: first = %d must not be negative" % (who, first))
-    if nsig is not None and nframes > 0 and first + (nframes - 1) * hop + n > nsig:
-        raise SubRefused("%s: %d frames of %d at hop %d from %d on reach outside the %d samples of a row" % (who, nframes, n, hop, first, nsig))
-    if not (math.isfinite(mean.real) and math.isfinite(mean.imag)):
-        raise SubRefused("%s: mean_value must be finite" % who)
+    _frames_check(SubRefused, who, n, hop, first, nframes, rows, nsig, None, mean)
 
 
 def _sub_record(who, what, x, n, hop, first, nframes, m, detrend, mean_value):
-    """the record of `covmat` and `ar_ls`, judged as `_ar_fit` judges its own -> (md, rows of x, their pitch, nsig, rows, lead, cplx,
-    the detrend code, the constant)"""
-    md = _enter(x)
-    x = md.checked(x)
-    if x.ndim < 1:
-        raise SubRefused("%s: x needs at least one axis" % who)
-    code, mean = _ar_detrend(who, detrend, mean_value, SubRefused)
-    lead, rows = _lead_rows(x.shape)
-    nsig = int(x.shape[-1])
-    sub_check(who, what, n, hop, first, nframes, m, rows, nsig, mean)
-    cplx = md.code(x) == _ffi.DTYPE_C64
-    if not cplx and mean.imag != 0.0:
-        raise SubRefused("%s: a real record takes a real mean_value" % who)
-    if not md.dev and not np.all(np.isfinite(x)):
-        raise SubRefused("%s: x must be finite" % who)
-    if md.dev and x.ndim != 2:
-        x = x.reshape(rows, nsig)
-    xs, xld = md.rows(x)
-    return md, xs, xld, nsig, rows, lead, cplx, code, mean
+    """the record of `covmat` and `ar_ls`: `_framed_record`, judged by `sub_check`"""
+    return _framed_record(who, SubRefused, x, detrend, mean_value,
+                          lambda rows, nsig, mean: sub_check(who, what, n, hop, first, nframes, m, rows, nsig, mean))
 
 
 def covmat(x, n, hop, first, nframes, m, fb=True, detrend=True, mean_value=None):
@@ -2365,20 +2372,7 @@ def pseudospectrum(V, w, p, nbins, start, step, weighting="music", out64=False):
     p, nbins, start, step = int(p), int(nbins), float(start), float(step)
     if weighting not in SUB_WEIGHTINGS:
         raise SubRefused("%s: weighting must be 'music' or 'ev', not %r" % (who, weighting))
-    md = _enter(V)
-    if _mode(w) is not md:
-        raise TypeError("%s: V and w must both be numpy arrays or both device tensors" % who)
-    if md.dev:
-        if V.dtype != torch.complex128 or w.dtype != torch.float64:
-            raise SubRefused("%s: on the device V is a complex128 tensor and w float64" % who)
-        V, w = V.contiguous(), w.contiguous()
-    else:
-        V = np.ascontiguousarray(np.asarray(V), dtype=np.complex128)
-        w = np.ascontiguousarray(np.asarray(w), dtype=np.float64)
-    shape = tuple(V.shape)
-    if len(shape) < 2 or shape[-1] != shape[-2] or tuple(w.shape) != shape[:-1]:
-        raise SubRefused("%s: V must be [..., m, m] and w [..., m]" % who)
-    m = int(shape[-1])
+    md, V, w, shape, m = _eigen_models(who, SubRefused, V, w)
     if m < 2 or m > SUB_MAX_M:
         raise SubRefused("%s: m = %d is outside 2 .. %d" % (who, m, SUB_MAX_M))
     if p < 0 or p > m - 1:
@@ -2469,20 +2463,7 @@ def beamscan(V, w, pos, kv, method="bartlett", p=0, loading=0.0, scale=None, out
     device tensors on torch's current stream; the two agree bitwise."""
     who = "beamscan"
     p, loading = int(p), float(loading)
-    md = _enter(V)
-    if _mode(w) is not md:
-        raise TypeError("%s: V and w must both be numpy arrays or both device tensors" % who)
-    if md.dev:
-        if V.dtype != torch.complex128 or w.dtype != torch.float64:
-            raise BeamRefused("%s: on the device V is a complex128 tensor and w float64" % who)
-        V, w = V.contiguous(), w.contiguous()
-    else:
-        V = np.ascontiguousarray(np.asarray(V), dtype=np.complex128)
-        w = np.ascontiguousarray(np.asarray(w), dtype=np.float64)
-    shape = tuple(V.shape)
-    if len(shape) < 2 or shape[-1] != shape[-2] or tuple(w.shape) != shape[:-1]:
-        raise BeamRefused("%s: V must be [..., m, m] and w [..., m]" % who)
-    m = int(shape[-1])
+    md, V, w, shape, m = _eigen_models(who, BeamRefused, V, w)
     pos = _beam_table(who, "pos", pos)
     kv = _beam_table(who, "kv", kv, pos.shape[1])
     ndim, nk = int(pos.shape[1]), int(kv.shape[0])

@@ -20,12 +20,14 @@ except Exception:                       # pragma: no cover
 # entries whose result the engine reads: answered by the built library, which needs no GPU for them; not recorded
 HOST_ARITHMETIC = ("sp_xcorr_frames_len", "sp_csd_epilogue_doubles", "sp_ddc_tile", "sp_upfirdn_tile", "sp_pfb_synth_plan", "sp_skf_plan",
                    "sp_welch_blocks_plan", "sp_cwt_plan", "sp_eigh_plan", "sp_version", "sp_max_wg_fft", "sp_wct_plan", "sp_ssq_plan",
-                   "sp_wvd_plan", "sp_cyclic_plan", "sp_lomb_plan", "sp_last_passes")
+                   "sp_wvd_plan", "sp_cyclic_plan", "sp_lomb_plan", "sp_last_passes", "sp_ar_plan", "sp_sub_plan", "sp_beamscan_plan")
 REFUSAL_TYPES = (ValueError, TypeError, NotImplementedError)
 MODES = ("host", "dev")
 
 _INTS, _FLOATS = (int, np.integer), (float, np.floating)
-DECLARED = {name: sig for table in _ffi.TABLES for name, sig in table.items()}      # every entry of the six signature tables
+# the signature tables whose entries the case table drives: the six of _ffi.TABLES, then one more for every family traced since
+TRACED_TABLES = _ffi.TABLES + (_ffi.AR_SIGNATURES, _ffi.SUB_SIGNATURES, _ffi.ARRAY_SIGNATURES)
+DECLARED = {name: sig for table in TRACED_TABLES for name, sig in table.items()}     # every entry of the traced tables
 
 
 class StandIn:
@@ -717,8 +719,167 @@ case("lomb_finish", "normalize-refused", lambda A: K(sums(A), FREQ, normalize="p
 case("lomb_finish", "mean-nonfinite-refused", lambda A: K(sums(A, mean=[0.25, float("nan")]), FREQ))
 case("lomb_finish", "N-refused", lambda A: K(sums(A)._replace(N=0), FREQ))
 
+
+# -- the framed record of the autoregressive fits and the covariance entries
+AR_P = 4                                       # the order of a fit, or the m of covmat
+
+
+def framed(fn, name, rec, n=NFFT, hop=HOP, first=0, nframes=NFR, P=AR_P, **kw):
+    """a case of an entry that takes a framed record: rec(A) makes the record, P is the order (for covmat its m)"""
+    if fn == "ar_ls":                              # the stand-in writes no status: check=True would judge uninitialised memory
+        kw.setdefault("check", False)
+    case(fn, name, lambda A: K(rec(A), n, hop, first, nframes, P, **kw))
+
+
+def with_nan(a):
+    a[..., 5] = float("nan")
+    return a
+
+
+for fn in ("burg", "yule", "covmat", "ar_ls"):
+    low, high = {"covmat": (1, 65), "ar_ls": (0, 64)}.get(fn, (0, 257))
+    framed(fn, "f32-1d", lambda A: A((N,), F32))
+    framed(fn, "c64-rows", lambda A: A((2, N), C64))
+    framed(fn, "3d", lambda A: A((2, 2, N), F32))
+    framed(fn, "strided-rows", lambda A: A((3, N + 3), F32)[:, :N])
+    framed(fn, "transposed", lambda A: A((N, 3), C64).T)
+    framed(fn, "f64", lambda A: A((N,), F64))
+    framed(fn, "no-detrend", lambda A: A((N,), F32), detrend=False)
+    framed(fn, "detrend-none", lambda A: A((N,), F32), detrend=None)
+    framed(fn, "mean-real", lambda A: A((2, N), F32), mean_value=0.25)
+    framed(fn, "mean-complex", lambda A: A((N,), C64), mean_value=0.25 - 0.5j)
+    framed(fn, "nframes-0", lambda A: A((2, N), F32), nframes=0)
+    framed(fn, "rows-0", lambda A: A((0, N), F32))
+    framed(fn, "first", lambda A: A((N,), F32), first=7, nframes=NFR - 1)
+    framed(fn, "0d", lambda A: A((1,), F32).reshape(()))
+    framed(fn, "P-low-refused", lambda A: A((N,), F32), P=low)
+    framed(fn, "P-high-refused", lambda A: A((N,), F32), P=high)
+    framed(fn, "n-refused", lambda A: A((N,), F32), n=1, hop=0)                                        # n before hop
+    if fn == "burg":
+        framed(fn, "n-16385-refused", lambda A: A((N,), F32), n=16385)
+    if fn == "covmat":
+        framed(fn, "m-above-n-refused", lambda A: A((N,), F32), n=3)
+        framed(fn, "fb-false", lambda A: A((N,), C64), fb=False)
+    else:
+        framed(fn, "order-above-half-refused", lambda A: A((N,), F32), P=33)
+    if fn == "ar_ls":
+        framed(fn, "fb-true", lambda A: A((N,), C64), fb=True)
+        framed(fn, "nframes-0-checked", lambda A: A((2, N), F32), nframes=0, check=True)
+    framed(fn, "hop-refused", lambda A: A((N,), F32), hop=0, nframes=-1)                               # hop before nframes
+    framed(fn, "nframes-refused", lambda A: A((65536, 0), F32), nframes=-1)                            # nframes before the segments
+    framed(fn, "segments-refused", lambda A: A((65536, 0), F32), nframes=(1 << 31) - 1, first=-1)      # the segments before first
+    framed(fn, "first-refused", lambda A: A((N,), F32), first=-1, nframes=NFR + 1)                     # first before the reach
+    framed(fn, "reach-refused", lambda A: A((N,), F32), nframes=NFR + 1, mean_value=float("nan"))      # the reach before the mean
+    framed(fn, "mean-nonfinite-refused", lambda A: with_nan(A((N,), F32)), mean_value=float("nan"))     # the mean before the samples
+    framed(fn, "mean-complex-real-x-refused", lambda A: with_nan(A((N,), F32)), mean_value=0.5j)       # ... and its kind
+    framed(fn, "detrend-linear-refused", lambda A: A((N,), F32), detrend="linear", P=low)              # detrend before the order
+    framed(fn, "mean-detrend-off-refused", lambda A: A((N,), F32), detrend=False, mean_value=0.25)
+    framed(fn, "nan-sample", lambda A: with_nan(A((2, N), F32)))                                        # refused in host mode only
+    framed(fn, "nan-sample-c64", lambda A: with_nan(A((N,), C64)))
+
+# -- spectra of all-pole models; pseudospectra and array scans of eigen-models
+PM_, PSTART, PSTEP = 50, 0.1, 0.001            # the bins of a spectrum: the m, start, step of the czt cases
+
+
+def model(A, lead=(), dt=F64, nco=AR_P + 1, edt=F64, host=False):
+    """-> (a, e) of ar_psd: polynomials of nco coefficients and their error powers, which must not be negative"""
+    return A(tuple(lead) + (nco,), dt), squared(A(tuple(lead) or (1,), edt, host=host)).reshape(tuple(lead))
+
+
+def eig(A, lead=(), m=4, dt=C128, wdt=F64, host=False):
+    """-> (V, w) as eigh leaves them: V[..., m, m] and w[..., m], which must not be negative"""
+    return A(tuple(lead) + (m, m), dt), squared(A(tuple(lead) + (m,), wdt, host=host))
+
+
+for lead in ((), (3,), (2, 3)):
+    case("ar_psd", "lead-%d" % len(lead), lambda A, lead=lead: K(*model(A, lead), PM_, PSTART, PSTEP))
+    case("pseudospectrum", "lead-%d" % len(lead), lambda A, lead=lead: K(*eig(A, lead), 1, PM_, PSTART, PSTEP))
+case("ar_psd", "c128-scale", lambda A: K(*model(A, (3,), C128), PM_, PSTART, PSTEP, scale=0.5))
+case("ar_psd", "out64", lambda A: K(*model(A, (3,)), PM_, PSTART, PSTEP, out64=True))
+case("ar_psd", "c128-out64", lambda A: K(*model(A, (3,), C128), PM_, PSTART, PSTEP, out64=True))
+case("ar_psd", "order-0", lambda A: K(*model(A, (3,), nco=1), PM_, PSTART, PSTEP))
+case("ar_psd", "models-0", lambda A: K(*model(A, (0,)), PM_, PSTART, PSTEP))
+case("ar_psd", "a-f32", lambda A: K(*model(A, (3,), F32), PM_, PSTART, PSTEP))                        # device mode refuses, host mode casts
+case("ar_psd", "a-c64", lambda A: K(*model(A, (3,), C64), PM_, PSTART, PSTEP))
+case("ar_psd", "e-f32", lambda A: K(*model(A, (3,), edt=F32), PM_, PSTART, PSTEP))
+case("ar_psd", "host-e", lambda A: K(*model(A, (3,), host=True), PM_, PSTART, PSTEP))
+case("ar_psd", "e-shape-refused", lambda A: K(A((3, 5), F64), squared(A((2,), F64)), PM_, PSTART, PSTEP))
+case("ar_psd", "0d-refused", lambda A: K(A((1,), F64).reshape(()), A((1,), F64).reshape(()), PM_, PSTART, PSTEP))
+case("ar_psd", "order-refused", lambda A: K(*model(A, (3,), nco=258), 0, PSTART, PSTEP))                    # the order before m
+case("ar_psd", "m-refused", lambda A: K(*model(A, (3,)), 0, float("nan"), PSTEP))                           # m before start
+case("ar_psd", "start-refused", lambda A: K(*model(A, (4096,), nco=1), (1 << 31) - 1, float("nan"), PSTEP))    # start before the launch
+case("ar_psd", "step-refused", lambda A: K(*model(A, (3,)), PM_, PSTART, float("inf")))
+case("ar_psd", "scale-refused", lambda A: K(*model(A, (3,)), PM_, PSTART, PSTEP, scale=float("nan")))
+case("ar_psd", "launch-refused", lambda A: K(*model(A, (4096,), nco=1), (1 << 31) - 1, PSTART, PSTEP))
+case("ar_psd", "nan-a", lambda A: K(with_nan(A((3, 8), F64)), squared(A((3,), F64)), PM_, PSTART, PSTEP))      # refused in host mode only
+case("ar_psd", "nan-e", lambda A: K(A((8, 5), F64), with_nan(A((8,), F64)), PM_, PSTART, PSTEP))
+
+case("pseudospectrum", "ev", lambda A: K(*eig(A, (3,)), 1, PM_, PSTART, PSTEP, weighting="ev"))
+case("pseudospectrum", "out64-p0", lambda A: K(*eig(A, (3,)), 0, PM_, PSTART, PSTEP, out64=True))
+case("pseudospectrum", "ev-out64-p-most", lambda A: K(*eig(A, (3,)), 3, PM_, PSTART, PSTEP, weighting="ev", out64=True))
+case("pseudospectrum", "models-0", lambda A: K(*eig(A, (0,)), 1, PM_, PSTART, PSTEP))
+case("pseudospectrum", "V-real", lambda A: K(*eig(A, (3,), dt=F64), 1, PM_, PSTART, PSTEP))            # device mode refuses, host mode casts
+case("pseudospectrum", "V-c64", lambda A: K(*eig(A, (3,), dt=C64), 1, PM_, PSTART, PSTEP))
+case("pseudospectrum", "w-f32", lambda A: K(*eig(A, (3,), wdt=F32), 1, PM_, PSTART, PSTEP))
+case("pseudospectrum", "host-w", lambda A: K(*eig(A, (3,), host=True), 1, PM_, PSTART, PSTEP))
+case("pseudospectrum", "weighting-refused", lambda A: K(*eig(A), 1, PM_, PSTART, PSTEP, weighting="capon"))
+case("pseudospectrum", "V-not-square-refused", lambda A: K(A((4, 5), C128), squared(A((4,), F64)), 1, PM_, PSTART, PSTEP))
+case("pseudospectrum", "V-1d-refused", lambda A: K(A((4,), C128), squared(A((4,), F64)), 1, PM_, PSTART, PSTEP))
+case("pseudospectrum", "w-shape-refused", lambda A: K(A((3, 4, 4), C128), squared(A((3, 5), F64)), 1, PM_, PSTART, PSTEP))
+case("pseudospectrum", "m-low-refused", lambda A: K(*eig(A, m=1), -1, PM_, PSTART, PSTEP))              # m before p
+case("pseudospectrum", "m-high-refused", lambda A: K(*eig(A, m=65), 1, PM_, PSTART, PSTEP))
+case("pseudospectrum", "p-low-refused", lambda A: K(*eig(A), -1, 0, PSTART, PSTEP))                     # p before nbins
+case("pseudospectrum", "p-high-refused", lambda A: K(*eig(A), 4, PM_, PSTART, PSTEP))
+case("pseudospectrum", "nbins-refused", lambda A: K(*eig(A), 1, 0, float("nan"), PSTEP))                # nbins before start
+case("pseudospectrum", "start-refused", lambda A: K(*eig(A, (4096,), m=2), 1, (1 << 31) - 1, float("nan"), PSTEP))   # start before the launch
+case("pseudospectrum", "step-refused", lambda A: K(*eig(A), 1, PM_, PSTART, float("inf")))
+case("pseudospectrum", "launch-refused", lambda A: K(*eig(A, (4096,), m=2), 1, (1 << 31) - 1, PSTART, PSTEP))
+case("pseudospectrum", "nan-V", lambda A: K(with_nan(A((3, 8, 8), C128)), squared(A((3, 8), F64)), 1, PM_, PSTART, PSTEP))   # host mode only
+case("pseudospectrum", "nan-w", lambda A: K(A((3, 8, 8), C128), with_nan(A((3, 8), F64)), 1, PM_, PSTART, PSTEP))
+
+BM, BNK = 4, 33
+BPOS, BKV = np.arange(BM) * 0.5, np.linspace(-0.5, 0.5, BNK)
+BPOS2 = np.stack([BPOS, BPOS[::-1] * 0.25], axis=1)
+BKV2 = np.stack([BKV, BKV * BKV], axis=1)
+for method in ("bartlett", "capon", "music", "ev"):
+    case("beamscan", method, lambda A, method=method: K(*eig(A, (3,)), BPOS, BKV, method=method, p=1))
+case("beamscan", "defaults-lead-0", lambda A: K(*eig(A), BPOS, BKV))
+case("beamscan", "lead-2-pos-2d", lambda A: K(*eig(A, (2, 3)), BPOS2, BKV2, method="music", p=1))
+case("beamscan", "capon-loading-out64", lambda A: K(*eig(A, (3,)), BPOS2, BKV2, method="capon", loading=0.01, out64=True))
+case("beamscan", "scale-scalar", lambda A: K(*eig(A, (3,)), BPOS, BKV, scale=0.5))
+case("beamscan", "scale-per-model", lambda A: K(*eig(A, (2, 3)), BPOS, BKV, scale=np.linspace(0.5, 1.5, 6).reshape(2, 3)))
+case("beamscan", "scale-row", lambda A: K(*eig(A, (2, 3)), BPOS, BKV, scale=[0.5, 1.0, 1.5]))
+case("beamscan", "tables-tensors", lambda A: K(*eig(A, (3,)), as_tensor(A, A((BM, 2), F64)), as_tensor(A, A((BNK, 2), F32)),
+                                               scale=as_tensor(A, A((3,), F64))))
+case("beamscan", "tables-lists", lambda A: K(*eig(A, (3,)), list(BPOS), list(BKV), method="ev", p=3))
+case("beamscan", "models-0", lambda A: K(*eig(A, (0,)), BPOS, BKV))
+case("beamscan", "V-real", lambda A: K(*eig(A, (3,), dt=F64), BPOS, BKV))                              # device mode refuses, host mode casts
+case("beamscan", "w-f32", lambda A: K(*eig(A, (3,), wdt=F32), BPOS, BKV))
+case("beamscan", "host-w", lambda A: K(*eig(A, (3,), host=True), BPOS, BKV))
+case("beamscan", "V-not-square-refused", lambda A: K(A((4, 5), C128), squared(A((4,), F64)), BPOS, BKV))
+case("beamscan", "w-shape-refused", lambda A: K(A((3, 4, 4), C128), squared(A((3, 5), F64)), BPOS, BKV))
+case("beamscan", "pos-3d-refused", lambda A: K(*eig(A), BPOS2[None], BKV2))
+case("beamscan", "pos-width-refused", lambda A: K(*eig(A), np.zeros((BM, 4)), np.zeros((BNK, 4))))
+case("beamscan", "pos-nonfinite-refused", lambda A: K(*eig(A), BPOS + float("inf"), BKV2))             # pos before kv
+case("beamscan", "kv-width-refused", lambda A: K(*eig(A), BPOS, BKV2))
+case("beamscan", "kv-nonfinite-refused", lambda A: K(*eig(A), BPOS, BKV + float("nan"), method="esprit"))   # kv before the method
+case("beamscan", "method-refused", lambda A: K(*eig(A, m=1), BPOS, BKV, method="esprit"))              # the method before m
+case("beamscan", "m-low-refused", lambda A: K(*eig(A, m=1), BPOS[:1], BKV[:0]))                          # m before nk
+case("beamscan", "m-high-refused", lambda A: K(*eig(A, m=65), BPOS, BKV))
+case("beamscan", "nk-refused", lambda A: K(*eig(A), BPOS, BKV[:0], method="music", p=4))                # nk before p
+case("beamscan", "p-low-refused", lambda A: K(*eig(A), BPOS, BKV, method="music", p=-1, loading=-1.0))  # p before the loading
+case("beamscan", "p-high-refused", lambda A: K(*eig(A), BPOS, BKV, method="ev", p=4))
+case("beamscan", "p-unjudged", lambda A: K(*eig(A, (3,)), BPOS, BKV, method="capon", p=9))              # p is the eigen methods' alone
+case("beamscan", "loading-refused", lambda A: K(*eig(A), BPOS[:3], BKV, loading=-1.0))                  # the loading before pos's length
+case("beamscan", "loading-nonfinite-refused", lambda A: K(*eig(A), BPOS, BKV, loading=float("inf")))
+case("beamscan", "pos-length-refused", lambda A: K(*eig(A), BPOS[:3], BKV, scale=float("nan")))         # pos's length before the scale
+case("beamscan", "scale-nonfinite-refused", lambda A: K(*eig(A, (3,)), BPOS, BKV, scale=[1.0, float("nan"), 1.0]))
+case("beamscan", "nan-V", lambda A: K(with_nan(A((3, 8, 8), C128)), squared(A((3, 8), F64)), np.arange(8.0), BKV))   # refused in host mode only
+case("beamscan", "nan-w", lambda A: K(A((3, 8, 8), C128), with_nan(A((3, 8), F64)), np.arange(8.0), BKV))
+
 FUNCTIONS = ("fft", "mean","welch_psd", "welch_accum", "welch_export", "welch_apply", "welch_finish", "welch_csd", "csd_matrix",
              "channel_means", "stft_frames", "istft_frames", "bispectrum", "multitaper", "czt", "zoom_welch", "ddc", "upfirdn", "pfb",
              "pfb_synth", "stft_cog", "hilbert_rows", "frame_sum", "spectral_filter_rows", "xcorr_normalised", "xcorr_frames", "skf",
              "welch_blocks", "cwt", "icwt_sum", "eigh", "fir_filter", "biquad_filter", "sos_filter", "sos_filtfilt", "csd_epilogue",
-             "wct_time", "wct_scale", "ssq", "ssq_bands", "ssq_sum", "wvd", "cyclic", "lomb", "lomb_sums", "lomb_finish")
+             "wct_time", "wct_scale", "ssq", "ssq_bands", "ssq_sum", "wvd", "cyclic", "lomb", "lomb_sums", "lomb_finish", "burg", "yule", "covmat",
+             "ar_ls", "ar_psd", "pseudospectrum", "beamscan")

@@ -13,7 +13,9 @@ word some of them differently, and a host array among device tensors is refused 
 message; otherwise both modes refuse alike (type and message) or both return arrays of the same dtype, shape and bytes, compared as
 integer words -- the arrays that come back and every output array the engine allocated for the library to write.  Every output array
 the engine allocates in host mode lies inside a sentinel-filled allocation (tests/guard_ref.py) with 1 KiB on either side that must
-survive the call: a copy-back with too large a byte count lands there.
+survive the call: a copy-back with too large a byte count lands there.  The device allocations start from the same sentinel, so an
+element that a call leaves alone (the last column of the reflection coefficients of burg and yule, which share the pitch of the
+polynomials) must be left alone in both modes.
 
 EXEMPT names the cases whose result is not reproducible between two calls in the SAME mode, with the kernel that causes it
 (float64 atomicAdd sums); they are held to their entry's tolerance in the GPU suite instead of to the bits.  OTHER_CALL and ASSEMBLED
@@ -147,6 +149,7 @@ def run(case, mode, guards=None):
 
     def noted(self, shape, dt, like):
         raw.append(saved[1](self, shape, dt, like))
+        G._words(raw[-1].reshape(-1)).fill_(G._SENTINEL_I32)     # as the host interior: an element no mode writes compares equal
         return raw[-1]
     try:
         args, kwargs = build(A)
@@ -179,7 +182,7 @@ def golden_refusals():
 
 
 def test_the_cases_reach_what_the_table_does_not():
-    assert len(T.CASES) == 425 and len({c[1] for c in T.CASES}) == 46
+    assert len(T.CASES) == 628 and len({c[1] for c in T.CASES}) == 53
     # one workgroup transforms powers of two up to max_wg_fft() and, by Bluestein, other lengths n with 2 n - 1 below it
     assert LWIN.size == 4097 and 2 * 4096 - 1 <= E.max_wg_fft() < 2 * LWIN.size - 1
     assert len({i for i in IDS if i.startswith(("cwt/subset-", "ssq/subset-"))}) == 32

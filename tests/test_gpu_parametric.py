@@ -218,6 +218,21 @@ def test_host_models_further_apart_keep_what_lies_between():
         assert np.array_equal(np.array(G.interior_of(base, 1, ne, rows=segs, pitch=o_ld)).view(np.uint64), np.ascontiguousarray(w).reshape(segs, ne).view(np.uint64))
 
 
+def test_host_spectra_further_apart_keep_what_lies_between():
+    """sp_ar_psd on host memory with P_ld > m, float32 and float64: the rows are staged in both directions, so the room between them
+    comes back as it was, every bin is written and the bits are those of the dense call"""
+    a, e = np.array([[1.0, -0.5, 0.25, -0.1], [1.0, 0.3, -0.2, 0.05]]), np.array([1.0, 2.5])
+    m, P_ld = 100, 107
+    _ffi.init()
+    for out64 in (False, True):
+        base, inner = G.sentinel_output(m, np.float64 if out64 else np.float32, 1, rows=2, pitch=P_ld)
+        rc = _ffi.lib().sp_ar_psd(_ffi.ptr(a), 0, 4, _ffi.ptr(e), 1, 3, 2, m, 0.1, 0.003, 1.0, int(out64), _ffi.ptr(int(inner.ctypes.data)), P_ld, 0)
+        assert rc == 0, _ffi.lib().sp_last_error()
+        assert G.guards_intact(base, 1, m, rows=2, pitch=P_ld) and G.all_written(base, 1, m, rows=2, pitch=P_ld)
+        want = E.ar_psd(a, e, m, 0.1, 0.003, out64=out64)
+        assert want.dtype == inner.dtype and np.array(G.interior_of(base, 1, m, rows=2, pitch=P_ld)).tobytes() == want.tobytes()
+
+
 @pytest.mark.parametrize("method", ("burg", "yule"))
 def test_refusals_and_bad_records_leave_the_outputs_untouched(method):
     name = "frames"

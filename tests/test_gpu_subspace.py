@@ -346,6 +346,25 @@ def test_host_matrices_further_apart_keep_what_lies_between():
     assert np.array_equal(bits(np.array(G.interior_of(base, 1, m * m, rows=segs, pitch=C_ld))), bits(covmat_of(name, True).reshape(segs, m * m)))
 
 
+def test_host_pseudospectra_further_apart_keep_what_lies_between():
+    """sp_pseudospectrum on host memory with P_ld > nbins, float32 and float64: the rows are staged in both directions, so the room
+    between them comes back as it was, every bin is written and the bits are those of the dense call"""
+    rng = np.random.default_rng(5)
+    X = rng.standard_normal((2, 9, 4)) + 1j * rng.standard_normal((2, 9, 4))
+    w, V = (np.ascontiguousarray(np.stack(t)) for t in zip(*(R.eigh_desc(x.conj().T @ x) for x in X)))
+    nbins, P_ld = 100, 107
+    _ffi.init()
+    for out64 in (False, True):
+        base, inner = G.sentinel_output(nbins, np.float64 if out64 else np.float32, 1, rows=2, pitch=P_ld)
+        st = np.full(2, -77, dtype=np.int32)
+        rc = _ffi.lib().sp_pseudospectrum(_ffi.ptr(V), 4, _ffi.ptr(w), 4, 2, 2, 1, nbins, 0.1, 0.003, int(out64), _ffi.ptr(int(inner.ctypes.data)), P_ld,
+                                          _ffi.ptr(st), 0)
+        assert rc == 0, _ffi.lib().sp_last_error()
+        assert G.guards_intact(base, 1, nbins, rows=2, pitch=P_ld) and G.all_written(base, 1, nbins, rows=2, pitch=P_ld) and not st.any()
+        want = E.pseudospectrum(V, w, 2, nbins, 0.1, 0.003, "ev", out64=out64)[0]
+        assert want.dtype == inner.dtype and np.array_equal(bits(np.array(G.interior_of(base, 1, nbins, rows=2, pitch=P_ld))), bits(want))
+
+
 @pytest.mark.parametrize("entry", ("sp_covmat", "sp_ar_ls"))
 def test_refusals_and_bad_records_leave_the_outputs_untouched(entry):
     name = "frames"

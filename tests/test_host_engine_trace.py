@@ -54,12 +54,13 @@ def test_replay_equals_golden(golden_trace, replayed):
 
 def test_every_abi_entry_has_a_case(replayed):
     seen = {ev[0] for kept in replayed.values() for ev in kept["events"] if ev[0].startswith("sp_")}
-    assert NOT_TRACED <= set(T.DECLARED) and len(T.DECLARED) == sum(len(table) for table in _ffi.TABLES)
+    assert len(T.TRACED_TABLES) == 9 and T.TRACED_TABLES[:6] == _ffi.TABLES
+    assert NOT_TRACED <= set(T.DECLARED) and len(T.DECLARED) == sum(len(table) for table in T.TRACED_TABLES) == 91
     assert seen == set(T.DECLARED) - NOT_TRACED
 
 
 def test_every_function_in_both_modes(replayed):
-    assert len(T.FUNCTIONS) == 46 and {c[1] for c in T.CASES} == set(T.FUNCTIONS)
+    assert len(T.FUNCTIONS) == 53 and {c[1] for c in T.CASES} == set(T.FUNCTIONS)
     for fn in T.FUNCTIONS:
         for mode in T.MODES:
             calls = [kept for k, kept in replayed.items() if k.startswith(fn + "/") and k.endswith("/" + mode)]

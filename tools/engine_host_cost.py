@@ -6,7 +6,8 @@ after it.  One line: label, microseconds per call on the device tensor and on th
   python tools/engine_host_cost.py [TREE [LABEL [ENTRY]]]
 
 ENTRY (default welch_psd) may also be cyclic (the same record and frames, 4 cycle frequencies, mean_value given so that it is one
-library call) or ssq (the same record and frames, T only).
+library call), ssq (the same record and frames, T only), burg or ar_ls (the same segments, order 8; ar_ls with check=False, so that no
+status is read back) or beamscan (31 eigen-models of order 8, one per frame, against 128 scan points).
 
 TREE (default: this repository) is where pyfft_amd is imported from, so that the Python files of another commit, unpacked elsewhere and
 pointed at the same library with SP_LIB_PATH, can be timed in the same session: profiles/engine_host_cost.txt."""
@@ -30,9 +31,17 @@ xh = (rng.standard_normal(n) + 1j * rng.standard_normal(n)).astype(np.complex64)
 xd = torch.from_numpy(xh).cuda()
 win = np.hanning(nfft)
 dwin = np.gradient(win)
+order, nk = 8, 128
+Vh = np.linalg.qr(rng.standard_normal((nframes, order, order)) + 1j * rng.standard_normal((nframes, order, order)))[0]
+wh = np.sort(rng.random((nframes, order)) + 0.1)[:, ::-1].copy()
+eig = {True: (torch.from_numpy(Vh).cuda(), torch.from_numpy(wh).cuda()), False: (Vh, wh)}
+pos, kv = np.arange(order) * 0.5, np.linspace(-0.5, 0.5, nk)
 call = {"welch_psd": lambda x: E.welch_psd(x, win, hop, nframes),
         "cyclic": lambda x: E.cyclic(x, win, hop, nframes, [0.0, 0.05, 0.1, 0.25], mean_value=0.0),
-        "ssq": lambda x: E.ssq(x, win, dwin, hop, 0, nframes)}[entry]
+        "ssq": lambda x: E.ssq(x, win, dwin, hop, 0, nframes),
+        "burg": lambda x: E.burg(x, nfft, hop, 0, nframes, order),
+        "ar_ls": lambda x: E.ar_ls(x, nfft, hop, 0, nframes, order, check=False),
+        "beamscan": lambda x: E.beamscan(*eig[torch.is_tensor(x)], pos, kv)}[entry]
 us = []
 for x in (xd, xh):
     for _ in range(200):
